@@ -21,6 +21,9 @@ torch.manual_seed(0)), `--points 1485000` (10M tets), `--dtype bf16` (bf16 stora
 
 After the timed steps the run CHECKS itself: the CPU oracle (the timed CPU baseline, same graph, same weights) and the
 GPU logits are compared (`check`), and the process exits non-zero when they differ by more than the stated tolerance.
+
+`--dump-outputs DIR` writes what the last timed step returned as .npy files (see the option's help).  Inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -167,15 +170,18 @@ def load_probe(step, seconds=1.5):
             "source": "rocm-smi sampled by a thread while the step ran back to back for %.1f s right after the timed region" % seconds}
 
 
-def timed_steps(step, steps, sync, world, dev):
+def timed_steps(step, steps, sync, world, dev, keep=None):
     """EXACTLY `steps` steps between barrier + synchronize on both sides (wall clock, max over ranks) and, from events recorded on the
-    launch stream between the steps, the per-step times.  -> (seconds, [ms per step])"""
+    launch stream between the steps, the per-step times.  -> (seconds, [ms per step]).  `keep` (a dict): keep["out"] = what the last step returned."""
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     sync()
     t0 = time.perf_counter()
     for i in range(steps):
         evs[i].record()
-        step()
+        if keep is None:
+            step()
+        else:
+            keep["out"] = step()
     evs[steps].record()
     sync()
     dt = time.perf_counter() - t0
@@ -188,6 +194,27 @@ def timed_steps(step, steps, sync, world, dev):
     if os.environ.get("DGNN_BENCH_DEBUG_STEPS"):
         sys.stderr.write("timed_steps: wall %.3f ms; per step (events) %s\n" % (dt * 1e3, " ".join("%.2f" % v for v in per)))
     return dt, per
+
+
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: at most this much on disk per run
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_output(out_dir, name, t, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: tensor `t` (one row per cell) as out_dir/<name>.npy, float64 kept, anything else as float32.  Larger than `budget`:
+    a fixed seeded sample of its rows in ascending order, and out_dir/<name>_rows.npy (float64) names them.  -> rows written"""
+    a = t.detach().cpu()
+    a = (a.double() if a.dtype == torch.float64 else a.float()).numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    room = budget - 2 * 1024          # (an .npy header takes 128 bytes; two files when sampled)
+    if a.nbytes > room:
+        # a sampled row costs its values plus its float64 row number
+        k = int(room // (a.nbytes // a.shape[0] + 8))
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], k, replace=False))
+        np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return a.shape[0]
 
 
 def logits_check(got, ref, bf16, bf16_compensated=True):
@@ -424,7 +451,13 @@ def main():
                          "the whole run stays under ~150 s, on = wait for it, off = skip")
     ap.add_argument("--gemm-mode", choices=["f32", "bf16x3", "bf16x3f", "f16x2d", "f16x2"], default=None,
                     help="dense part of the fused fp32 layer: exact fp32 MFMA, or 3-way split-bf16 MFMA (fp32-class accuracy)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the logits, in the cell order the step ran on) as DIR/logits.npy "
+                         "(N > 1: DIR/logits_rank<r>.npy, each rank its own cells), float32, at most 64 MB in all: a larger output keeps a fixed seeded "
+                         "sample of its rows and names them in DIR/<name>_rows.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     t_bench0 = time.perf_counter()
     rank = int(os.environ.get("RANK", "0"))
@@ -655,7 +688,10 @@ def main():
             return step()
         finally:
             ops.LAYER_HOOK = None
-    dt, per_step = timed_steps(step_timed if events_in_timed else step, args.steps, sync, world, dev)
+    last = {} if args.dump_outputs else None
+    dt, per_step = timed_steps(step_timed if events_in_timed else step, args.steps, sync, world, dev, keep=last)
+    if last is not None:
+        dump_output(args.dump_outputs, "logits" if world == 1 else "logits_rank%d" % rank, last.pop("out"), budget=DUMP_BUDGET_BYTES // world)
     if not events_in_timed:
         ops.LAYER_HOOK = hook
         for _ in range(args.steps):

@@ -44,6 +44,30 @@ def test_logits_check_accepts_rounding_noise_and_flags_real_errors():
     assert bench.logits_check(noisy, ref, bf16=True)["ok"] and not bench.logits_check(ref + 0.3, ref, bf16=True)["ok"]
 
 
+def test_dump_outputs_writes_float_arrays_and_samples_past_the_budget(tmp_path):
+    g = torch.Generator().manual_seed(0)
+    small = torch.randn(1000, 2, generator=g)
+    assert bench.dump_output(str(tmp_path / "a"), "logits", small) == 1000
+    got = np.load(str(tmp_path / "a" / "logits.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["logits.npy"]
+    # bf16 rows come out as float32, float64 stays float64
+    bench.dump_output(str(tmp_path / "b"), "h", small.bfloat16())
+    bench.dump_output(str(tmp_path / "b"), "d", small.double())
+    assert np.load(str(tmp_path / "b" / "h.npy")).dtype == np.float32 and np.load(str(tmp_path / "b" / "d.npy")).dtype == np.float64
+    # past the budget: the same seeded rows on every call, ascending, and both files together within the budget
+    big = torch.randn(100000, 2, generator=g)
+    budget = 256 * 1024
+    dirs = [tmp_path / "c", tmp_path / "d"]
+    for d in dirs:
+        assert bench.dump_output(str(d), "logits", big, budget=budget) < big.shape[0]
+        assert sum(p.stat().st_size for p in d.iterdir()) <= budget
+    rows = np.load(str(dirs[0] / "logits_rows.npy"))
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and 0 < rows.size < big.shape[0]
+    assert np.array_equal(rows, np.load(str(dirs[1] / "logits_rows.npy")))
+    assert np.array_equal(np.load(str(dirs[0] / "logits.npy")), big.numpy()[rows.astype(np.int64)])
+
+
 def test_algorithmic_bytes_are_the_survey_figures():
     assert [bench.layer_bytes(a, b) for a, b in ((28, 64), (64, 128), (128, 128))] == [704, 1104, 1360]
     assert bench.path_bytes(28, (64, 128, 128, 128)) == 5048 and bench.path_bytes(28, (64, 128, 128, 128), 2) == 3200
