@@ -425,6 +425,30 @@ def batch_norm_act(x, bn: torch.nn.BatchNorm1d, relu: bool):
     return _BatchNormAct.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, momentum, bn.eps, relu)
 
 
+class _GraphLayerNormAct(torch.autograd.Function):
+    """y = act(graph LayerNorm(x)) (PyG 2.0.2 LayerNorm, batch=None): one mean and one biased std over the whole tensor, the same in train and
+    eval mode.  Forward: standalone statistics pass, finaliser, apply; backward: one column pass + the two global scalars + the dx pass."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, relu):
+        if x.dim() != 2 or x.dtype != torch.float32:
+            raise TypeError("graph_layer_norm_act takes fp32 [M, C] rows, got %s %s" % (x.dtype, tuple(x.shape)))
+        y, stats, scale = ops.graph_ln_forward(x, weight, bias, eps, relu)
+        ctx.save_for_backward(x, weight, bias, stats, scale)
+        ctx.relu = bool(relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, bias, stats, scale = ctx.saved_tensors
+        dx, dw, db = ops.graph_ln_relu_bwd(x, dy.contiguous(), stats, weight, scale, bias, ctx.relu)
+        return dx, (dw if weight is not None else None), (db if bias is not None else None), None, None
+
+
+def graph_layer_norm_act(x, weight, bias, eps=1e-5, relu=False):
+    return _GraphLayerNormAct.apply(x, weight, bias, float(eps), bool(relu))
+
+
 class _ReLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

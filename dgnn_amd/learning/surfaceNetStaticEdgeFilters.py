@@ -8,13 +8,18 @@ of data/models/kf96/model_best.ptm (``convs.N.conv.lin_{i,j,e}.*``, ``convs.N.no
 ``decoder.{0,3}.*``, ``decoder.1.module.*``).  The nn.Linear / BatchNorm1d sub-modules are parameter
 containers only -- their ``forward`` is never called; all arithmetic runs in libdgnn_hip.so.
 
+``normalization`` is 'b' (BatchNorm, the shipped configs), 'l' (PyG's graph LayerNorm: one mean and one std over all rows of the
+call, see `LayerNorm`) or anything else (no norm).  An 'l' model runs each conv layer as aggregate -> GEMM with the statistics in its
+epilogue -> LayerNorm finaliser -> apply + ReLU; the one-call, fused-decoder and whole-model training paths decline it.  Its results
+depend on the schedule by design (inference_layer normalises over the scene, the batched inferences per batch).  bf16 storage and
+the partitioned scene are not available for it.
+
 Ownership and errors follow the reference: inputs are never mutated, logits are returned on the
 device, config errors ``print`` and ``sys.exit(1)`` (learning/runModel.py:190-191), everything else
 raises.  There is no CPU execution path.
 """
 from __future__ import annotations
 
-import sys
 
 import torch
 import torch.nn as nn
@@ -34,6 +39,37 @@ class BatchNorm(nn.Module):
 
     def forward(self, x, relu: bool = False):
         return Fn.batch_norm_act(x, self.module, relu)
+
+
+class LayerNorm(nn.Module):
+    """Key-compatible stand-in for torch_geometric.nn.norm.LayerNorm (PyG 2.0.2), as the reference calls it (batch=None):
+
+        LayerNorm(in_channels, eps=1e-5, affine=True)   parameters: weight [C] (init 1), bias [C] (init 0); no buffers
+        forward(x):  x = x - x.mean()                    # ONE scalar mean over all M*C elements
+                     out = x / (x.std(unbiased=False) + eps)   # eps is added to the STD, not inside the sqrt
+                     out = out * weight + bias
+
+    Train and eval mode are the same (no running statistics); the statistics cover exactly the rows of the call, so results depend on
+    how the caller batches rows.  A constant input gives `bias`; zero rows give zero rows.  This reading of PyG 2.0.2 is ours (PyG is
+    not part of the reference tree), like the MessagePassing semantics of the fixtures.  `forward(x, relu=True)` also applies the ReLU
+    that follows the norm in every place the model uses it (csrc/lnorm.hip)."""
+
+    def __init__(self, in_channels: int, eps: float = 1e-5, affine: bool = True):
+        super().__init__()
+        self.in_channels = in_channels
+        self.eps = eps
+        if affine:
+            self.weight = nn.Parameter(torch.ones(in_channels))
+            self.bias = nn.Parameter(torch.zeros(in_channels))
+        else:
+            self.register_parameter("weight", None)
+            self.register_parameter("bias", None)
+
+    def forward(self, x, relu: bool = False):
+        return Fn.graph_layer_norm_act(x, self.weight, self.bias, self.eps, relu)
+
+    def __repr__(self):
+        return "{}({})".format(self.__class__.__name__, self.in_channels)
 
 
 def _block_x(x_all, n_id, col0, dev):
@@ -100,8 +136,7 @@ class SurfaceNet(nn.Module):
         if self.norm_type == 'b':
             return BatchNorm(size)
         elif self.norm_type == 'l':
-            print("normalization 'l' (graph LayerNorm) is not supported by the MI355X path")
-            sys.exit(1)
+            return LayerNorm(size)
         return None
 
     def sageLayer(self, input, output):
@@ -157,6 +192,8 @@ class SurfaceNet(nn.Module):
         parameters stay fp32.  Tolerance of that path: |dlogit| <= 5e-2 * max(1, |logit|/8), arg-max agreement >= 99.9 %."""
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("storage dtype must be torch.float32 or torch.bfloat16")
+        if dtype == torch.bfloat16 and self.norm_type == 'l':
+            raise NotImplementedError("bf16 storage is not available for normalization 'l' (graph LayerNorm): keep torch.float32")
         self.storage_dtype = dtype
         return self
 
@@ -201,8 +238,8 @@ class SurfaceNet(nn.Module):
         return ops.cast_to_bf16(x)
 
     def _norm_act(self, layer, x):
-        """convs[i][1] then convs[i][2] (reference :218-219): BatchNorm (if any) + ReLU, one kernel chain."""
-        norm = layer[1] if len(layer) > 1 and isinstance(layer[1], BatchNorm) else None
+        """convs[i][1] then convs[i][2] (reference :218-219): BatchNorm / LayerNorm (if any) + ReLU, one kernel chain."""
+        norm = layer[1] if len(layer) > 1 and isinstance(layer[1], (BatchNorm, LayerNorm)) else None
         if norm is not None:
             return norm(x, relu=True)
         return Fn.relu(x)
@@ -574,6 +611,8 @@ class SurfaceNet(nn.Module):
         """One eval-mode conv layer + BN + ReLU (see _eval_layers); `decode`: + the decoder, logits come back."""
         layer = self.convs[i]
         conv = layer[0]
+        if isinstance(layer[1], LayerNorm):
+            return self._eval_layer_ln(i, x, xe, plan, sorted_attr, out, rows, decode)
         if decode:
             le_ = conv.lin_e
             if self.storage_dtype == torch.bfloat16:
@@ -688,6 +727,30 @@ class SurfaceNet(nn.Module):
             a = Fn.aggregate(x, plan, **conv._filter_args(xe))
         return ops.linear_fwd(a, conv.lin_j.weight, x_dst, conv.lin_i.weight, conv.lin_j.bias, scale, shift, True, out=out_v)
 
+    @staticmethod
+    def _ln_act(norm, A1, W1, A2=None, W2=None, bias=None):
+        """relu(LayerNorm(A1 . W1^T + A2 . W2^T + bias)): the GEMM leaves the statistics in its epilogue where it can, then finaliser + apply"""
+        if A1.dtype != torch.float32:
+            raise ops.DgnnError("graph LayerNorm takes fp32 rows, got %s" % (A1.dtype,))
+        return ops.linear_fwd_ln(A1, W1, A2, W2, bias, norm.weight, norm.bias, norm.eps, relu=True)[0]
+
+    def _eval_layer_ln(self, i, x, xe, plan, sorted_attr, out, rows, decode):
+        """conv + graph LayerNorm + ReLU of layer i in eval mode: aggregate, then _ln_act over all n_dst rows of the call"""
+        if out is not None or rows is not None or decode:
+            raise ops.DgnnError("graph LayerNorm (layer %d): the statistics span every row of the call; destination sub-ranges, caller buffers and "
+                                "the decoder-carrying launch are not available" % i)
+        if isinstance(x, ops.SplitRows):
+            x = x.float()
+        conv = self.convs[i][0]
+        le = conv.lin_e
+        n = plan.n_dst
+        if isinstance(le, Linear) and le.in_features in (2, 20):
+            ea = plan.sorted_edge_attr(xe) if sorted_attr else xe
+            a = ops.aggregate_fwd(plan.rowptr, plan.src, None, n, x, ea, le.weight, le.bias)
+        else:
+            a = Fn.aggregate(x, plan, **conv._filter_args(xe))
+        return self._ln_act(self.convs[i][1], a, conv.lin_j.weight, x[:n], conv.lin_i.weight, conv.lin_j.bias)
+
     # ---- wide conv layers on split rows (round 5; csrc/wide.hip) -------------------------------------------------------------------------------
     def wide_layer_split_rows(self, c_in, c_out):
         """True when the eval-mode conv layer c_in -> c_out runs on dgnn_sage_aggregate_sr + dgnn_linear_sr (fp32 storage, default arithmetic, the widths
@@ -771,6 +834,9 @@ class SurfaceNet(nn.Module):
             return x.float() if x.dtype == torch.bfloat16 else x
         if len(dec) == 1:
             return ops.linear_fwd(x, dec[0].weight, bias=dec[0].bias, out_dtype=torch.float32)
+        if isinstance(dec[1], LayerNorm):     # statistics over every row handed to the decoder (reference :185, :314, :351)
+            h = self._ln_act(dec[1], x, dec[0].weight, bias=dec[0].bias)
+            return ops.linear_fwd(h, dec[3].weight, bias=dec[3].bias)
         scale, shift = self._fold(dec[1] if isinstance(dec[1], BatchNorm) else None, dec[0].out_features, x.device)
         if x.dtype == torch.bfloat16:
             if ops.decoder_fused_supported(dec[0].in_features, dec[0].out_features, dec[3].out_features) and x.stride(0) % 8 == 0:
@@ -816,6 +882,8 @@ class SurfaceNet(nn.Module):
             a = ops.aggregate_fwd(plan.rowptr, plan.src, plan.eid, plan.n_dst, x, ea, le.weight, le.bias)
         else:
             a = Fn.aggregate(x, plan, **conv._filter_args(ea))
+        if isinstance(layer[1], LayerNorm):
+            return self._ln_act(layer[1], a, conv.lin_j.weight, x[:plan.n_dst], conv.lin_i.weight, conv.lin_j.bias)
         return ops.linear_fwd(a, conv.lin_j.weight, x[:plan.n_dst], conv.lin_i.weight, conv.lin_j.bias, scale, shift, True)
 
     # ---- INFERENCE, layer-major 1-hop blocks (reference :279-320) -------------------------------

@@ -416,6 +416,97 @@ def bn_relu_bwd_apply(x, y, dy, gamma, mean, var, eps, relu, sums, count):
     return dx
 
 
+# ---- graph LayerNorm (csrc/lnorm.hip) -----------------------------------------------------------
+def _f64_view(buf):
+    """8-byte aligned address inside an fp32 work buffer"""
+    return (buf.data_ptr() + 7) & ~7
+
+
+@on_device_of
+def graph_ln_stats(x):
+    """standalone statistics pass over x [M, c] -> (fp32 work buffer holding the fp64 partials [nblk][2], nblk)"""
+    _req(x, "x", dim=2)
+    M, c = x.shape
+    nblk = int(lib().dgnn_graph_ln_stats_blocks(M, c))
+    buf = _f32(4 * max(nblk, 1) + 2, x.device)
+    check(lib().dgnn_graph_ln_stats(ptr(x), _ld(x), M, c, _f64_view(buf), stream_ptr()), "dgnn_graph_ln_stats")
+    return buf, nblk
+
+
+@on_device_of
+def graph_ln_finalize(partials_addr, nblk, pc, M, c, weight, bias, eps, device):
+    """(m, sigma, r, M c) and the per-channel fold scale = w r, shift = b - m w r from partial sums [nblk][2][pc] at `partials_addr`
+    -> (stats [4], scale [c], shift [c])"""
+    out = torch.empty((2 * c + 4,), dtype=torch.float32, device=device)
+    work = _f32(2 * 512 + 2, device)
+    stats, scale, shift = out[:4], out[4:4 + c], out[4 + c:]
+    if M > 0:
+        check(lib().dgnn_graph_ln_finalize_fold(partials_addr, nblk, pc, M, c, ptr(weight), ptr(bias), float(eps), ptr(stats), ptr(scale), ptr(shift),
+                                                _f64_view(work), stream_ptr()), "dgnn_graph_ln_finalize_fold")
+    return stats, scale, shift
+
+
+@on_device_of
+def graph_ln_apply(x, stats, scale, bias, relu, out=None):
+    """y = act((x - m) * scale + bias) -- the apply of graph_ln_finalize's fold"""
+    _req(x, "x", dim=2)
+    M, c = x.shape
+    y = torch.empty((M, c), dtype=torch.float32, device=x.device) if out is None else out
+    check(lib().dgnn_graph_ln_apply(ptr(x), _ld(x), M, c, ptr(stats), ptr(scale), ptr(bias), int(bool(relu)), ptr(y), _ld(y) if M else c, stream_ptr()),
+          "dgnn_graph_ln_apply")
+    return y
+
+
+def graph_ln_forward(x, weight, bias, eps, relu):
+    """act(LayerNorm(x)) with the standalone statistics pass -> (y, stats, scale)"""
+    M, c = x.shape
+    buf, nblk = graph_ln_stats(x)
+    stats, scale, _ = graph_ln_finalize(_f64_view(buf), nblk, 1, M, c, weight, bias, eps, x.device)
+    return graph_ln_apply(x, stats, scale, bias, relu), stats, scale
+
+
+@on_device_of
+def linear_fwd_ln(A1, W1, A2=None, W2=None, bias=None, weight=None, ln_bias=None, eps=1e-5, relu=True):
+    """relu(LayerNorm(A1 . W1^T + A2 . W2^T + bias)): the statistics come from the GEMM's own epilogue (dgnn_linear_fwd_x3_stats colstats) where it
+    takes the shape, from the standalone pass over z otherwise.  -> (y, z, stats, scale)"""
+    _req(A1, "A1", dim=2)
+    M, n_out = A1.size(0), W1.size(0)
+    z = None
+    if M > 0:
+        z = torch.empty((M, n_out), dtype=torch.float32, device=A1.device)
+        scratch = _f32(lib().dgnn_colstats_scratch_elems(M, n_out) + 2, A1.device)
+        cs = _f64_view(scratch)
+        W1c = W1.contiguous()
+        W2c = W2.contiguous() if W2 is not None else None
+        rc = lib().dgnn_linear_fwd_x3_stats(ptr(A1), _ld(A1), A1.size(1), ptr(W1c), W1c.size(1), ptr(A2), _ld(A2) if A2 is not None else 0,
+                                            A2.size(1) if A2 is not None else 0, ptr(W2c), W2c.size(1) if W2c is not None else 0, ptr(bias), M, n_out,
+                                            ptr(z), n_out, cs, stream_ptr())
+        if rc != DGNN_E_UNSUPPORTED:
+            check(rc, "dgnn_linear_fwd_x3_stats")
+            stats, scale, _ = graph_ln_finalize(cs, (M + 31) // 32, n_out, M, n_out, weight, ln_bias, eps, A1.device)
+            return graph_ln_apply(z, stats, scale, ln_bias, relu, out=z), None, stats, scale
+    z = linear_fwd(A1, W1, A2, W2, bias)
+    y, stats, scale = graph_ln_forward(z, weight, ln_bias, eps, relu)
+    return y, z, stats, scale
+
+
+@on_device_of
+def graph_ln_relu_bwd(x, dy, stats, weight, scale, bias, relu):
+    """backward of y = act(LayerNorm(x)) -> (dx, dweight, dbias)"""
+    _req(x, "x", dim=2)
+    _req(dy, "dy", dim=2)
+    M, c = x.shape
+    dx = torch.empty((M, c), dtype=torch.float32, device=x.device)
+    dw = torch.zeros(c, dtype=torch.float32, device=x.device)
+    db = torch.zeros(c, dtype=torch.float32, device=x.device)
+    if M == 0:
+        return dx, dw, db
+    scratch = _f32(lib().dgnn_graph_ln_scratch_elems(M, c), x.device)
+    check(lib().dgnn_graph_ln_relu_bwd(ptr(x), _ld(x), ptr(dy), _ld(dy), ptr(stats), ptr(weight), ptr(scale), ptr(bias), int(bool(relu)), M, c, ptr(dx), c,
+                                       ptr(dw), ptr(db), ptr(scratch), stream_ptr()), "dgnn_graph_ln_relu_bwd")
+    return dx, dw, db
+
+
 # ---- wide conv layers on split rows (csrc/wide.hip) ---------------------------------------------
 # DGNN_WIDE_SR=0: the layers wider than the fused kernels keep the fp32 aggregate + x2h / x3 GEMM pair of rounds 2-4
 WIDE_SR = __import__("os").environ.get("DGNN_WIDE_SR", "1") != "0"

@@ -473,6 +473,7 @@ class PartitionedScene:
     @torch.no_grad()
     def inference_layer(self, net, rebuild_plan: bool = True) -> torch.Tensor:
         """Partitioned equivalent of SurfaceNet.inference_layer: logits [n_own, 2] of the owned tets."""
+        _refuse_graph_layer_norm(net)
         n_src = self.n_own + self.n_halo
         x = self.x_local[:, 1:] if net.clf.regularization.cell_type else self.x_local
         x = net._storage_input(x) if hasattr(net, "_storage_input") else x
@@ -634,9 +635,18 @@ def build_self_halo_part(edge_index: np.ndarray, n: int, remote: np.ndarray) -> 
                      loc[remote], [k], [k])
 
 
+def _refuse_graph_layer_norm(net):
+    """graph LayerNorm (normalization 'l') takes ONE mean and std over all rows of a layer: a global scalar per layer, which the collective-free
+    ring forward and the per-part training forward do not exchange"""
+    if getattr(net, "norm_type", None) == "l":
+        raise NotImplementedError("PartitionedScene: normalization 'l' (graph LayerNorm) needs statistics over the whole scene per layer; "
+                                  "run the model on one GPU (SurfaceNet.inference_layer / forward)")
+
+
 def _partitioned_scene_train_forward(self, net, group=None):
     """Train-mode forward of `net` (the Static SurfaceNet) over this rank's part of the scene -> logits [n_own, out] of the owned cells with a
     backward (halo gradients return to their owners, BatchNorm statistics span the scene): see partitioned_train_forward."""
+    _refuse_graph_layer_norm(net)
     x = self.x_local[:, 1:] if net.clf.regularization.cell_type else self.x_local
     return partitioned_train_forward(self.lp, x.contiguous() if x.stride(1) != 1 else x, self.edge_attr, self.edge_index, [blk[0] for blk in net.convs],
                                      [getattr(blk[1], "module", None) if len(blk) > 1 else None for blk in net.convs],

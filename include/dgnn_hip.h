@@ -205,6 +205,30 @@ int dgnn_bn_relu_bwd(const float* x, int64_t ldx, const float* y, int64_t ldy, c
                      const float* gamma, const float* mean, const float* var, float eps, int train, int relu,
                      int64_t M, int c, float* dx, int64_t lddx, float* dgamma, float* dbeta, float* scratch,
                      void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * Graph LayerNorm (torch_geometric.nn.norm.LayerNorm, PyG 2.0.2, batch=None; surfaceNetStaticEdgeFilters.py:116-123 with
+ * normalization 'l'): ONE mean and ONE biased std over all M*c elements, out = (x - m) / (std + eps) * weight + bias.
+ * No running statistics (train = eval).  Deterministic fp64 reductions; the statistics stay on the device.
+ * ---------------------------------------------------------------------------------------------- */
+/* partial rows dgnn_graph_ln_stats writes (its `partials` hold 2 * that many doubles) */
+int64_t dgnn_graph_ln_stats_blocks(int64_t M, int c);
+/* floats of scratch for dgnn_graph_ln_relu_bwd and for the first stage of dgnn_graph_ln_finalize_fold */
+int64_t dgnn_graph_ln_scratch_elems(int64_t M, int c);
+/* standalone statistics pass over x [M, c]: partials[nblk][2] = (sum x, sum x^2) per block of rows, fp64 */
+int dgnn_graph_ln_stats(const float* x, int64_t ldx, int64_t M, int c, double* partials, void* stream);
+/* partials [nblk][2][pc] (pc = 1: dgnn_graph_ln_stats; pc = c: the colstats of dgnn_linear_fwd_x3_stats, nblk = ceil(M / 32)) ->
+ * stats[4] = (m, sigma, r = 1 / (sigma + eps), M c) and scale[c] = w r, shift[c] = b - m w r (weight / bias NULL: 1 / 0).
+ * scratch (8-byte aligned, >= 512 doubles) is used when there are many partial rows. */
+int dgnn_graph_ln_finalize_fold(const double* partials, int64_t nblk, int pc, int64_t M, int c, const float* weight, const float* bias,
+                                float eps, float* stats, float* scale, float* shift, double* scratch, void* stream);
+/* y = act((x - m) * scale + bias): the apply centres first, as PyG does (in place allowed) */
+int dgnn_graph_ln_apply(const float* x, int64_t ldx, int64_t M, int c, const float* stats, const float* scale, const float* bias, int relu,
+                        float* y, int64_t ldy, void* stream);
+/* backward of y = act(LayerNorm(x)) from the forward's stats / scale (the ReLU mask is recomputed from x, y is not read): dx (WRITTEN),
+ * dweight = sum g xhat, dbias = sum g (NULL: not stored).  scratch: dgnn_graph_ln_scratch_elems(M, c) floats. */
+int dgnn_graph_ln_relu_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* stats, const float* weight, const float* scale,
+                           const float* bias, int relu, int64_t M, int c, float* dx, int64_t lddx, float* dweight, float* dbias, float* scratch,
+                           void* stream);
 /* out[c] (+)= sum over rows (bias gradients) */
 /* dgnn_bn_relu_bwd in two halves, for batch statistics that span several ranks (a scene cut across GPUs; SURVEY 8e: the [2 C] all-reduce per layer):
  * _sums: sums[0..c) = sum g, sums[c..2c) = sum g * x_hat over the M local rows (g = dy behind the ReLU mask; also this rank's dbeta / dgamma terms);
