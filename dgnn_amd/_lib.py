@@ -85,6 +85,8 @@ SIGNATURES = {
     "dgnn_compact_scratch_elems": (i64, [i64]),
     "dgnn_compact_i32": (i32, [vp, vp, i32, i64, vp, vp, vp, vp]),
     "dgnn_interface_flags": (i32, [vp, vp, i64, vp, vp]),
+    "dgnn_graph_cut_scratch_bytes": (i64, [i64, i64]),
+    "dgnn_graph_cut_binary": (i32, [vp, i64, i64, vp, i64, f32, i32, vp, vp, vp, vp, vp, vp]),
     "dgnn_khop_scratch_elems": (i64, [i64, i64]),
     "dgnn_khop_count": (i32, [vp, vp, i64, i32, vp, vp, vp, vp]),
     "dgnn_khop_expand": (i32, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1,7 +1,7 @@
 // Logits -> labels -> interface facets on the device: the step right after the hot path,
 // reference processing/generate_mesh.py:75 (labels of the finite cells) and :93-105 (two interpreter loops over
 // all facets: infinite neighbour = one extra OUTSIDE cell; a facet is on the surface iff its two cells differ).
-// The optional integer graph cut between the two (:84-91, third-party gco) stays on the CPU.
+// The optional integer graph cut between the two (:84-91, third-party gco) is graphcut.hip.
 #include "common.h"
 
 int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* sums_scratch, hipStream_t stream);  // plan.hip

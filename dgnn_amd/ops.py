@@ -1570,3 +1570,54 @@ def static_train_bwd(x0, layers, buf, meta_widths, dy, keep=None):
     if keep is not None:
         keep["static_bwd"] = (sig, sizes, flat, grads)
     return grads
+
+
+# ---- graph cut (reference processing/generate_mesh.py:15-58) ----------------------------------------------------------------------
+def potts_weight(binary_weight) -> int:
+    """The Potts weight as the reference's `np.ones(n, int64) * binary_weight` reaches gco's integer costs (truncation); ValueError when
+    it is negative (not a cut problem) or does not fit int32."""
+    import numpy as np
+
+    bw = float(binary_weight)
+    if not np.isfinite(bw) or bw < 0:
+        raise ValueError("graph cut: binary_weight %r must be finite and >= 0" % (binary_weight,))
+    w = int(np.trunc(bw))
+    if w > 0x7FFFFFFF:
+        raise ValueError("graph cut: binary_weight %r does not fit int32" % (binary_weight,))
+    return w
+
+
+@on_device_of
+def binary_graph_cut(logits, edges, unary_weight, binary_weight, return_stats=False):
+    """Exact minimum of the reference's two-label graph-cut energy (dgnn_graph_cut_binary):
+    D_i(0) = round(logits[i,1] * uw), D_i(1) = round(logits[i,0] * uw) in fp32, Potts weight `binary_weight` per row of `edges`.
+    logits fp32 [n, 2], edges int [F, 2] (tensors or arrays; CPU inputs are moved to the GPU).
+    -> (labels int32 [n] on the GPU: 0 inside / 1 outside, the minimiser with the fewest outside cells; energy int; max-flow value int)
+    (+ {"steps", "relabels"} with return_stats).  Raises ValueError for a negative weight, DgnnError for an edge id outside [0, n),
+    non-finite logits, |cost| >= 2^30 or capacities that overflow int32."""
+    import ctypes as C
+
+    w = potts_weight(binary_weight)
+    dev = logits.device if isinstance(logits, torch.Tensor) and logits.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    logits = torch.as_tensor(logits).to(dev, torch.float32)
+    edges = torch.as_tensor(edges).to(dev, torch.int32).contiguous()
+    if logits.dim() != 2 or logits.size(1) != 2:
+        raise ValueError("logits must be [n, 2], got %s" % (tuple(logits.shape),))
+    if edges.numel() == 0:
+        edges = edges.reshape(0, 2)
+    if edges.dim() != 2 or edges.size(1) != 2:
+        raise ValueError("edges must be [F, 2], got %s" % (tuple(edges.shape),))
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    n, f = logits.size(0), edges.size(0)
+    labels = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    out64 = torch.zeros(2, dtype=torch.int64, device=dev)
+    stats = torch.zeros(2, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib().dgnn_graph_cut_scratch_bytes(n, f)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_graph_cut_binary(ptr(logits), max(_ld(logits), 2) if n else 2, n, ptr(edges), f, float(unary_weight), w, ptr(labels),
+                                      ptr(out64), C.c_void_p(out64.data_ptr() + 8), ptr(stats), ptr(scratch), stream_ptr()), "dgnn_graph_cut_binary")
+    energy, flow = (int(v) for v in out64.cpu())
+    if return_stats:
+        s = stats.cpu()
+        return labels, energy, flow, {"steps": int(s[0]), "relabels": int(s[1])}
+    return labels, energy, flow

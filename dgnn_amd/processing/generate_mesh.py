@@ -3,9 +3,9 @@
 ``extract_interface(prediction, infinite, nfacets)`` reproduces what ``generate`` does between the network output
 and the trimesh call: labels of the finite cells (:75), the infinite cell appended as OUTSIDE (:93-99) and the list
 of facets whose two cells carry different labels (:101-105) -- two Python loops over all facets in the reference,
-three small kernels here.  The optional integer alpha-expansion graph cut (:15-58, third-party ``gco``) and the
-``trimesh`` mesh object are CPU-side third-party steps and stay outside; ``labels`` can be replaced by the
-graph-cut labels before ``interface_from_labels``.
+three small kernels here.  The optional integer alpha-expansion graph cut (:15-58, third-party ``gco``) runs exactly on
+the device with ``graph_cut.solver: gpu`` (``graph_cut_gpu``); the ``trimesh`` mesh object stays a CPU-side third-party
+step.  ``labels`` can be replaced by the graph-cut labels before ``interface_from_labels``.
 """
 from __future__ import annotations
 
@@ -100,6 +100,27 @@ def graph_cut(labels, prediction, edges, clf):
     return gc.get_labels()
 
 
+def graph_cut_gpu(labels, prediction, edges, clf):
+    """`graph_cut` solved exactly on the device (dgnn_graph_cut_binary): same arguments, same energy.  With two labels and a
+    non-negative Potts weight the energy is submodular and gco's converged alpha-expansion is a global minimum, so the minimum cut
+    reaches the energy gco reaches; where several labellings share it, the one with the fewest outside cells is returned.
+    `prediction` fp32 [Nf, 2] logits of the finite cells (a GPU tensor is read in place), `edges` [F, 2] finite-finite facets,
+    clf.graph_cut.unary_weight / binary_weight as in the reference.  `labels` is only checked for its length (the solver needs no
+    initial labelling).  Returns what it was given: an ndarray of int32 labels for an ndarray / list `labels` (as gco's
+    get_labels), an int32 tensor on the device for a tensor."""
+    from ..ops import binary_graph_cut
+
+    n = len(labels)
+    if n != len(prediction):
+        raise ValueError("graph cut: %d labels for %d finite cells" % (n, len(prediction)))
+    if not isinstance(prediction, torch.Tensor):
+        prediction = torch.from_numpy(np.ascontiguousarray(prediction, dtype=np.float32))
+    if not isinstance(edges, torch.Tensor):
+        edges = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.int32))
+    lab, _, _ = binary_graph_cut(prediction, edges, clf.graph_cut.unary_weight, clf.graph_cut.binary_weight)
+    return lab if isinstance(labels, torch.Tensor) else lab.cpu().numpy()
+
+
 def generate(data, prediction, clf):
     """Same signature and return value as the reference's processing/generate_mesh.py:61 ``generate(data, prediction, clf)``
     -> ``(mesh, eval_dict)``; what runs where:
@@ -107,8 +128,9 @@ def generate(data, prediction, clf):
     * labels of the finite cells (``log_softmax(prediction[infinite == 0]).argmax(1)``, :75) and the interface facets
       (``labels[f0] != labels[f1]`` over all facets with the infinite cell = outside, :93-105 -- two nested Python loops in
       the reference) run on the GPU (dgnn_argmax_rows / dgnn_interface_flags / dgnn_compact_i32); integer results, identical;
-    * the optional graph cut (``clf.temp.graph_cut``) is the reference's CPU solver when `gco` imports, otherwise the raw
-      labels are kept with the reference's warning;
+    * the optional graph cut (``clf.temp.graph_cut``): with ``clf.graph_cut.solver == "gpu"`` the exact device solver
+      (graph_cut_gpu, on the device logits); otherwise the reference's CPU solver when `gco` imports.  Either way a failure keeps
+      the raw labels with the reference's warning;
     * the mesh object is a trimesh.Trimesh (``process=True``, optional fix_normals) when trimesh imports, else an
       InterfaceMesh with the same vertices / faces and an ``export``; the evaluation metrics (watertight / iou / chamfer,
       :115-163) need trimesh + utils/libmesh and are computed only when those import -- otherwise eval_dict stays empty.
@@ -129,9 +151,13 @@ def generate(data, prediction, clf):
     if getattr(clf.temp, "graph_cut", None):
         mask = (nfacets >= 0).all(axis=1)
         try:
-            finite = (infinite == 0).to(prediction.device)
-            lab = graph_cut(labels_dev.cpu().numpy(), prediction[finite].detach().cpu().numpy(), nfacets[mask], clf)
-            labels_dev = torch.as_tensor(np.asarray(lab), dtype=torch.int32, device=dev)
+            if getattr(getattr(clf, "graph_cut", None), "solver", None) == "gpu":
+                finite = (infinite == 0).to(dev)
+                labels_dev = graph_cut_gpu(labels_dev, pred_dev.detach()[finite], torch.from_numpy(nfacets[mask]), clf)
+            else:
+                finite = (infinite == 0).to(prediction.device)
+                lab = graph_cut(labels_dev.cpu().numpy(), prediction[finite].detach().cpu().numpy(), nfacets[mask], clf)
+                labels_dev = torch.as_tensor(np.asarray(lab), dtype=torch.int32, device=dev)
         except Exception:  # noqa: BLE001  (the reference: bare except, :88-91)
             print("WARNING: Graph cut for {} didn't work. Using raw predictions for mesh generation.".format(data.filename))
     interfaces = interface_from_labels(labels_dev, torch.from_numpy(nfacets)).cpu().numpy()

@@ -744,12 +744,36 @@ int dgnn_khop_blocks_regular_wait(void* job, int hops, int64_t* counts_out);
  *   dgnn_argmax_rows     labels[i] = argmax_c logits[i,c]             (log_softmax(...).argmax(1), ties -> 0)
  *   dgnn_compact_i32     order-preserving stream compaction (finite-cell labels; interface facet ids)
  *   dgnn_interface_flags flags[f] = label(nfacets[f,0]) != label(nfacets[f,1]), cell -1 = outside
+ *   dgnn_graph_cut_binary the optional graph cut between the two (:84-91), exact, on the device
  * ---------------------------------------------------------------------------------------------- */
 int dgnn_argmax_rows(const float* logits, int64_t ld, int64_t n, int c, int32_t* labels, void* stream);
 int64_t dgnn_compact_scratch_elems(int64_t n);
 int dgnn_compact_i32(const int32_t* values, const int32_t* keep, int invert, int64_t n, int32_t* out, int32_t* count_out,
                      int32_t* scratch, void* stream);
 int dgnn_interface_flags(const int32_t* nfacets, const int32_t* labels_finite, int64_t n_facets, int32_t* flags, void* stream);
+
+/* Exact binary graph cut of the finite cells' labels (reference processing/generate_mesh.py:15-58: gco alpha-expansion, two labels,
+ * Potts term; with two labels a converged expansion is a global minimum, so one s-t minimum cut reaches the same energy).
+ *   logits      fp32 [n, 2] (row stride ld >= 2), the finite cells in file order
+ *   edges       int32 [n_rows, 2], the facets with two finite cells; duplicate rows add up, self-loops contribute nothing
+ *   costs       D_i(0) = rint(fl(logits[i,1] * unary_weight)), D_i(1) = rint(fl(logits[i,0] * unary_weight)): the fp32 product and
+ *               half-to-even rounding of `(prediction[:, [1, 0]] * uw).round()`; label 0 = inside, 1 = outside
+ *   energy      E(l) = sum_i D_i(l_i) + binary_weight * #{rows (i, j): l_i != l_j}
+ *   labels_out  int32 [n]: the minimiser with the FEWEST outside cells (unique; ties in the unary cost resolve to inside): the nodes that
+ *               reach t in the residual graph of a maximum preflow (s -> i: max(D_i(1) - D_i(0), 0), i -> t: max(D_i(0) - D_i(1), 0),
+ *               i <-> j: binary_weight per row)
+ *   energy_out  int64 [1] E(labels_out); flow_out int64 [1] the maximum flow (E = flow + sum_i min D_i(.), checked before returning);
+ *   stats_out   int32 [2] push-relabel steps, global relabels.  All three are DEVICE pointers (NULL: not written).
+ *   scratch     dgnn_graph_cut_scratch_bytes(n, n_rows) bytes, 256-byte aligned.
+ * DGNN_E_INVALID: binary_weight < 0, an edge id outside [0, n), non-finite logits, |D_i| >= 2^30, or a node whose capacities could overflow
+ * int32 (terminal capacity + max(degree, 2) * binary_weight).  DGNN_E_UNSUPPORTED: the step / relabel cap was reached (never spins).
+ * Unlike the rest of this header the call SYNCHRONISES `stream`: after the graph is built (error check), after every few BFS levels of each
+ * global relabel (the frontier size and the stop flag are read on the host) and at the end (energy identity).  Synchronous push-relabel
+ * without atomics on the flow: labels, energy and step counts are bit-identical from run to run. */
+int64_t dgnn_graph_cut_scratch_bytes(int64_t n, int64_t n_rows);
+int dgnn_graph_cut_binary(const float* logits, int64_t ld, int64_t n, const int32_t* edges, int64_t n_rows, float unary_weight,
+                          int32_t binary_weight, int32_t* labels_out, int64_t* energy_out, int64_t* flow_out, int32_t* stats_out,
+                          void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Per-scene standardisation (reference processing/data.py:444-506 sklearn StandardScaler + :512-519
