@@ -513,6 +513,26 @@ def test_train_forward_backward_bf16_static_f3():
             continue   # biases ahead of a train-mode BatchNorm: analytically zero gradient
         cos = float((q @ r_) / (q.norm() * r_.norm()))
         assert cos > 0.995 and 0.9 < float(q.norm() / r_.norm()) < 1.1, (k, cos, float(q.norm() / r_.norm()))
+    # ... and against the storage-rounding model of this step (tests/bf16_training_model.py::static_step, fp64) on the same block.  Spread of two
+    # correct implementations of the model here (static_step in fp32 against fp64): gradients worst rms 8.6e-3, worst entry 1.25e-2 of the tensor's
+    # largest, worst row / column 6.1e-2 of the tensor's rms; logits 3.0e-3 of the largest; running buffers 8.5e-5 of their largest; the biases ahead of
+    # a BatchNorm 1.1e-5 of the largest gradient.  Leaving out one forward site family (x, w, a, z, y) moves the worst tensor by 0.064-0.10 rms.
+    from bf16_training_model import static_step
+    from helpers import kf96_state_dict
+    from test_gpu_scale import assert_grads_within_rounding_model
+    sd = {k: torch.as_tensor(v) for k, v in kf96_state_dict().items()}
+    mlogits, mgrads, mbufs = static_step(sd, (64, 128, 128, 128), d.all.x, d.all.edge_attr, d.batch_n_id, d.batch_adjs, torch.from_numpy(g["G"]))
+    dl = (logits.detach().double().cpu() - mlogits).abs()
+    assert dl.max().item() <= 2.0 ** -6 * mlogits.abs().max().item(), dl.max().item()
+    hb = dict(net.named_buffers())
+    for k, b in mbufs.items():
+        if k.endswith("num_batches_tracked"):
+            assert int(hb[k]) == int(b) == int(sd[k]) + 1, k
+        else:
+            assert (hb[k].double().cpu() - b).abs().max().item() <= 5e-4 * b.abs().max().item() + 1e-7, (k, (hb[k].double().cpu() - b).abs().max().item())
+    zero = [k for k in mgrads if k.endswith("conv.lin_j.bias") or k == "decoder.0.bias"]
+    assert_grads_within_rounding_model(mgrads, {k: p.grad for k, p in net.named_parameters()}, rms_bound=0.02, outside_per=None, cap=0.05, line_bound=0.2,
+                                       zero_keys=zero, zero_floor=1e-4)
 
 
 def test_updated_variant_bf16_forward_backward():
@@ -661,3 +681,70 @@ def test_lane_group_given_phi_backward_gives_the_bits_of_the_lane_per_channel_ke
     want = torch.zeros(n_src, c_in, device=DEV, dtype=torch.float64).index_add_(0, ei[0].to(DEV), dm * phi.double())
     tol = 2 ** -7 if dtype == torch.bfloat16 else 1e-5
     assert (dx_g.double() - want).abs().max().item() <= tol * max(1.0, want.abs().max().item())
+
+
+@pytest.mark.parametrize("M", [1, 2, 3, 257, 70001])
+@pytest.mark.parametrize("c", [28, 70, 128, 1024])
+@pytest.mark.parametrize("padded", [False, True])
+def test_bf16_batchnorm_kernels_edges_vs_fp64(M, c, padded):
+    """The bf16 BatchNorm chain of the training step (dgnn_bn_batch_stats_bf16 with the running buffers and momentum, dgnn_bn_fold,
+    dgnn_scale_shift_act_bf16, dgnn_bn_relu_bwd_bf16, dgnn_colsum_bf16) against fp64 on the bf16 rows as the kernels read them: 1 .. 70 001 rows,
+    packed or padded / strided rows (cast_to_bf16(cols_pad=...) viewed back to c columns), a constant column (variance 0), a column with mean 1e3 and
+    unit spread (E[x^2] - E[x]^2 in fp32 would lose it; the kernels sum in fp64), the unbiased running variance (n / (n - 1); one row keeps the biased
+    value, 0).  The ReLU mask of the backward is the kernel's own bf16 y, so every bound is per element and fp32-tight."""
+    from dgnn_amd import ops
+    g = torch.Generator().manual_seed(M * 7 + c)
+    x = torch.randn(M, c, generator=g) * 2 + torch.randn(c, generator=g)
+    x[:, 0] = 0.75                                              # constant column
+    if c > 1:
+        x[:, 1] = 1e3 + torch.randn(M, generator=g)             # large mean, unit spread
+    dy = torch.randn(M, c, generator=g)
+    gamma, beta = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.3
+    rm0, rv0 = torch.randn(c, generator=g), torch.rand(c, generator=g) + 0.5
+    momentum, eps = 0.1, 1e-5
+    pad = c + 6 if padded else None
+    xb = ops.cast_to_bf16(x.to(DEV), pad)[:, :c]
+    dyb = ops.cast_to_bf16(dy.to(DEV), pad)[:, :c]
+    assert padded == (xb.stride(0) != c)
+    X, DY = xb.double().cpu(), dyb.double().cpu()
+    rm, rv = rm0.to(DEV), rv0.to(DEV)
+    mean, var = ops.bn_batch_stats(xb, rm, rv, momentum)
+    m64 = X.mean(0)
+    v64 = (X - m64).pow(2).mean(0)
+    f32 = 2.0 ** -23
+    assert ((mean.double().cpu() - m64).abs() <= 2 * f32 * X.abs().max(0).values).all()
+    assert ((var.double().cpu() - v64).abs() <= 4 * f32 * v64 + 1e-12 * X.pow(2).max(0).values).all()
+    assert var[0].item() == 0.0 and abs(var[1].item() - v64[1].item()) <= 1e-5 * v64[1].item() + 1e-30
+    unb = v64 * (M / (M - 1)) if M > 1 else v64
+    erm = (1 - momentum) * rm0.double() + momentum * m64
+    erv = (1 - momentum) * rv0.double() + momentum * unb
+    assert ((rm.double().cpu() - erm).abs() <= 4 * f32 * (rm0.double().abs() + m64.abs())).all()
+    assert ((rv.double().cpu() - erv).abs() <= 4 * f32 * (rv0.double().abs() + unb)).all()
+    scale, shift = ops.bn_fold(gamma.to(DEV), beta.to(DEV), mean, var, eps)
+    inv = 1.0 / torch.sqrt(v64 + eps)
+    s64, t64 = gamma.double() * inv, beta.double() - m64 * gamma.double() * inv
+    assert ((scale.double().cpu() - s64).abs() <= 8 * f32 * s64.abs()).all()
+    y = ops.scale_shift_act(xb, scale, shift, True)
+    assert y.dtype == BF and y.shape == (M, c)
+    # y against fp64 of the same fold: within one bf16 step of the value (rounding) plus the fold's fp32 error around zero / the mean-1e3 column
+    S, T = scale.double().cpu(), shift.double().cpu()
+    y64 = torch.relu(X * S + T)
+    Y = y.double().cpu()
+    assert ((Y - y64).abs() <= EPS * y64 + 4 * f32 * (X.abs() * S.abs() + T.abs())).all()      # (round to 8 significant bits: <= 2^-8 of the value)
+    # backward, mask from the kernel's y
+    dx, dgamma, dbeta = ops.bn_relu_bwd(xb, y, dyb, gamma.to(DEV), mean, var, eps, True, True)
+    gm = DY * (Y > 0)
+    Mv, Vv = mean.double().cpu(), var.double().cpu()
+    is64 = 1.0 / torch.sqrt(Vv + eps)
+    xh = (X - Mv) * is64
+    db64, dg64 = gm.sum(0), (gm * xh).sum(0)
+    assert ((dbeta.double().cpu() - db64).abs() <= 2 * f32 * gm.abs().sum(0)).all()
+    assert ((dgamma.double().cpu() - dg64).abs() <= 8 * f32 * (gm.abs() * xh.abs()).sum(0) + 1e-30).all()
+    gs = gamma.double() * is64
+    dx64 = gs * (gm - db64 / M - xh * dg64 / M)
+    mag = gs.abs() * (gm.abs() + gm.abs().sum(0) / M + xh.abs() * (gm.abs() * xh.abs()).sum(0) / M)     # the terms and the sums' own error scales
+    DX = dx.double().cpu()
+    assert dx.dtype == BF and ((DX - dx64).abs() <= EPS * dx64.abs() + 16 * f32 * mag).all(), ((DX - dx64).abs() - EPS * dx64.abs()).max().item()
+    # column sums of bf16 rows (the biases' gradients)
+    cs = ops.colsum(dyb)
+    assert ((cs.double().cpu() - DY.sum(0)).abs() <= 2 * f32 * DY.abs().sum(0)).all()

@@ -834,7 +834,8 @@ def test_block_builder_buffer_ring_gives_the_same_training_run():
 
 def test_static_composite_layer_in_bf16_storage_matches_the_separate_calls(monkeypatch):
     """bf16 storage through dgnn_sage_layer_train_fwd_bf16 / _bwd_bf16 vs the separate bf16 Functions: identical forward; gradients at
-    bf16 resolution (the composite adds dz.Wi into dx before the rounding to bf16, the separate path after)"""
+    bf16 resolution (the composite rounds dx twice -- the aggregate backward stores it in bf16, then the dz.Wi GEMM adds its fp32 product to
+    that bf16 dx and rounds again (DGNN_LINEAR_ACCUMULATE); the separate path also rounds dz.Wi on its own before autograd adds the two)"""
     from dgnn_amd import ops
     from dgnn_amd.sampler import NeighborSampler
     from dgnn_amd.synthetic import delaunay_tet_graph, hashed_normal
