@@ -87,6 +87,13 @@ SIGNATURES = {
     "dgnn_interface_flags": (i32, [vp, vp, i64, vp, vp]),
     "dgnn_graph_cut_scratch_bytes": (i64, [i64, i64]),
     "dgnn_graph_cut_binary": (i32, [vp, i64, i64, vp, i64, f32, i32, vp, vp, vp, vp, vp, vp]),
+    "dgnn_locate_scratch_bytes": (i64, [i64]),
+    "dgnn_locate_points": (i32, [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp]),
+    "dgnn_mesh_iou_counts": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+    "dgnn_sample_faces_scratch_bytes": (i64, [i64]),
+    "dgnn_sample_faces": (i32, [vp, i64, vp, i64, vp, i64, i64, C.c_uint64, vp, vp, vp, vp, vp]),
+    "dgnn_nearest_scratch_bytes": (i64, [i64, i64]),
+    "dgnn_nearest_neighbor": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp]),
     "dgnn_khop_scratch_elems": (i64, [i64, i64]),
     "dgnn_khop_count": (i32, [vp, vp, i64, i32, vp, vp, vp, vp]),
     "dgnn_khop_expand": (i32, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -8,8 +8,9 @@ Same names, arguments and error convention (``print`` + ``sys.exit(1)`` for conf
 on the HIP kernels; the loss itself is a few elementwise ops on [batch, 2] tensors and uses torch on the GPU.
 New (no reference counterpart, single process there): ``group=`` on ``train`` / ``train_test`` = data-parallel
 replicas, one flat RCCL all-reduce of the gradients between ``backward()`` and ``step()`` (BASELINE config 5).
-Validation by mesh metrics (chamfer / iou, :355-362) needs the reference's CPU post-processing (gco, trimesh) and is used
-only when those import; the loss metric always works.  The device string is no longer hard-wired to cuda:<gpu> (:287).
+Validation by mesh metrics (chamfer / iou, :355-362) goes through ``generate``: with ``evaluation.solver: gpu`` both metrics are
+computed on the device; otherwise they need the reference's CPU post-processing (trimesh) and are computed only when it imports.
+The loss metric always works.  The device string is no longer hard-wired to cuda:<gpu> (:287).
 """
 from __future__ import annotations
 

@@ -1621,3 +1621,125 @@ def binary_graph_cut(logits, edges, unary_weight, binary_weight, return_stats=Fa
         s = stats.cpu()
         return labels, energy, flow, {"steps": int(s[0]), "relabels": int(s[1])}
     return labels, energy, flow
+
+
+# ---- mesh metrics (reference processing/generate_mesh.py:126-163, processing/evaluate_mesh.py) ----------------------------------
+def _dev_of(*xs):
+    for x in xs:
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _on(x, dev, dtype, cols=None):
+    t = torch.as_tensor(x).to(dev, dtype).contiguous()
+    if cols is not None:
+        if t.numel() == 0:
+            t = t.reshape(0, cols)
+        if t.dim() != 2 or t.size(1) != cols:
+            raise ValueError("expected [n, %d], got %s" % (cols, tuple(t.shape)))
+    return t
+
+
+@on_device_of
+def locate_points(vertices, tetrahedra, facets, nfacets, points, return_steps=False):
+    """The finite cell of `<scene>_3dt.npz` that contains each point (dgnn_locate_points): vertices fp64 [V, 3], tetrahedra int [N, 4],
+    facets int [F, 3], nfacets int [F, 2] (-1 = infinite cell), points [P, 3] (cast to fp32).  -> int32 [P] on the GPU, -1 = outside the
+    convex hull (+ the longest walk with return_steps).  Points on a shared face / vertex get the first cell of the walk that has them on
+    its boundary (include/dgnn_hip.h).  DgnnError for malformed input or a walk that hits the step cap."""
+    dev = _dev_of(points, vertices)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    fac = _on(facets, dev, torch.int32, 3)
+    nfac = _on(nfacets, dev, torch.int32, 2)
+    pts = _on(points, dev, torch.float32, 3)
+    if fac.size(0) != nfac.size(0):
+        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
+    n_p, n_c = pts.size(0), tets.size(0)
+    cells = torch.empty(max(n_p, 1), dtype=torch.int32, device=dev)[:n_p]
+    steps = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib().dgnn_locate_scratch_bytes(n_c)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_locate_points(ptr(v), v.size(0), ptr(tets), n_c, ptr(fac), ptr(nfac), fac.size(0), ptr(pts), n_p, ptr(cells), ptr(steps),
+                                   ptr(scratch), stream_ptr()), "dgnn_locate_points")
+    return (cells, int(steps.item())) if return_steps else cells
+
+
+@on_device_of
+def iou_counts(cells, labels, occ_gt):
+    """(occupancy int32 [P] on the GPU: 1 = inside = cells[i] >= 0 with labels[cells[i]] == 0; |A n B|; |A u B|) against the ground-truth
+    occupancies occ_gt [P] (non-zero = inside) (dgnn_mesh_iou_counts)."""
+    dev = _dev_of(cells, labels)
+    cells = _on(cells, dev, torch.int32)
+    labels = _on(labels, dev, torch.int32)
+    occ = _on(occ_gt, dev, torch.bool).view(torch.uint8)
+    if occ.numel() != cells.numel():
+        raise ValueError("%d occupancies for %d points" % (occ.numel(), cells.numel()))
+    n = cells.numel()
+    out = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    scratch = torch.empty(256, dtype=torch.uint8, device=dev)
+    check(lib().dgnn_mesh_iou_counts(ptr(cells), n, ptr(labels), labels.numel(), ptr(occ), ptr(out), ptr(counts), ptr(scratch), stream_ptr()),
+          "dgnn_mesh_iou_counts")
+    inter, union = (int(c) for c in counts.cpu())
+    return out, inter, union
+
+
+def mesh_iou(vertices, tetrahedra, facets, nfacets, labels, points, occ_gt):
+    """IoU of the reconstructed surface (the facets between inside (label 0) and outside cells, the infinite cell outside) with the
+    ground-truth occupancies, as compute_iou computes it: float32(|A n B|) / float32(|A u B|) (nan for an empty union).  Runs on the
+    device of the first GPU tensor among labels, points, vertices.
+    -> (iou float, occupancy int32 [P] on the GPU, |A n B|, |A u B|)."""
+    import numpy as np
+
+    dev = _dev_of(labels, points, vertices)          # the work goes where the labels are (not the thread's current device)
+    cells = locate_points(vertices, tetrahedra, facets, nfacets, torch.as_tensor(points).to(dev))
+    occ, inter, union = iou_counts(cells, labels, occ_gt)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        iou = float(np.float32(inter) / np.float32(union))
+    return iou, occ, inter, union
+
+
+@on_device_of
+def sample_interface(vertices, facets, face_ids, n_samples, seed=0, return_cum=False):
+    """n_samples fp32 points [n, 3] on the GPU drawn on the faces facets[face_ids] by area (dgnn_sample_faces; the hash and the barycentric
+    map are in include/dgnn_hip.h) and the position in face_ids of each sample's face (int32).  face_ids None = every facet.  With
+    return_cum also the fp64 cumulative areas.  DgnnError when samples are asked of faces with no area."""
+    dev = _dev_of(face_ids, vertices)
+    v = _on(vertices, dev, torch.float64, 3)
+    fac = _on(facets, dev, torch.int32, 3)
+    ids = None if face_ids is None else _on(face_ids, dev, torch.int32).reshape(-1)
+    nfc = fac.size(0) if ids is None else ids.numel()
+    n = int(n_samples)
+    pts = torch.empty(max(n, 1), 3, dtype=torch.float32, device=dev)[:n]
+    face = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    cum = torch.empty(max(nfc, 1), dtype=torch.float64, device=dev)[:nfc]
+    scratch = torch.empty(int(lib().dgnn_sample_faces_scratch_bytes(nfc)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_sample_faces(ptr(v), v.size(0), ptr(fac), fac.size(0), ptr(ids), nfc, n, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(pts), ptr(face),
+                                  ptr(cum) if nfc else None, ptr(scratch), stream_ptr()), "dgnn_sample_faces")
+    return (pts, face, cum) if return_cum else (pts, face)
+
+
+@on_device_of
+def nearest_neighbor(ref, query):
+    """Exact nearest neighbour of every query point among `ref` (both cast to fp32 [n, 3]; dgnn_nearest_neighbor): (dist fp32 [Q], index
+    int32 [Q], sum of dist in fp64 in a fixed order) -- d2 = (dx*dx + dy*dy) + dz*dz in fp32, ties to the smaller index, dist = sqrtf(d2)."""
+    dev = _dev_of(query, ref)
+    r = _on(ref, dev, torch.float32, 3)
+    q = _on(query, dev, torch.float32, 3)
+    nr, nq = r.size(0), q.size(0)
+    if nr == 0:
+        raise ValueError("nearest_neighbor: the reference set is empty")
+    dist = torch.empty(max(nq, 1), dtype=torch.float32, device=dev)[:nq]
+    idx = torch.empty(max(nq, 1), dtype=torch.int32, device=dev)[:nq]
+    total = torch.zeros(1, dtype=torch.float64, device=dev)
+    scratch = torch.empty(int(lib().dgnn_nearest_scratch_bytes(nr, nq)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_nearest_neighbor(ptr(r), nr, ptr(q), nq, ptr(dist), ptr(idx), ptr(total), ptr(scratch), stream_ptr()), "dgnn_nearest_neighbor")
+    return dist, idx, float(total.item())
+
+
+def chamfer_distance(gt_points, recon_points):
+    """compute_chamfer (processing/evaluate_mesh.py): (mean NN distance gt -> recon + mean NN distance recon -> gt) / 2, each mean an fp64
+    sum in a fixed order over the fp32 distances."""
+    _, _, s1 = nearest_neighbor(recon_points, gt_points)
+    _, _, s2 = nearest_neighbor(gt_points, recon_points)
+    return 0.5 * (s1 / len(gt_points) + s2 / len(recon_points))

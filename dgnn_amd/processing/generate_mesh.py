@@ -4,8 +4,8 @@
 and the trimesh call: labels of the finite cells (:75), the infinite cell appended as OUTSIDE (:93-99) and the list
 of facets whose two cells carry different labels (:101-105) -- two Python loops over all facets in the reference,
 three small kernels here.  The optional integer alpha-expansion graph cut (:15-58, third-party ``gco``) runs exactly on
-the device with ``graph_cut.solver: gpu`` (``graph_cut_gpu``); the ``trimesh`` mesh object stays a CPU-side third-party
-step.  ``labels`` can be replaced by the graph-cut labels before ``interface_from_labels``.
+the device with ``graph_cut.solver: gpu`` (``graph_cut_gpu``), and the iou / chamfer metrics with ``evaluation.solver: gpu``
+(``iou_gpu`` / ``chamfer_gpu``); the ``trimesh`` mesh object stays a CPU-side third-party step.  ``labels`` can be replaced by the graph-cut labels before ``interface_from_labels``.
 """
 from __future__ import annotations
 
@@ -121,6 +121,49 @@ def graph_cut_gpu(labels, prediction, edges, clf):
     return lab if isinstance(labels, torch.Tensor) else lab.cpu().numpy()
 
 
+def _occupancy_file(data):
+    """The reference's lookup (:129-137): data["ioufile"] when it is set, else eval/points.npz, else eval/<id or category>/points.npz"""
+    if "ioufile" in data and data["ioufile"]:
+        return os.path.join(data.path, data["ioufile"])
+    if os.path.exists(os.path.join(data.path, "eval", "points.npz")):
+        return os.path.join(data.path, "eval", "points.npz")
+    subfolder = data['id'] if data['id'] else data['category']
+    return os.path.join(data.path, "eval", subfolder, "points.npz")
+
+
+def iou_gpu(data, mdata, labels):
+    """The reference's `iou` (:127-145) on the device: ONet's points.npz (`points`, bit-packed `occupancies`, unpacked and cut to
+    len(points)) against the labelled tetrahedralization `mdata` (`_3dt.npz`) with the finite cells' labels `labels` (0 = inside).  A
+    point is inside the reconstructed surface iff the finite cell that contains it is labelled inside; the ratio is
+    compute_iou's.  Raises on failure (`generate` turns that into the reference's warning and 0.0)."""
+    from ..ops import mesh_iou
+
+    occ = np.load(_occupancy_file(data))
+    points = np.asarray(occ["points"], dtype=np.float32)
+    gt = np.unpackbits(occ["occupancies"])[:len(points)]
+    dev = labels.device if isinstance(labels, torch.Tensor) and labels.is_cuda else None
+    if dev is not None:
+        points = torch.from_numpy(points).to(dev)
+    iou, _, _, _ = mesh_iou(mdata["vertices"], mdata["tetrahedra"], mdata["facets"], mdata["nfacets"], labels, points, gt)
+    return iou
+
+
+def chamfer_gpu(data, mdata, interfaces, clf):
+    """The reference's `chamfer` (:147-159, compute_chamfer) on the device: len(gt) points sampled on the interface facets by area
+    (seed clf.evaluation.seed, default 0) against eval/<id or category>/pointcloud.npz, exact nearest neighbours both ways.  An interface
+    without faces returns inf with a warning (the reference would crash in recon_mesh.sample).  Raises on other failures."""
+    from ..ops import chamfer_distance, sample_interface
+
+    subfolder = data['id'] if data['id'] else data['category']
+    gt_points = np.load(os.path.join(data.path, "eval", subfolder, "pointcloud.npz"))["points"].astype(np.float32)
+    if len(interfaces) == 0:
+        print("WARNING: Mesh {} has no faces; Chamfer distance set to inf".format(getattr(data, "filename", "")))
+        return float("inf")
+    seed = getattr(getattr(clf, "evaluation", None), "seed", None) or 0
+    recon_points, _ = sample_interface(mdata["vertices"], mdata["facets"], interfaces, len(gt_points), seed=seed)
+    return chamfer_distance(torch.from_numpy(gt_points).to(recon_points.device), recon_points)
+
+
 def generate(data, prediction, clf):
     """Same signature and return value as the reference's processing/generate_mesh.py:61 ``generate(data, prediction, clf)``
     -> ``(mesh, eval_dict)``; what runs where:
@@ -133,7 +176,9 @@ def generate(data, prediction, clf):
       the raw labels with the reference's warning;
     * the mesh object is a trimesh.Trimesh (``process=True``, optional fix_normals) when trimesh imports, else an
       InterfaceMesh with the same vertices / faces and an ``export``; the evaluation metrics (watertight / iou / chamfer,
-      :115-163) need trimesh + utils/libmesh and are computed only when those import -- otherwise eval_dict stays empty.
+      :115-163) need trimesh + utils/libmesh and are computed only when those import -- otherwise eval_dict stays empty;
+    * with ``clf.evaluation.solver == "gpu"`` iou and chamfer come from the device (iou_gpu / chamfer_gpu, no trimesh needed), from the
+      labels and interface facets above; the mesh object is the same.
     """
     dev = prediction.device if prediction.is_cuda else torch.device(getattr(clf.temp, "device", "cuda:0"))
     pred_dev = prediction.to(dev, torch.float32)
@@ -160,13 +205,16 @@ def generate(data, prediction, clf):
                 labels_dev = torch.as_tensor(np.asarray(lab), dtype=torch.int32, device=dev)
         except Exception:  # noqa: BLE001  (the reference: bare except, :88-91)
             print("WARNING: Graph cut for {} didn't work. Using raw predictions for mesh generation.".format(data.filename))
-    interfaces = interface_from_labels(labels_dev, torch.from_numpy(nfacets)).cpu().numpy()
+    interfaces_dev = interface_from_labels(labels_dev, torch.from_numpy(nfacets))
+    interfaces = interfaces_dev.cpu().numpy()
     faces = mdata["facets"][interfaces]
     eval_dict = dict()
     try:
         import trimesh
     except ImportError:
         trimesh = None
+    if getattr(getattr(clf, "evaluation", None), "solver", None) == "gpu":
+        return _generate_gpu_metrics(data, clf, mdata, labels_dev, interfaces_dev, faces, trimesh)
     if trimesh is None:
         wanted = [m for m in ("watertight", "iou", "chamfer") if m in (getattr(clf.temp, "metrics", None) or [])]
         if wanted:
@@ -187,3 +235,35 @@ def generate(data, prediction, clf):
         d2, _ = cKDTree(gt_points).query(recon_points)
         eval_dict["chamfer"] = 0.5 * (float(d1.mean()) + float(d2.mean()))
     return recon_mesh, eval_dict
+
+
+def _generate_gpu_metrics(data, clf, mdata, labels, interfaces, faces, trimesh):
+    """`generate`'s tail with ``evaluation.solver: gpu``: the same mesh object, iou / chamfer from iou_gpu / chamfer_gpu, watertight
+    from trimesh as before (skipped with a warning when trimesh is missing).  Failures keep the reference's warnings; a failing
+    chamfer gives inf (the reference writes its 0.0 into "iou" there)."""
+    metrics = getattr(clf.temp, "metrics", None) or []
+    if trimesh is not None:
+        mesh = trimesh.Trimesh(mdata["vertices"], faces, process=True)
+        if getattr(clf.temp, "fix_orientation", None):
+            trimesh.repair.fix_normals(mesh)
+    else:
+        mesh = InterfaceMesh(mdata["vertices"], faces)
+    eval_dict = dict()
+    if "watertight" in metrics:
+        if trimesh is not None:
+            eval_dict["watertight"] = int(mesh.is_watertight)
+        else:
+            print("WARNING: trimesh is not installed; mesh metrics {} are not computed for {}".format(["watertight"], getattr(data, "filename", "")))
+    if "iou" in metrics:
+        try:
+            eval_dict["iou"] = iou_gpu(data, mdata, labels)
+        except Exception:  # noqa: BLE001  (the reference: bare except, :142-145)
+            print("WARNING: Could not calculate IoU for mesh ", data['filename'])
+            eval_dict["iou"] = 0.0
+    if "chamfer" in metrics:
+        try:
+            eval_dict["chamfer"] = chamfer_gpu(data, mdata, interfaces, clf)
+        except Exception:  # noqa: BLE001  (the reference: bare except, :157-159)
+            print("WARNING: Could not calculate Chamfer distance for mesh ", data['filename'])
+            eval_dict["chamfer"] = float("inf")
+    return mesh, eval_dict

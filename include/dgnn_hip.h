@@ -776,6 +776,60 @@ int dgnn_graph_cut_binary(const float* logits, int64_t ld, int64_t n, const int3
                           void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh metrics of the interface surface (reference processing/generate_mesh.py:126-163, processing/evaluate_mesh.py compute_iou /
+ * compute_chamfer).  DESIGN.md section 14.
+ *
+ * dgnn_locate_points: the finite cell that contains each query point, by a walk in the tetrahedralization of `<scene>_3dt.npz`.
+ *   vertices  fp64 [n_vertices, 3]; tets int32 [n_cells, 4] (the finite cells); facets int32 [n_facets, 3] vertex ids; nfacets int32
+ *             [n_facets, 2] the two cells of each facet, -1 = the infinite cell.  Every face of every cell must have its facet.
+ *   points    fp32 [n_points, 3]; cell_out int32 [n_points]: a cell whose four orientation signs are >= 0 (see below), -1 = outside the
+ *             convex hull.  steps_out: DEVICE int32 [1], the longest walk (NULL: not written).
+ *   rule      orientations are det[b - a, c - a, p - a] in fp64 with (a, b, c) the facet's vertices in ascending id order, so the two
+ *             cells of a facet see one number with opposite signs.  The walk starts at the lowest-id cell whose centroid bins with the
+ *             point (uniform grid of about n_cells / 2 bins over the vertices' box; an empty bin takes the start of the nearest non-empty
+ *             bin along x, ties to the lower index, then of the nearest filled one along y, then along z), accepts the first cell on its path whose four signs are >= 0, and otherwise steps across the
+ *             lowest-k face (opposite tets[c][k]) whose sign is < 0.  A point on a shared face or vertex is given the first cell on that
+ *             path that has it on its boundary.  Deterministic.
+ *   scratch   dgnn_locate_scratch_bytes(n_cells) bytes, 256-byte aligned.
+ * DGNN_E_INVALID: a vertex / cell id out of range, non-finite vertices or points, or facets / nfacets that do not describe the tets' faces
+ * (a facet whose vertices are not three of a listed cell's, a face without a facet, a neighbour that does not point back).
+ * DGNN_E_UNSUPPORTED: a walk reached 65536 steps (it never spins).  SYNCHRONISES `stream` three times (input check, table check, end).
+ *
+ * dgnn_mesh_iou_counts: occ_out[i] = (cells[i] in [0, n_cells) and labels[cells[i]] == 0) (0 = inside; NULL: not written);
+ *   counts_out DEVICE int64 [2] = (|A n B|, |A u B|) with A = occ_out, B = occ_gt[i] != 0 (uint8).  scratch: 256 bytes.  Asynchronous.
+ *
+ * dgnn_sample_faces: n_samples points on the faces face_ids[0 .. n_faces) of `facets` (face_ids NULL: facets 0 .. n_faces), chosen by area:
+ *   area_j = 0.5 |(b - a) x (c - a)| (fp64), cum = their inclusive sum in a fixed order (cumarea_out: DEVICE fp64 [n_faces], NULL = kept in
+ *   scratch).  Sample i draws r_k = mm_hash(seed, 3 i + k + 1), k = 0, 1, 2, with
+ *       mm_hash(s, c): z = s + c * 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *                      return z ^ (z >> 31)                                          (uint64 arithmetic, wrapping)
+ *   x = ((r_0 >> 11) + 1) 2^-53 * cum[n_faces - 1]; face j = the first with cum[j] >= x (zero-area faces get no samples);
+ *   u = (r_1 >> 11) 2^-53, v = (r_2 >> 11) 2^-53, both replaced by 1 - u, 1 - v when u + v > 1;
+ *   point = float((u (b - a) + v (c - a)) + a) per coordinate in fp64.  face_out int32 [n_samples] = j (NULL: not written).
+ *   scratch: dgnn_sample_faces_scratch_bytes(n_faces) bytes.  DGNN_E_INVALID: ids out of range, non-finite areas, or samples asked of a
+ *   total area of 0.  SYNCHRONISES `stream` once (after the areas).
+ *
+ * dgnn_nearest_neighbor: for every query point the nearest reference point (both fp32 [n, 3]): idx_out int32 = the smallest index among
+ *   the minimisers of d2 = (dx*dx + dy*dy) + dz*dz (fp32, no contraction), dist_out fp32 = sqrtf(d2).  sum_out: DEVICE fp64 [1], the sum of
+ *   dist_out in a fixed order (NULL: not computed).  n_ref >= 1.  scratch: dgnn_nearest_scratch_bytes(n_ref, n_query) bytes.
+ *   DGNN_E_INVALID: non-finite coordinates.  SYNCHRONISES `stream` twice (the reference set's box, the end).
+ * All four are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_locate_scratch_bytes(int64_t n_cells);
+int dgnn_locate_points(const double* vertices, int64_t n_vertices, const int32_t* tets, int64_t n_cells, const int32_t* facets,
+                       const int32_t* nfacets, int64_t n_facets, const float* points, int64_t n_points, int32_t* cell_out, int32_t* steps_out,
+                       void* scratch, void* stream);
+int dgnn_mesh_iou_counts(const int32_t* cells, int64_t n_points, const int32_t* labels, int64_t n_cells, const uint8_t* occ_gt, int32_t* occ_out,
+                         int64_t* counts_out, void* scratch, void* stream);
+int64_t dgnn_sample_faces_scratch_bytes(int64_t n_faces);
+int dgnn_sample_faces(const double* vertices, int64_t n_vertices, const int32_t* facets, int64_t n_facets, const int32_t* face_ids,
+                      int64_t n_faces, int64_t n_samples, uint64_t seed, float* points_out, int32_t* face_out, double* cumarea_out,
+                      void* scratch, void* stream);
+int64_t dgnn_nearest_scratch_bytes(int64_t n_ref, int64_t n_query);
+int dgnn_nearest_neighbor(const float* ref, int64_t n_ref, const float* query, int64_t n_query, float* dist_out, int32_t* idx_out,
+                          double* sum_out, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-scene standardisation (reference processing/data.py:444-506 sklearn StandardScaler + :512-519
  * float32 cast): out[i,c] = float((x[i,c] - mean_c) / std_c) for c >= c_first, plain cast for c < c_first;
  * fp64 statistics (population variance, zero scale -> 1).  scratch: dgnn_standardize_scratch_doubles(c) doubles.
