@@ -94,6 +94,12 @@ SIGNATURES = {
     "dgnn_sample_faces": (i32, [vp, i64, vp, i64, vp, i64, i64, C.c_uint64, vp, vp, vp, vp, vp]),
     "dgnn_nearest_scratch_bytes": (i64, [i64, i64]),
     "dgnn_nearest_neighbor": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+    "dgnn_orient_interface_scratch_bytes": (i64, []),
+    "dgnn_orient_interface": (i32, [vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
+    "dgnn_compact_vertices_scratch_bytes": (i64, [i64]),
+    "dgnn_compact_vertices": (i32, [vp, i64, i64, vp, vp, vp, vp, vp]),
+    "dgnn_mesh_topology_scratch_bytes": (i64, [i64, i64]),
+    "dgnn_mesh_topology": (i32, [vp, i64, i64, vp, vp, vp]),
     "dgnn_khop_scratch_elems": (i64, [i64, i64]),
     "dgnn_khop_count": (i32, [vp, vp, i64, i32, vp, vp, vp, vp]),
     "dgnn_khop_expand": (i32, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -1,0 +1,383 @@
+// The mesh `generate` returns (reference processing/generate_mesh.py:107-124: trimesh.Trimesh(process=True), fix_normals, Open3D's
+// is_watertight), built on the device.  DESIGN §15.
+//
+//   orient     every interface facet wound so that its normal points away from its inside cell: the exact sign of
+//              det[b - a, c - a, d - a] for the inside cell's opposite vertex d (exact_orient.h), the outside cell's when the inside
+//              cell is flat, the stored winding (counted) when both are flat or the outside cell is the infinite one.  One thread per facet.
+//   compact    the referenced vertices in ascending id (flags, then dgnn_compact_i32) and the faces renumbered onto them.
+//   topology   edge counts from the sorted undirected edge keys (one thread per run of equal keys); vertex fans from the sorted
+//              (vertex, link vertex) keys of every face corner: corners that share a key are joined in a union-find (hooking the larger
+//              root under the smaller by compare-and-swap), and a vertex is non-manifold when its corners keep two or more roots.
+//              Integer sums only: the counts do not depend on the schedule.
+#include "common.h"
+#include "exact_orient.h"
+
+int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* sums_scratch, hipStream_t stream);   // plan.hip
+int64_t dgnn_radix_sort_hist_elems(int64_t n);                                                                       // reorder.hip
+int dgnn_radix_sort_u64_i32(uint64_t* const keys[2], int32_t* const vals[2], int64_t n, int bits, int32_t* hist, int32_t* scanned, int32_t* sums,
+                            hipStream_t stream, int* cur);
+
+namespace {
+
+using dgnn_exact::V3;
+
+constexpr int MT_THREADS = 256;
+// status bits
+constexpr int32_t MT_BAD_ID = 1, MT_NONFINITE = 2, MT_NOT_FACE = 4, MT_NOT_INTERFACE = 8, MT_RANGE = 16, MT_DEGENERATE = 32;
+
+struct MtState {
+    int32_t err, exact_used, pad[2];
+    unsigned long long undetermined;
+};
+
+dim3 mt_grid(int64_t items) { return dim3(dgnn_grid_cap(dgnn_cdiv(items > 0 ? items : 1, MT_THREADS))); }
+
+__device__ __forceinline__ V3 ldv(const double* v, int32_t i) { return V3{v[3 * (int64_t)i], v[3 * (int64_t)i + 1], v[3 * (int64_t)i + 2]}; }
+
+__device__ __forceinline__ int32_t coord_bits(const V3& p) {
+    int32_t e = 0;
+    const double c[3] = {p.x, p.y, p.z};
+    for (int k = 0; k < 3; ++k) {
+        if (!isfinite(c[k])) e |= MT_NONFINITE;
+        else if (!dgnn_exact::orient_coord_ok(c[k])) e |= MT_RANGE;
+    }
+    return e;
+}
+
+// the vertex of cell c that is not x, y or z; -1 when (x, y, z) is not a face of c
+__device__ __forceinline__ int32_t opposite_vertex(const int32_t* __restrict__ tets, int32_t c, int32_t x, int32_t y, int32_t z) {
+    int32_t miss = -1, hits = 0, n_miss = 0;
+    for (int k = 0; k < 4; ++k) {
+        const int32_t t = tets[4 * (int64_t)c + k];
+        if (t == x || t == y || t == z) ++hits;
+        else { miss = t; ++n_miss; }
+    }
+    return (hits == 3 && n_miss == 1) ? miss : -1;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// ---- orientation -------------------------------------------------------------------------------------------------------------
+__global__ void k_orient(const double* __restrict__ vert, int64_t nv, const int32_t* __restrict__ tets, int64_t nc,
+                         const int32_t* __restrict__ facets, const int32_t* __restrict__ nfacets, int64_t nf, const int32_t* __restrict__ labels,
+                         const int32_t* __restrict__ ids, int64_t n, int orient, int32_t* __restrict__ out, MtState* st) {
+    unsigned long long n_und = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t f = ids[i];
+        int32_t err = 0, und = 0, used = 0;
+        int32_t x = 0, y = 0, z = 0;
+        if (f < 0 || f >= nf) err = MT_BAD_ID;
+        else {
+            x = facets[3 * (int64_t)f];
+            y = facets[3 * (int64_t)f + 1];
+            z = facets[3 * (int64_t)f + 2];
+            const int32_t c0 = nfacets[2 * (int64_t)f], c1 = nfacets[2 * (int64_t)f + 1];
+            if (x < 0 || x >= nv || y < 0 || y >= nv || z < 0 || z >= nv || c0 < -1 || c0 >= nc || c1 < -1 || c1 >= nc) err = MT_BAD_ID;
+            else {
+                const bool in0 = c0 >= 0 && labels[c0] == 0, in1 = c1 >= 0 && labels[c1] == 0;   // -1 = the infinite cell = outside
+                const int32_t ci = in0 ? c0 : c1, co = in0 ? c1 : c0;
+                int32_t d_in = -1, d_out = -1;
+                if (in0 == in1) err = MT_NOT_INTERFACE;
+                else if ((d_in = opposite_vertex(tets, ci, x, y, z)) < 0 || (co >= 0 && (d_out = opposite_vertex(tets, co, x, y, z)) < 0)) err = MT_NOT_FACE;
+                else if (d_in >= nv || d_out >= nv) err = MT_BAD_ID;
+                else if (orient) {
+                    const V3 a = ldv(vert, x), b = ldv(vert, y), c = ldv(vert, z), din = ldv(vert, d_in);
+                    err = coord_bits(a) | coord_bits(b) | coord_bits(c) | coord_bits(din);
+                    if (co >= 0) err |= coord_bits(ldv(vert, d_out));
+                    if (!err) {
+                        int s = dgnn_exact::orient_sign(a, b, c, din, &used);
+                        if (s == 0 && co >= 0) s = -dgnn_exact::orient_sign(a, b, c, ldv(vert, d_out), &used);
+                        if (s > 0) { const int32_t t = y; y = z; z = t; }
+                        und = s == 0;
+                    }
+                }
+            }
+        }
+        if (err) atomicOr(&st->err, err);
+        if (used) atomicOr(&st->exact_used, 1);
+        n_und += und;
+        out[3 * i] = x;
+        out[3 * i + 1] = y;
+        out[3 * i + 2] = z;
+    }
+    n_und = wave_sum_u64(n_und);   // every lane is here: the loop has ended for all of them
+    if (lane_id() == 0 && n_und) atomicAdd(&st->undetermined, n_und);
+}
+
+// ---- vertex compaction ---------------------------------------------------------------------------------------------------------
+__global__ void k_mark_vertices(const int32_t* __restrict__ faces, int64_t n3, int64_t nv, int32_t* __restrict__ flags, MtState* st) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t v = faces[i];
+        if (v < 0 || v >= nv) atomicOr(&st->err, MT_BAD_ID);
+        else flags[v] = 1;   // every writer stores the same value
+    }
+}
+
+__global__ void k_new_ids(const int32_t* __restrict__ kept, const int32_t* __restrict__ n_kept, int32_t* __restrict__ new_id) {
+    const int64_t m = *n_kept;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) new_id[kept[j]] = (int32_t)j;
+}
+
+__global__ void k_renumber(const int32_t* __restrict__ faces, int64_t n3, const int32_t* __restrict__ new_id, int32_t* __restrict__ out) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x) out[i] = new_id[faces[i]];
+}
+
+// ---- topology ------------------------------------------------------------------------------------------------------------------
+__global__ void k_check_faces(const int32_t* __restrict__ faces, int64_t n, int64_t nv, MtState* st) {
+    for (int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; f < n; f += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+        if (a < 0 || a >= nv || b < 0 || b >= nv || c < 0 || c >= nv) atomicOr(&st->err, MT_BAD_ID);
+        else if (a == b || b == c || a == c) atomicOr(&st->err, MT_DEGENERATE);
+    }
+}
+
+// edge e = 3 f + k runs from corner k to corner k + 1 of face f: key (min, max), value +1 when it runs from min to max, else -1
+__global__ void k_edge_keys(const int32_t* __restrict__ faces, int64_t n3, int vb, uint64_t* __restrict__ keys, int32_t* __restrict__ vals) {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n3; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t f = e / 3;
+        const int k = (int)(e - 3 * f);
+        const uint32_t u = (uint32_t)faces[3 * f + k], v = (uint32_t)faces[3 * f + (k + 1) % 3];
+        const uint32_t lo = u < v ? u : v, hi = u < v ? v : u;
+        keys[e] = ((uint64_t)lo << vb) | hi;
+        vals[e] = u < v ? 1 : -1;
+    }
+}
+
+// one thread per run of equal keys (its first element): faces on the edge = run length, directed balance = sum of the values
+__global__ void k_edge_runs(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, int64_t n, long long* __restrict__ counts) {
+    unsigned long long edges = 0, boundary = 0, nonmanifold = 0, mismatch = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i > 0 && keys[i - 1] == keys[i]) continue;
+        int64_t len = 0, bal = 0;
+        for (int64_t j = i; j < n && keys[j] == keys[i]; ++j) { ++len; bal += vals[j]; }
+        ++edges;
+        boundary += len == 1;
+        nonmanifold += len >= 3;
+        mismatch += bal != 0;
+    }
+    edges = wave_sum_u64(edges);
+    boundary = wave_sum_u64(boundary);
+    nonmanifold = wave_sum_u64(nonmanifold);
+    mismatch = wave_sum_u64(mismatch);
+    if (lane_id() == 0) {
+        if (edges) atomicAdd((unsigned long long*)&counts[0], edges);
+        if (boundary) atomicAdd((unsigned long long*)&counts[1], boundary);
+        if (nonmanifold) atomicAdd((unsigned long long*)&counts[2], nonmanifold);
+        if (mismatch) atomicAdd((unsigned long long*)&counts[4], mismatch);
+    }
+}
+
+// corner c = 3 f + k (vertex v = faces[c]) gives keys (v, x) and (v, y) for the face's two other vertices x, y; value c.  parent[c] = c.
+__global__ void k_link_keys(const int32_t* __restrict__ faces, int64_t n3, int vb, uint64_t* __restrict__ keys, int32_t* __restrict__ vals,
+                            int32_t* __restrict__ parent) {
+    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < n3; c += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t f = c / 3;
+        const int k = (int)(c - 3 * f);
+        const uint64_t v = (uint32_t)faces[c], x = (uint32_t)faces[3 * f + (k + 1) % 3], y = (uint32_t)faces[3 * f + (k + 2) % 3];
+        keys[2 * c] = (v << vb) | x;
+        keys[2 * c + 1] = (v << vb) | y;
+        vals[2 * c] = vals[2 * c + 1] = (int32_t)c;
+        parent[c] = (int32_t)c;
+    }
+}
+
+__device__ __forceinline__ int32_t uf_load(int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// root of x (parent pointers only ever move to an ancestor: path halving is a benign race)
+__device__ __forceinline__ int32_t uf_find(int32_t* parent, int32_t x) {
+    for (;;) {
+        const int32_t p = uf_load(parent + x);
+        if (p == x) return x;
+        const int32_t g = uf_load(parent + p);
+        if (g != p) __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = p;
+    }
+}
+
+// joins the sets of a and b: the larger root is hooked under the smaller one; a failed compare-and-swap (the root was hooked meanwhile) retries
+__device__ __forceinline__ void uf_union(int32_t* parent, int32_t a, int32_t b) {
+    for (;;) {
+        a = uf_find(parent, a);
+        b = uf_find(parent, b);
+        if (a == b) return;
+        if (a < b) { const int32_t t = a; a = b; b = t; }
+        int32_t expected = a;
+        if (__hip_atomic_compare_exchange_strong(parent + a, &expected, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    }
+}
+
+// corners with equal (v, x) keys share the edge (v, x) at v: join each with its predecessor in the sorted order
+__global__ void k_link_union(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals, int64_t n, int32_t* parent) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        if (i > 0 && keys[i - 1] == keys[i]) uf_union(parent, vals[i - 1], vals[i]);
+}
+
+// after every union: one root per fan; roots[v] = number of fans of v
+__global__ void k_fan_roots(const int32_t* __restrict__ faces, const int32_t* __restrict__ parent, int64_t n3, int32_t* __restrict__ roots) {
+    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < n3; c += (int64_t)gridDim.x * blockDim.x)
+        if (parent[c] == (int32_t)c) atomicAdd(roots + faces[c], 1);
+}
+
+__global__ void k_fan_count(const int32_t* __restrict__ roots, int64_t nv, long long* __restrict__ counts) {
+    unsigned long long bad = 0;
+    for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < nv; v += (int64_t)gridDim.x * blockDim.x) bad += roots[v] >= 2;
+    bad = wave_sum_u64(bad);
+    if (lane_id() == 0 && bad) atomicAdd((unsigned long long*)&counts[3], bad);
+}
+
+// ---- scratch layouts, status ---------------------------------------------------------------------------------------------------
+struct Take {
+    char* p;
+    int64_t off;
+    template <typename T>
+    T* take(int64_t elems) {
+        T* q = (T*)(p ? p + off : nullptr);
+        off += (((elems > 0 ? elems : 1) * (int64_t)sizeof(T) + 255) / 256) * 256;
+        return q;
+    }
+};
+
+struct CompactLayout { MtState* st; int32_t *flags, *new_id, *cscratch; int64_t bytes; };
+CompactLayout compact_layout(void* base, int64_t nv) {
+    Take t{(char*)base, 256};
+    CompactLayout L{};
+    L.st = (MtState*)base;
+    L.flags = t.take<int32_t>(nv);
+    L.new_id = t.take<int32_t>(nv);
+    L.cscratch = t.take<int32_t>(dgnn_compact_scratch_elems(nv));
+    L.bytes = t.off;
+    return L;
+}
+
+struct TopoLayout { MtState* st; uint64_t* keys[2]; int32_t *vals[2], *hist, *scanned, *sums, *parent, *roots; int64_t bytes; };
+TopoLayout topo_layout(void* base, int64_t nfc, int64_t nv) {
+    Take t{(char*)base, 256};
+    TopoLayout L{};
+    const int64_t m = 6 * nfc;   // link keys; the 3 nfc edge keys use the front
+    const int64_t h = dgnn_radix_sort_hist_elems(m);
+    L.st = (MtState*)base;
+    L.keys[0] = t.take<uint64_t>(m);
+    L.keys[1] = t.take<uint64_t>(m);
+    L.vals[0] = t.take<int32_t>(m);
+    L.vals[1] = t.take<int32_t>(m);
+    L.hist = t.take<int32_t>(h);
+    L.scanned = t.take<int32_t>(h);
+    L.sums = t.take<int32_t>(dgnn_cdiv(h, 2048) + 4);
+    L.parent = t.take<int32_t>(3 * nfc);
+    L.roots = t.take<int32_t>(nv);
+    L.bytes = t.off;
+    return L;
+}
+
+int mt_read_status(MtState* hs, const MtState* st, hipStream_t stream, const char* what) {
+    int rc = dgnn_check_launch(what);
+    if (rc) return rc;
+    if (hipMemcpyAsync(hs, st, sizeof(MtState), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+        dgnn_set_error("%s: %s", what, hipGetErrorString(hipGetLastError()));
+        return DGNN_E_LAUNCH;
+    }
+    if (!hs->err) return DGNN_OK;
+    const int32_t e = hs->err;
+    dgnn_set_error("%s: %s%s%s%s%s%s", what, e & MT_BAD_ID ? "an id out of range; " : "", e & MT_NONFINITE ? "non-finite coordinates; " : "",
+                   e & MT_NOT_FACE ? "a facet that is not a face of the cell nfacets names; " : "",
+                   e & MT_NOT_INTERFACE ? "a facet that does not separate an inside cell from an outside one; " : "",
+                   e & MT_RANGE ? "a coordinate magnitude outside [2^-300, 2^300] (the exact predicate's range); " : "",
+                   e & MT_DEGENERATE ? "a face with a repeated vertex; " : "");
+    return e == MT_RANGE ? DGNN_E_UNSUPPORTED : DGNN_E_INVALID;
+}
+
+int key_bits(int64_t nv) {
+    int b = 1;
+    while (b < 31 && ((int64_t)1 << b) < nv) ++b;
+    return b;
+}
+
+}  // namespace
+
+// ================================================================================================================================
+extern "C" int64_t dgnn_orient_interface_scratch_bytes(void) { return 256; }
+
+extern "C" int dgnn_orient_interface(const double* vertices, int64_t n_vertices, const int32_t* tets, int64_t n_cells, const int32_t* facets,
+                                     const int32_t* nfacets, int64_t n_facets, const int32_t* labels, const int32_t* face_ids, int64_t n_faces,
+                                     int orient, int32_t* faces_out, int64_t* n_undetermined_out, int32_t* exact_used_out, void* scratch,
+                                     void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DGNN_REQUIRE(n_vertices >= 0 && n_cells >= 0 && n_facets >= 0 && n_faces >= 0 && scratch &&
+                     (n_faces == 0 || (vertices && tets && facets && nfacets && labels && face_ids && faces_out)),
+                 DGNN_E_INVALID, "orient_interface: bad args");
+    DGNN_REQUIRE(n_cells < INT32_MAX / 4 && n_vertices < INT32_MAX && n_facets < INT32_MAX && n_faces < INT32_MAX / 3, DGNN_E_UNSUPPORTED,
+                 "orient_interface: sizes exceed the int32 indexing");
+    MtState* st = (MtState*)scratch;
+    (void)hipMemsetAsync(st, 0, sizeof(MtState), stream);
+    if (n_faces > 0)
+        hipLaunchKernelGGL(k_orient, mt_grid(n_faces), dim3(MT_THREADS), 0, stream, vertices, n_vertices, tets, n_cells, facets, nfacets, n_facets,
+                           labels, face_ids, n_faces, orient, faces_out, st);
+    if (n_undetermined_out) (void)hipMemcpyAsync(n_undetermined_out, &st->undetermined, sizeof(int64_t), hipMemcpyDeviceToDevice, stream);
+    if (exact_used_out) (void)hipMemcpyAsync(exact_used_out, &st->exact_used, sizeof(int32_t), hipMemcpyDeviceToDevice, stream);
+    MtState hs{};
+    return mt_read_status(&hs, st, stream, "orient_interface");
+}
+
+extern "C" int64_t dgnn_compact_vertices_scratch_bytes(int64_t n_vertices) {
+    if (n_vertices < 0) return 0;
+    return compact_layout(nullptr, n_vertices).bytes;
+}
+
+extern "C" int dgnn_compact_vertices(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int32_t* faces_out, int32_t* kept_out,
+                                     int32_t* n_kept_out, void* scratch, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DGNN_REQUIRE(n_faces >= 0 && n_vertices >= 0 && scratch && n_kept_out && (n_faces == 0 || (faces && faces_out)) && (n_vertices == 0 || kept_out),
+                 DGNN_E_INVALID, "compact_vertices: bad args");
+    DGNN_REQUIRE(n_faces < INT32_MAX / 3 && n_vertices < INT32_MAX, DGNN_E_UNSUPPORTED, "compact_vertices: sizes exceed the int32 indexing");
+    const CompactLayout L = compact_layout(scratch, n_vertices);
+    (void)hipMemsetAsync(L.st, 0, sizeof(MtState), stream);
+    (void)hipMemsetAsync(L.flags, 0, sizeof(int32_t) * (n_vertices > 0 ? n_vertices : 1), stream);
+    if (n_faces > 0) hipLaunchKernelGGL(k_mark_vertices, mt_grid(3 * n_faces), dim3(MT_THREADS), 0, stream, faces, 3 * n_faces, n_vertices, L.flags, L.st);
+    MtState hs{};
+    int rc = mt_read_status(&hs, L.st, stream, "compact_vertices");
+    if (rc) return rc;
+    if ((rc = dgnn_compact_i32(nullptr, L.flags, 0, n_vertices, kept_out, n_kept_out, L.cscratch, stream))) return rc;
+    if (n_faces > 0) {
+        hipLaunchKernelGGL(k_new_ids, mt_grid(n_vertices), dim3(MT_THREADS), 0, stream, kept_out, n_kept_out, L.new_id);
+        hipLaunchKernelGGL(k_renumber, mt_grid(3 * n_faces), dim3(MT_THREADS), 0, stream, faces, 3 * n_faces, L.new_id, faces_out);
+    }
+    return dgnn_check_launch("compact_vertices");
+}
+
+extern "C" int64_t dgnn_mesh_topology_scratch_bytes(int64_t n_faces, int64_t n_vertices) {
+    if (n_faces < 0 || n_vertices < 0) return 0;
+    return topo_layout(nullptr, n_faces, n_vertices).bytes;
+}
+
+extern "C" int dgnn_mesh_topology(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int64_t* counts_out, void* scratch, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DGNN_REQUIRE(n_faces >= 0 && n_vertices >= 0 && scratch && counts_out && (n_faces == 0 || faces), DGNN_E_INVALID, "mesh_topology: bad args");
+    DGNN_REQUIRE(n_faces < INT32_MAX / 6 && n_vertices < INT32_MAX, DGNN_E_UNSUPPORTED, "mesh_topology: sizes exceed the int32 indexing");
+    const TopoLayout L = topo_layout(scratch, n_faces, n_vertices);
+    const dim3 block(MT_THREADS);
+    (void)hipMemsetAsync(L.st, 0, sizeof(MtState), stream);
+    (void)hipMemsetAsync(counts_out, 0, 5 * sizeof(int64_t), stream);
+    if (n_faces > 0) hipLaunchKernelGGL(k_check_faces, mt_grid(n_faces), block, 0, stream, faces, n_faces, n_vertices, L.st);
+    MtState hs{};
+    int rc = mt_read_status(&hs, L.st, stream, "mesh_topology");
+    if (rc || n_faces == 0) return rc;
+    const int vb = key_bits(n_vertices);
+    const int64_t n3 = 3 * n_faces;
+    int cur = 0;
+    long long* counts = (long long*)counts_out;
+    // edges
+    hipLaunchKernelGGL(k_edge_keys, mt_grid(n3), block, 0, stream, faces, n3, vb, L.keys[0], L.vals[0]);
+    if ((rc = dgnn_radix_sort_u64_i32(L.keys, L.vals, n3, 2 * vb, L.hist, L.scanned, L.sums, stream, &cur))) return rc;
+    hipLaunchKernelGGL(k_edge_runs, mt_grid(n3), block, 0, stream, L.keys[cur], L.vals[cur], n3, counts);
+    // vertex fans
+    hipLaunchKernelGGL(k_link_keys, mt_grid(n3), block, 0, stream, faces, n3, vb, L.keys[0], L.vals[0], L.parent);
+    if ((rc = dgnn_radix_sort_u64_i32(L.keys, L.vals, 2 * n3, 2 * vb, L.hist, L.scanned, L.sums, stream, &cur))) return rc;
+    hipLaunchKernelGGL(k_link_union, mt_grid(2 * n3), block, 0, stream, L.keys[cur], L.vals[cur], 2 * n3, L.parent);
+    (void)hipMemsetAsync(L.roots, 0, sizeof(int32_t) * (n_vertices > 0 ? n_vertices : 1), stream);
+    hipLaunchKernelGGL(k_fan_roots, mt_grid(n3), block, 0, stream, faces, L.parent, n3, L.roots);
+    hipLaunchKernelGGL(k_fan_count, mt_grid(n_vertices), block, 0, stream, L.roots, n_vertices, counts);
+    return dgnn_check_launch("mesh_topology");
+}

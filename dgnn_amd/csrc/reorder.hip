@@ -338,6 +338,27 @@ extern "C" int dgnn_cell_centroids_3dt(const float* vertices, int64_t n_vertices
     return dgnn_check_launch("cell_centroids_3dt");
 }
 
+// Stable LSD radix sort of (u64 key, i32 value) pairs on the low `bits` bits of the keys (ceil(bits / 8) passes of 8-bit digits), shared
+// with meshtopo.hip.  keys[0] / vals[0] hold the input; the result is in keys[*cur] / vals[*cur].  hist and scanned hold
+// 256 * cdiv(n, RX_TILE) + 2 int32 each, sums the exclusive scan's dgnn_cdiv(256 * nblk, 2048) + 4.
+int64_t dgnn_radix_sort_hist_elems(int64_t n) { return 256 * dgnn_cdiv(n > 0 ? n : 1, RX_TILE) + 2; }
+
+int dgnn_radix_sort_u64_i32(uint64_t* const keys[2], int32_t* const vals[2], int64_t n, int bits, int32_t* hist, int32_t* scanned, int32_t* sums,
+                            hipStream_t stream, int* cur) {
+    *cur = 0;
+    if (n <= 0) return DGNN_OK;
+    const int nblk = (int)dgnn_cdiv(n, RX_TILE);
+    for (int shift = 0; shift < bits; shift += 8) {
+        hipLaunchKernelGGL(k_radix_hist, dim3(nblk), dim3(RX_THREADS), 0, stream, keys[*cur], n, shift, nblk, hist);
+        const int rc = dgnn_exclusive_scan_i32(hist, 256 * (int64_t)nblk, scanned, sums, stream);
+        if (rc != DGNN_OK) return rc;
+        hipLaunchKernelGGL(k_radix_scatter, dim3(nblk), dim3(RX_THREADS), 0, stream, keys[*cur], vals[*cur], n, shift, nblk, scanned,
+                           keys[*cur ^ 1], vals[*cur ^ 1]);
+        *cur ^= 1;
+    }
+    return DGNN_OK;
+}
+
 // scratch (int32 units): keys 2 x n u64 | vals 2 x n | hist 256 x nblk + 2 | scanned hist | scan sums | bbox partials
 extern "C" int64_t dgnn_cell_order_morton_scratch_elems(int64_t n) {
     if (n < 0) return 0;
@@ -363,13 +384,8 @@ extern "C" int dgnn_cell_order_morton(const float* centroids, int64_t n, int32_t
     hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(64), 0, stream, partial, bb, bbox);
     hipLaunchKernelGGL(k_morton_keys, dim3(dgnn_grid_cap(dgnn_cdiv(n, 256))), dim3(256), 0, stream, centroids, n, bbox, keys[0], vals[0]);
     int cur = 0;
-    for (int shift = 0; shift < 48; shift += 8) {
-        hipLaunchKernelGGL(k_radix_hist, dim3(nblk), dim3(RX_THREADS), 0, stream, keys[cur], n, shift, nblk, hist);
-        const int rc = dgnn_exclusive_scan_i32(hist, 256 * (int64_t)nblk, scanned, sums, stream);
-        if (rc != DGNN_OK) return rc;
-        hipLaunchKernelGGL(k_radix_scatter, dim3(nblk), dim3(RX_THREADS), 0, stream, keys[cur], vals[cur], n, shift, nblk, scanned, keys[cur ^ 1], vals[cur ^ 1]);
-        cur ^= 1;
-    }
+    const int rc = dgnn_radix_sort_u64_i32(keys, vals, n, 48, hist, scanned, sums, stream, &cur);
+    if (rc != DGNN_OK) return rc;
     hipLaunchKernelGGL(k_order_to_rank, dim3(dgnn_grid_cap(dgnn_cdiv(n, 256))), dim3(256), 0, stream, vals[cur], n, order, rank);
     return dgnn_check_launch("cell_order_morton");
 }

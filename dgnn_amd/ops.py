@@ -1743,3 +1743,65 @@ def chamfer_distance(gt_points, recon_points):
     _, _, s1 = nearest_neighbor(recon_points, gt_points)
     _, _, s2 = nearest_neighbor(gt_points, recon_points)
     return 0.5 * (s1 / len(gt_points) + s2 / len(recon_points))
+
+
+# ---- the exported mesh: orientation, vertex compaction, topology (reference processing/generate_mesh.py:107-124) ------------------
+@on_device_of
+def orient_interface(vertices, tetrahedra, facets, nfacets, labels, face_ids, orient=True, return_exact_used=False):
+    """The interface facets facets[face_ids] as faces int32 [K, 3] on the GPU, each wound so that its normal points away from its inside
+    cell (labels[c] == 0; cell -1 = the infinite cell, outside), by the EXACT sign of det[b - a, c - a, d - a] (dgnn_orient_interface; the
+    rule and its flat-cell cases are in include/dgnn_hip.h).  orient=False keeps the stored winding (the facets are still checked).
+    -> (faces, n_undetermined) (+ whether the exact stage ran for some facet with return_exact_used).  DgnnError for malformed input."""
+    dev = _dev_of(labels, face_ids, vertices)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    fac = _on(facets, dev, torch.int32, 3)
+    nfac = _on(nfacets, dev, torch.int32, 2)
+    lab = _on(labels, dev, torch.int32).reshape(-1)
+    ids = _on(face_ids, dev, torch.int32).reshape(-1)
+    if fac.size(0) != nfac.size(0):
+        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
+    if lab.numel() != tets.size(0):
+        raise ValueError("%d labels for %d cells" % (lab.numel(), tets.size(0)))
+    k = ids.numel()
+    faces = torch.empty(max(k, 1), 3, dtype=torch.int32, device=dev)[:k]
+    und = torch.zeros(1, dtype=torch.int64, device=dev)
+    used = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib().dgnn_orient_interface_scratch_bytes()), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_orient_interface(ptr(v), v.size(0), ptr(tets), tets.size(0), ptr(fac), ptr(nfac), fac.size(0), ptr(lab), ptr(ids), k,
+                                      int(bool(orient)), ptr(faces), ptr(und), ptr(used), ptr(scratch), stream_ptr()), "dgnn_orient_interface")
+    return (faces, int(und.item()), bool(used.item())) if return_exact_used else (faces, int(und.item()))
+
+
+@on_device_of
+def compact_vertices(faces, n_vertices):
+    """The vertices that `faces` references, in ascending id, and the faces renumbered onto them (dgnn_compact_vertices, which
+    compacts with dgnn_compact_i32).  -> (faces int32 [K, 3], kept vertex ids int32 [M]) on the GPU."""
+    dev = _dev_of(faces)
+    f = _on(faces, dev, torch.int32, 3)
+    nv, k = int(n_vertices), f.size(0)
+    out = torch.empty(max(k, 1), 3, dtype=torch.int32, device=dev)[:k]
+    kept = torch.empty(max(nv, 1), dtype=torch.int32, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib().dgnn_compact_vertices_scratch_bytes(nv)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_compact_vertices(ptr(f), k, nv, ptr(out), ptr(kept), ptr(cnt), ptr(scratch), stream_ptr()), "dgnn_compact_vertices")
+    return out, kept[:int(cnt.item())]
+
+
+MESH_TOPOLOGY_KEYS = ("n_edges", "boundary_edges", "nonmanifold_edges", "nonmanifold_vertices", "winding_mismatch_edges")
+
+
+@on_device_of
+def mesh_topology(faces, n_vertices):
+    """Edge and vertex counts of a triangle mesh (dgnn_mesh_topology): dict of MESH_TOPOLOGY_KEYS -> int, plus
+    watertight = boundary_edges == nonmanifold_edges == nonmanifold_vertices == 0 (Open3D's is_watertight without its self-intersection
+    test; an empty mesh is not watertight).  DgnnError for ids out of range or a face with a repeated vertex."""
+    dev = _dev_of(faces)
+    f = _on(faces, dev, torch.int32, 3)
+    nv, k = int(n_vertices), f.size(0)
+    counts = torch.zeros(5, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(lib().dgnn_mesh_topology_scratch_bytes(k, nv)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_mesh_topology(ptr(f), k, nv, ptr(counts), ptr(scratch), stream_ptr()), "dgnn_mesh_topology")
+    out = dict(zip(MESH_TOPOLOGY_KEYS, (int(c) for c in counts.cpu())))
+    out["watertight"] = int(k > 0 and out["boundary_edges"] == 0 and out["nonmanifold_edges"] == 0 and out["nonmanifold_vertices"] == 0)
+    return out

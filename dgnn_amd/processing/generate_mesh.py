@@ -5,7 +5,8 @@ and the trimesh call: labels of the finite cells (:75), the infinite cell append
 of facets whose two cells carry different labels (:101-105) -- two Python loops over all facets in the reference,
 three small kernels here.  The optional integer alpha-expansion graph cut (:15-58, third-party ``gco``) runs exactly on
 the device with ``graph_cut.solver: gpu`` (``graph_cut_gpu``), and the iou / chamfer metrics with ``evaluation.solver: gpu``
-(``iou_gpu`` / ``chamfer_gpu``); the ``trimesh`` mesh object stays a CPU-side third-party step.  ``labels`` can be replaced by the graph-cut labels before ``interface_from_labels``.
+(``iou_gpu`` / ``chamfer_gpu``), and the mesh object with its watertight metric with ``mesh.solver: gpu`` (``mesh_gpu`` /
+``watertight_gpu``); without that key the ``trimesh`` mesh object stays a CPU-side third-party step.  ``labels`` can be replaced by the graph-cut labels before ``interface_from_labels``.
 """
 from __future__ import annotations
 
@@ -164,6 +165,40 @@ def chamfer_gpu(data, mdata, interfaces, clf):
     return chamfer_distance(torch.from_numpy(gt_points).to(recon_points.device), recon_points)
 
 
+def mesh_gpu(mdata, labels, interfaces, fix_orientation):
+    """The mesh `generate` returns, built on the device: the interface facets `interfaces` (int32 ids into mdata["facets"],
+    e.g. interface_from_labels) of the labelled tetrahedralization `mdata` (`_3dt.npz`; labels of the finite cells, 0 = inside), wound so
+    that every normal points away from its inside cell when `fix_orientation` is set (ops.orient_interface: exact signs; a facet between
+    flat cells keeps its stored winding and is counted), else in the stored winding; then only the vertices the faces reference, in
+    ascending id, with the faces renumbered (ops.compact_vertices).  Runs on the device of `labels` / `interfaces`.
+    -> InterfaceMesh, with three more attributes: vertex_ids (the kept original ids, int32 ndarray), n_undetermined, faces_dev (the
+    faces on the device)."""
+    from ..ops import compact_vertices, orient_interface
+
+    faces, n_undetermined = orient_interface(mdata["vertices"], mdata["tetrahedra"], mdata["facets"], mdata["nfacets"], labels, interfaces,
+                                             orient=bool(fix_orientation))
+    faces, kept = compact_vertices(faces, len(mdata["vertices"]))
+    ids = kept.cpu().numpy()
+    mesh = InterfaceMesh(np.asarray(mdata["vertices"], dtype=np.float64)[ids], faces.cpu().numpy())
+    mesh.vertex_ids, mesh.n_undetermined, mesh.faces_dev = ids, n_undetermined, faces
+    return mesh
+
+
+def watertight_gpu(mesh, name=""):
+    """Open3D's is_watertight (edge-manifold without boundary, vertex-manifold; the reference's metric, generate_mesh.py:115-124) of an
+    InterfaceMesh from mesh_gpu, from the device's edge and vertex counts (ops.mesh_topology) -> 0 / 1.  Self-intersection is not tested:
+    the interface of a tetrahedralization cannot intersect itself.  A mesh without faces gives 0 with a warning."""
+    from ..ops import mesh_topology
+
+    faces = getattr(mesh, "faces_dev", None)
+    if faces is None:
+        faces = torch.from_numpy(np.ascontiguousarray(mesh.faces, dtype=np.int32).reshape(-1, 3))
+    if faces.shape[0] == 0:
+        print("WARNING: Mesh {} has no faces; watertight set to 0".format(name))
+        return 0
+    return mesh_topology(faces, len(mesh.vertices))["watertight"]
+
+
 def generate(data, prediction, clf):
     """Same signature and return value as the reference's processing/generate_mesh.py:61 ``generate(data, prediction, clf)``
     -> ``(mesh, eval_dict)``; what runs where:
@@ -178,7 +213,9 @@ def generate(data, prediction, clf):
       InterfaceMesh with the same vertices / faces and an ``export``; the evaluation metrics (watertight / iou / chamfer,
       :115-163) need trimesh + utils/libmesh and are computed only when those import -- otherwise eval_dict stays empty;
     * with ``clf.evaluation.solver == "gpu"`` iou and chamfer come from the device (iou_gpu / chamfer_gpu, no trimesh needed), from the
-      labels and interface facets above; the mesh object is the same.
+      labels and interface facets above; the mesh object is the same;
+    * with ``clf.mesh.solver == "gpu"`` the mesh object is built on the device whether or not trimesh imports (mesh_gpu: exact outward
+      orientation under ``fix_orientation``, only the referenced vertices) and watertight comes from the device (watertight_gpu).
     """
     dev = prediction.device if prediction.is_cuda else torch.device(getattr(clf.temp, "device", "cuda:0"))
     pred_dev = prediction.to(dev, torch.float32)
@@ -213,6 +250,8 @@ def generate(data, prediction, clf):
         import trimesh
     except ImportError:
         trimesh = None
+    if getattr(getattr(clf, "mesh", None), "solver", None) == "gpu":
+        return _generate_gpu_mesh(data, clf, mdata, labels_dev, interfaces_dev, trimesh)
     if getattr(getattr(clf, "evaluation", None), "solver", None) == "gpu":
         return _generate_gpu_metrics(data, clf, mdata, labels_dev, interfaces_dev, faces, trimesh)
     if trimesh is None:
@@ -227,14 +266,18 @@ def generate(data, prediction, clf):
     if "watertight" in metrics:
         eval_dict["watertight"] = int(recon_mesh.is_watertight)
     if "chamfer" in metrics:
-        from scipy.spatial import cKDTree
-        subfolder = data['id'] if data['id'] else data['category']
-        gt_points = np.load(os.path.join(data.path, "eval", subfolder, "pointcloud.npz"))["points"].astype(np.float32)
-        recon_points = recon_mesh.sample(gt_points.shape[0], return_index=False)
-        d1, _ = cKDTree(recon_points).query(gt_points)
-        d2, _ = cKDTree(gt_points).query(recon_points)
-        eval_dict["chamfer"] = 0.5 * (float(d1.mean()) + float(d2.mean()))
+        eval_dict["chamfer"] = _chamfer_trimesh(data, recon_mesh)
     return recon_mesh, eval_dict
+
+
+def _chamfer_trimesh(data, recon_mesh):
+    from scipy.spatial import cKDTree
+    subfolder = data['id'] if data['id'] else data['category']
+    gt_points = np.load(os.path.join(data.path, "eval", subfolder, "pointcloud.npz"))["points"].astype(np.float32)
+    recon_points = recon_mesh.sample(gt_points.shape[0], return_index=False)
+    d1, _ = cKDTree(recon_points).query(gt_points)
+    d2, _ = cKDTree(gt_points).query(recon_points)
+    return 0.5 * (float(d1.mean()) + float(d2.mean()))
 
 
 def _generate_gpu_metrics(data, clf, mdata, labels, interfaces, faces, trimesh):
@@ -254,6 +297,11 @@ def _generate_gpu_metrics(data, clf, mdata, labels, interfaces, faces, trimesh):
             eval_dict["watertight"] = int(mesh.is_watertight)
         else:
             print("WARNING: trimesh is not installed; mesh metrics {} are not computed for {}".format(["watertight"], getattr(data, "filename", "")))
+    _gpu_iou_chamfer(data, clf, mdata, labels, interfaces, metrics, eval_dict)
+    return mesh, eval_dict
+
+
+def _gpu_iou_chamfer(data, clf, mdata, labels, interfaces, metrics, eval_dict):
     if "iou" in metrics:
         try:
             eval_dict["iou"] = iou_gpu(data, mdata, labels)
@@ -266,4 +314,31 @@ def _generate_gpu_metrics(data, clf, mdata, labels, interfaces, faces, trimesh):
         except Exception:  # noqa: BLE001  (the reference: bare except, :157-159)
             print("WARNING: Could not calculate Chamfer distance for mesh ", data['filename'])
             eval_dict["chamfer"] = float("inf")
+
+
+def _generate_gpu_mesh(data, clf, mdata, labels, interfaces, trimesh):
+    """`generate`'s tail with ``mesh.solver: gpu``: the mesh from mesh_gpu, watertight from watertight_gpu; iou / chamfer from the device
+    with ``evaluation.solver: gpu``, else chamfer by trimesh's sampler when trimesh imports (as without the key).  A facet whose winding
+    could not be decided is reported once; a failing metric keeps the reference's warning."""
+    metrics = getattr(clf.temp, "metrics", None) or []
+    name = getattr(data, "filename", "")
+    mesh = mesh_gpu(mdata, labels, interfaces, getattr(clf.temp, "fix_orientation", None))
+    if mesh.n_undetermined:
+        print("WARNING: {} faces of mesh {} lie on flat cells only; they keep their stored winding".format(mesh.n_undetermined, name))
+    eval_dict = dict()
+    if "watertight" in metrics:
+        try:
+            eval_dict["watertight"] = watertight_gpu(mesh, name)
+        except Exception:  # noqa: BLE001  (the reference's style: warn and go on)
+            print("WARNING: Could not calculate watertightness for mesh ", name)
+            eval_dict["watertight"] = 0
+    if getattr(getattr(clf, "evaluation", None), "solver", None) == "gpu":
+        _gpu_iou_chamfer(data, clf, mdata, labels, interfaces, metrics, eval_dict)
+        return mesh, eval_dict
+    wanted = [m for m in ("iou", "chamfer") if m in metrics]
+    if trimesh is None:
+        if wanted:
+            print("WARNING: trimesh is not installed; mesh metrics {} are not computed for {}".format(wanted, name))
+    elif "chamfer" in metrics:
+        eval_dict["chamfer"] = _chamfer_trimesh(data, trimesh.Trimesh(mesh.vertices, mesh.faces, process=False))
     return mesh, eval_dict

@@ -830,6 +830,48 @@ int dgnn_nearest_neighbor(const float* ref, int64_t n_ref, const float* query, i
                           double* sum_out, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The mesh `generate` returns (reference processing/generate_mesh.py:107-124: trimesh.Trimesh(process=True), fix_normals, Open3D's
+ * is_watertight).  DESIGN.md section 15.
+ *
+ * dgnn_orient_interface: faces_out int32 [n_faces, 3] = the facets face_ids[0 .. n_faces) (ids into facets / nfacets, the scene layout of
+ *   dgnn_locate_points), wound by the rule below when `orient` != 0, else as stored.  labels int32 [n_cells]: 0 = inside; cell -1 (the
+ *   infinite cell) is outside.
+ *   rule      for facet (a, b, c) let o(p) = det[b - a, c - a, p - a], evaluated EXACTLY on the fp64 coordinates, and d_in the vertex of
+ *             the inside cell that is not on the facet.  o(d_in) != 0: emit (a, b, c) when o(d_in) < 0, else (a, c, b) (the normal points
+ *             away from the inside cell).  o(d_in) == 0 and a finite outside cell: the same with its opposite vertex d_out, (a, b, c) when
+ *             o(d_out) > 0, else (a, c, b).  Otherwise the stored winding, counted in n_undetermined_out (DEVICE int64 [1], NULL: not
+ *             written).  exact_used_out: DEVICE int32 [1], 1 when the fp64 filter left some sign to the exact stage (NULL: not written).
+ *   scratch   dgnn_orient_interface_scratch_bytes() bytes.
+ * DGNN_E_INVALID: an id out of range; a facet whose three vertices are not a face of a finite cell nfacets names; a facet that does not
+ * separate an inside cell from an outside one; a non-finite coordinate (orient != 0).  DGNN_E_UNSUPPORTED: a coordinate that is not 0 and
+ * has a magnitude outside [2^-300, 2^300] (where the exact stage is not exact).  SYNCHRONISES `stream` once (status).
+ *
+ * dgnn_compact_vertices: kept_out int32 [n_vertices] = the vertex ids `faces` references, ascending (dgnn_compact_i32), n_kept_out DEVICE
+ *   int32 [1] = their number, faces_out int32 [n_faces, 3] = faces renumbered onto them.  scratch: dgnn_compact_vertices_scratch_bytes
+ *   (n_vertices) bytes.  DGNN_E_INVALID: an id out of range.  SYNCHRONISES `stream` once (status).
+ *
+ * dgnn_mesh_topology: counts_out DEVICE int64 [5] of the triangle mesh faces int32 [n_faces, 3]:
+ *   [0] n_edges                 undirected edges
+ *   [1] boundary_edges          edges in exactly 1 face
+ *   [2] nonmanifold_edges       edges in 3 or more faces
+ *   [3] nonmanifold_vertices    referenced vertices whose incident faces are not ONE set connected through shared edges that contain the
+ *                               vertex (Open3D's IsVertexManifold)
+ *   [4] winding_mismatch_edges  undirected edges {u, v} with #(u -> v) != #(v -> u) over the faces' directed edges (a, b), (b, c), (c, a)
+ *   watertight = [1] == 0 && [2] == 0 && [3] == 0 (Open3D's IsEdgeManifold(false) && IsVertexManifold(); self-intersection is not tested).
+ *   Integer counts: independent of the schedule.  scratch: dgnn_mesh_topology_scratch_bytes(n_faces, n_vertices) bytes.
+ *   DGNN_E_INVALID: an id out of range or a face with a repeated vertex.  SYNCHRONISES `stream` once (input check).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_orient_interface_scratch_bytes(void);
+int dgnn_orient_interface(const double* vertices, int64_t n_vertices, const int32_t* tets, int64_t n_cells, const int32_t* facets,
+                          const int32_t* nfacets, int64_t n_facets, const int32_t* labels, const int32_t* face_ids, int64_t n_faces, int orient,
+                          int32_t* faces_out, int64_t* n_undetermined_out, int32_t* exact_used_out, void* scratch, void* stream);
+int64_t dgnn_compact_vertices_scratch_bytes(int64_t n_vertices);
+int dgnn_compact_vertices(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int32_t* faces_out, int32_t* kept_out, int32_t* n_kept_out,
+                          void* scratch, void* stream);
+int64_t dgnn_mesh_topology_scratch_bytes(int64_t n_faces, int64_t n_vertices);
+int dgnn_mesh_topology(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int64_t* counts_out, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-scene standardisation (reference processing/data.py:444-506 sklearn StandardScaler + :512-519
  * float32 cast): out[i,c] = float((x[i,c] - mean_c) / std_c) for c >= c_first, plain cast for c < c_first;
  * fp64 statistics (population variance, zero scale -> 1).  scratch: dgnn_standardize_scratch_doubles(c) doubles.
