@@ -10,7 +10,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# DGNN_LIB_PATH: another build of the same library (kernel variants for A/B measurements, tools/build_variant.sh) -- never a fallback
+# DGNN_LIB_PATH: another build of the same library (e.g. for whole-library A/B measurements, tools/gpu_ab_libs.sh) -- never a fallback
 LIB_PATH = os.environ.get("DGNN_LIB_PATH") or os.path.join(_HERE, "libdgnn_hip.so")
 
 i64, i32, f32, vp = C.c_int64, C.c_int, C.c_float, C.c_void_p

@@ -1240,20 +1240,17 @@ int agg_fwd_t(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int
     }
     if constexpr (sizeof(T) == 4) {
         // the filter product on the fp32 matrix cores (k_agg_fwd_m; the bits of k_agg_fwd): rows in 8- / 16-byte pieces per lane.  DGNN_AGG_MFMA=0: the VALU forms
-        // (a training batch's blocks: 28 channels 35.9 -> 27.5 us, 64 channels 22.7 -> 14.0 us; 128 channels 10.1 -> 10.8 us: those keep k_agg_fwd unless DGNN_AGG_MFMA=2)
+        // (a training batch's blocks: 28 channels 35.9 -> 27.5 us, 64 channels 22.7 -> 14.0 us; 128 channels keep k_agg_fwd: DESIGN 5)
         static const bool mfma_on = !(getenv("DGNN_AGG_MFMA") && getenv("DGNN_AGG_MFMA")[0] == '0');
-        static const int mfma_max = getenv("DGNN_AGG_MFMA") && getenv("DGNN_AGG_MFMA")[0] == '2' ? 128 : 64;
         const int vw = c_in <= 32 ? 2 : 4;
-        if (mfma_on && fused && f_e == 20 && !phi_out && c_in <= mfma_max && c_in % vw == 0 && ldx % vw == 0 && lda % vw == 0 &&
+        if (mfma_on && fused && f_e == 20 && !phi_out && c_in <= 64 && c_in % vw == 0 && ldx % vw == 0 && lda % vw == 0 &&
             (((uintptr_t)x_src | (uintptr_t)a) % (4 * vw)) == 0) {
-            const int rs = c_in <= 32 ? 16 : (c_in <= 64 ? 8 : 4);
+            const int rs = c_in <= 32 ? 16 : 8;
             dim3 mgrid((unsigned)dgnn_grid_cap(dgnn_cdiv(dgnn_cdiv(n_dst, rs), 4), 8));
             if (c_in <= 32)
                 hipLaunchKernelGGL((k_agg_fwd_m<2>), mgrid, dim3(256), 0, stream, rowptr, src, eid, n_dst, (const float*)x_src, ldx, c_in, edge_attr, lde, We, be, (float*)a, lda);
-            else if (c_in <= 64)
-                hipLaunchKernelGGL((k_agg_fwd_m<4>), mgrid, dim3(256), 0, stream, rowptr, src, eid, n_dst, (const float*)x_src, ldx, c_in, edge_attr, lde, We, be, (float*)a, lda);
             else
-                hipLaunchKernelGGL((k_agg_fwd_m<8>), mgrid, dim3(256), 0, stream, rowptr, src, eid, n_dst, (const float*)x_src, ldx, c_in, edge_attr, lde, We, be, (float*)a, lda);
+                hipLaunchKernelGGL((k_agg_fwd_m<4>), mgrid, dim3(256), 0, stream, rowptr, src, eid, n_dst, (const float*)x_src, ldx, c_in, edge_attr, lde, We, be, (float*)a, lda);
             return dgnn_check_launch("aggregate_fwd");
         }
         // (measured on a training batch's blocks: 38 -> 31 us at 28 channels, 19 -> 23 us at 64 -- the five replicated attribute loads per lane
@@ -1332,29 +1329,21 @@ int agg_bwd_t(const int32_t* t_rowptr, const int32_t* t_dst, const int32_t* t_ei
         return dgnn_check_launch("aggregate_bwd");
     }
     if constexpr (sizeof(T) == 4) {
-        // rows of up to 32 channels (the first conv layer; DGNN_AGG_MFMA=2: up to 64 -- measured 49 us against k_agg_bwd_c's 46.5 on a training batch's 64-wide
-        // layer): the filter's two products on the fp32 matrix cores (k_agg_bwd_mm).  DGNN_AGG_MFMA=0: the VALU form
+        // rows of up to 32 channels (the first conv layer; 64-wide rows keep k_agg_bwd_c: DESIGN 5): the filter's two products on the fp32 matrix
+        // cores (k_agg_bwd_mm).  DGNN_AGG_MFMA=0: the VALU form
         static const bool mfma_on = !(getenv("DGNN_AGG_MFMA") && getenv("DGNN_AGG_MFMA")[0] == '0');
-        static const int mfma_max = getenv("DGNN_AGG_MFMA") && getenv("DGNN_AGG_MFMA")[0] == '2' ? 64 : 32;
-        const int vw = c_in <= 32 ? 2 : 4;
-        auto al = [&](const void* p_, int64_t ld_) { return p_ == nullptr || (((uintptr_t)p_ % (4 * vw)) == 0 && ld_ % vw == 0); };
-        if (mfma_on && fused && f_e == 20 && c_in <= mfma_max && c_in % vw == 0 && !mask_dx && !dphi_out && al(x_src, ldx) && al(da, ldda) && al(dx_src, lddx) &&
+        auto al = [&](const void* p_, int64_t ld_) { return p_ == nullptr || (((uintptr_t)p_ % 8) == 0 && ld_ % 2 == 0); };
+        if (mfma_on && fused && f_e == 20 && c_in <= 32 && c_in % 2 == 0 && !mask_dx && !dphi_out && al(x_src, ldx) && al(da, ldda) && al(dx_src, lddx) &&
             al(add, ldadd)) {
-            const int rs = c_in <= 32 ? 16 : 8;
+            const int rs = 16;
             const int64_t want_m = dgnn_cdiv(dgnn_cdiv(n_src, rs), 4);
             const int nb_m = (int)(want_m < BWD_BLOCKS ? want_m : BWD_BLOCKS);
 #define LAUNCH_M(NBK_, DXV, ADDV)                                                                                                                     \
             hipLaunchKernelGGL((k_agg_bwd_mm<NBK_, DXV, ADDV>), dim3(nb_m), dim3(256), 0, stream, t_rowptr, t_dst, t_eid, n_src, rowptr_dst, (const float*)x_src, \
                                ldx, c_in, edge_attr, lde, We, be, (const float*)da, ldda, (float*)dx_src, lddx, partials, (const float*)add, ldadd, n_add)
-            if (c_in <= 32) {
-                if (!dx_src) LAUNCH_M(2, false, false);
-                else if (add) LAUNCH_M(2, true, true);
-                else LAUNCH_M(2, true, false);
-            } else {
-                if (!dx_src) LAUNCH_M(4, false, false);
-                else if (add) LAUNCH_M(4, true, true);
-                else LAUNCH_M(4, true, false);
-            }
+            if (!dx_src) LAUNCH_M(2, false, false);
+            else if (add) LAUNCH_M(2, true, true);
+            else LAUNCH_M(2, true, false);
 #undef LAUNCH_M
             SlabReduceDesc d;
             d.slabs = partials, d.nblocks = nb_m, d.nchunks = 1, d.per = 64 * 21, d.c_in = c_in, d.fe = 20, d.cpl = 1, d.dWe = dWe, d.dbe = dbe;

@@ -19,13 +19,6 @@
 // Algorithmic bytes per tet: 2*C_in (own row) + 320 (4 attribute rows) + 16 (4 source ids) + 2*C_out.
 #include "fused_common.h"
 
-#ifndef DGNN_BF16_DENSE_GROUP
-#define DGNN_BF16_DENSE_GROUP 0
-#endif
-#ifndef DGNN_BF16_CB_GROUP
-#define DGNN_BF16_CB_GROUP 2
-#endif
-
 namespace {
 using namespace fused;
 
@@ -63,14 +56,10 @@ struct DecB {      // the decoder behind the last conv layer (DEC instantiation)
 template <int CIN_PAD, int COUT, int NW = 4, int PR = 0, int XF = 0, bool DEC = false, int UB = 0>
 struct CfgB {
     static constexpr bool UBI = (UB & 1) != 0, UBO = (UB & 2) != 0;
-#ifndef DGNN_UB_OWN_PAIR
-#define DGNN_UB_OWN_PAIR 0
-#endif
     // own-row parts in the A-tile.  An unsigned own row (UBI) goes to the matrix cores rounded to bf16 (one part): its ninth bit would cost a (hi, lo)
     // split per tet and a sixth product per k-step for 2^-10 of ONE of the layer's two terms -- measured on the 1M-tet graph (CPU model of the
     // storage roundings): max |dlogit| 2.1e-2 -> 2.8e-2 without it, rms 2.1e-3 -> 2.6e-3; the gathered rows keep all nine bits
-    // (DGNN_UB_OWN_PAIR=1 builds the pair form)
-    static constexpr int XPARTS = (PR && (XF || (UBI && DGNN_UB_OWN_PAIR))) ? 2 : 1;
+    static constexpr int XPARTS = (PR && XF) ? 2 : 1;
     static constexpr int APARTS = PR ? 2 : 1;             // mean parts
     static constexpr int K = (APARTS + XPARTS) * CIN_PAD; // A-tile row: [a_hi | a_lo | x_hi | x_lo] ... [a | x_i]
     // NW == 4: four waves, each a 32-column slice of v_mfma_f32_32x32x16_bf16 blocks.  NW == 8: eight waves, each a 16-column slice
@@ -112,13 +101,8 @@ __device__ __forceinline__ float bf16_round(float v) { return bf_lo(pack_bf16(v,
 // unsigned rows (UB): value = bits << 15; two values per dword, round to nearest even on bit 15 of the fp32 pattern (the sign is cleared: -0 -> +0)
 // (one instruction each, like the bf16 decodes: the low half's shift leaves the neighbour's last bit in the sign position, which the |.| source
 // modifier of the consuming instruction drops for free; the high half is a sub-dword (SDWA WORD_1) shift)
-#ifdef DGNN_UB_MASK_DECODE
-__device__ __forceinline__ float ub_lo(uint32_t u) { return __builtin_bit_cast(float, (u & 0xFFFFu) << 15); }
-__device__ __forceinline__ float ub_hi(uint32_t u) { return __builtin_bit_cast(float, (u >> 1) & 0x7FFF8000u); }
-#else
 __device__ __forceinline__ float ub_lo(uint32_t u) { return __builtin_fabsf(__builtin_bit_cast(float, u << 15)); }
 __device__ __forceinline__ float ub_hi(uint32_t u) { return __builtin_bit_cast(float, (u >> 16) << 15); }
-#endif
 __device__ __forceinline__ uint32_t ub_enc(float v) {
     const uint32_t b = __builtin_bit_cast(uint32_t, v) & 0x7FFFFFFFu;
     return (b + 0x3FFFu + ((b >> 15) & 1u)) >> 15;
@@ -480,9 +464,9 @@ k_sage_fused_bf16(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
                     a *= 0.25f;
                     if (cb & 1) split2(prev, a, aout[cb >> 1], alo[cb >> 1]);
                     else prev = a;
-                    // keep at most DGNN_BF16_CB_GROUP channel blocks in flight: fully interleaved, their operands and results
+                    // keep at most two channel blocks in flight: fully interleaved, their operands and results
                     // push the 128 -> 128 compensated kernel over the register file (73 spilled VGPRs)
-                    if (PR && NB == 8 && (cb % DGNN_BF16_CB_GROUP) == DGNN_BF16_CB_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
+                    if (PR && NB == 8 && (cb & 1)) __builtin_amdgcn_sched_barrier(0);
                 }
                 put_seg((int)(it & 1), w * TPW + rb * 4 + tq, aout, alo, xd[rb]);
             }

@@ -24,87 +24,23 @@
 //
 // Template parameters DSP / FSP choose the arithmetic of the dense / filter product: 3 = the exact 3-part bf16 split described above
 // (6 products), 2 = the fp16 two-part form of fused_common.h (power-of-two scale per A-tile row, per edge and per weight matrix, 3 products;
-// gemm modes DGNN_GEMM_F16X2_DENSE / DGNN_GEMM_F16X2, the Python host's default).  The compile-time switches below record what was measured
-// and not kept; DGNN_WHATIF builds remove one ingredient at a time.
+// gemm modes DGNN_GEMM_F16X2_DENSE / DGNN_GEMM_F16X2, the Python host's default).  What was measured and not kept: DESIGN.md 5.
 #include "fused_common.h"
-
-#ifndef DGNN_SMALL_NW
-#define DGNN_SMALL_NW 4  // wavefronts per workgroup for C_in <= 64 (4: two independent workgroups per CU; 8: one)
-#endif
-#ifndef DGNN_EARLY_ISSUE
-#define DGNN_EARLY_ISSUE 0  // measured: the tile period does not move (5.03 -> 5.19 us): the issue phase is address arithmetic and index shuffles, not memory stalls, and it costs ~100 register moves
-#endif
-#ifndef DGNN_DENSE_PREFETCH
-#define DGNN_DENSE_PREFETCH 0  // measured: no gain (0.527 vs 0.521 ms): the second wavefront of the SIMD already covers the LDS round trips
-#endif
-#ifndef DGNN_FILTER_PIPE
-#define DGNN_FILTER_PIPE 0  // measured: no gain (0.531 vs 0.527 ms at 128 -> 128)
-#endif
-#ifndef DGNN_SKEW
-#define DGNN_SKEW 0  // measured: 0.52 -> 0.84 ms at 128 -> 128.  A lone filter-phase wavefront per SIMD takes as long as two interleaved ones (1.14 us: the phase is a chain of LDS -> matrix core -> vector ALU dependencies, latency-bound per wavefront), so a slot lasts a whole P and the tile two of them
-#endif
-#ifndef DGNN_FILTER_BREG
-#define DGNN_FILTER_BREG 0  // measured: slower on both small layers (0.24 -> 0.25, 0.36 -> 0.38 ms; 16 / 32 more live registers, spills at 64 -> 128)
-#endif
-#ifndef DGNN_SMALL_OCC
-#define DGNN_SMALL_OCC 2
-#endif
-#ifndef DGNN_TR
-#define DGNN_TR 0  // measured (tools/variants.py, same box): 16-byte stores of 32-byte row pieces cost the small layers 7 % (0.229 -> 0.247, 0.360 -> 0.380 ms: each store
-                   // instruction touches 32 cache lines instead of 2) and leave 128 -> 128 where it was
-#endif
-// What-if builds (tools/build_variant.sh <name> -DDGNN_WHATIF=<bits>): one ingredient removed, results garbage, only the time matters.
-//   1 no dense-phase products, 2 no filter products, 4 no output stores (K-split kernels), 8 neighbour rows = own row (no gathers),
-//   16 no attribute DMA.  Reading them needs care: removing the DMA made every layer 17-27 % faster, yet neither requesting it a whole
-//   phase earlier (double-buffered strips) nor replacing it by coalesced reads of a pre-split operand cache written by the first layer
-//   moved the time at all -- with the DMA gone the filter operand no longer changes from tile to tile, and this part clocks visibly
-//   higher on quieter operands.
-#ifndef DGNN_WHATIF
-#define DGNN_WHATIF 0
-#endif
-#ifndef DGNN_PLANAR
-#define DGNN_PLANAR 1
-#endif
-#ifndef DGNN_ROW_SHIFT
-#define DGNN_ROW_SHIFT 1
-#endif
-#ifndef DGNN_NT_STORES
-#define DGNN_NT_STORES 1
-#endif
-#ifndef DGNN_NT_ATTR
-#define DGNN_NT_ATTR 0  // measured: streaming the attribute DMA past the caches costs 1.7 % (1.764 -> 1.795 ms per step)
-#endif
-#ifndef DGNN_PHASE_PRIO
-#define DGNN_PHASE_PRIO 0  // measured: balances the barrier waits (0.6/0.4 us instead of 1.4/0.2) but the tile period does not move
-#endif
-#ifndef DGNN_YOUNG_PRIO
-#define DGNN_YOUNG_PRIO 0  // measured: it only swaps which wave of a SIMD waits at the barrier (zero-sum)
-#endif
 
 namespace {
 using namespace fused;
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 #define H8(v) __builtin_bit_cast(f16x8, v)
-template <int V> struct IC { static constexpr int value = V; };
-// output rows are written once and read by the NEXT launch: streamed past the caches (DGNN_NT_STORES) they do not evict the feature rows
+// output rows are written once and read by the NEXT launch: streamed past the caches they do not evict the feature rows
 // the gathers of this launch hit in L2 / Infinity Cache
-// the edge attributes are read once per launch: non-temporal DMA (aux bit 1 = nt) keeps them from displacing feature rows
 __device__ __forceinline__ void glds16_s(const float* g, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0,
-                                     DGNN_NT_ATTR ? 2 : 0);
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 __device__ __forceinline__ void glds4_s(const float* g, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0,
-                                     DGNN_NT_ATTR ? 2 : 0);
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
 }
-__device__ __forceinline__ void st_out(float* p, float v) {
-#if DGNN_NT_STORES
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+__device__ __forceinline__ void st_out(float* p, float v) { __builtin_nontemporal_store(v, p); }
 
 // NW wavefronts per workgroup, KS = how many ways the dense phase splits K between wavefronts.
 //   (8, 2): 8 waves = (32-column slice) x (K half) [x row group]; the only arrangement whose resident weights fit at C_in = 128.
@@ -137,7 +73,7 @@ struct Cfg2 {
     static constexpr int ROWF_BYTES = DSP == 2 ? 4 * TILE * 4 : 0;  // per-row inverse scales, 4 tiles deep (written in P(it), read up to the
                                                                     // delayed epilogue after barrier it+1 while P(it+2) may already write)
     static constexpr int SC_BYTES = 16;                   // launch-wide weight maxima (prologue)
-    static constexpr int COLP_BYTES = (DSP == 2 && (DGNN_TR || DEC)) ? 3 * COUT * 4 : 0;  // [bias | scale | shift][COUT]: the transposed epilogue's lanes own 8 / 16 columns
+    static constexpr int COLP_BYTES = DEC ? 3 * COUT * 4 : 0;  // [bias | scale | shift][COUT]: the transposed epilogue's lanes own 8 columns
     // decoder stage: W0 as matrix-core fragments [2 output blocks][8 column slabs][hi | lo][64 lanes] x 16 B, then A1 | B1 [64] (folded bias / BatchNorm),
     // W3 [2][64], b3 [2] (+2 pad), per-(slab, row) inverse scales [8][32], the second output block's partial logits [32][2], a hand-off flag
     static constexpr int DEC_W0 = 2 * 8 * 2 * 1024, DEC_CONST = (64 + 64 + 128 + 4) * 4, DEC_SCALE = 8 * 32 * 4, DEC_PBUF = 32 * 2 * 4 + 16;
@@ -153,21 +89,16 @@ struct Cfg2 {
     static_assert(RG >= 1 && NQ <= 64, "wave roles");
 };
 
-// part: -1 = the lane's NB channels; 0 / 1 = their first / second half (NB == 8, where the row piece is two 16-byte loads)
-template <int NB, int part = -1>
+// the lane's NB channels of one row
+template <int NB>
 __device__ __forceinline__ void ld_vec(float (&v)[NB], const float* p, bool vec) {
-    if (NB == 8 && (vec || part >= 0)) {
-        if (part != 1) {
-            const f32x4_t a = *reinterpret_cast<const f32x4_t*>(p);
+    if (NB == 8 && vec) {
+        const f32x4_t a = *reinterpret_cast<const f32x4_t*>(p);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = a[i];
-        }
-        if (part != 0) {
-            const f32x4_t b = *reinterpret_cast<const f32x4_t*>(p + 4);
+        for (int i = 0; i < 4; ++i) v[i] = a[i];
+        const f32x4_t b = *reinterpret_cast<const f32x4_t*>(p + 4);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[(4 + i) % NB] = b[i];
-        }
-    } else if (part == 1) {
+        for (int i = 0; i < 4; ++i) v[(4 + i) % NB] = b[i];
     } else if (NB == 4 && vec) {
         const f32x4_t a = *reinterpret_cast<const f32x4_t*>(p);
 #pragma unroll
@@ -177,11 +108,6 @@ __device__ __forceinline__ void ld_vec(float (&v)[NB], const float* p, bool vec)
         for (int i = 0; i < NB; ++i) v[i] = p[i];
     }
 }
-
-// wavefronts per SIMD the register allocation aims at: 2 (eight-wave workgroup, or two four-wave ones per CU); DGNN_SMALL_OCC = 3 asks for three
-// four-wave workgroups per CU where their LDS allows it (<= 53 KB each)
-template <int CIN_PAD, int COUT, int NW, int KS, int DSP, int FSP>
-constexpr int occ_of() { return (NW == 4 && Cfg2<CIN_PAD, COUT, NW, KS, DSP, FSP>::SMEM_BYTES <= 53 * 1024) ? DGNN_SMALL_OCC : 2; }
 
 // parameters of the decoder stage (DEC): reference learning/surfaceNetStaticEdgeFilters.py:180-187, applied at :350-351
 struct DecArgs {
@@ -200,8 +126,9 @@ struct DecArgs {
     int prep_mode;
 };
 
+// two wavefronts per SIMD: one eight-wave workgroup, or two four-wave ones per CU
 template <int CIN_PAD, int COUT, int NW, int KS, int DSP, int FSP, bool DEC = false>
-__global__ void __launch_bounds__(64 * NW, (occ_of<CIN_PAD, COUT, NW, KS, DSP, FSP>()))
+__global__ void __launch_bounds__(64 * NW, 2)
 k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src, const int32_t* __restrict__ eid, int64_t n_dst,
                   const float* __restrict__ x, const float* __restrict__ xdst, int64_t ldx, int c_in, const float* __restrict__ ea, int64_t lde,
                   const float* __restrict__ We, const float* __restrict__ be, const float* __restrict__ Wj,
@@ -210,9 +137,6 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
                   int xvec, int64_t* __restrict__ trace, int64_t trace_cap, DecArgs dec) {
     using C = Cfg2<CIN_PAD, COUT, NW, KS, DSP, FSP, DEC>;
     constexpr int ROWB = C::ROWB, TILE = C::TILE, TPW = C::TPW, RB = C::RB, NB = C::NB, NWB = C::NWB, OCT = C::OCT;
-    // the next tile's gathers are issued between the pieces of the filter phase (fp16 forms: the bf16 x 3 form at 128 -> 128 has no
-    // registers left for the overlap of old and new rows) or as one burst at its end
-    constexpr bool EARLY = DSP == 2 && DGNN_EARLY_ISSUE;
     extern __shared__ __attribute__((aligned(16))) char smem2[];
     char* const abuf = smem2;                                        // [2][A_BYTES]
     char* const eabuf = smem2 + 2 * C::A_BYTES;                      // [NW][EA_BYTES] fp32 attribute strips
@@ -221,36 +145,23 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
     float* const rowf = reinterpret_cast<float*>(bpbuf + C::BP_BYTES);            // [4][TILE] (DSP == 2 only)
     uint32_t* const scbuf = reinterpret_cast<uint32_t*>(bpbuf + C::BP_BYTES + C::ROWF_BYTES);
     float* const colp = reinterpret_cast<float*>(bpbuf + C::BP_BYTES + C::ROWF_BYTES + C::SC_BYTES);
-    // DSP == 2: the dense product is taken transposed (weights as the A operand, tet rows as the B operand -- the per-lane fragments are the
-    // same either way), so a lane ends up with ONE tet row and 4-column runs of it: the result leaves as 16-byte stores (2 or 4 per lane and
-    // tile instead of 8 or 16 dword stores whose addresses each cost 64-bit arithmetic), the row's inverse scale is one LDS word per lane.
-    constexpr bool TR = DSP == 2 && (DGNN_TR || DEC);
+    // DEC: the dense product is taken transposed (weights as the A operand, tet rows as the B operand -- the per-lane fragments are the
+    // same either way), so a lane ends up with ONE tet row and 4-column runs of it, which are the decoder's operand as they stand.
+    constexpr bool TR = DEC;
     // decoder stage buffers (DEC)
     char* const w0buf = reinterpret_cast<char*>(colp) + C::COLP_BYTES;                 // [2][8][2][64] x 16 B
     float* const dconst = reinterpret_cast<float*>(w0buf + C::DEC_W0);                 // A1[64] | B1[64] | W3[2][64] | b3[2]
     float* const dscale = dconst + C::DEC_CONST / 4;                                   // [8 slabs][32 rows]
     float* const pbuf = dscale + C::DEC_SCALE / 4;                                     // [32 rows][2]
     volatile int32_t* const pflag = reinterpret_cast<volatile int32_t*>(pbuf + 64);
-    constexpr bool PLANAR = DSP == 2 && DGNN_PLANAR;
-    // Skewed schedule (128 -> 128, fp16 dense form): the eight waves are two groups, A = the K-half-0 waves 0..3 and B = the K-half-1 waves
-    // 4..7, one of each per SIMD, and at any time one group is in its filter phase P (vector ALU, LDS, gathers) while the other is in its dense
-    // phase C (matrix cores, stores).  In the plain schedule both wavefronts of a SIMD are always in the SAME phase and queue for the same
-    // unit -- the memory front end in front of the barrier, the matrix cores behind it -- and the phases' latencies have nobody to hide them.
-    // Costs a second barrier per tile.  The tile's rows 0..15 come from group A, rows 16..31 from group B; C(t) of either group runs only
-    // after both have delivered (two slots after P_A(t), one after P_B(t)).
-    constexpr bool SKEW = DGNN_SKEW && DSP == 2 && KS == 2 && C::NSLICE == 4 && NW == 8;
+    constexpr bool PLANAR = DSP == 2;
 
     const int lane = lane_id(), w = wave_id_uniform();
-#if DGNN_YOUNG_PRIO
-    // the second wave of every SIMD loses VALU/MFMA arbitration to the older one on every phase (priority, then age);
-    // one static priority bump evens the two out so neither idles long at the tile barrier
-    if (w >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
     const int h = lane >> 5, l31 = lane & 31;
     const int jcol = lane & 15, tq = lane >> 4;  // filter phase: channel group / tet within a row block; also MFMA (col, k-group)
     const int ldx32 = (int)ldx;
     // row offset = row * ldx: a shift when the stride is a power of two (64 / 128 floats in layers 1..3; v_mul_lo_u32 runs at a quarter of the rate)
-    const int ldx_sh = (DGNN_ROW_SHIFT && (ldx32 & (ldx32 - 1)) == 0) ? __builtin_ctz((unsigned)ldx32) : -1;
+    const int ldx_sh = (ldx32 & (ldx32 - 1)) == 0 ? __builtin_ctz((unsigned)ldx32) : -1;
     constexpr bool vec = NB >= 4;  // the host side only takes rows that can be read as 16-byte pieces when NB >= 4 (xvec); NB == 2 reads 8 bytes
     (void)xvec;
 
@@ -420,19 +331,6 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
         return;
     }
 
-    // ---- filter operand parts of this lane kept in registers where they fit (NB <= 4: 8 registers per channel block): no LDS reads
-    // inside the channel-block loop
-    constexpr bool BREG = DGNN_FILTER_BREG && FSP == 2 && NB <= 4;
-    uint4 breg[BREG ? NB : 1][2];
-    if constexpr (BREG) {
-#pragma unroll
-        for (int cb = 0; cb < NB; ++cb) {
-            const char* bp = bpbuf + ((cb * FSP) * 48 + (tq < 3 ? tq : 0) * 16 + jcol) * 16;
-            breg[cb][0] = *reinterpret_cast<const uint4*>(bp);
-            breg[cb][1] = *reinterpret_cast<const uint4*>(bp + 768);
-        }
-    }
-
     // ---- filter-phase role
     const int c0 = NB * jcol;            // this lane's NB contiguous channels
     const bool on = c0 < c_in;           // c_in is a multiple of NB (host-checked)
@@ -469,13 +367,11 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
             }
         }
     };
-    // Gathers of tile `it` (S1), in pieces so that they can be issued between the pieces of P(it-1)'s arithmetic instead of as one
-    // burst in front of the barrier (the CU's vector-memory front end takes ~0.6 us per tile to accept them: 92 KB at 64 B/clk).
-    //   issue_x(it, rb, part): own row + the 4 neighbour rows of row block rb (part: see ld_vec)
+    // Gathers of tile `it` (S1), issued as one burst at the end of P(it-1):
+    //   issue_x(it, rb): own row + the 4 neighbour rows of row block rb
     //   issue_ea(it): LDS-DMA of the attribute block into the private strip -- the strip's reads of the current tile must have returned
     int sidx[RB][4];
-    auto issue_x = [&](int64_t it, int rb, auto part_c) {
-        constexpr int part = decltype(part_c)::value;
+    auto issue_x = [&](int64_t it, int rb) {
         if (!regular) return;
         const int i0 = (int)(tile_of(it) * TILE) + w * TPW;
         const int tl = rb * 4 + tq;  // this lane's tet within the wave
@@ -485,10 +381,8 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
         constexpr bool BATCH = !(DSP == 3 && CIN_PAD == 128);  // the bf16 x 3 form at 128 -> 128 has no registers for five offsets at once (2 spills)
         auto off_of = [&](int row) -> uint32_t { return ldx_sh >= 0 ? (uint32_t)row << ldx_sh : (uint32_t)(row * ldx32); };
         if constexpr (BATCH) {
-            if (part != 1) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) sidx[rb][r] = (DGNN_WHATIF & 8) ? own : __shfl(vsrc1, tl * 4 + r);
-            }
+            for (int r = 0; r < 4; ++r) sidx[rb][r] = __shfl(vsrc1, tl * 4 + r);
             uint32_t off[5];
             if (ldx_sh >= 0) {
                 off[4] = (uint32_t)own << ldx_sh;
@@ -499,20 +393,20 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
 #pragma unroll
                 for (int r = 0; r < 4; ++r) off[r] = (uint32_t)(sidx[rb][r] * ldx32);
             }
-            ld_vec<NB, part>(xd[rb], xdst + off[4] + c0l, vec);
+            ld_vec<NB>(xd[rb], xdst + off[4] + c0l, vec);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) ld_vec<NB, part>(xr[rb][r], x + off[r] + c0l, vec);
+            for (int r = 0; r < 4; ++r) ld_vec<NB>(xr[rb][r], x + off[r] + c0l, vec);
         } else {
-            ld_vec<NB, part>(xd[rb], xdst + off_of(own) + c0l, vec);
+            ld_vec<NB>(xd[rb], xdst + off_of(own) + c0l, vec);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (part != 1) sidx[rb][r] = (DGNN_WHATIF & 8) ? own : __shfl(vsrc1, tl * 4 + r);
-                ld_vec<NB, part>(xr[rb][r], x + off_of(sidx[rb][r]) + c0l, vec);
+                sidx[rb][r] = __shfl(vsrc1, tl * 4 + r);
+                ld_vec<NB>(xr[rb][r], x + off_of(sidx[rb][r]) + c0l, vec);
             }
         }
     };
     auto issue_ea = [&](int64_t it) {
-        if (!regular || (DGNN_WHATIF & 16)) return;
+        if (!regular) return;
         // eid == nullptr: the rows are in plan order, one contiguous block.  Otherwise every 80-byte row is
         // fetched from its place in the caller's edge_attr (row eid[k]) -- no staging copy of the edge features.
         if (eid) {
@@ -548,7 +442,7 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
     };
     auto issue_loads = [&](int64_t it) {  // everything at once (prologue, and after a group that took the generic path)
 #pragma unroll
-        for (int rb = 0; rb < RB; ++rb) issue_x(it, rb, IC<-1>{});
+        for (int rb = 0; rb < RB; ++rb) issue_x(it, rb);
         issue_ea(it);
     };
     // start of P(it), everything requested so far has landed: the stages move up, then S2's sources and S3's row starts are requested
@@ -659,11 +553,9 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
                     av[4 + i] = tq < 2 ? q1[i] : 0.f;
                 }
                 if (tq == 2) av[4] = 1.0f;
-                if (EARLY && rb == RB - 1) {
-                    // the strip has been read for the last time: the next tile's attribute block may land in it
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    issue_ea(it + 1);
-                }
+                // (phaseP names the two issue lambdas, which it otherwise reaches through issue_loads only: that keeps its closure, and with it the
+                // compiler's schedule of the FSP == 3 forms, as measured -- without them gemm mode f16x2d ran 2.5 % slower)
+                (void)issue_ea;
                 uint32_t ph[4], pm[4], pl[4];
                 float fmean = 0.25f;  // 1/4 (regular group) times the inverse scale of the filter weights
                 float inv_e[4];       // FSP == 2: inverse scales of the 4 in-edges of this lane's tet
@@ -692,23 +584,12 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
                 for (int cb = 0; cb < NB; ++cb) {
                     const char* bp = bpbuf + ((cb * FSP) * 48 + (tq < 3 ? tq : 0) * 16 + jcol) * 16;
                     // k-group 3 re-reads group 0: its A operand is all zero, so any finite B will do (saves 12 selects)
-                    uint4 u0, u1, u2;
-                    if constexpr (BREG) {
-                        u0 = breg[cb][0];
-                        u1 = u2 = breg[cb][1];
-                    } else {
-                        u0 = *reinterpret_cast<const uint4*>(bp), u1 = *reinterpret_cast<const uint4*>(bp + 768),
-                        u2 = *reinterpret_cast<const uint4*>(bp + 768 * (FSP - 1));
-                    }
+                    const uint4 u0 = *reinterpret_cast<const uint4*>(bp), u1 = *reinterpret_cast<const uint4*>(bp + 768),
+                                u2 = *reinterpret_cast<const uint4*>(bp + 768 * (FSP - 1));
                     const bf16x8 bh = __builtin_bit_cast(bf16x8, u0), bm = __builtin_bit_cast(bf16x8, u1),
                                  bl = __builtin_bit_cast(bf16x8, u2);
                     f32x4_t d = {0.f, 0.f, 0.f, 0.f};
-                    if (DGNN_WHATIF & 2) {
-                        d[0] = __builtin_bit_cast(float, u0.x) + __builtin_bit_cast(float, ph[0]);
-                        d[1] = __builtin_bit_cast(float, u2.y);
-                        d[2] = __builtin_bit_cast(float, u0.z);
-                        d[3] = __builtin_bit_cast(float, pl[1]);
-                    } else if constexpr (FSP == 2) {
+                    if constexpr (FSP == 2) {
                         d = __builtin_amdgcn_mfma_f32_16x16x32_f16(H8(al), H8(bh), d, 0, 0, 0);
                         d = __builtin_amdgcn_mfma_f32_16x16x32_f16(H8(ah), H8(bl), d, 0, 0, 0);
                         d = __builtin_amdgcn_mfma_f32_16x16x32_f16(H8(ah), H8(bh), d, 0, 0, 0);
@@ -732,23 +613,8 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
                     for (int r = 1; r < 4; ++r) a = __fmaf_rn(xr[rb][r][cb], d[r], a);
                     aout[cb] = a;
                     xv[cb] = xd[rb][cb];
-                    // the registers of this row block are free again: request its rows of the next tile right here, between
-                    // the arithmetic (NB == 8: in two halves, the first as soon as channels 0..3 are through)
-                    if (EARLY && RB == 1 && NB == 8 && cb == 3) issue_x(it + 1, rb, IC<0>{});
                 }
-                if (EARLY) issue_x(it + 1, rb, IC<(RB == 1 && NB == 8) ? 1 : -1>{});
-                if constexpr (FSP == 2 && DGNN_FILTER_PIPE) {
-                    // instruction order of the channel-block loop: operand reads two blocks ahead of their products, the x.phi sums of a
-                    // block behind the next block's products (left alone, every read is waited for right where it is issued)
-                    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-#pragma unroll
-                    for (int cb = 0; cb < NB; ++cb) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-                        if (cb + 2 < NB) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                        if (cb > 0) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                }
+                (void)issue_x;
                 put_seg(it, w * TPW + rb * 4 + tq, aout, xv, fmean);
             }
         } else {
@@ -781,10 +647,8 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
             }
         }
         stamp(trace, trace_cap, it, w, 2);
-        if (!was_regular || !EARLY) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // strip reads returned before the next DMA may land
-            issue_loads(it + 1);
-        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // strip reads returned before the next DMA may land
+        issue_loads(it + 1);
         stamp(trace, trace_cap, it, w, 3);
     };
     // C(it): this wave's block of the dense product over its share of K
@@ -795,7 +659,7 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
         const char* A = abuf + (it & 1) * C::A_BYTES + (rg * 32 + l31) * ROWB + (PLANAR ? (kh * CIN_PAD + 8 * h) * 2 : (kh * (CIN_PAD / 8) + h) * OCT);
         constexpr int SSTEP = PLANAR ? 32 : 2 * OCT, LOFF = PLANAR ? C::K * 2 : 16 * (DSP - 1);
 #pragma unroll
-        for (int S = 0; S < ((DGNN_WHATIF & 1) ? 1 : NWB); ++S) {
+        for (int S = 0; S < NWB; ++S) {
             const bf16x8 ah = *reinterpret_cast<const bf16x8*>(A + S * SSTEP);
             const bf16x8 al = *reinterpret_cast<const bf16x8*>(A + S * SSTEP + LOFF);
             if constexpr (DSP == 2) {
@@ -819,16 +683,6 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, wb[S][0], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wb[S][1], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wb[S][0], acc, 0, 0, 0);
-            }
-        }
-        if constexpr (DSP == 2 && DGNN_DENSE_PREFETCH > 0) {
-            // instruction order of the block above: the A fragments of DGNN_DENSE_PREFETCH k-steps are requested ahead of the products
-            // that use them (left alone, the scheduler requests each pair right in front of its use and every k-step pays an LDS round trip)
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 * DGNN_DENSE_PREFETCH, 0);
-#pragma unroll
-            for (int S = 0; S < NWB; ++S) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-                if (S + DGNN_DENSE_PREFETCH < NWB) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
             }
         }
     };
@@ -905,12 +759,7 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
             if (has_scale) v[r] = __fmaf_rn(v[r], sc, sh);
             if (relu) v[r] = fmaxf(v[r], 0.f);
         }
-        if (DGNN_WHATIF & 4) {
-            float t = 0.f;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) t += v[r];
-            if (t == 123.456f) o[0] = t;
-        } else if ((tile + 1) * TILE <= n_dst) {
+        if ((tile + 1) * TILE <= n_dst) {
 #pragma unroll
             for (int r = 0; r < 8; ++r) st_out(&o[(int64_t)((r & 3) + 8 * (r >> 2)) * ldo], v[r]);
         } else {
@@ -992,31 +841,6 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
         } else {
             // full K in this wave: finish the 32 x 32 block right away (row (r&3) + 8(r>>2) + 4h, column `col`)
             const int64_t tile = tile_of(it);
-            if constexpr (TR) {
-                // transposed block: columns cs*32 + 4h + 8g + c (g < 4, c < 4) of tet row rg*32 + l31
-                const int row = rg * 32 + l31, cbase = cs * 32 + 4 * h;
-                const int64_t grow = tile * TILE + row;
-                const float rf = rowf[(int)(it & 3) * TILE + row];
-                float* o = out + grow * ldo + cbase;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4_t b4 = *reinterpret_cast<const f32x4_t*>(colp + cbase + 8 * g);
-                    f32x4_t v;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = __fmaf_rn(acc[4 * g + c], rf, b4[c]);
-                    if (has_scale) {
-                        const f32x4_t s4 = *reinterpret_cast<const f32x4_t*>(colp + COUT + cbase + 8 * g);
-                        const f32x4_t h4 = *reinterpret_cast<const f32x4_t*>(colp + 2 * COUT + cbase + 8 * g);
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) v[c] = __fmaf_rn(v[c], s4[c], h4[c]);
-                    }
-                    if (relu) {
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f);
-                    }
-                    if (grow < n_dst) *reinterpret_cast<f32x4_t*>(o + 8 * g) = v;
-                }
-            } else {
             const int64_t row0 = tile * TILE + rg * 32 + 4 * h;
             float* o = out + row0 * ldo + col;
             const bool full = (tile + 1) * TILE <= n_dst;
@@ -1038,51 +862,9 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
                 const int rr = (r & 3) + 8 * (r >> 2);
                 if (full || row0 + rr < n_dst) st_out(&o[(int64_t)rr * ldo], v);
             }
-            }
         }
     };
 
-    if constexpr (SKEW) {
-        // Skewed schedule (see SKEW above).  Slot 2t+1: group A runs P(t+1), group B runs C(t) and finishes tile t-1;
-        // slot 2t+2: group A runs C(t) and finishes tile t, group B runs P(t+1).  One barrier per slot.
-        const bool grpA = kh == 0;
-        if (my_n > 0) phaseP(0);
-        tile_barrier();
-        for (int64_t slot = 1; slot <= 2 * my_n + 1; ++slot) {
-            const int64_t t = (slot - 1) >> 1;
-            const bool doP = ((slot & 1) != 0) == grpA;
-            if (doP) {
-                if (t + 1 < my_n) phaseP(t + 1);
-            } else {
-                const bool hasC = t < my_n;
-                f32x16 acc;
-                stamp(trace, trace_cap, t, w, 4);
-                if (hasC) {
-                    phaseC(t, acc);
-                    stamp(trace, trace_cap, t, w, 6);
-                    float* red = redbuf + (t & 1) * (C::RED_BYTES / 4) + w * 512 + lane;
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) red[r * 64] = kh ? acc[r] : acc[8 + r];
-                }
-                if (grpA) {
-                    // the partner's half of tile t was written in the previous slot
-                    if (hasC) {
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) mine[r] = acc[r];
-                        epilogueK2(t);
-                    }
-                } else {
-                    if (t >= 1) epilogueK2(t - 1);
-                    if (hasC) {
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) mine[r] = acc[8 + r];
-                    }
-                }
-                stamp(trace, trace_cap, t, w, 5);
-            }
-            tile_barrier();
-        }
-    } else {
     for (int64_t it = 0; it <= my_n; ++it) {
         if (it < my_n) phaseP(it);
         tile_barrier();  // A-tile `it` complete; partial sums of tile `it-1` complete
@@ -1102,7 +884,6 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
             stamp(trace, trace_cap, it, w, 5);
         }
     }
-    }
 }
 
 template <int CIN_PAD, int COUT, int DSP, int FSP, bool DEC = false>
@@ -1111,13 +892,13 @@ int launch2(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64
             const float* scale, const float* shift, int relu, float* out, int64_t ldo, int xvec, hipStream_t stream, DecArgs dec = DecArgs{}) {
     // C_in <= 64: four-wave workgroups, two per CU (see Cfg2); C_in = 128: eight waves with the K split
     // (64 -> 64 would need 16 tets per wave with 4 channels per lane: 110 spilled registers -- it keeps the 8-wave form)
-    constexpr int NW = (CIN_PAD <= 64 && !(CIN_PAD == 64 && COUT == 64)) ? DGNN_SMALL_NW : 8, KS = NW == 8 ? 2 : 1;
+    constexpr int NW = (CIN_PAD <= 64 && !(CIN_PAD == 64 && COUT == 64)) ? 4 : 8, KS = NW == 8 ? 2 : 1;
     using C = Cfg2<CIN_PAD, COUT, NW, KS, DSP, FSP, DEC>;
     const int64_t ntiles = dgnn_cdiv(n_dst, C::TILE);
     const size_t smem = C::SMEM_BYTES;
     static bool attr_set[DGNN_MAX_DEVICES] = {};
     dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_mfma<CIN_PAD, COUT, NW, KS, DSP, FSP, DEC>), smem, attr_set);
-    const int wg_max = DGNN_NUM_CU * (NW == 8 ? 1 : occ_of<CIN_PAD, COUT, NW, KS, DSP, FSP>());
+    const int wg_max = DGNN_NUM_CU * (NW == 8 ? 1 : 2);
     int grid = (int)(ntiles < wg_max ? ntiles : wg_max);
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL((k_sage_fused_mfma<CIN_PAD, COUT, NW, KS, DSP, FSP, DEC>), dim3(grid), dim3(64 * NW), smem, stream, rowptr, src, eid, n_dst, x, xdst,
@@ -1231,8 +1012,8 @@ extern "C" int64_t dgnn_sage_layer_prepared_bytes(int c_in, int c_out, int with_
     const int cp = c_in <= 32 ? 32 : (c_in <= 64 ? 64 : 128);
     if (cp == 128 && c_out != 128) return 0;
     if (with_decoder) return (cp == 128 && c_out == 128) ? Cfg2<128, 128, 8, 2, 2, 2, true>::PREP_BYTES : 0;
-    if (cp == 32) return c_out == 64 ? Cfg2<32, 64, DGNN_SMALL_NW, DGNN_SMALL_NW == 8 ? 2 : 1, 2, 2>::PREP_BYTES : Cfg2<32, 128, DGNN_SMALL_NW, DGNN_SMALL_NW == 8 ? 2 : 1, 2, 2>::PREP_BYTES;
-    if (cp == 64) return c_out == 64 ? Cfg2<64, 64, 8, 2, 2, 2>::PREP_BYTES : Cfg2<64, 128, DGNN_SMALL_NW, DGNN_SMALL_NW == 8 ? 2 : 1, 2, 2>::PREP_BYTES;
+    if (cp == 32) return c_out == 64 ? Cfg2<32, 64, 4, 1, 2, 2>::PREP_BYTES : Cfg2<32, 128, 4, 1, 2, 2>::PREP_BYTES;
+    if (cp == 64) return c_out == 64 ? Cfg2<64, 64, 8, 2, 2, 2>::PREP_BYTES : Cfg2<64, 128, 4, 1, 2, 2>::PREP_BYTES;
     return Cfg2<128, 128, 8, 2, 2, 2>::PREP_BYTES;
 }
 

@@ -3,8 +3,8 @@
 // Reference: SAGEConv.forward + BatchNorm(eval) + ReLU, learning/surfaceNetStaticEdgeFilters.py:66-96, :345-346 -- the shipped model's layers 1, 2 and 3
 // (the description below is for C_in = 128; 64: half the channels per producer lane, 512-byte ring rows, 4 k-steps).
 // k_sage_fused_mfma<128,128> runs eight wavefronts that ALL walk the same two phases (filter / mean, barrier, dense product): 44-48 % of its wave cycles
-// are parked, the matrix pipe is 26 % busy, and at 229-250 VGPRs two wavefronts per SIMD is all it admits (docs/history_r1-r4.md 5a, 5b).  The probe
-// tools/probe_producer.py says what the split buys: the producer side ALONE (gathers, filter product, mean, row split -- k_agg_sr<8, false> with its HBM
+// are parked, the matrix pipe is 26 % busy, and at 229-250 VGPRs two wavefronts per SIMD is all it admits (docs/history_r1-r4.md 5a, 5b).  A probe of
+// round 5 says what the split buys: the producer side ALONE (gathers, filter product, mean, row split -- k_agg_sr<8, false> with its HBM
 // stores off) runs 1M cells in 0.31-0.34 ms at 4 resp. 2 wavefronts per SIMD: it is bound by its reads, not by latency, once nothing else shares its
 // wavefronts.  So here a 1024-thread workgroup (16 wavefronts, 4 per SIMD, <= 128 VGPRs each) is
 //   8 PRODUCERS  one group of 4 cells each per 32-cell tile: index chain two tiles ahead, 4 neighbour rows + own row as 16-byte loads, filter product on
@@ -50,9 +50,7 @@ template <int CIN> struct WsC {
     static constexpr int SLOT = WS_TILE * ROWB;
     static constexpr int BP = NCH * 2 * 48 * 16;
 };
-// RING slots of the hand-off.  FLAGS = false (RING 2 only): one s_barrier per tile instead of the counters (producers on tile t, consumers on t - 1, everybody
-// meets once per tile: ties all 16 wavefronts to the slowest gather of every tile; DGNN_WS_RING=2, kept as the simple form to test against).
-// FLAGS = true: the counters; 2, 3 or 4 slots measure the same (DGNN_WS_RING=22 / 3 / 4), the decoder-carrying launch has LDS for 2.
+// RING slots of the hand-off (counters, below): 2 for the 128-wide rows, 4 for the 64-wide 16-bit rows.
 template <int CIN, int RING> struct WsL {
     static constexpr int OFF_BP = RING * WsC<CIN>::SLOT;
     static constexpr int OFF_ROWF = OFF_BP + WsC<CIN>::BP;          // [RING][32] inverse row scales
@@ -104,17 +102,16 @@ __device__ __forceinline__ uint32_t ub16_enc(float v) {
 }
 __device__ __forceinline__ uint32_t bits(float f) { return __builtin_bit_cast(uint32_t, f); }
 
-#ifndef DGNN_WS_LINE_OWN
-#define DGNN_WS_LINE_OWN 1      // 0: round 5's ownership (8 contiguous channels per lane) -- for A/B builds only
-#endif
-template <int CIN, int RING, bool FLAGS, bool DEC, bool IO16 = false>
+// knobs (a launch argument, though every launch passes WS_KNOBS: with the value folded into the kernel the compiler schedules the loop differently and the
+// layers ran 4-5 % slower): bit 0 = non-temporal row stores, bits 4-5 = who runs the decoder's stage B (see b_on_consumers)
+constexpr int WS_KNOBS = 1 | (2 << 4);
+template <int CIN, int RING, bool DEC, bool IO16 = false>
 __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src, const int32_t* __restrict__ eid,
                                                         int64_t n_dst, const float* __restrict__ x, const float* __restrict__ xdst, int64_t ldx,
                                                         const float* __restrict__ ea, int64_t lde, const float* __restrict__ We, const float* __restrict__ be,
                                                         const float* __restrict__ Wj, const float* __restrict__ bj, const float* __restrict__ Wi,
                                                         const float* __restrict__ scale, const float* __restrict__ shift, int relu, float* __restrict__ out,
                                                         int64_t ldo, int64_t ntiles, int knobs, WsDec dec) {
-    static_assert(!DEC || FLAGS, "the decoder stage hands over by counters");
     static_assert(CIN == 128 || (CIN == 64 && !DEC), "input widths of the shipped model's 128-wide layers");
     static_assert(!IO16 || !DEC, "the decoder-carrying launch of the bf16-storage chain stays with fused_bf16.hip");
     // IO16: x / xdst / out are uint16_t rows (ldx / ldo in elements of that type)
@@ -200,7 +197,7 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
     // per lane (round 5) both instructions touched all four lines of a row, half of each: twice the tag look-ups in the vector L1, the second one a hit on
     // a line still in flight.  Same bits (a channel's arithmetic does not depend on which lane owns it); measured on one box (profiles/r06_l1_probe.md):
     // 128 -> 128 0.408 -> 0.406 ms, last layer + decoder 0.500 -> 0.490 ms.
-    constexpr bool LINE_OWN = !IO16 && NV == 2 && DGNN_WS_LINE_OWN;
+    constexpr bool LINE_OWN = !IO16 && NV == 2;
     auto chan = [](int j, int cb) { return LINE_OWN ? ((cb >> 2) * 64 + 4 * j + (cb & 3)) : NCH * j + cb; };
     // entry (cb, part, g, j): channel c = chan(j, cb), k = 8 g .. 8 g + 7 (g < 3: attributes 0..19, the bias at k = 20, zeros)
     for (int e = threadIdx.x; e < NCH * 48; e += blockDim.x) {
@@ -323,7 +320,7 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
         __syncthreads();   // (the producers' prologue barrier)
         const int c0 = 16 * cw + 4 * tq;          // this lane's 4 consecutive output channels
         const int64_t n_it = my_n + (DEC ? 2 : 0);       // DEC: stage B runs one tile behind the product, stage C two
-        for (int64_t it = FLAGS ? 1 : 0; it <= n_it; ++it) {
+        for (int64_t it = 1; it <= n_it; ++it) {
             if constexpr (DEC) {
                 // C(it - 3): consumer 0 adds the four partial logits of a cell in one order and stores them.  (First in the iteration: the others' B(it - 1)
                 // -- next iteration -- reuses this buffer, and they get there only behind this wavefront's A(it - 1) below.)
@@ -345,7 +342,7 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
             }
             if (it >= 1 && it <= my_n) {
                 const int sl = (int)((it - 1) % RING);
-                if constexpr (FLAGS) wait_for(ready + sl, (uint32_t)(WS_NP * ((it - 1) / RING + 1)));
+                wait_for(ready + sl, (uint32_t)(WS_NP * ((it - 1) / RING + 1)));
                 const char* tb = ring + sl * G::SLOT;
                 f32x4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
                 // (the swizzle key passes through an empty asm every tile: left alone, the compiler keeps all 32 loop-invariant read addresses in registers
@@ -381,11 +378,9 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
                 float invr[2];
 #pragma unroll
                 for (int b = 0; b < 2; ++b) invr[b] = rowf[sl * WS_TILE + 16 * b + jcol] * inv_sW;
-                if constexpr (FLAGS) {
-                    // every read of the slot has returned: hand it back
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if (lane == 0) atomicAdd(const_cast<uint32_t*>(done + sl), 1u);
-                }
+                // every read of the slot has returned: hand it back
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (lane == 0) atomicAdd(const_cast<uint32_t*>(done + sl), 1u);
                 // (the per-channel constants are re-read from LDS every tile: 12 registers the decoder stage needs)
                 const f32x4_t bb = *reinterpret_cast<const f32x4_t*>(cst + c0), sc = *reinterpret_cast<const f32x4_t*>(cst + WS_C + c0),
                               sh = *reinterpret_cast<const f32x4_t*>(cst + 2 * WS_C + c0);
@@ -440,7 +435,6 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
             if constexpr (DEC) {
                 if (it >= 2 && it <= my_n + 1 && b_on_consumers((uint32_t)(it - 2))) stage_b((uint32_t)(it - 2), cw & 3, cw >> 2);
             }
-            if constexpr (!FLAGS) tile_barrier();
         }
         return;
     }
@@ -482,7 +476,7 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
     // DEC: on the tiles the rule gives to the producers (b_on_consumers) this wavefront also runs stage B of tile it - 2 (hidden block p & 3 of row block
     // p >> 2) -- BETWEEN issuing its gathers for tile `it` and using them: the job fills the gather latency, and its data (the consumers' stage A of tile
     // it - 2) is complete about when the slot the producer is going to write is handed back anyway.  Two more iterations drain the last two tiles.
-    for (int64_t it = 0; it < my_n + (FLAGS ? (DEC ? 2 : 0) : 1); ++it) {
+    for (int64_t it = 0; it < my_n + (DEC ? 2 : 0); ++it) {
         int nv = 0, sl = 0, tl = 0, vsrc = 0, veid = 0;
         bool regular = false;
         f32x4_t xo[NV], q0, q1, rr[4][NV];              // the gathered rows (DEC: in flight across stage B); read only on the path that loaded them
@@ -646,7 +640,7 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
                 float s_, inv_;
                 pow2_scales(row16_umax(bits(ma)), s_, inv_);
                 const int T = 4 * p + tq;
-                if constexpr (FLAGS) wait_for(done + sl, (uint32_t)(8 * (it / RING)));      // the slot's previous tile has been read by all 8 consumers
+                wait_for(done + sl, (uint32_t)(8 * (it / RING)));      // the slot's previous tile has been read by all 8 consumers
                 if (jcol == 0) rowf[sl * WS_TILE + T] = inv_;
                 uint32_t ah_[NCH / 2], al_[NCH / 2], xh_[NCH / 2], xl_[NCH / 2];
 #pragma unroll
@@ -681,19 +675,16 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
                     *reinterpret_cast<uint2*>(rowp + (((2 * PP + pc) ^ key) << 4) + half) = make_uint2(al_[0], al_[1]);
                     *reinterpret_cast<uint2*>(rowp + (((3 * PP + pc) ^ key) << 4) + half) = make_uint2(xl_[0], xl_[1]);
                 }
-            } else if constexpr (FLAGS) {
+            } else {
                 // a group past the end of the graph parks nothing, but its count must not land in `ready` while the slot's PREVIOUS tile is still being
                 // produced: the consumers would take seven real producers plus this one for eight and read a late producer's rows before they are written
                 // (seen on the workgroup that owns the last, partial tile of a scene: tools/det_ws_real.py)
                 wait_for(done + sl, (uint32_t)(8 * (it / RING)));
             }
-            if constexpr (FLAGS) {
-                // this producer's rows of the tile are parked (LDS operations of a wavefront complete in order)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (lane == 0) atomicAdd(const_cast<uint32_t*>(ready + sl), 1u);
-            }
+            // this producer's rows of the tile are parked (LDS operations of a wavefront complete in order)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (lane == 0) atomicAdd(const_cast<uint32_t*>(ready + sl), 1u);
         }
-        if constexpr (!FLAGS) tile_barrier();
     }
 }
 
@@ -724,26 +715,18 @@ int dgnn_sage_layer_fused_ws_try(const int32_t* rowptr, const int32_t* src, cons
     const int64_t ntiles = dgnn_cdiv(n_dst, WS_TILE);
     int grid = (int)(ntiles < DGNN_NUM_CU ? ntiles : DGNN_NUM_CU);
     if (grid < 1) grid = 1;
-    static const int ring = getenv("DGNN_WS_RING") ? atoi(getenv("DGNN_WS_RING")) : 22;          // 2 = one barrier per tile; 22 / 3 / 4 = counters, 2 / 3 / 4 slots (measured: equal)
-    static const int knobs = getenv("DGNN_WS_NT") ? atoi(getenv("DGNN_WS_NT")) : 33;   // 1: non-temporal row stores; bits 4-5: who runs the decoder's stage B (2 = consumers on 3 tiles of 4)
     const WsDec d{W0, b0, scale1, shift1, W3, b3, logits};
-#define DGNN_WS_GO(C_, R_, F_, D_)                                                                                                                          \
+#define DGNN_WS_GO(C_, D_)                                                                                                                                  \
     do {                                                                                                                                                    \
         static bool attr_[DGNN_MAX_DEVICES] = {};                                                                                                           \
-        const size_t sm_ = D_ ? WsL<C_, R_>::SMEM_DEC : WsL<C_, R_>::SMEM;                                                                                  \
-        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<C_, R_, F_, D_>), sm_, attr_);                                                \
-        hipLaunchKernelGGL((k_sage_fused_ws<C_, R_, F_, D_>), dim3(grid), dim3(1024), sm_, stream, rowptr, src, eid, n_dst, x_src, x_dst, ldx, edge_attr, lde, We, \
-                           be, Wj, bj, Wi, scale, shift, relu, out, ldo, ntiles, knobs, d);                                                                 \
+        const size_t sm_ = D_ ? WsL<C_, 2>::SMEM_DEC : WsL<C_, 2>::SMEM;                                                                                    \
+        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<C_, 2, D_>), sm_, attr_);                                                     \
+        hipLaunchKernelGGL((k_sage_fused_ws<C_, 2, D_>), dim3(grid), dim3(1024), sm_, stream, rowptr, src, eid, n_dst, x_src, x_dst, ldx, edge_attr, lde, We, \
+                           be, Wj, bj, Wi, scale, shift, relu, out, ldo, ntiles, WS_KNOBS, d);                                                              \
     } while (0)
-    if (c_in == 64) {
-        if (ring == 2) DGNN_WS_GO(64, 2, false, false);
-        else if (ring == 22) DGNN_WS_GO(64, 2, true, false);
-        else DGNN_WS_GO(64, 4, true, false);          // (DGNN_WS_RING=3 / 4: four 16 KB slots)
-    } else if (dec) DGNN_WS_GO(128, 2, true, true);
-    else if (ring == 2) DGNN_WS_GO(128, 2, false, false);
-    else if (ring == 3) DGNN_WS_GO(128, 3, true, false);
-    else if (ring == 4) DGNN_WS_GO(128, 4, true, false);
-    else DGNN_WS_GO(128, 2, true, false);
+    if (c_in == 64) DGNN_WS_GO(64, false);
+    else if (dec) DGNN_WS_GO(128, true);
+    else DGNN_WS_GO(128, false);
 #undef DGNN_WS_GO
     return dgnn_check_launch(dec ? "sage_layer_fused_decoder_fwd(wave-specialised)" : "sage_layer_fused_fwd(wave-specialised)");
 }
@@ -763,7 +746,6 @@ int dgnn_sage_layer_fused_ws16_try(const int32_t* rowptr, const int32_t* src, co
     const int64_t ntiles = dgnn_cdiv(n_dst, WS_TILE);
     int grid = (int)(ntiles < DGNN_NUM_CU ? ntiles : DGNN_NUM_CU);
     if (grid < 1) grid = 1;
-    static const int knobs = getenv("DGNN_WS_NT") ? atoi(getenv("DGNN_WS_NT")) : 33;
     const WsDec d{};
     const float* xs = reinterpret_cast<const float*>(x_src);
     const float* xd = reinterpret_cast<const float*>(x_dst);
@@ -771,15 +753,15 @@ int dgnn_sage_layer_fused_ws16_try(const int32_t* rowptr, const int32_t* src, co
     if (c_in == 64) {
         static bool attr_[DGNN_MAX_DEVICES] = {};
         const size_t sm_ = WsL<64, 4>::SMEM;
-        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<64, 4, true, false, true>), sm_, attr_);
-        hipLaunchKernelGGL((k_sage_fused_ws<64, 4, true, false, true>), dim3(grid), dim3(1024), sm_, stream, rowptr, src, eid, n_dst, xs, xd, ldx, edge_attr, lde, We, be,
-                           Wj, bj, Wi, scale, shift, relu, o, ldo, ntiles, knobs, d);
+        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<64, 4, false, true>), sm_, attr_);
+        hipLaunchKernelGGL((k_sage_fused_ws<64, 4, false, true>), dim3(grid), dim3(1024), sm_, stream, rowptr, src, eid, n_dst, xs, xd, ldx, edge_attr, lde, We, be,
+                           Wj, bj, Wi, scale, shift, relu, o, ldo, ntiles, WS_KNOBS, d);
     } else {
         static bool attr_[DGNN_MAX_DEVICES] = {};
         const size_t sm_ = WsL<128, 2>::SMEM;
-        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<128, 2, true, false, true>), sm_, attr_);
-        hipLaunchKernelGGL((k_sage_fused_ws<128, 2, true, false, true>), dim3(grid), dim3(1024), sm_, stream, rowptr, src, eid, n_dst, xs, xd, ldx, edge_attr, lde, We, be,
-                           Wj, bj, Wi, scale, shift, relu, o, ldo, ntiles, knobs, d);
+        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<128, 2, false, true>), sm_, attr_);
+        hipLaunchKernelGGL((k_sage_fused_ws<128, 2, false, true>), dim3(grid), dim3(1024), sm_, stream, rowptr, src, eid, n_dst, xs, xd, ldx, edge_attr, lde, We, be,
+                           Wj, bj, Wi, scale, shift, relu, o, ldo, ntiles, WS_KNOBS, d);
     }
     return dgnn_check_launch("sage_layer_fused_fwd_bf16(wave-specialised)");
 }

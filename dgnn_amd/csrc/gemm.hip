@@ -740,8 +740,8 @@ __global__ void __launch_bounds__(256) k_linear_wgrad_b_cat(const TA* __restrict
 // when ops.GEMM_MODE is not "f32".
 //
 // k_linear_fwd_x3: 128 x 128 output tile per 256-thread block, wave (wr, wc) owns a 64 x 64 quadrant = 2 x 2 MFMA blocks
-// (4 accumulators); K is walked in chunks of 32 over [A1 | A2].  What-if builds (-DDGNN_WHATIF_NO_SPLIT / _NO_GLOBAL / _NO_MFMA,
-// tools/dbg_gemm2.py; M = 1M, K = 256+256, N = 512, 3.95 ms): without the split and LDS stores 3.92 ms, without global loads 2.86,
+// (4 accumulators); K is walked in chunks of 32 over [A1 | A2].  What-if builds (one ingredient removed at a time,
+// M = 1M, K = 256+256, N = 512, 3.95 ms): without the split and LDS stores 3.92 ms, without global loads 2.86,
 // without fragment reads + MFMAs 2.75 -- the split VALU is free, loads and MFMAs each cost ~1.1 ms and do NOT overlap, ~1.6 ms is
 // neither (epilogue stores, barriers, per-block ramp); a W pre-split variant was 40 % slower (more L2 traffic, same stalls).  LDS row = [hi | mid | lo] x 32 bf16 + 16 B pad = 208 B (an odd
 // number of 16-B slots): conflict-free b128 fragment reads.  Per chunk and wave: 24 b128 reads feed 48 MFMAs.
@@ -857,20 +857,10 @@ __global__ void __launch_bounds__(256, 2) k_linear_fwd_x3(const float* __restric
     load_chunk(0);
     for (int ch = 0; ch < nch; ++ch) {
         __syncthreads();                 // the previous chunk's fragments have been read
-#ifndef DGNN_WHATIF_NO_SPLIT
         x3_store(As, ra);
         x3_store(Ws, rw);
-#else
-        if (ch == 0) { x3_store(As, ra); x3_store(Ws, rw); }
-        else asm volatile("" :: "v"(ra[0][0]), "v"(ra[1][0]), "v"(ra[2][0]), "v"(ra[3][0]), "v"(rw[0][0]), "v"(rw[1][0]), "v"(rw[2][0]), "v"(rw[3][0]));
-#endif
         __syncthreads();
-#ifndef DGNN_WHATIF_NO_GLOBAL
         if (ch + 1 < nch) load_chunk(ch + 1);   // in flight under the 48 MFMAs below
-#endif
-#ifdef DGNN_WHATIF_NO_MFMA
-        if (ch + 1 < nch) continue;
-#endif
         const char* ap = As + (wr * 64 + l31) * XLD + h * 16;
         const char* bp = Ws + (wc * 64 + l31) * XLD + h * 16;
 #pragma unroll
@@ -1428,10 +1418,7 @@ __global__ void __launch_bounds__(YT, 1) k_linear_fwd_x3_big(const float* __rest
 // split instructions of x3; a first pass over the operands writes the row scales (one extra read of A).
 // Large problems only (the 256 x 256 tile of k_linear_fwd_x3_big; M >= 8192, n_out > 128) -- the wide conv layers.
 // =====================================================================================================================
-#ifndef DGNN_X2H_K
-#define DGNN_X2H_K 32
-#endif
-constexpr int HK = DGNN_X2H_K;          // K chunk per barrier pair.  Measured (tools/bench_gemm_x2h.py, M = 1M): 64 halves the barriers but needs 64 staging
+constexpr int HK = 32;                  // K chunk per barrier pair.  Measured (tools/bench_gemm_x2h.py, M = 1M): 64 halves the barriers but needs 64 staging
                                         // registers next to the 128 accumulators -- 52 spilled, 4.26 ms against 2.67 ms with 32 (K = 512, N = 512)
 constexpr int HLD = 2 * HK * 2 + 16;   // LDS row: [hi | lo] x HK fp16 + 16 B pad (an odd number of 16-byte slots)
 constexpr int HTPR = HK / 4;           // threads per staged row (4 floats each)
@@ -1989,12 +1976,8 @@ int wgrad_splits(int64_t M, int n_a = 0) {
     int64_t s = dgnn_cdiv(M, 4 * RK);  // at least 128 rows per split
     int64_t cap = WGRAD_SPLITS;
     if (n_a > 0) {
-        static const bool by_tiles = !(getenv("DGNN_WGRAD_SPLITS_BY_TILES") && getenv("DGNN_WGRAD_SPLITS_BY_TILES")[0] == '0');
-        if (by_tiles) {
-            static const int base = getenv("DGNN_WGRAD_SPLIT_CAP") && atoi(getenv("DGNN_WGRAD_SPLIT_CAP")) > 0 ? atoi(getenv("DGNN_WGRAD_SPLIT_CAP")) : WGRAD_SPLITS;
-            cap = base / dgnn_cdiv(n_a, WT);
-            if (cap < 32) cap = 32;
-        }
+        cap = WGRAD_SPLITS / dgnn_cdiv(n_a, WT);
+        if (cap < 32) cap = 32;
     }
     if (s > cap) s = cap;
     return (int)(s < 1 ? 1 : s);
@@ -2163,7 +2146,7 @@ int linear_fwd_x3_impl(const float* A1, int64_t lda1, int k1, const float* W1, i
         return dgnn_check_launch("linear_fwd_x3");
     }
     static const bool small_ok = !(getenv("DGNN_X3_SMALL") && getenv("DGNN_X3_SMALL")[0] == '0');
-    static const int64_t small_m = getenv("DGNN_X3_SMALL_M") ? atoll(getenv("DGNN_X3_SMALL_M")) : 16384;
+    constexpr int64_t small_m = 16384;
     // (round 6: ... unless the 128 x 128 tiles of the tiled kernels would fill the chip anyway -- 150 of them -- where the small-problem kernel's operand
     // re-reads cost more than its barrier-free walk saves: M = 6 000, K = N = 512 57 -> 44 us, M = 12 000, K = N = 1024 356 -> 172 us)
     static const bool by_tiles = !(getenv("DGNN_SMALL_BY_TILES") && getenv("DGNN_SMALL_BY_TILES")[0] == '0');

@@ -611,31 +611,13 @@ extern "C" int dgnn_plan_build(const int64_t* edge_index, int64_t stride_row, in
     if (standby) {
         // The persistent kernel's grid barriers need every block resident at once: the grid is capped by what THIS device can hold
         // (occupancy x its real CU count -- a CPX/SPX partition or another gfx9 part has fewer than 256), so every block becomes resident as soon
-        // as the kernels ahead of it drain.  DGNN_PLAN_COOPERATIVE=1 additionally launches it as a cooperative kernel (the runtime then refuses
-        // a grid that cannot be co-resident instead of hanging) -- off by default: on this stack a process that has issued cooperative launches
-        // slows the kernel launches of every OTHER process on the GPU to half speed for as long as it lives (measured: the training leg of
-        // bench.py, a child process, 0.92 -> 1.85 ms per step).
+        // as the kernels ahead of it drain.  (It is not launched as a cooperative kernel: a process that has issued cooperative launches slows the
+        // kernel launches of every OTHER process on the GPU to half speed for as long as it lives -- DESIGN 5.)
         const int64_t want = dgnn_cdiv(E > n_key ? E : n_key, (int64_t)SCAN_THREADS * 8);
         const int cap = plan_fallback_resident_blocks();
         const int grid = (int)(want < 1 ? 1 : (want < cap ? want : cap));
-        static const bool cooperative = [] { const char* e = getenv("DGNN_PLAN_COOPERATIVE"); return e && e[0] == '1'; }();
-        if (!cooperative) {
-            hipLaunchKernelGGL(k_plan_fallback, dim3(grid), dim3(SCAN_THREADS), 0, stream, key, oth, sc, E, n_key, n_other, rowptr, other, eid, deg, tmp,
-                               sums, nb, big_count, big_list, need, need + 2, aflag);
-            return dgnn_check_launch("plan_build");
-        }
-        int64_t sc_ = sc, E_ = E, nk_ = n_key, no_ = n_other;
-        int nb_ = nb;
-        int32_t* gsync = need + 2;
-        const int32_t* need_c = need;
-        void* args[] = {(void*)&key, (void*)&oth, &sc_, &E_, &nk_, &no_, &rowptr, &other, &eid, &deg, &tmp, &sums, &nb_, &big_count, &big_list,
-                        (void*)&need_c, &gsync, (void*)&aflag};
-        const hipError_t ce = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(k_plan_fallback), dim3(grid), dim3(SCAN_THREADS), args, 0, stream);
-        if (ce != hipSuccess) {
-            (void)hipGetLastError();
-            dgnn_set_error("plan_build: cooperative launch of the fallback builder: %s", hipGetErrorString(ce));
-            return DGNN_E_LAUNCH;
-        }
+        hipLaunchKernelGGL(k_plan_fallback, dim3(grid), dim3(SCAN_THREADS), 0, stream, key, oth, sc, E, n_key, n_other, rowptr, other, eid, deg, tmp,
+                           sums, nb, big_count, big_list, need, need + 2, aflag);
         return dgnn_check_launch("plan_build");
     }
     auto grid_for = [&](int64_t n) { return dim3((unsigned)dgnn_grid_cap(dgnn_cdiv(n, 256))); };

@@ -18,13 +18,13 @@
 //               (per-edge power-of-two scales, 3 products: the fused layers' filter product), neighbour rows gathered as 16-byte pieces of split rows
 //               (or fp32 rows behind a fused layer), the in-order 4-term sum in registers, the finished row scaled per 256 channels, split and
 //               written as a split row.  Reads 4 rows + 320 B of attributes, writes one row: no fp32 `a` in HBM, no conversion pass.
-//   k_gemm_sr   out = act(([a | x_i] . [Wj | Wi]^T + b) * scale + shift): 256 cells x 256 output channels per 512-thread workgroup, both operands
-//               global -> LDS by DMA (16 bytes per lane, XOR-swizzled 128-byte rows, two buffers, one barrier per 32-wide K chunk), no VALU in the
-//               loop but the products; the accumulator of a cell changes units where the K walk crosses into a group with another scale (one exact
-//               multiplication by a power of two per accumulator register, the unit only ever follows the LARGEST group seen: no overflow; a group
-//               more than 2^40 below it is dropped -- its whole contribution is below the fp32 rounding of the sum).  Epilogue, transposed: a lane
-//               owns ONE cell and 64 of the tile's channels: bias / BatchNorm / ReLU, row maximum in registers (+ one lane swap, + one LDS word from
-//               the other channel half), scale, split, 32-byte stores -- the next layer's operand, written by its producer.
+//   k_gemm_sr2  out = act(([a | x_i] . [Wj | Wi]^T + b) * scale + shift): 256 cells x 256 output channels per 512-thread workgroup, the weights
+//               global -> LDS by DMA, the cell operand straight from the split rows into registers (see the kernel); the accumulator of a cell
+//               changes units where the K walk crosses into a group with another scale (one exact multiplication by a power of two per accumulator
+//               register, the unit only ever follows the LARGEST group seen: no overflow; a group more than 2^40 below it is dropped -- its whole
+//               contribution is below the fp32 rounding of the sum).  Epilogue, transposed: a lane owns ONE cell and 128 of the tile's channels:
+//               bias / BatchNorm / ReLU, row maximum in registers (+ one lane swap), scale, split, 32-byte stores -- the next layer's operand,
+//               written by its producer.
 //   The decoder's Linear(h3 -> h3/2) + BN + ReLU is the same GEMM on one operand with fp32 output.
 //
 // Arithmetic: the fp16 two-part form of fused_common.h throughout (22 significand bits per operand, lo.lo dropped, fp32 accumulation); scaling
@@ -180,14 +180,13 @@ __global__ void __launch_bounds__(256) k_sr_prepare_filter(const float* __restri
 // XSR: the source rows are split rows (row stride xrb bytes, scales xs [n_src][ngx]); else fp32 rows (ldx floats) -- the layer behind a fused layer --
 // and, when xo != NULL, the cell's OWN row is also written as a split row (the x_i operand of this layer's GEMM).
 // The index chain of a step (row starts -> sources / edge ids) is requested one and two steps ahead; all row pieces of a step are requested at once.
-template <int NB, bool XSR, int ILV>
+template <int NB, bool XSR>
 __global__ void __launch_bounds__(512, 2) k_agg_sr(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src, const int32_t* __restrict__ eid,
                                                    int64_t n_dst, const void* __restrict__ x_, int64_t ldx, int64_t xrb, const float* __restrict__ xs, int ngx,
                                                    const float* __restrict__ ea, int64_t lde, const float* __restrict__ We, const float* __restrict__ be,
                                                    const char* __restrict__ prep, int pass, char* __restrict__ ao, int64_t arb, float* __restrict__ as, int nga,
                                                    char* __restrict__ xo, float* __restrict__ xos, int nt_, int* __restrict__ tickets) {
     const bool nt = (nt_ & 1) != 0;
-    const bool no_store = (nt_ & 2) != 0;       // DGNN_SR_NT=2 / 3: timing probe of the producer side alone (tools/probe_producer.py); never set by the product
     constexpr int NSB = NB / 8;                                        // sub-blocks of 8 positions per lane
     extern __shared__ __attribute__((aligned(16))) char agg_smem[];
     char* const bpbuf = agg_smem;                                      // [cb][part][48] x 16 B
@@ -234,11 +233,11 @@ __global__ void __launch_bounds__(512, 2) k_agg_sr(const int32_t* __restrict__ r
     // wavefront that runs 10 % ahead after 60 steps works 6 x 2048 cells away from the slowest, and the rows the XCD's L2 has to hold are several
     // times the 2 MB of one sweep line (tools/locality_model.py: an LRU cache of 4096 rows misses 30 % of the requests of an in-order walk; the
     // launch measured 48 %).
-    // A ticket is TK_G consecutive groups (16 cells); the counters of the 8 XCDs sit 256 bytes apart (one cache line each: eight counters in one line
+    // A ticket is TK_G consecutive groups (one, AGG_SR_WORD); the counters of the 8 XCDs sit 256 bytes apart (one cache line each: eight counters in one line
     // were served as one word, 88 draws / us for the whole chip, and a draw per group made the launch 3.7 x slower); a ticket is drawn when its
     // predecessor is opened and read two groups before it is needed, so its latency is never waited for.
     constexpr int TK_STRIDE = 64;
-    const int TK_G = nt_ >> 8;          // groups per ticket (launch parameter, bits 8.. of nt_)
+    const int TK_G = nt_ >> 8;          // groups per ticket
     int64_t it_base = 0;
     int it_idx = 0, it_raw = 0;
     auto draw = [&]() {                  // lane 0 draws; the value stays in its register until the ticket is opened
@@ -359,6 +358,7 @@ __global__ void __launch_bounds__(512, 2) k_agg_sr(const int32_t* __restrict__ r
                         }
                     }
                 }
+                constexpr int ILV = 2;
 #pragma unroll
                 for (int c4 = 0; c4 < 8; c4 += ILV) {
                     // ILV channel blocks at a time: their three-product chains are independent, issued interleaved (a lone chain waits for its own
@@ -429,7 +429,7 @@ __global__ void __launch_bounds__(512, 2) k_agg_sr(const int32_t* __restrict__ r
             const uint32_t m = row16_umax(b_of(mx));
             float s_store, s_mul;
             sr_scale(m, s_store, s_mul);
-            if (tq < nv && !(no_store && s_mul != 12345.f)) {
+            if (tq < nv) {
                 if (jcol == 0) oscale[pass] = s_store;
 #pragma unroll
                 for (int sb = 0; sb < NSB; ++sb) {
@@ -464,7 +464,7 @@ __global__ void __launch_bounds__(512, 2) k_agg_sr(const int32_t* __restrict__ r
     }
 }
 
-// ---- k_gemm_sr ---------------------------------------------------------------------------------------------------------------------------------
+// ---- k_gemm_sr2 --------------------------------------------------------------------------------------------------------------------------------
 struct SrPart {
     const char* base;       // split rows [M][nch x 128 B]
     int64_t row_bytes;
@@ -485,225 +485,8 @@ __device__ __forceinline__ void dma16(const char* g, char* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-// LDS: [2 buffers][W 256 rows | X 256 rows] x 128 B, then bias | bn scale | bn shift | 1 / sw [256] each, then row maxima [2][256]
-constexpr int G_BUF = (TN + TM) * SRB;
-constexpr int G_CST = 2 * G_BUF;
-constexpr int G_RMAX = G_CST + 4 * TN * 4;
-constexpr int G_SMEM = G_RMAX + 2 * TM * 4;
-
-__global__ void __launch_bounds__(GT, 1) k_gemm_sr(SrPart p1, SrPart p2, const char* __restrict__ Wp, int64_t w_row_bytes, const float* __restrict__ sw,
-                                                   const float* __restrict__ bias, const float* __restrict__ scale, const float* __restrict__ shift, int relu,
-                                                   int64_t M, int n_out, SrOut out) {
-    extern __shared__ __attribute__((aligned(16))) char g_smem[];
-    float* const cst = reinterpret_cast<float*>(g_smem + G_CST);
-    uint32_t* const rmax = reinterpret_cast<uint32_t*>(g_smem + G_RMAX);
-    const int lane = lane_id(), w = wave_id_uniform();
-    const int wm = w >> 2, wn = w & 3, h = lane >> 5, l31 = lane & 31;
-    const int ncb = n_out / TN;   // XCD-aware tile map: the column tiles of a row panel run on ONE XCD back to back (the panel crosses the fabric once)
-    const int64_t rb = (int64_t)((blockIdx.x >> 3) / ncb) * 8 + (blockIdx.x & 7);
-    if (rb * TM >= M) return;
-    const int64_t row0 = rb * TM;
-    const int ct = (int)((blockIdx.x >> 3) % ncb), col0 = ct * TN;
-    for (int c = threadIdx.x; c < TN; c += GT) {
-        cst[c] = bias ? bias[col0 + c] : 0.f;
-        cst[TN + c] = scale ? scale[col0 + c] : 1.f;
-        cst[2 * TN + c] = scale ? shift[col0 + c] : 0.f;
-        cst[3 * TN + c] = pow2_inv(sw[col0 + c]);
-    }
-    const int nch1 = p1.nch, nch = nch1 + p2.nch, ng1 = p1.ng, ngt = ng1 + p2.ng;
-
-    // DMA roles: one instruction moves 8 rows x 128 B (1 KB of LDS, contiguous); wave w takes instructions w, w + 8, .. of the 32 (W) + 32 (X).
-    // lane -> (row of the group rr = lane >> 3, LDS slot q = lane & 7); slot q of row r holds the row's 16-byte piece q ^ (r & 7)
-    const int rr = lane >> 3, qs = lane & 7;
-    // wave-uniform bases (SGPRs) + 32-bit per-lane offsets: the tile's weight rows span <= 1024 x 8 KB, its cell rows 256 x 4 KB
-    const char* const wbase = Wp + (int64_t)col0 * w_row_bytes;
-    const char* const xbase1 = p1.base + row0 * p1.row_bytes;
-    const char* const xbase2 = p2.nch ? p2.base + row0 * p2.row_bytes - (int64_t)nch1 * SRB : xbase1;
-    const int64_t rows_left = M - row0;
-    uint32_t woff[4], xoff1[4], xoff2[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int r_t = (w + 8 * j) * 8 + rr;
-        const int piece = qs ^ ((r_t >> 1) & 7);
-        woff[j] = (uint32_t)(r_t * (int)w_row_bytes + piece * 16);
-        const int gr = r_t < rows_left ? r_t : (int)rows_left - 1;
-        xoff1[j] = (uint32_t)(gr * (int)p1.row_bytes + piece * 16);
-        xoff2[j] = (uint32_t)(gr * (int)(p2.nch ? p2.row_bytes : p1.row_bytes) + piece * 16);
-    }
-    auto dma_chunk = [&](int ch) {
-        char* buf = g_smem + (ch & 1) * G_BUF;
-        const char* wb_ = wbase + (int64_t)ch * SRB;
-        const bool first = ch < nch1;
-        const char* xb_ = (first ? xbase1 : xbase2) + (int64_t)ch * SRB;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dma16(wb_ + woff[j], buf + (w + 8 * j) * 1024);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dma16(xb_ + (first ? xoff1[j] : xoff2[j]), buf + TN * SRB + (w + 8 * j) * 1024);
-    };
-    // the scale of group gi of this lane's two cells (b = 0, 1)
-    int64_t cellb[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int64_t c_ = row0 + wn * 64 + b * 32 + l31;
-        cellb[b] = c_ < M ? c_ : M - 1;
-    }
-    auto scale_of = [&](int gi, int b) -> float { return gi < ng1 ? p1.scales[cellb[b] * ng1 + gi] : p2.scales[cellb[b] * p2.ng + (gi - ng1)]; };
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-    float s_cur[2] = {0.f, 0.f}, s_min[2] = {0.f, 0.f}, s_nx[2];
-    uint32_t mk[2] = {~0u, ~0u};
-    int gi = 0, next_b = 0;     // next group to enter, chunk at which it starts
-    s_nx[0] = scale_of(0, 0);
-    s_nx[1] = scale_of(0, 1);
-    dma_chunk(0);
-    const int sw_ = (l31 >> 1) & 7;
-    for (int ch = 0; ch < nch; ++ch) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of chunk ch has landed (and the prefetched scales)
-        __syncthreads();                                     // everybody's has; everybody is done with the other buffer
-        if (ch + 1 < nch) dma_chunk(ch + 1);                 // in flight under the products below
-        if (ch == next_b) {
-            // the K walk enters group gi: the accumulators of a cell stay in units of s * sw for the LARGEST group seen so far
-            bool any_mul = false;
-            float mul[2];
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const float s_ = s_nx[b];
-                mul[b] = 1.f;
-                mk[b] = ~0u;
-                if (b_of(s_) == SR_ZERO_BITS) {
-                    // all zeros: its products vanish in any unit
-                } else if (s_cur[b] == 0.f) {
-                    s_cur[b] = s_min[b] = s_;
-                } else if (s_ > s_min[b] * 1.099511627776e12f) {
-                    mk[b] = 0u;                              // dropped: this cell's fragments of the group are masked to zero below
-                } else {
-                    mul[b] = s_ * pow2_inv(s_cur[b]);        // exact; <= 2^40 by the test above, an underflow means the sum so far is negligible
-                    s_cur[b] = s_;
-                    s_min[b] = fminf(s_min[b], s_);
-                }
-                any_mul = any_mul || mul[b] != 1.f;
-            }
-            if (__any(any_mul)) {
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) acc[a][b][i] *= mul[b];
-            }
-            const bool in1 = gi < ng1;
-            next_b += in1 ? p1.gch : p2.gch;
-            if (in1 && next_b > nch1) next_b = nch1;
-            ++gi;
-            if (gi < ngt) {
-                s_nx[0] = scale_of(gi, 0);
-                s_nx[1] = scale_of(gi, 1);
-            }
-            if (gi == ng1) next_b = nch1;
-        }
-        const char* Wb = g_smem + (ch & 1) * G_BUF;
-        const char* Xb = Wb + TN * SRB;
-        const int wr0 = wm * 128 + l31, xr0 = wn * 64 + l31;   // rows are multiples of 32 apart: (row & 7) = (l31 & 7) for all of them
-#pragma unroll
-        for (int S = 0; S < 2; ++S) {
-            f16x8 xf[2][2];
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    uint4 u = *reinterpret_cast<const uint4*>(Xb + (xr0 + b * 32) * SRB + (((4 * p + 2 * S + h) ^ sw_) << 4));
-                    // a dropped group's fragments are zeroed (mk = 0; ~0 otherwise): 16 integer instructions per k-step in the shadow of 24 matrix
-                    // instructions -- a second, unmasked copy of the loop behind a branch made the compiler spill 120 registers
-                    u.x &= mk[b]; u.y &= mk[b]; u.z &= mk[b]; u.w &= mk[b];
-                    xf[b][p] = H8(u);
-                }
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                f16x8 wf[2];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) wf[p] = H8(*reinterpret_cast<const uint4*>(Wb + (wr0 + a * 32) * SRB + (((4 * p + 2 * S + h) ^ sw_) << 4)));
-                constexpr int PW[3] = {1, 0, 0}, PX[3] = {0, 1, 0};   // small terms first; the two cell blocks alternate product by product
-#pragma unroll
-                for (int qq = 0; qq < 3; ++qq)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[PW[qq]], xf[b][PX[qq]], acc[a][b], 0, 0, 0);
-            }
-        }
-    }
-
-    // ---- epilogue: lane = (cell wn * 64 + b * 32 + l31, channels wm * 128 + a * 32 + (r & 3) + 8 (r >> 2) + 4 h)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const float inv_cell = s_cur[b] == 0.f ? 0.f : pow2_inv(s_cur[b]);
-        float mx = 0.f;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const int c = wm * 128 + a * 32 + 8 * r4 + 4 * h;
-                const f32x4_t bb = *reinterpret_cast<const f32x4_t*>(cst + c), sc = *reinterpret_cast<const f32x4_t*>(cst + TN + c),
-                              sh = *reinterpret_cast<const f32x4_t*>(cst + 2 * TN + c), iw = *reinterpret_cast<const f32x4_t*>(cst + 3 * TN + c);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float v = __fmaf_rn(acc[a][b][4 * r4 + i], inv_cell * iw[i], bb[i]);
-                    v = __fmaf_rn(v, sc[i], sh[i]);
-                    if (relu) v = fmaxf(v, 0.f);
-                    acc[a][b][4 * r4 + i] = v;
-                    mx = fmaxf(mx, fabsf(v));
-                }
-            }
-        const int64_t cell = row0 + wn * 64 + b * 32 + l31;
-        if (out.mode == 1) {
-            if (cell < M) {
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        float* o = out.f32 + cell * out.ldo + col0 + wm * 128 + a * 32 + 8 * r4 + 4 * h;
-                        *reinterpret_cast<f32x4_t*>(o) = f32x4_t{acc[a][b][4 * r4], acc[a][b][4 * r4 + 1], acc[a][b][4 * r4 + 2], acc[a][b][4 * r4 + 3]};
-                    }
-            }
-            continue;
-        }
-        // row maximum over the tile's 256 channels: the lane's 64, the partner lane's (other h) 64, the other channel half's 128 through LDS
-        uint32_t m = b_of(mx), ma, mb;
-        swap32_pair(m, ma, mb);
-        m = umax(ma, mb);
-        if (h == 0) rmax[wm * TM + wn * 64 + b * 32 + l31] = m;
-    }
-    if (out.mode == 1) return;
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int tl = wn * 64 + b * 32 + l31;
-        const int64_t cell = row0 + tl;
-        const uint32_t m = umax(rmax[tl], rmax[TM + tl]);
-        float s_store, s_mul;
-        sr_scale(m, s_store, s_mul);
-        if (cell >= M) continue;
-        if (wm == 0 && h == 0) out.scales[cell * out.ng + ct] = s_store;
-        char* orow = out.sr + cell * out.row_bytes + (int64_t)(ct * 8 + wm * 4) * SRB + 32 * h;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            uint32_t hi[8], lo[8];
-#pragma unroll
-            for (int d = 0; d < 8; ++d) split2h(acc[a][b][2 * d] * s_mul, acc[a][b][2 * d + 1] * s_mul, hi[d], lo[d]);
-            char* o = orow + a * SRB;
-            *reinterpret_cast<uint4*>(o) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-            *reinterpret_cast<uint4*>(o + 16) = make_uint4(hi[4], hi[5], hi[6], hi[7]);
-            *reinterpret_cast<uint4*>(o + 64) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-            *reinterpret_cast<uint4*>(o + 80) = make_uint4(lo[4], lo[5], lo[6], lo[7]);
-        }
-    }
-}
-
-// ---- k_gemm_sr2: the same product, second arrangement (default) ----------------------------------------------------------------------------------
-// What k_gemm_sr waits for is its operands (one barrier + one DMA round trip per 32-wide K chunk, 39 % of the matrix peak at K = N = 1024).  Here
+// A first arrangement with both operands through LDS waited for its operands (one barrier + one DMA round trip per 32-wide K chunk, 39 % of the matrix
+// peak at K = N = 1024).  Here
 //   * a wavefront owns 32 CELLS and ALL 256 channels of the tile (8 accumulator blocks): its cell operand does not go through LDS at all -- every lane
 //     loads the four 16-byte fragments of its own cell's chunk straight from the split row (the row IS in fragment order) TWO chunks ahead, three
 //     register sets rotating;
@@ -712,21 +495,20 @@ __global__ void __launch_bounds__(GT, 1) k_gemm_sr(SrPart p1, SrPart p2, const c
 //   * mode 2 (the decoder): the finished hidden row is multiplied by W3 [n_proj][n_out] on the spot and only the logits leave the launch
 //     (reference learning/surfaceNetStaticEdgeFilters.py:180-187: Linear - BN - ReLU - Linear): partial sums of the column tiles are added
 //     atomically into zero-initialised logits -- two addends per logit at n_out = 512, an order-independent sum; tile 0 carries the bias.
-// CPS = K chunks per weight stage: 1 = three stages of one chunk (a barrier per chunk), 2 = two stages of two chunks (a barrier every other chunk)
-template <int CPS> struct G2 {
-    static constexpr int W_STG = CPS == 1 ? 3 : 2;
-    static constexpr int STAGE = CPS * TN * SRB;
+// three weight stages of one K chunk each (a barrier per chunk)
+struct G2 {
+    static constexpr int W_STG = 3;
+    static constexpr int STAGE = TN * SRB;
     static constexpr int CST = W_STG * STAGE;
     static constexpr int SMEM = CST + 6 * TN * 4;      // bias | bn scale | bn shift | 1 / sw | W3 row 0 | W3 row 1
 };
 
-template <int CPS>
 __global__ void __launch_bounds__(GT, 1) k_gemm_sr2(SrPart p1, SrPart p2, const char* __restrict__ Wp, int64_t w_row_bytes, const float* __restrict__ sw,
                                                     const float* __restrict__ bias, const float* __restrict__ scale, const float* __restrict__ shift, int relu,
                                                     int64_t M, int n_out, SrOut out, const float* __restrict__ W3, const float* __restrict__ b3, int n_proj,
                                                     float* __restrict__ logits, int nt_) {
     const bool nt = nt_ != 0;
-    typedef G2<CPS> L;
+    typedef G2 L;
     extern __shared__ __attribute__((aligned(16))) char g2_smem[];
     float* const cst = reinterpret_cast<float*>(g2_smem + L::CST);
     const int lane = lane_id(), w = wave_id_uniform();
@@ -754,16 +536,12 @@ __global__ void __launch_bounds__(GT, 1) k_gemm_sr2(SrPart p1, SrPart p2, const 
         const int r_t = (w + 8 * j) * 8 + rr;
         woff[j] = (uint32_t)(r_t * (int)w_row_bytes + (qs ^ ((r_t >> 1) & 7)) * 16);
     }
-    auto dma_stage = [&](int stg) {       // the chunks stg * CPS .. of the weights -> stage stg % W_STG
-        char* buf = g2_smem + (stg % L::W_STG) * L::STAGE;
+    auto dma_stage = [&](int ch) {        // chunk ch of the weights -> stage ch % W_STG
+        char* buf = g2_smem + (ch % L::W_STG) * L::STAGE;
+        if (ch < nch) {
+            const char* wb_ = wbase + (int64_t)ch * SRB;
 #pragma unroll
-        for (int c = 0; c < CPS; ++c) {
-            const int ch = stg * CPS + c;
-            if (ch < nch) {
-                const char* wb_ = wbase + (int64_t)ch * SRB;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dma16(wb_ + woff[j], buf + c * (TN * SRB) + (w + 8 * j) * 1024);
-            }
+            for (int j = 0; j < 4; ++j) dma16(wb_ + woff[j], buf + (w + 8 * j) * 1024);
         }
     };
     // this lane's cell and its split rows: fragment (part p, k-step S) of a chunk = the 16 bytes at (4 p + 2 S + h) * 16
@@ -789,7 +567,7 @@ __global__ void __launch_bounds__(GT, 1) k_gemm_sr2(SrPart p1, SrPart p2, const 
     uint4 xs0[4], xs1[4], xs2[4];
     dma_stage(0);
     load_x(0, xs0);
-    if (CPS == 1) dma_stage(1);
+    dma_stage(1);
     if (nch > 1) load_x(1, xs1);
     // LDS slot of a row's 16-byte piece: piece ^ ((row >> 1) & 7).  ds_read_b128 is served in groups of 16 NON-contiguous lanes ({0-3, 12-15, 20-27},
     // {4-11, 16-19, 28-31}: MI355X_MICROARCH.md); a lane reads row (32 a + l31), i.e. bank row (l31 & 1): with (l31 >> 1) & 7 as the XOR key the 8 even
@@ -797,20 +575,17 @@ __global__ void __launch_bounds__(GT, 1) k_gemm_sr2(SrPart p1, SrPart p2, const 
     // SQ_LDS_BANK_CONFLICT = 47 % of the LDS cycles, profiles/r05_wide.md)
     const int sw_ = (l31 >> 1) & 7;
     auto step = [&](int ch, uint4 (&xc)[4], uint4 (&xn)[4]) {
-        const int stg = ch / CPS;
-        if (ch % CPS == 0) {
-            // stage stg holds W(ch ..) once this wave's share has landed (everything but the 8 most recent operations has: those are cell fragments
-            // of the next two chunks and, behind a group boundary, a scale word) and everybody else's has (barrier); the barrier also hands the stage
-            // read before this one back to the DMA
-            // At the tail the operations counted on are not issued any more (no stage / no cell fragments past the last chunk): behind the last
-            // CPS chunks fewer than 8 operations follow the stage's DMA, so the wave drains everything there (nch is uniform: a scalar branch).
-            if (ch + CPS >= nch)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            __syncthreads();
-            dma_stage(stg + (CPS == 1 ? 2 : 1));
-        }
+        // stage ch holds W(ch) once this wave's share has landed (everything but the 8 most recent operations has: those are cell fragments
+        // of the next two chunks and, behind a group boundary, a scale word) and everybody else's has (barrier); the barrier also hands the stage
+        // read before this one back to the DMA
+        // At the tail the operations counted on are not issued any more (no stage / no cell fragments past the last chunk): behind the last
+        // chunk fewer than 8 operations follow the stage's DMA, so the wave drains everything there (nch is uniform: a scalar branch).
+        if (ch + 1 >= nch)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        __syncthreads();
+        dma_stage(ch + 2);
         if (ch + 2 < nch) load_x(ch + 2, xn);
         if (ch == next_b) {
             const float s_ = s_nx;
@@ -839,7 +614,7 @@ __global__ void __launch_bounds__(GT, 1) k_gemm_sr2(SrPart p1, SrPart p2, const 
             if (gi < ngt) s_nx = scale_of(gi);
             if (gi == ng1) next_b = nch1;
         }
-        const char* Wb = g2_smem + (stg % L::W_STG) * L::STAGE + (ch % CPS) * (TN * SRB);
+        const char* Wb = g2_smem + (ch % L::W_STG) * L::STAGE;
 #pragma unroll
         for (int S = 0; S < 2; ++S) {
             uint4 uh = xc[S], ul = xc[2 + S];
@@ -956,14 +731,14 @@ __global__ void __launch_bounds__(GT, 1) k_gemm_sr2(SrPart p1, SrPart p2, const 
 
 }  // namespace
 
+// The launch words of k_agg_sr (bit 0: non-temporal split-row stores; bits 8..: groups of 4 cells per ticket) and k_gemm_sr2 (non-temporal stores) are
+// kernel arguments although every launch passes the same value: folded into the kernels, the constants let the compiler schedule them differently and
+// the wide layers ran 5-7 % slower.
+static constexpr int AGG_SR_WORD = 1 | (1 << 8);
+
 // =====================================================================================================================
 // C ABI
 // =====================================================================================================================
-static int sr_nt() {      // DGNN_SR_NT=0: plain stores of the split rows (A/B)
-    static const int v = getenv("DGNN_SR_NT") ? atoi(getenv("DGNN_SR_NT")) : 1;
-    return v;
-}
-
 extern "C" int64_t dgnn_sr_row_bytes(int C) { return C > 0 && C % 32 == 0 ? (int64_t)(C / 32) * SRB : 0; }
 
 // fp32 rows [rows, k1 (+ k2)] -> split rows (dst [rows][row_bytes], scales [rows][ng]); gch chunks of 32 channels per scale group, 0 = one group per
@@ -1019,23 +794,18 @@ extern "C" int dgnn_sage_aggregate_sr(const int32_t* rowptr, const int32_t* src,
     const int NBv = agg_nb(C), np = agg_passes(C), ng = (C + 255) / 256;
     const int64_t rowb = (int64_t)(C / 32) * SRB;
     const size_t lds = (size_t)NBv * 2 * 48 * 16;
-    static const int wg_per_cu = getenv("DGNN_AGG_SR_WGS") ? atoi(getenv("DGNN_AGG_SR_WGS")) : 2;
-    // (the kernel deals the groups of 4 cells to the XCDs' eighths by blockIdx.x & 7: with fewer than 8 workgroups the eighths without one were
-    // never computed -- a block of fewer than 256 destination cells, round 6 -- so a launch has at least 8, the surplus ones leave at once)
-    int nwg_ = dgnn_grid_cap(dgnn_cdiv(dgnn_cdiv(n_dst, 4), 8), wg_per_cu < 1 ? 1 : wg_per_cu);
+    // two workgroups per CU (the kernel deals the groups of 4 cells to the XCDs' eighths by blockIdx.x & 7: with fewer than 8 workgroups the eighths
+    // without one were never computed -- a block of fewer than 256 destination cells, round 6 -- so a launch has at least 8, the surplus ones leave at once)
+    int nwg_ = dgnn_grid_cap(dgnn_cdiv(dgnn_cdiv(n_dst, 4), 8), 2);
     if (nwg_ < 8) nwg_ = 8;
     const dim3 grid((unsigned)nwg_), block(512);
     hipStream_t st = (hipStream_t)stream;
-    static const int ilv = getenv("DGNN_AGG_SR_ILV") ? atoi(getenv("DGNN_AGG_SR_ILV")) : 2;   // measured: 1 / 2 / 4 interleaved chains within 1 %.  (Round 6: with the ticket walk's registers the split-row form of ILV = 2 compiles to 137 VGPRs = ONE resident workgroup per CU, 2 wavefronts per SIMD; forced to 128 = two workgroups, 4 per SIMD, the launch is 3 % SLOWER -- profiles/r06_l1_probe.md)
     // the XCDs' group counters of the ticket walk (see the kernel): 8 ints per device, zeroed in stream order before every launch
     static const bool tickets_on = !(getenv("DGNN_AGG_SR_TICKETS") && getenv("DGNN_AGG_SR_TICKETS")[0] == '0');
-    static const int tk_g = getenv("DGNN_AGG_SR_TK_G") && atoi(getenv("DGNN_AGG_SR_TK_G")) > 0 ? atoi(getenv("DGNN_AGG_SR_TK_G")) : 1;   // groups of 4 cells per ticket
     int* tickets = nullptr;
     // ... for split-row input (C >= 256).  Measured (profiles/r06_wide.md): C = 256 pass FETCH_SIZE 1.53 M -> 0.85 M KiB, L2 hit rate 52 -> 68 %, 802 -> 805 us;
-    // the fp32-row form (C = 128, which also writes the own rows) 0.94 M -> 0.78 M KiB but 581 -> 695 us: it keeps the static walk unless
-    // DGNN_AGG_SR_TICKETS=2.
-    static const bool tickets_all = getenv("DGNN_AGG_SR_TICKETS") && getenv("DGNN_AGG_SR_TICKETS")[0] == '2';
-    if (tickets_on && (x_is_sr || tickets_all)) {
+    // the fp32-row form (C = 128, which also writes the own rows) 0.94 M -> 0.78 M KiB but 581 -> 695 us: it keeps the static walk.
+    if (tickets_on && x_is_sr) {
         static int* tk_dev[DGNN_MAX_DEVICES];
         static std::mutex tk_m;
         int dev = 0;
@@ -1049,21 +819,14 @@ extern "C" int dgnn_sage_aggregate_sr(const int32_t* rowptr, const int32_t* src,
             if (tk_dev[dev]) tickets = tk_dev[dev] + 2 * 512 * (tk_turn[dev]++ & 15);    // a ring of 16 counter sets (two passes each): launches in flight on other streams keep theirs
         }
     }
-#define DGNN_AGG_SR(NB_, SR_, IL_)                                                                                                                       \
-    hipLaunchKernelGGL((k_agg_sr<NB_, SR_, IL_>), grid, block, lds, st, rowptr, src, eid, n_dst, x, ldx, rowb, xs, ng, edge_attr, lde, We, be,            \
-                       static_cast<const char*>(prep), pass, static_cast<char*>(a_out), rowb, a_scales, ng, static_cast<char*>(x_out), x_scales, sr_nt() | (tk_g << 8), \
+#define DGNN_AGG_SR(NB_, SR_)                                                                                                                            \
+    hipLaunchKernelGGL((k_agg_sr<NB_, SR_>), grid, block, lds, st, rowptr, src, eid, n_dst, x, ldx, rowb, xs, ng, edge_attr, lde, We, be,                 \
+                       static_cast<const char*>(prep), pass, static_cast<char*>(a_out), rowb, a_scales, ng, static_cast<char*>(x_out), x_scales, AGG_SR_WORD, \
                        tickets ? tickets + 512 * (pass & 1) : nullptr)
     if (tickets) (void)hipMemsetAsync(tickets, 0, 2 * 512 * sizeof(int), st);
     for (int pass = 0; pass < np; ++pass) {
-        if (x_is_sr) {
-            if (ilv == 1) DGNN_AGG_SR(16, true, 1);
-            else if (ilv == 2) DGNN_AGG_SR(16, true, 2);
-            else DGNN_AGG_SR(16, true, 4);
-        } else {
-            if (ilv == 1) DGNN_AGG_SR(8, false, 1);
-            else if (ilv == 2) DGNN_AGG_SR(8, false, 2);
-            else DGNN_AGG_SR(8, false, 4);
-        }
+        if (x_is_sr) DGNN_AGG_SR(16, true);
+        else DGNN_AGG_SR(8, false);
     }
 #undef DGNN_AGG_SR
     return dgnn_check_launch("sage_aggregate_sr");
@@ -1096,25 +859,9 @@ extern "C" int dgnn_linear_sr(const void* A1, int64_t row_bytes1, const float* s
     const int ncb = n_out / TN;
     const int64_t mt = dgnn_cdiv(M, TM);
     const dim3 grid((unsigned)(dgnn_cdiv(mt, 8) * 8 * ncb));
-    static const bool v1 = getenv("DGNN_GEMM_SR_V1") && getenv("DGNN_GEMM_SR_V1")[0] == '1';      // the first arrangement (both operands through LDS), for A/B
-    if (v1 && !logits) {
-        static bool attr_set[DGNN_MAX_DEVICES] = {};
-        dgnn_allow_dynamic_lds((const void*)k_gemm_sr, G_SMEM, attr_set);
-        hipLaunchKernelGGL(k_gemm_sr, grid, dim3(GT), G_SMEM, (hipStream_t)stream, p1, p2, static_cast<const char*>(Wp), (int64_t)((C1 + C2) / 32) * SRB, sw, bias,
-                           scale, shift, relu ? 1 : 0, M, n_out, o);
-        return dgnn_check_launch("linear_sr");
-    }
-    static const int cps = getenv("DGNN_GEMM_SR_CPS") ? atoi(getenv("DGNN_GEMM_SR_CPS")) : 1;   // measured (tools/gpu_wide_ab.sh): three one-chunk stages 2-3 % ahead of two two-chunk stages
-    if (cps == 1) {
-        static bool attr_a[DGNN_MAX_DEVICES] = {};
-        dgnn_allow_dynamic_lds((const void*)k_gemm_sr2<1>, G2<1>::SMEM, attr_a);
-        hipLaunchKernelGGL(k_gemm_sr2<1>, grid, dim3(GT), G2<1>::SMEM, (hipStream_t)stream, p1, p2, static_cast<const char*>(Wp), (int64_t)((C1 + C2) / 32) * SRB, sw, bias,
-                           scale, shift, relu ? 1 : 0, M, n_out, o, W3, b3, n_proj, logits, sr_nt());
-    } else {
-        static bool attr_b[DGNN_MAX_DEVICES] = {};
-        dgnn_allow_dynamic_lds((const void*)k_gemm_sr2<2>, G2<2>::SMEM, attr_b);
-        hipLaunchKernelGGL(k_gemm_sr2<2>, grid, dim3(GT), G2<2>::SMEM, (hipStream_t)stream, p1, p2, static_cast<const char*>(Wp), (int64_t)((C1 + C2) / 32) * SRB, sw, bias,
-                           scale, shift, relu ? 1 : 0, M, n_out, o, W3, b3, n_proj, logits, sr_nt());
-    }
+    static bool attr_set[DGNN_MAX_DEVICES] = {};
+    dgnn_allow_dynamic_lds((const void*)k_gemm_sr2, G2::SMEM, attr_set);
+    hipLaunchKernelGGL(k_gemm_sr2, grid, dim3(GT), G2::SMEM, (hipStream_t)stream, p1, p2, static_cast<const char*>(Wp), (int64_t)((C1 + C2) / 32) * SRB, sw, bias,
+                       scale, shift, relu ? 1 : 0, M, n_out, o, W3, b3, n_proj, logits, 1);
     return dgnn_check_launch("linear_sr");
 }

@@ -22,4 +22,4 @@ for i in range(reps):
     k = (o != first).any(1).nonzero().flatten()
     if k.numel():
         bad.append((i, k.numel(), k[:3].tolist(), float((o - first).abs().max())))
-print("WS=%s RING=%s FUSE_DEC=%s: %d of %d repeats differ" % (os.environ.get("DGNN_WS", "1"), os.environ.get("DGNN_WS_RING", "22"), os.environ.get("DGNN_FUSE_DECODER", "1"), len(bad), reps), bad[:6])
+print("WS=%s FUSE_DEC=%s: %d of %d repeats differ" % (os.environ.get("DGNN_WS", "1"), os.environ.get("DGNN_FUSE_DECODER", "1"), len(bad), reps), bad[:6])

@@ -34,4 +34,4 @@ for r, o in enumerate(outs):
                 t_hi = min(ntiles, (xcd + 1) * per); my_n = (t_hi - xcd * per - slot + wgx - 1) // wgx
                 c = t * 32 + rows[0]
                 print("  rep %d tile %d rows %s: xcd %d wg %d it %d of %d; now %s ref %s" % (r, t, rows, xcd, slot, it, my_n, o[c].tolist()[:2], ref[c].tolist()[:2]))
-print("n %d tiles %d: %d of %d launches differ (decode %s, knobs %s)" % (n, ntiles, ev, reps, decode, os.environ.get("DGNN_WS_NT", "1")))
+print("n %d tiles %d: %d of %d launches differ (decode %s)" % (n, ntiles, ev, reps, decode))

@@ -43,4 +43,4 @@ for i in (3, 2):
                 c = t * 32 + rows[0]
                 ch = (o[c] != ref[c]).nonzero().flatten().tolist()
                 print("  layer %d rep %d tile %d rows %s: xcd %d wg %d it %d of %d; row %d: %d channels %d..%d" % (i, r, t, rows, xcd, slot, it, my_n, rows[0], len(ch), ch[0], ch[-1]))
-    print("layer %d: %d of %d launches differ (RING=%s)" % (i, ev, reps, os.environ.get("DGNN_WS_RING", "22")))
+    print("layer %d: %d of %d launches differ" % (i, ev, reps))

@@ -1,7 +1,6 @@
 #!/bin/bash
 # Round-6 end-state set, bench lines first (a fresh box): bash tools/gpu_final6.sh <tag>
 #   bench lines (default with its nested legs, bf16, both wide widths, 10M tets, exact fp32 alone) -> gpurun_out/<tag>_bench*.json
-#   training-step set of tools/gpu_round6.sh (six bench lines + four kernel traces)            -> gpurun_out/<tag>t/
 #   pytest -m gpu (whole suite)                                                                 -> gpurun_out/<tag>_tests.log
 T=${1:-r6v}
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
@@ -16,5 +15,4 @@ import json,sys
 j=json.loads(open('$f').read().strip().splitlines()[-1])
 r=j.get('roofline') or {}
 print('$f', j.get('value'), j['ms_per_step'], j.get('ms_per_step_median'), str(r.get('kernel'))[:40], r.get('frac'), r.get('traffic'), (j.get('check') or {}).get('ok'))"; done
-bash tools/gpu_round6.sh train ${T}t > gpurun_out/${T}_train.txt 2>&1; tail -n 20 gpurun_out/${T}_train.txt
 timeout 3000 python -m pytest tests -q -m gpu > gpurun_out/${T}_tests.log 2>&1; echo "rc=$?" >> gpurun_out/${T}_tests.log; tail -n 5 gpurun_out/${T}_tests.log

@@ -1,4 +1,4 @@
-"""profiles/r06h_training.md out of the files of `bash tools/gpu_round6.sh train <tag>`, `... floor <tag2>`, `... gemm <tag3>` under gpurun_out/:
+"""profiles/r06h_training.md out of the files of the round-6 training, floor and GEMM-shape runs in the output directory `G` below:
     python tools/prof_train_summarize6.py <train tag> [<floor tag> [<gemm tag>]]"""
 import json, os, sys
 import pandas as pd
@@ -10,7 +10,7 @@ rd = lambda *p: open(os.path.join(G, *p)).read().strip()
 names = ["Static fp32, shipped widths [64,128,128,128], 2048 targets", "Updated bf16 storage, shipped widths, 2048 targets",
          "Static fp32, [128,256,512,1024], 1024 targets (configs/modelnet.yaml:44,56)", "Updated bf16 storage, [128,256,512,1024], 1024 targets (BASELINE config 3's workload)"]
 out = ["# Round 6: training step (block builder + forward + backward + Adam) -- MI355X, rocprofv3 kernel trace", "",
-       "Commands (`bash tools/gpu_round6.sh train %s` on the GPU box): `python tools/bench_train.py <config> --steps 300 --warmup 300 --no-roofline` (un-profiled lines)," % T,
+       "Commands (tag %s, on the GPU box): `python tools/bench_train.py <config> --steps 300 --warmup 300 --no-roofline` (un-profiled lines)," % T,
        "`rocprofv3 --kernel-trace --stats -- python3 tools/bench_train.py <config> --steps 60 --warmup 100 --no-roofline`, `python tools/trace_gaps.py <kernel_trace.csv> 105 40 --seq`",
        "(steps delimited by the library's Adam kernel; queue of the Adam kernel = the training step's stream, the other queue = the block builder's).  Under the profiler the host",
        "issues more slowly: `span` is longer than the un-profiled `ms_per_step`; `main-queue busy` is the GPU time of the step itself.", "",
@@ -25,7 +25,7 @@ for l in rd(T, "train.log").split("\n"):
 out += ["```", ""]
 if TF:
     out += ["## the step's floor: a tiny scene (3000 points, batch 8: 566-cell blocks, every kernel at its fixed cost) and the host's share", "",
-            "`bash tools/gpu_round6.sh floor %s`: bench lines of the tiny scene, then `tools/host_profile_train.py` (the loop timed un-profiled, then under cProfile)." % TF, "", "```"]
+            "Floor (tag %s): bench lines of the tiny scene, then `tools/host_profile_train.py` (the loop timed un-profiled, then under cProfile)." % TF, "", "```"]
     for l in rd(TF, "floor.log").split("\n"):
         if l.startswith("{"):
             d = json.loads(l)
@@ -51,7 +51,7 @@ for i, nm in enumerate(names, 1):
         cut = next((j for j, l in enumerate(seq) if l.startswith("sequence of step")), len(seq))
         out += ["## GPU timeline and launch sequence: %s" % nm, "", "```"] + [l[:170] for l in seq[:cut][:42]] + [l[:170] for l in seq[cut:]] + ["```", ""]
 if TG:
-    out += ["## the step's GEMM shapes under three kernel selections (`bash tools/gpu_round6.sh gemm %s`; `tools/bench_gemm_train_shapes.py`)" % TG, "",
+    out += ["## the step's GEMM shapes under three kernel selections (tag %s; `tools/bench_gemm_train_shapes.py`)" % TG, "",
             "Left: the library's own choice (round 6).  Middle: the tiled kernels everywhere (`DGNN_X3_SMALL=0 DGNN_BF16_SMALL=0 DGNN_GEMM_MID=0`).  Right: round 5's choice", 
             "(`DGNN_SMALL_BY_TILES=0 DGNN_GEMM_MID=0 DGNN_SMALL_SPLITK=0`: the small-problem kernel for every M <= 16384).", "", "```"]
     a, b, c = (rd(TG, f).split("\n") for f in ("gemm_default.txt", "gemm_tiled.txt", "gemm_small.txt"))
