@@ -595,31 +595,21 @@ k_sage_fused(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src
 }
 
 template <int CIN_PAD, int COUT, int MODE, int FM = 0>
-int launch_fused(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const float* x, const float* xdst,
-                 int64_t ldx, int c_in,
-                 const float* ea, int64_t lde, const float* We, const float* be, const float* Wj, const float* bj,
-                 const float* Wi, const float* scale, const float* shift, int relu, float* out, int64_t ldo,
-                 hipStream_t stream) {
+int launch_fused(const LayerCall& c) {
     using C = FusedCfg<CIN_PAD, COUT, MODE>;
-    const int64_t ntiles = dgnn_cdiv(n_dst, C::TILE);
+    const int64_t ntiles = dgnn_cdiv(c.n_dst, C::TILE);
     const size_t smem = sizeof(float) * (C::SMEM_FLOATS + (FM ? C::FW_FLOATS : 0));
     static bool attr_set[DGNN_MAX_DEVICES] = {};
     dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused<CIN_PAD, COUT, MODE, FM>), smem, attr_set);
     int grid = (int)(ntiles < DGNN_NUM_CU ? ntiles : DGNN_NUM_CU);
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((k_sage_fused<CIN_PAD, COUT, MODE, FM>), dim3(grid), dim3(512), smem, stream, rowptr, src, eid, n_dst, x, xdst, ldx, c_in,
-                       ea, lde, We, be, Wj, bj, Wi, scale, shift, relu, out, ldo, ntiles, g_dgnn_trace_buf, g_dgnn_trace_cap);
+    hipLaunchKernelGGL((k_sage_fused<CIN_PAD, COUT, MODE, FM>), dim3(grid), dim3(512), smem, c.stream, c.rowptr, c.src, c.eid, c.n_dst, c.x_src, c.x_dst,
+                       c.ldx, c.c_in, c.edge_attr, c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, c.out, c.ldo, ntiles, g_dgnn_trace_buf,
+                       g_dgnn_trace_cap);
     return dgnn_check_launch("sage_layer_fused_fwd");
 }
 
 }  // namespace
-
-int dgnn_sage_layer_fused_mfma_try(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const float* x_src,
-                                   const float* x_dst, int64_t ldx,
-                                   int c_in, const float* edge_attr, int64_t lde, const float* We, const float* be,
-                                   const float* Wj, const float* bj, const float* Wi, const float* scale, const float* shift,
-                                   int relu, int c_out, float* out, int64_t ldo, int f16_parts, hipStream_t stream, void* prep = nullptr,
-                                   int prep_mode = 0);  // fused_mfma.hip (prep: prepared parameters, see dgnn_sage_layer_prepare)
 
 extern "C" int dgnn_sage_layer_fused_fwd(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const float* x_src,
                                          const float* x_dst, int64_t ldx, int c_in, const float* edge_attr, int64_t lde, int f_e,
@@ -640,10 +630,9 @@ extern "C" int dgnn_sage_layer_fused_fwd(const int32_t* rowptr, const int32_t* s
     DGNN_REQUIRE(n_dst * ldx < ((int64_t)1 << 31), DGNN_E_UNSUPPORTED, "sage_layer_fused_fwd: activations beyond 2^31 elements");
     DGNN_REQUIRE(c_in <= 128 && (c_out == 64 || c_out == 128), DGNN_E_UNSUPPORTED,
                  "sage_layer_fused_fwd: supports c_in <= 128 and c_out in {64,128} (got %d -> %d)", c_in, c_out);
+    const LayerCall c{{rowptr, src, eid, n_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, c_out, ldo, stream}, x_src, x_dst, out};
     if (gemm_mode >= DGNN_GEMM_BF16X3_FILTER) {
-        const int rc = dgnn_sage_layer_fused_mfma_try(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi,
-                                                      scale, shift, relu, c_out, out, ldo,
-                                                      gemm_mode == DGNN_GEMM_F16X2 ? 2 : (gemm_mode == DGNN_GEMM_F16X2_DENSE ? 1 : 0), stream);
+        const int rc = dgnn_sage_layer_fused_mfma_try(c, gemm_mode == DGNN_GEMM_F16X2 ? 2 : (gemm_mode == DGNN_GEMM_F16X2_DENSE ? 1 : 0), nullptr, 0);
         if (rc != DGNN_E_UNSUPPORTED) return rc;
         gemm_mode = DGNN_GEMM_BF16X3;  // shape not covered by the all-MFMA variant
     }
@@ -653,16 +642,11 @@ extern "C" int dgnn_sage_layer_fused_fwd(const int32_t* rowptr, const int32_t* s
         const int vw = cp / 16 < 4 ? cp / 16 : 4;      // (pairs: the kernel falls back to dword loads by itself; quads: only aligned rows)
         return fm_on && gemm_mode == DGNN_GEMM_F32 && (vw < 4 || (c_in % 4 == 0 && ldx % 4 == 0 && (((uintptr_t)x_src | (uintptr_t)x_dst) % 16) == 0));
     };
-#define GO(CP, CO)                                                                                                              \
-    do {                                                                                                                        \
-        if (fm_ok(CP))                                                                                                          \
-            return launch_fused<CP, CO, 0, 1>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, \
-                                              shift, relu, out, ldo, stream);                                                   \
-        if (gemm_mode == DGNN_GEMM_F32)                                                                                         \
-            return launch_fused<CP, CO, 0>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, \
-                                           shift, relu, out, ldo, stream);                                                      \
-        return launch_fused<CP, CO, 1>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale,     \
-                                       shift, relu, out, ldo, stream);                                                          \
+#define GO(CP, CO)                                                     \
+    do {                                                               \
+        if (fm_ok(CP)) return launch_fused<CP, CO, 0, 1>(c);           \
+        if (gemm_mode == DGNN_GEMM_F32) return launch_fused<CP, CO, 0>(c); \
+        return launch_fused<CP, CO, 1>(c);                             \
     } while (0)
     if (c_in <= 32) { if (c_out == 64) GO(32, 64); else GO(32, 128); }
     if (c_in <= 64) { if (c_out == 64) GO(64, 64); else GO(64, 128); }

@@ -657,11 +657,9 @@ k_sage_fused_bf16(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
 }
 
 template <int CIN_PAD, int COUT, int OCC, int PR, int NW = 4, int XF = 0, bool DEC = false, int UB = 0>
-int launch_b(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const void* x, const void* xdst, int64_t ldx,
-             int c_in, const float* ea, int64_t lde, const float* We, const float* be, const float* Wj, const float* bj, const float* Wi,
-             const float* scale, const float* shift, int relu, uint16_t* out, int64_t ldo, hipStream_t stream, DecB dec = DecB{}) {
+int launch_b(const LayerCall16& c, DecB dec = DecB{}) {
     using C = CfgB<CIN_PAD, COUT, NW, PR, XF, DEC, UB>;
-    const int64_t ntiles = dgnn_cdiv(n_dst, C::TILE);
+    const int64_t ntiles = dgnn_cdiv(c.n_dst, C::TILE);
     const size_t smem = C::SMEM_BYTES;
     static bool attr_set[DGNN_MAX_DEVICES] = {};
     dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_bf16<CIN_PAD, COUT, NW, OCC, PR, XF, DEC, UB>), smem, attr_set);
@@ -669,8 +667,8 @@ int launch_b(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int6
     const int wg_max = DGNN_NUM_CU * (per_cu < 1 ? 1 : per_cu);
     int grid = (int)(ntiles < wg_max ? ntiles : wg_max);
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((k_sage_fused_bf16<CIN_PAD, COUT, NW, OCC, PR, XF, DEC, UB>), dim3(grid), dim3(64 * NW), smem, stream, rowptr, src, eid, n_dst, x, xdst,
-                       ldx, c_in, ea, lde, We, be, Wj, bj, Wi, scale, shift, relu, out, ldo, ntiles, dec);
+    hipLaunchKernelGGL((k_sage_fused_bf16<CIN_PAD, COUT, NW, OCC, PR, XF, DEC, UB>), dim3(grid), dim3(64 * NW), smem, c.stream, c.rowptr, c.src, c.eid, c.n_dst,
+                       c.x_src, c.x_dst, c.ldx, c.c_in, c.edge_attr, c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, c.out, c.ldo, ntiles, dec);
     return dgnn_check_launch(DEC ? "sage_layer_fused_decoder_fwd_bf16" : "sage_layer_fused_fwd_bf16");
 }
 
@@ -847,10 +845,6 @@ extern "C" int dgnn_cast_bf16_to_f32(const uint16_t* in, int64_t ld_in, int64_t 
     return dgnn_check_launch("cast_bf16_to_f32");
 }
 
-int dgnn_sage_layer_fused_ws16_try(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const uint16_t* x_src, const uint16_t* x_dst,
-                                   int64_t ldx, int c_in, const float* edge_attr, int64_t lde, const float* We, const float* be, const float* Wj, const float* bj,
-                                   const float* Wi, const float* scale, const float* shift, int relu, int c_out, uint16_t* out, int64_t ldo, hipStream_t stream);   // fused_ws.hip
-
 extern "C" int dgnn_sage_layer_fused_fwd_bf16(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst,
                                               const void* x_src, int x_f32, const void* x_dst, int64_t ldx, int c_in, const float* edge_attr,
                                               int64_t lde, int f_e, const float* We, const float* be, const float* Wj, const float* bj,
@@ -865,15 +859,14 @@ extern "C" int dgnn_sage_layer_fused_fwd_bf16(const int32_t* rowptr, const int32
     DGNN_REQUIRE(f_e == FE && lde == FE && ((uintptr_t)edge_attr % 16) == 0, DGNN_E_UNSUPPORTED,
                  "sage_layer_fused_fwd_bf16: needs f_e == 20, packed 16-byte aligned edge rows");
     DGNN_REQUIRE(n_dst * ldx < ((int64_t)1 << 31), DGNN_E_UNSUPPORTED, "sage_layer_fused_fwd_bf16: activations beyond 2^31 elements");
-    const int cin_pad = c_in <= 32 ? 32 : (c_in <= 64 ? 64 : 128);
-    const int nb = cin_pad / 16;
+    const int cp = cin_pad(c_in), nb = cp / 16;
     DGNN_REQUIRE(c_in <= 128 && (c_out == 64 || c_out == 128), DGNN_E_UNSUPPORTED,
                  "sage_layer_fused_fwd_bf16: supports c_in <= 128 and c_out in {64,128} (got %d -> %d)", c_in, c_out);
     // a lane reads nb contiguous bf16 of a row: rows must be aligned to that, and every lane's piece must lie inside the row
-    DGNN_REQUIRE(c_in % nb == 0, DGNN_E_UNSUPPORTED, "sage_layer_fused_fwd_bf16: c_in must be a multiple of %d", nb);
+    DGNN_REQUIRE(takes_bf16_rows(c_in, c_out), DGNN_E_UNSUPPORTED, "sage_layer_fused_fwd_bf16: c_in must be a multiple of %d", nb);
     DGNN_REQUIRE(x_f32 || (ldx % nb == 0 && (((uintptr_t)x_src | (uintptr_t)x_dst) % (2 * nb)) == 0), DGNN_E_UNSUPPORTED,
                  "sage_layer_fused_fwd_bf16: the row stride must be a multiple of %d, rows %d-byte aligned", nb, 2 * nb);
-    DGNN_REQUIRE(!x_f32 || (cin_pad == 32 && (((uintptr_t)x_src | (uintptr_t)x_dst) % 4) == 0), DGNN_E_UNSUPPORTED,
+    DGNN_REQUIRE(!x_f32 || (cp == 32 && (((uintptr_t)x_src | (uintptr_t)x_dst) % 4) == 0), DGNN_E_UNSUPPORTED,
                  "sage_layer_fused_fwd_bf16: fp32 input rows are supported for c_in <= 32 (the first layer)");
     DGNN_REQUIRE(ldo % 2 == 0 && ((uintptr_t)out % 4) == 0, DGNN_E_UNSUPPORTED, "sage_layer_fused_fwd_bf16: out rows must be 4-byte aligned");
     const bool ub_in = (mode & DGNN_BF16_ROWS_IN_UNSIGNED) != 0, ub_out = (mode & DGNN_BF16_ROWS_OUT_UNSIGNED) != 0;
@@ -885,42 +878,32 @@ extern "C" int dgnn_sage_layer_fused_fwd_bf16(const int32_t* rowptr, const int32
     DGNN_REQUIRE(!ub_out || relu, DGNN_E_INVALID, "sage_layer_fused_fwd_bf16: unsigned output rows need relu (values >= 0)");
     DGNN_REQUIRE(x_f32 ? !ub_in : ub_in == ub_out, DGNN_E_UNSUPPORTED, "sage_layer_fused_fwd_bf16: a layer on bf16 rows keeps the row format (in == out)");
     const bool ub = ub_out;
+    const LayerCall16 c{{rowptr, src, eid, n_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, c_out, ldo, stream}, x_src, x_dst, out};
     if (ub && ub_in && !x_f32 && c_out == 128 && (c_in == 128 || c_in == 64)) {
         // round 5: the wave-specialised kernel (fused_ws.hip) reads and writes unsigned 16-bit rows too (DGNN_WS=0 / DGNN_WS_16=0: the kernels below)
-        const int rc = dgnn_sage_layer_fused_ws16_try(rowptr, src, eid, n_dst, static_cast<const uint16_t*>(x_src), static_cast<const uint16_t*>(x_dst), ldx, c_in,
-                                                      edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, c_out, out, ldo, stream);
+        const int rc = dgnn_sage_layer_fused_ws16_try(c);
         if (rc != DGNN_E_UNSUPPORTED) return rc;
     }
-#define GOB(CP, CO, OCC)                                                                                                                  \
-    do {                                                                                                                                  \
-        if (ub)                                                                                                                           \
-            return launch_b<CP, CO, OCC, 1, 4, 0, false, 3>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, \
-                                                            scale, shift, relu, out, ldo, stream);                                        \
-        if (mode == DGNN_BF16_COMPENSATED)                                                                                                \
-            return launch_b<CP, CO, OCC, 1>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale,  \
-                                            shift, relu, out, ldo, stream);                                                               \
-        return launch_b<CP, CO, OCC, 0>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale,      \
-                                        shift, relu, out, ldo, stream);                                                                   \
+#define GOB(CP, CO, OCC)                                                            \
+    do {                                                                            \
+        if (ub) return launch_b<CP, CO, OCC, 1, 4, 0, false, 3>(c);                 \
+        if (mode == DGNN_BF16_COMPENSATED) return launch_b<CP, CO, OCC, 1>(c);      \
+        return launch_b<CP, CO, OCC, 0>(c);                                         \
     } while (0)
     if (x_f32) {
         const bool pr = mode == DGNN_BF16_COMPENSATED;
-#define GOX(CO, PRV, UBV) return launch_b<32, CO, 2, PRV, 4, 1, false, UBV>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, \
-                                                                          scale, shift, relu, out, ldo, stream)
+#define GOX(CO, PRV, UBV) return launch_b<32, CO, 2, PRV, 4, 1, false, UBV>(c)
         if (c_out == 64) { if (ub) GOX(64, 1, 2); if (pr) GOX(64, 1, 0); else GOX(64, 0, 0); }
         if (ub) GOX(128, 1, 2);
         if (pr) GOX(128, 1, 0); else GOX(128, 0, 0);
 #undef GOX
     }
-    if (cin_pad == 32) { if (c_out == 64) GOB(32, 64, 2); else GOB(32, 128, 2); }
-    if (cin_pad == 64) { if (c_out == 64) GOB(64, 64, 2); else GOB(64, 128, 2); }
+    if (cp == 32) { if (c_out == 64) GOB(32, 64, 2); else GOB(32, 128, 2); }
+    if (cp == 64) { if (c_out == 64) GOB(64, 64, 2); else GOB(64, 128, 2); }
     if (c_out == 64) GOB(128, 64, 2);
     // 128 -> 128: the compensated form keeps four weight parts resident -> eight-wave workgroups with 16-column slices
-    if (ub)
-        return launch_b<128, 128, 1, 1, 8, 0, false, 3>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu,
-                                                        out, ldo, stream);
-    if (mode == DGNN_BF16_COMPENSATED)
-        return launch_b<128, 128, 1, 1, 8>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu,
-                                           out, ldo, stream);
+    if (ub) return launch_b<128, 128, 1, 1, 8, 0, false, 3>(c);
+    if (mode == DGNN_BF16_COMPENSATED) return launch_b<128, 128, 1, 1, 8>(c);
     GOB(128, 128, 2);
 #undef GOB
 }
@@ -946,11 +929,10 @@ extern "C" int dgnn_sage_layer_fused_decoder_fwd_bf16(const int32_t* rowptr, con
                     n_logits == 2 && ((uintptr_t)edge_attr % 16) == 0 && ldx % 8 == 0 && (((uintptr_t)x_src | (uintptr_t)x_dst) % 16) == 0 &&
                     ((uintptr_t)logits % 8) == 0 && n_dst * ldx < ((int64_t)1 << 31);
     if (!ok) return DGNN_E_UNSUPPORTED;     // the caller runs dgnn_sage_layer_fused_fwd_bf16 and dgnn_decoder_fused_fwd_bf16
-    if (ub_in)
-        return launch_b<128, 128, 1, 1, 8, 0, true, 1>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, nullptr,
-                                                       0, (hipStream_t)stream_, DecB{W0, b0, scale1, shift1, W3, b3, logits});
-    return launch_b<128, 128, 1, 1, 8, 0, true>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, nullptr, 0,
-                                                (hipStream_t)stream_, DecB{W0, b0, scale1, shift1, W3, b3, logits});
+    const LayerCall16 c{{rowptr, src, eid, n_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, c_out, 0, (hipStream_t)stream_}, x_src, x_dst, nullptr};
+    const DecB dec{W0, b0, scale1, shift1, W3, b3, logits};
+    if (ub_in) return launch_b<128, 128, 1, 1, 8, 0, true, 1>(c, dec);
+    return launch_b<128, 128, 1, 1, 8, 0, true>(c, dec);
 }
 
 extern "C" int dgnn_decoder_fused_fwd_bf16(const uint16_t* y, int64_t ldy, int64_t M, int k, const float* W0, const float* b0, const float* scale,

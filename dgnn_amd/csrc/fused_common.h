@@ -173,4 +173,59 @@ __device__ __forceinline__ f16x8 pack8h(const uint32_t (&d)[4]) {
                                            __builtin_bit_cast(float, d[2]), __builtin_bit_cast(float, d[3])});
 }
 
+// ---- host side: ONE description of a fused layer call ---------------------------------------------------------------------------------
+// The extern "C" entry points fill these once from their arguments; the dispatch below them passes the struct and the kernels receive the same
+// scalars in the same order, read from it at the hipLaunchKernelGGL site.  dgnn_sage_layer_prepare fills the parameters only (the rest stays zero).
+struct LayerArgs {                       // everything but the rows: the same for fp32 and 16-bit storage
+    const int32_t *rowptr, *src, *eid;   // destination-sorted plan; eid NULL: edge_attr is in plan order
+    int64_t n_dst;
+    int64_t ldx;                         // row stride of x_src / x_dst, in elements of their storage type
+    int c_in;
+    const float* edge_attr;
+    int64_t lde;
+    const float *We, *be, *Wj, *bj, *Wi; // filter Linear(20 -> c_in), neighbour / own Linear(c_in -> c_out); bj may be NULL
+    const float *scale, *shift;          // folded BatchNorm(eval), both or neither
+    int relu, c_out;
+    int64_t ldo;
+    hipStream_t stream;
+};
+struct LayerCall : LayerArgs {           // fp32 rows
+    const float *x_src, *x_dst;
+    float* out;
+};
+struct LayerCall16 : LayerArgs {         // bf16-storage rows (x: 16-bit rows, or the first layer's fp32 rows)
+    const void *x_src, *x_dst;
+    uint16_t* out;
+};
+// Linear(c_out -> c_hidden) - BatchNorm(eval, folded) - ReLU - Linear(c_hidden -> n_logits) behind the last layer; W0 NULL: no decoder
+struct DecoderTail {
+    const float *W0, *b0, *scale1, *shift1;
+    int c_hidden;
+    const float *W3, *b3;
+    int n_logits;
+    float* logits;
+};
+
+// ---- host side: ONE statement of each shape rule (dgnn_amd/ops.py fused_layer_supported* mirror these) ------------------------------
+// input width the kernels are instantiated for (rows are zero-padded to it in LDS); a lane reads cin_pad / 16 contiguous channels of a row
+inline int cin_pad(int c_in) { return c_in <= 32 ? 32 : (c_in <= 64 ? 64 : 128); }
+// the fused fp32-row kernels (fused.hip, fused_mfma.hip, fused_ws.hip) take c_in -> c_out
+inline bool takes_f32_rows(int c_in, int c_out) {
+    return c_in > 0 && c_in <= 128 && (c_out == 64 || c_out == 128) && (cin_pad(c_in) != 128 || c_out == 128);
+}
+// the bf16-storage kernels (fused_bf16.hip): every lane's piece of a row must lie inside the row
+inline bool takes_bf16_rows(int c_in, int c_out) {
+    return c_in > 0 && c_in <= 128 && (c_out == 64 || c_out == 128) && c_in % (cin_pad(c_in) / 16) == 0;
+}
+
 }  // namespace fused
+
+// ---- the functions that cross translation units ------------------------------------------------------------------------------------------
+// fused_mfma.hip.  f16_parts: 0 = bf16 x 3 everywhere, 1 = dense product on fp16 x 2, 2 = both products on fp16 x 2; prep / prep_mode: prepared
+// parameters (see DecArgs there; NULL / 0: none).  DGNN_E_UNSUPPORTED when the shape does not fit (the caller then uses fused.hip MODE 1).
+int dgnn_sage_layer_fused_mfma_try(const fused::LayerCall& c, int f16_parts, void* prep, int prep_mode);
+// fused_ws.hip.  Same contract for c_in in {64, 128}, c_out == 128; with dec.W0 != NULL (c_in == 128) the launch carries the decoder 128 -> 64 -> 2 and
+// writes dec.logits [n_dst, 2] instead of rows (`out` unused).  DGNN_E_UNSUPPORTED: the caller keeps the two-phase kernel.
+int dgnn_sage_layer_fused_ws_try(const fused::LayerCall& c, const fused::DecoderTail& dec);
+int dgnn_sage_layer_fused_ws16_try(const fused::LayerCall16& c);   // the same kernel on the UNSIGNED 16-bit rows of the bf16-storage chain
+int dgnn_ws_enabled();                                             // DGNN_WS (default 1): the wave-specialised kernel takes the layers it covers

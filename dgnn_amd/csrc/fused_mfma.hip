@@ -887,68 +887,53 @@ k_sage_fused_mfma(const int32_t* __restrict__ rowptr, const int32_t* __restrict_
 }
 
 template <int CIN_PAD, int COUT, int DSP, int FSP, bool DEC = false>
-int launch2(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const float* x, const float* xdst, int64_t ldx, int c_in, const float* ea,
-            int64_t lde, const float* We, const float* be, const float* Wj, const float* bj, const float* Wi,
-            const float* scale, const float* shift, int relu, float* out, int64_t ldo, int xvec, hipStream_t stream, DecArgs dec = DecArgs{}) {
+int launch2(const LayerCall& c, int xvec, DecArgs dec) {
     // C_in <= 64: four-wave workgroups, two per CU (see Cfg2); C_in = 128: eight waves with the K split
     // (64 -> 64 would need 16 tets per wave with 4 channels per lane: 110 spilled registers -- it keeps the 8-wave form)
     constexpr int NW = (CIN_PAD <= 64 && !(CIN_PAD == 64 && COUT == 64)) ? 4 : 8, KS = NW == 8 ? 2 : 1;
     using C = Cfg2<CIN_PAD, COUT, NW, KS, DSP, FSP, DEC>;
-    const int64_t ntiles = dgnn_cdiv(n_dst, C::TILE);
+    const int64_t ntiles = dgnn_cdiv(c.n_dst, C::TILE);
     const size_t smem = C::SMEM_BYTES;
     static bool attr_set[DGNN_MAX_DEVICES] = {};
     dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_mfma<CIN_PAD, COUT, NW, KS, DSP, FSP, DEC>), smem, attr_set);
     const int wg_max = DGNN_NUM_CU * (NW == 8 ? 1 : 2);
     int grid = (int)(ntiles < wg_max ? ntiles : wg_max);
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((k_sage_fused_mfma<CIN_PAD, COUT, NW, KS, DSP, FSP, DEC>), dim3(grid), dim3(64 * NW), smem, stream, rowptr, src, eid, n_dst, x, xdst,
-                       ldx, c_in, ea, lde, We, be, Wj, bj, Wi, scale, shift, relu, out, ldo, ntiles, xvec, g_dgnn_trace_buf,
-                       g_dgnn_trace_cap, dec);
+    hipLaunchKernelGGL((k_sage_fused_mfma<CIN_PAD, COUT, NW, KS, DSP, FSP, DEC>), dim3(grid), dim3(64 * NW), smem, c.stream, c.rowptr, c.src, c.eid, c.n_dst,
+                       c.x_src, c.x_dst, c.ldx, c.c_in, c.edge_attr, c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, c.out, c.ldo, ntiles, xvec,
+                       g_dgnn_trace_buf, g_dgnn_trace_cap, dec);
     return dgnn_check_launch(DEC ? "sage_layer_fused_decoder_fwd" : "sage_layer_fused_fwd(mfma filter)");
 }
 
 }  // namespace
 
-int dgnn_ws_enabled();      // fused_ws.hip
-int dgnn_sage_layer_fused_ws_try(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const float* x_src, const float* x_dst, int64_t ldx,
-                                 int c_in, const float* edge_attr, int64_t lde, const float* We, const float* be, const float* Wj, const float* bj, const float* Wi,
-                                 const float* scale, const float* shift, int relu, int c_out, float* out, int64_t ldo, hipStream_t stream, const float* W0 = nullptr,
-                                 const float* b0 = nullptr, const float* scale1 = nullptr, const float* shift1 = nullptr, const float* W3 = nullptr,
-                                 const float* b3 = nullptr, float* logits = nullptr);
-
 // Returns DGNN_E_UNSUPPORTED when the shape does not fit this variant (the caller then uses fused.hip MODE 1).
-int dgnn_sage_layer_fused_mfma_try(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const float* x_src,
-                                   const float* x_dst, int64_t ldx, int c_in, const float* edge_attr, int64_t lde, const float* We, const float* be,
-                                   const float* Wj, const float* bj, const float* Wi, const float* scale, const float* shift,
-                                   int relu, int c_out, float* out, int64_t ldo, int f16_parts, hipStream_t stream, void* prep, int prep_mode) {
-    const int cin_pad = c_in <= 32 ? 32 : (c_in <= 64 ? 64 : 128);
-    const int nb = cin_pad / 16;
-    if (c_in % nb != 0 || (c_out != 64 && c_out != 128) || (cin_pad == 128 && c_out != 128)) return DGNN_E_UNSUPPORTED;
-    if ((c_in == 128 || c_in == 64) && c_out == 128 && f16_parts == 2 && prep_mode != 1 && dgnn_ws_enabled()) {
+int dgnn_sage_layer_fused_mfma_try(const LayerCall& c, int f16_parts, void* prep, int prep_mode) {
+    const int cp = cin_pad(c.c_in), nb = cp / 16;
+    if (!takes_f32_rows(c.c_in, c.c_out) || c.c_in % nb != 0) return DGNN_E_UNSUPPORTED;
+    if ((c.c_in == 128 || c.c_in == 64) && c.c_out == 128 && f16_parts == 2 && prep_mode != 1 && dgnn_ws_enabled()) {
         // round 5: the plain 128 -> 128 and 64 -> 128 layers in the default arithmetic run wave-specialised (fused_ws.hip); it derives what it needs from the weights
         // itself (a prepared buffer is not read)
-        const int rc = dgnn_sage_layer_fused_ws_try(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, c_out, out,
-                                                    ldo, stream);
+        const int rc = dgnn_sage_layer_fused_ws_try(c, DecoderTail{});
         if (rc != DGNN_E_UNSUPPORTED) return rc;
     }
-    const int xvec = ((((uintptr_t)x_src | (uintptr_t)x_dst) % 16) == 0 && ldx % 4 == 0) ? 1 : 0;
+    const int xvec = ((((uintptr_t)c.x_src | (uintptr_t)c.x_dst) % 16) == 0 && c.ldx % 4 == 0) ? 1 : 0;
     if (nb >= 4 && !xvec && prep_mode != 1) return DGNN_E_UNSUPPORTED;
-    if (f16_parts && prep_mode != 1 && (ldo % 4 != 0 || ((uintptr_t)out % 16) != 0)) f16_parts = 0;  // the fp16 forms store 16-byte pieces of the output rows
+    if (f16_parts && prep_mode != 1 && (c.ldo % 4 != 0 || ((uintptr_t)c.out % 16) != 0)) f16_parts = 0;  // the fp16 forms store 16-byte pieces of the output rows
     if (prep_mode != 0 && f16_parts != 2) return DGNN_E_UNSUPPORTED;   // prepared parameters exist for the default arithmetic only
     DecArgs dargs{};
     dargs.prep = prep;
     dargs.prep_mode = prep_mode;
     // f16_parts: 0 = bf16 x 3 everywhere, 1 = dense product on fp16 x 2 (filter product bf16 x 3), 2 = both on fp16 x 2
-#define GO3(CP, CO, D, F) return launch2<CP, CO, D, F>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, \
-                                                       shift, relu, out, ldo, xvec, stream, dargs)
+#define GO3(CP, CO, D, F) return launch2<CP, CO, D, F>(c, xvec, dargs)
 #define GO2(CP, CO)                            \
     do {                                       \
         if (f16_parts == 2) GO3(CP, CO, 2, 2); \
         if (f16_parts == 1) GO3(CP, CO, 2, 3); \
         GO3(CP, CO, 3, 3);                     \
     } while (0)
-    if (cin_pad == 32) { if (c_out == 64) GO2(32, 64); else GO2(32, 128); }
-    if (cin_pad == 64) { if (c_out == 64) GO2(64, 64); else GO2(64, 128); }
+    if (cp == 32) { if (c.c_out == 64) GO2(32, 64); else GO2(32, 128); }
+    if (cp == 64) { if (c.c_out == 64) GO2(64, 64); else GO2(64, 128); }
     GO2(128, 128);
 #undef GO2
 #undef GO3
@@ -960,34 +945,27 @@ int dgnn_sage_layer_fused_mfma_try(const int32_t* rowptr, const int32_t* src, co
 // decoder 128 -> 64 -> 2; fp16 two-part arithmetic (gemm mode DGNN_GEMM_F16X2) throughout.  Anything else: DGNN_E_UNSUPPORTED (the caller
 // then runs the layer and dgnn_decoder_fused_fwd as two launches).
 namespace {
-int fused_decoder_impl(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const float* x_src, const float* x_dst, int64_t ldx, int c_in,
-                       const float* edge_attr, int64_t lde, int f_e, const float* We, const float* be, const float* Wj, const float* bj, const float* Wi,
-                       const float* scale, const float* shift, int relu, int c_out, const float* W0, const float* b0, const float* scale1,
-                       const float* shift1, int c_hidden, const float* W3, const float* b3, int n_logits, float* logits, void* prep, int prep_mode,
-                       hipStream_t stream) {
-    DGNN_REQUIRE(n_dst >= 0, DGNN_E_INVALID, "sage_layer_fused_decoder_fwd: bad sizes");
-    if (n_dst == 0 && prep_mode != 1) return DGNN_OK;
+int fused_decoder_impl(LayerCall c, int f_e, const DecoderTail& d, void* prep, int prep_mode) {
+    DGNN_REQUIRE(c.n_dst >= 0, DGNN_E_INVALID, "sage_layer_fused_decoder_fwd: bad sizes");
+    if (c.n_dst == 0 && prep_mode != 1) return DGNN_OK;
     if (prep_mode != 1) {
-        DGNN_REQUIRE(rowptr && src && x_src && edge_attr && logits, DGNN_E_INVALID, "sage_layer_fused_decoder_fwd: null pointer");
-        if (x_dst == nullptr) x_dst = x_src;
+        DGNN_REQUIRE(c.rowptr && c.src && c.x_src && c.edge_attr && d.logits, DGNN_E_INVALID, "sage_layer_fused_decoder_fwd: null pointer");
+        if (c.x_dst == nullptr) c.x_dst = c.x_src;
     }
-    DGNN_REQUIRE(We && be && Wj && Wi && W0 && b0 && W3 && b3, DGNN_E_INVALID, "sage_layer_fused_decoder_fwd: null parameter pointer");
-    DGNN_REQUIRE((scale == nullptr) == (shift == nullptr) && (scale1 == nullptr) == (shift1 == nullptr), DGNN_E_INVALID,
+    DGNN_REQUIRE(c.We && c.be && c.Wj && c.Wi && d.W0 && d.b0 && d.W3 && d.b3, DGNN_E_INVALID, "sage_layer_fused_decoder_fwd: null parameter pointer");
+    DGNN_REQUIRE((c.scale == nullptr) == (c.shift == nullptr) && (d.scale1 == nullptr) == (d.shift1 == nullptr), DGNN_E_INVALID,
                  "sage_layer_fused_decoder_fwd: scale/shift must come together");
-    bool ok = c_out == 128 && c_in > 64 && c_in <= 128 && c_in % 8 == 0 && f_e == fused::FE && c_hidden == 64 && n_logits == 2;
+    bool ok = c.c_out == 128 && c.c_in > 64 && c.c_in <= 128 && c.c_in % 8 == 0 && f_e == fused::FE && d.c_hidden == 64 && d.n_logits == 2;
     if (prep_mode != 1)
-        ok = ok && lde == fused::FE && ((((uintptr_t)x_src | (uintptr_t)x_dst | (uintptr_t)edge_attr) % 16) == 0) && ldx % 4 == 0 &&
-             ((uintptr_t)logits % 8) == 0 && n_dst * ldx < ((int64_t)1 << 31);
+        ok = ok && c.lde == fused::FE && ((((uintptr_t)c.x_src | (uintptr_t)c.x_dst | (uintptr_t)c.edge_attr) % 16) == 0) && c.ldx % 4 == 0 &&
+             ((uintptr_t)d.logits % 8) == 0 && c.n_dst * c.ldx < ((int64_t)1 << 31);
     if (prep_mode != 0) ok = ok && prep != nullptr && ((uintptr_t)prep % 16) == 0;
     if (!ok) return DGNN_E_UNSUPPORTED;
-    if (prep_mode != 1 && c_in == 128 && dgnn_ws_enabled()) {      // round 5: the wave-specialised kernel carries the decoder too (fused_ws.hip)
-        const int rc = dgnn_sage_layer_fused_ws_try(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, c_out, nullptr,
-                                                    0, stream, W0, b0, scale1, shift1, W3, b3, logits);
+    if (prep_mode != 1 && c.c_in == 128 && dgnn_ws_enabled()) {      // round 5: the wave-specialised kernel carries the decoder too (fused_ws.hip)
+        const int rc = dgnn_sage_layer_fused_ws_try(c, d);
         if (rc != DGNN_E_UNSUPPORTED) return rc;
     }
-    DecArgs dec{W0, b0, scale1, shift1, W3, b3, logits, prep, prep_mode};
-    return launch2<128, 128, 2, 2, true>(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, nullptr, 0, 1,
-                                         stream, dec);
+    return launch2<128, 128, 2, 2, true>(c, 1, DecArgs{d.W0, d.b0, d.scale1, d.shift1, d.W3, d.b3, d.logits, prep, prep_mode});
 }
 }  // namespace
 
@@ -997,8 +975,8 @@ extern "C" int dgnn_sage_layer_fused_decoder_fwd(const int32_t* rowptr, const in
                                                  const float* scale, const float* shift, int relu, int c_out, const float* W0, const float* b0,
                                                  const float* scale1, const float* shift1, int c_hidden, const float* W3, const float* b3, int n_logits,
                                                  float* logits, void* stream_) {
-    return fused_decoder_impl(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, f_e, We, be, Wj, bj, Wi, scale, shift, relu, c_out, W0, b0, scale1,
-                              shift1, c_hidden, W3, b3, n_logits, logits, nullptr, 0, (hipStream_t)stream_);
+    return fused_decoder_impl({{rowptr, src, eid, n_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, c_out, 0, (hipStream_t)stream_}, x_src, x_dst, nullptr},
+                              f_e, {W0, b0, scale1, shift1, c_hidden, W3, b3, n_logits, logits}, nullptr, 0);
 }
 
 // ---- prepared parameters (fp16 two-part arithmetic, DGNN_GEMM_F16X2) --------------------------------------------------------------------
@@ -1008,9 +986,8 @@ extern "C" int dgnn_sage_layer_fused_decoder_fwd(const int32_t* rowptr, const in
 // and parks the result; the *_p entry points read it back with coalesced 16-byte loads.  The values are the same: results are bit-identical.
 // The buffer belongs to (We, be, Wj, Wi[, W0, b0, scale1, shift1, W3, b3]) and to the layer shape; the caller prepares again when they change.
 extern "C" int64_t dgnn_sage_layer_prepared_bytes(int c_in, int c_out, int with_decoder) {
-    if (c_in <= 0 || c_in > 128 || (c_out != 64 && c_out != 128)) return 0;
-    const int cp = c_in <= 32 ? 32 : (c_in <= 64 ? 64 : 128);
-    if (cp == 128 && c_out != 128) return 0;
+    if (!takes_f32_rows(c_in, c_out)) return 0;
+    const int cp = cin_pad(c_in);
     if (with_decoder) return (cp == 128 && c_out == 128) ? Cfg2<128, 128, 8, 2, 2, 2, true>::PREP_BYTES : 0;
     if (cp == 32) return c_out == 64 ? Cfg2<32, 64, 4, 1, 2, 2>::PREP_BYTES : Cfg2<32, 128, 4, 1, 2, 2>::PREP_BYTES;
     if (cp == 64) return c_out == 64 ? Cfg2<64, 64, 8, 2, 2, 2>::PREP_BYTES : Cfg2<64, 128, 4, 1, 2, 2>::PREP_BYTES;
@@ -1021,13 +998,10 @@ extern "C" int dgnn_sage_layer_prepare(int c_in, int c_out, const float* We, con
                                        const float* b0, const float* scale1, const float* shift1, const float* W3, const float* b3, void* prepared,
                                        void* stream_) {
     DGNN_REQUIRE(We && be && Wj && Wi && prepared && ((uintptr_t)prepared % 16) == 0, DGNN_E_INVALID, "sage_layer_prepare: null / unaligned pointer");
-    if (W0)
-        return fused_decoder_impl(nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, c_in, nullptr, 0, fused::FE, We, be, Wj, nullptr, Wi, nullptr, nullptr, 1, c_out, W0,
-                                  b0, scale1, shift1, 64, W3, b3, 2, nullptr, prepared, 1, (hipStream_t)stream_);
-    const int cin_pad = c_in <= 32 ? 32 : (c_in <= 64 ? 64 : 128);
-    if (c_in % (cin_pad / 16) != 0) return DGNN_E_UNSUPPORTED;
-    return dgnn_sage_layer_fused_mfma_try(nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, c_in, nullptr, 0, We, be, Wj, nullptr, Wi, nullptr, nullptr, 1, c_out, nullptr,
-                                          0, 2, (hipStream_t)stream_, prepared, 1);
+    LayerCall c{};      // parameters only: the prologue reads nothing else
+    c.c_in = c_in, c.c_out = c_out, c.We = We, c.be = be, c.Wj = Wj, c.Wi = Wi, c.relu = 1, c.stream = (hipStream_t)stream_;
+    if (W0) return fused_decoder_impl(c, fused::FE, {W0, b0, scale1, shift1, 64, W3, b3, 2, nullptr}, prepared, 1);
+    return dgnn_sage_layer_fused_mfma_try(c, 2, prepared, 1);
 }
 
 // dgnn_sage_layer_fused_fwd (gemm mode DGNN_GEMM_F16X2) / dgnn_sage_layer_fused_decoder_fwd with the parameters prepared by dgnn_sage_layer_prepare
@@ -1043,8 +1017,8 @@ extern "C" int dgnn_sage_layer_fused_fwd_p(const int32_t* rowptr, const int32_t*
     if (f_e != fused::FE || lde != fused::FE || ((uintptr_t)edge_attr % 16) != 0 || ((uintptr_t)prepared % 16) != 0 || n_dst * ldx >= ((int64_t)1 << 31) ||
         ldo % 4 != 0 || ((uintptr_t)out % 16) != 0)
         return DGNN_E_UNSUPPORTED;
-    return dgnn_sage_layer_fused_mfma_try(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, c_out, out, ldo, 2,
-                                          (hipStream_t)stream_, const_cast<void*>(prepared), 2);
+    return dgnn_sage_layer_fused_mfma_try({{rowptr, src, eid, n_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, c_out, ldo, (hipStream_t)stream_}, x_src, x_dst, out},
+                                          2, const_cast<void*>(prepared), 2);
 }
 
 extern "C" int dgnn_sage_layer_fused_decoder_fwd_p(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const float* x_src,
@@ -1054,6 +1028,6 @@ extern "C" int dgnn_sage_layer_fused_decoder_fwd_p(const int32_t* rowptr, const 
                                                    const float* scale1, const float* shift1, int c_hidden, const float* W3, const float* b3,
                                                    int n_logits, float* logits, const void* prepared, void* stream_) {
     DGNN_REQUIRE(prepared != nullptr, DGNN_E_INVALID, "sage_layer_fused_decoder_fwd_p: null prepared buffer");
-    return fused_decoder_impl(rowptr, src, eid, n_dst, x_src, x_dst, ldx, c_in, edge_attr, lde, f_e, We, be, Wj, bj, Wi, scale, shift, relu, c_out, W0, b0, scale1,
-                              shift1, c_hidden, W3, b3, n_logits, logits, const_cast<void*>(prepared), 2, (hipStream_t)stream_);
+    return fused_decoder_impl({{rowptr, src, eid, n_dst, ldx, c_in, edge_attr, lde, We, be, Wj, bj, Wi, scale, shift, relu, c_out, 0, (hipStream_t)stream_}, x_src, x_dst, nullptr},
+                              f_e, {W0, b0, scale1, shift1, c_hidden, W3, b3, n_logits, logits}, const_cast<void*>(prepared), 2);
 }

@@ -699,32 +699,29 @@ int dgnn_ws_enabled() {
 // C ABI (include/dgnn_hip.h): which kernel dgnn_sage_layer_fused_fwd / _decoder_fwd launch for a 64 -> 128 / 128 -> 128 layer in DGNN_GEMM_F16X2
 extern "C" int dgnn_wave_specialised_enabled(void) { return dgnn_ws_enabled() != 0 ? 1 : 0; }
 
-// same contract as dgnn_sage_layer_fused_mfma_try for c_in in {64, 128}, c_out == 128; with W0 != NULL (c_in == 128) the launch carries the decoder
-// 128 -> 64 -> 2 and writes logits [n_dst, 2] instead of rows (`out` unused).  DGNN_E_UNSUPPORTED: the caller keeps the two-phase kernel
-int dgnn_sage_layer_fused_ws_try(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const float* x_src, const float* x_dst, int64_t ldx,
-                                 int c_in, const float* edge_attr, int64_t lde, const float* We, const float* be, const float* Wj, const float* bj, const float* Wi,
-                                 const float* scale, const float* shift, int relu, int c_out, float* out, int64_t ldo, hipStream_t stream, const float* W0,
-                                 const float* b0, const float* scale1, const float* shift1, const float* W3, const float* b3, float* logits) {
-    const bool dec = W0 != nullptr;
-    if ((c_in != WS_C && !(c_in == 64 && !dec)) || c_out != WS_C || lde != FE || ldx % 4 != 0 || (!dec && ldo % 4 != 0) ||
-        ((((uintptr_t)x_src | (uintptr_t)x_dst | (uintptr_t)edge_attr | (uintptr_t)(dec ? nullptr : out) | (uintptr_t)Wj | (uintptr_t)Wi | (uintptr_t)W0) % 16) != 0) ||
-        (dec && ((uintptr_t)logits % 8) != 0))
+// contract: fused_common.h
+int dgnn_sage_layer_fused_ws_try(const LayerCall& c, const DecoderTail& t) {
+    const bool dec = t.W0 != nullptr;
+    if ((c.c_in != WS_C && !(c.c_in == 64 && !dec)) || c.c_out != WS_C || c.lde != FE || c.ldx % 4 != 0 || (!dec && c.ldo % 4 != 0) ||
+        ((((uintptr_t)c.x_src | (uintptr_t)c.x_dst | (uintptr_t)c.edge_attr | (uintptr_t)(dec ? nullptr : c.out) | (uintptr_t)c.Wj | (uintptr_t)c.Wi |
+           (uintptr_t)t.W0) % 16) != 0) ||
+        (dec && ((uintptr_t)t.logits % 8) != 0))
         return DGNN_E_UNSUPPORTED;
     static const int ws64 = getenv("DGNN_WS_64") ? atoi(getenv("DGNN_WS_64")) : 1;     // 0: the 64 -> 128 layer stays on the two-phase kernel
-    if (c_in == 64 && !ws64) return DGNN_E_UNSUPPORTED;
-    const int64_t ntiles = dgnn_cdiv(n_dst, WS_TILE);
+    if (c.c_in == 64 && !ws64) return DGNN_E_UNSUPPORTED;
+    const int64_t ntiles = dgnn_cdiv(c.n_dst, WS_TILE);
     int grid = (int)(ntiles < DGNN_NUM_CU ? ntiles : DGNN_NUM_CU);
     if (grid < 1) grid = 1;
-    const WsDec d{W0, b0, scale1, shift1, W3, b3, logits};
+    const WsDec d{t.W0, t.b0, t.scale1, t.shift1, t.W3, t.b3, t.logits};
 #define DGNN_WS_GO(C_, D_)                                                                                                                                  \
     do {                                                                                                                                                    \
         static bool attr_[DGNN_MAX_DEVICES] = {};                                                                                                           \
         const size_t sm_ = D_ ? WsL<C_, 2>::SMEM_DEC : WsL<C_, 2>::SMEM;                                                                                    \
         dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<C_, 2, D_>), sm_, attr_);                                                     \
-        hipLaunchKernelGGL((k_sage_fused_ws<C_, 2, D_>), dim3(grid), dim3(1024), sm_, stream, rowptr, src, eid, n_dst, x_src, x_dst, ldx, edge_attr, lde, We, \
-                           be, Wj, bj, Wi, scale, shift, relu, out, ldo, ntiles, WS_KNOBS, d);                                                              \
+        hipLaunchKernelGGL((k_sage_fused_ws<C_, 2, D_>), dim3(grid), dim3(1024), sm_, c.stream, c.rowptr, c.src, c.eid, c.n_dst, c.x_src, c.x_dst, c.ldx,    \
+                           c.edge_attr, c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, c.out, c.ldo, ntiles, WS_KNOBS, d);                  \
     } while (0)
-    if (c_in == 64) DGNN_WS_GO(64, false);
+    if (c.c_in == 64) DGNN_WS_GO(64, false);
     else if (dec) DGNN_WS_GO(128, true);
     else DGNN_WS_GO(128, false);
 #undef DGNN_WS_GO
@@ -734,34 +731,32 @@ int dgnn_sage_layer_fused_ws_try(const int32_t* rowptr, const int32_t* src, cons
 // The same kernel on the UNSIGNED 16-bit rows of the bf16-storage chain (DGNN_BF16_COMPENSATED | _ROWS_IN_UNSIGNED | _ROWS_OUT_UNSIGNED, fused_bf16.hip): rows
 // decoded to fp32 where the producers use them (exact), the fp16 two-part arithmetic of the fp32-I/O kernel in between, rows encoded (round to nearest even
 // on bit 15) in the consumers' epilogue.  c_in in {64, 128}, c_out == 128, relu (the format has no sign).  DGNN_E_UNSUPPORTED: the caller keeps its own kernel.
-int dgnn_sage_layer_fused_ws16_try(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const uint16_t* x_src, const uint16_t* x_dst,
-                                   int64_t ldx, int c_in, const float* edge_attr, int64_t lde, const float* We, const float* be, const float* Wj, const float* bj,
-                                   const float* Wi, const float* scale, const float* shift, int relu, int c_out, uint16_t* out, int64_t ldo, hipStream_t stream) {
+int dgnn_sage_layer_fused_ws16_try(const LayerCall16& c) {
     static const int on = getenv("DGNN_WS_16") ? atoi(getenv("DGNN_WS_16")) : 1;
-    const int nch = c_in / 16;
-    if (!on || !dgnn_ws_enabled() || (c_in != 128 && c_in != 64) || c_out != WS_C || !relu || lde != FE || ldx % nch != 0 || ldo % 4 != 0 ||
-        ((((uintptr_t)x_src | (uintptr_t)x_dst) % (2 * nch)) != 0) || ((uintptr_t)out % 8) != 0 ||
-        ((((uintptr_t)edge_attr | (uintptr_t)Wj | (uintptr_t)Wi) % 16) != 0))
+    const int nch = c.c_in / 16;
+    if (!on || !dgnn_ws_enabled() || (c.c_in != 128 && c.c_in != 64) || c.c_out != WS_C || !c.relu || c.lde != FE || c.ldx % nch != 0 || c.ldo % 4 != 0 ||
+        ((((uintptr_t)c.x_src | (uintptr_t)c.x_dst) % (2 * nch)) != 0) || ((uintptr_t)c.out % 8) != 0 ||
+        ((((uintptr_t)c.edge_attr | (uintptr_t)c.Wj | (uintptr_t)c.Wi) % 16) != 0))
         return DGNN_E_UNSUPPORTED;
-    const int64_t ntiles = dgnn_cdiv(n_dst, WS_TILE);
+    const int64_t ntiles = dgnn_cdiv(c.n_dst, WS_TILE);
     int grid = (int)(ntiles < DGNN_NUM_CU ? ntiles : DGNN_NUM_CU);
     if (grid < 1) grid = 1;
     const WsDec d{};
-    const float* xs = reinterpret_cast<const float*>(x_src);
-    const float* xd = reinterpret_cast<const float*>(x_dst);
-    float* o = reinterpret_cast<float*>(out);
-    if (c_in == 64) {
+    const float* xs = static_cast<const float*>(c.x_src);
+    const float* xd = static_cast<const float*>(c.x_dst);
+    float* o = reinterpret_cast<float*>(c.out);
+    if (c.c_in == 64) {
         static bool attr_[DGNN_MAX_DEVICES] = {};
         const size_t sm_ = WsL<64, 4>::SMEM;
         dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<64, 4, false, true>), sm_, attr_);
-        hipLaunchKernelGGL((k_sage_fused_ws<64, 4, false, true>), dim3(grid), dim3(1024), sm_, stream, rowptr, src, eid, n_dst, xs, xd, ldx, edge_attr, lde, We, be,
-                           Wj, bj, Wi, scale, shift, relu, o, ldo, ntiles, WS_KNOBS, d);
+        hipLaunchKernelGGL((k_sage_fused_ws<64, 4, false, true>), dim3(grid), dim3(1024), sm_, c.stream, c.rowptr, c.src, c.eid, c.n_dst, xs, xd, c.ldx, c.edge_attr,
+                           c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, o, c.ldo, ntiles, WS_KNOBS, d);
     } else {
         static bool attr_[DGNN_MAX_DEVICES] = {};
         const size_t sm_ = WsL<128, 2>::SMEM;
         dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<128, 2, false, true>), sm_, attr_);
-        hipLaunchKernelGGL((k_sage_fused_ws<128, 2, false, true>), dim3(grid), dim3(1024), sm_, stream, rowptr, src, eid, n_dst, xs, xd, ldx, edge_attr, lde, We, be,
-                           Wj, bj, Wi, scale, shift, relu, o, ldo, ntiles, WS_KNOBS, d);
+        hipLaunchKernelGGL((k_sage_fused_ws<128, 2, false, true>), dim3(grid), dim3(1024), sm_, c.stream, c.rowptr, c.src, c.eid, c.n_dst, xs, xd, c.ldx, c.edge_attr,
+                           c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, o, c.ldo, ntiles, WS_KNOBS, d);
     }
     return dgnn_check_launch("sage_layer_fused_fwd_bf16(wave-specialised)");
 }

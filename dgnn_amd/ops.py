@@ -648,7 +648,7 @@ def linear_sr(A1, Wp, A2=None, bias=None, scale=None, shift=None, relu=False, ou
 
 # ---- fused inference layer ----------------------------------------------------------------------
 def fused_layer_supported(c_in: int, c_out: int, f_e: int, x: torch.Tensor = None) -> bool:
-    """Mirrors the shape dispatch of dgnn_sage_layer_fused_fwd (csrc/fused.hip): c_in <= 64 -> c_out in {64,128};
+    """Mirrors the shape dispatch of dgnn_sage_layer_fused_fwd (the rule is fused::takes_f32_rows in csrc/fused_common.h): c_in <= 64 -> c_out in {64,128};
     64 < c_in <= 128 -> c_out == 128 with even c_in / row stride and 8-byte aligned rows.  Everything else takes the
     aggregate + linear pair."""
     if not FUSED_ENABLED or f_e != 20:
@@ -688,6 +688,16 @@ FUSED_MAX_ELEMS = 1 << 31  # row offsets inside one fused-layer launch are 32-bi
 LAYER_HOOK = None
 
 
+def _out_rows(out, n_dst, cols, cols_name, dtype, like, out_dtypes=torch.float32):
+    """result buffer of a fused layer: a fresh [n_dst, cols] tensor, or the caller's contiguous [>= n_dst, cols] one (its first n_dst rows are written)"""
+    if out is None:
+        return torch.empty((n_dst, cols), dtype=dtype, device=like.device)
+    _req(out, "out", out_dtypes, dim=2)
+    if out.size(0) < n_dst or out.size(1) != cols or out.stride(0) != cols:
+        raise ValueError("out must be a contiguous [>= n_dst, %s] buffer" % cols_name)
+    return out
+
+
 @on_device_of
 def sage_layer_fused_fwd(rowptr, src, n_dst, x_src, edge_attr, We, be, Wj, bj, Wi, scale, shift, relu, gemm_mode=None,
                          out=None, eid=None, x_dst=None, prepared=None):
@@ -698,12 +708,7 @@ def sage_layer_fused_fwd(rowptr, src, n_dst, x_src, edge_attr, We, be, Wj, bj, W
     forward passes the next layer's [n_own + n_halo, C] activation buffer, so no copy is needed)."""
     _req(x_src, "x_src", dim=2)
     c_in, c_out = x_src.size(1), Wj.size(0)
-    if out is None:
-        out = torch.empty((n_dst, c_out), dtype=torch.float32, device=x_src.device)
-    else:
-        _req(out, "out", dim=2)
-        if out.size(0) < n_dst or out.size(1) != c_out or out.stride(0) != c_out:
-            raise ValueError("out must be a contiguous [>= n_dst, c_out] buffer")
+    out = _out_rows(out, n_dst, c_out, "c_out", torch.float32, x_src)
     mode = GEMM_MODE if gemm_mode is None else gemm_mode
     if prepared is not None and mode == GEMM_F16X2:
         # `prepared` (sage_layer_prepare): the launch skips its parameter prologue; a shape the prepared kernels do not take falls through
@@ -761,12 +766,7 @@ def sage_layer_fused_decoder_fwd(rowptr, src, n_dst, x_src, edge_attr, We, be, W
                                  out=None, eid=None, x_dst=None, prepared=None):
     """Last conv layer + decoder, one launch -> logits [n_dst, 2] (written into `out` when given: a contiguous [>= n_dst, 2] fp32 buffer)."""
     _req(x_src, "x_src", dim=2)
-    if out is None:
-        out = torch.empty((n_dst, 2), dtype=torch.float32, device=x_src.device)
-    else:
-        _req(out, "out", dim=2)
-        if out.size(0) < n_dst or out.size(1) != 2 or out.stride(0) != 2:
-            raise ValueError("out must be a contiguous [>= n_dst, 2] buffer")
+    out = _out_rows(out, n_dst, 2, "2", torch.float32, x_src)
     head = (ptr(rowptr), ptr(src), ptr(eid), n_dst, ptr(x_src), ptr(x_dst), _ld(x_src), x_src.size(1), ptr(edge_attr), _ld(edge_attr), We.size(1),
             ptr(We), ptr(be), ptr(Wj), ptr(bj), ptr(Wi), ptr(scale), ptr(shift), int(bool(relu)), Wj.size(0), ptr(W0.contiguous()), ptr(b0),
             ptr(scale1), ptr(shift1), W0.size(0), ptr(W3.contiguous()), ptr(b3), W3.size(0), ptr(out))
@@ -802,6 +802,44 @@ def _infer_tables(x_width, layers, decoder, prepared, cache):
     return out
 
 
+def _one_call(name, x, edge_attr, edge_index, plan_parts, hint, n_key, n_work, n_rows, mid, tables, tail):
+    """The body the one-call family shares (dgnn_static_infer_*; call under on_device_of): plan arrays of the first `n_key` cells (allocated and built
+    inside the call unless `plan_parts` brings them), logits [n_rows, n_out] and the workspace of `n_work` rows; the library call gets the edge_index
+    triple, the plan, `mid` (what the entry point takes between the plan and x), the rows, the tables and `tail` (what it takes between the tables and
+    the workspace).  -> (logits, plan parts), or None when the library refuses the configuration (nothing launched)."""
+    _req(x, "x", dim=2)
+    _req(edge_attr, "edge_attr", dim=2)
+    dev = x.device
+    L, w_arr, cols, _, _, n_out = tables
+    E = edge_index.size(1) if edge_index is not None else plan_parts[1].numel()
+    build = plan_parts is None
+    if build:
+        rowptr = torch.empty(n_key + 1, dtype=torch.int32, device=dev)
+        src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
+        eid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
+        scratch = torch.empty(int(lib().dgnn_plan_scratch_elems(E, n_key)), dtype=torch.int32, device=dev)
+        plan_parts = (rowptr, src, eid)
+    else:
+        rowptr, src, eid = plan_parts
+        scratch = None
+    logits = torch.empty((n_rows, n_out), dtype=torch.float32, device=dev)
+    work = torch.empty(int(lib().dgnn_static_infer_workspace_bytes(n_work, L, w_arr)), dtype=torch.uint8, device=dev)   # (the caching allocator hands out 512-byte aligned blocks)
+    rc = getattr(lib(), name)(
+        ptr(edge_index) if build else None, edge_index.stride(0) if build else 0, edge_index.stride(1) if build else 0, E, hint, ptr(rowptr), ptr(src),
+        ptr(eid), ptr(scratch), *mid, ptr(x), _ld(x), ptr(edge_attr), _ld(edge_attr), edge_attr.size(1), L, w_arr, *cols, *tail, ptr(work), ptr(logits),
+        stream_ptr())
+    if rc == DGNN_E_UNSUPPORTED:
+        return None
+    check(rc, name, poll=build)
+    return logits, plan_parts
+
+
+def _n_dst_array(n_dst, L):
+    import ctypes as C
+    assert len(n_dst) == L
+    return (C.c_int64 * L)(*[int(v) for v in n_dst])
+
+
 @on_device_of
 def static_infer_fwd(x, edge_attr, edge_index, plan_parts, layers, decoder, prepared=None, hint=PLAN_HINT_REFERENCE, gemm_mode=None, fuse_decoder=True, cache=None):
     """-> (logits | last activations, plan parts) or None when a shape is outside the fused kernels (nothing launched).
@@ -809,31 +847,10 @@ def static_infer_fwd(x, edge_attr, edge_index, plan_parts, layers, decoder, prep
     and its arrays are returned.  `layers`: per conv layer (We, be, Wj, bj, Wi, scale | None, shift | None); `decoder` = (W0, b0, scale1 | None,
     shift1 | None, W3, b3) or None; `prepared`: per-layer dgnn_sage_layer_prepare buffers or None; `fuse_decoder`: the last layer's launch carries the
     decoder (prepared[-1] is then the block made WITH the decoder), else layer and decoder run apart.  `cache`: see _infer_tables."""
-    _req(x, "x", dim=2)
-    _req(edge_attr, "edge_attr", dim=2)
-    n, dev = x.size(0), x.device
-    L, w_arr, cols, prep, dec, n_out = _infer_tables(x.size(1), layers, decoder, prepared, cache)
-    E = edge_index.size(1) if edge_index is not None else plan_parts[1].numel()
-    build = plan_parts is None
-    if build:
-        rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
-        src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-        eid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-        scratch = torch.empty(int(lib().dgnn_plan_scratch_elems(E, n)), dtype=torch.int32, device=dev)
-        plan_parts = (rowptr, src, eid)
-    else:
-        rowptr, src, eid = plan_parts
-        scratch = None
-    logits = torch.empty((n, n_out), dtype=torch.float32, device=dev)
-    work = torch.empty(int(lib().dgnn_static_infer_workspace_bytes(n, L, w_arr)), dtype=torch.uint8, device=dev)   # (the caching allocator hands out 512-byte aligned blocks)
-    rc = lib().dgnn_static_infer_fwd(
-        ptr(edge_index) if build else None, edge_index.stride(0) if build else 0, edge_index.stride(1) if build else 0, E, hint, ptr(rowptr), ptr(src),
-        ptr(eid), ptr(scratch), n, ptr(x), _ld(x), ptr(edge_attr), _ld(edge_attr), edge_attr.size(1), L, w_arr, *cols, prep, *dec, int(bool(fuse_decoder)),
-        GEMM_MODE if gemm_mode is None else gemm_mode, ptr(work), ptr(logits), stream_ptr())
-    if rc == DGNN_E_UNSUPPORTED:
-        return None
-    check(rc, "dgnn_static_infer_fwd", poll=build)
-    return logits, plan_parts
+    t = _infer_tables(x.size(1), layers, decoder, prepared, cache)
+    n = x.size(0)
+    return _one_call("dgnn_static_infer_fwd", x, edge_attr, edge_index, plan_parts, hint, n, n, n, (n,), t,
+                     (t[3], *t[4], int(bool(fuse_decoder)), GEMM_MODE if gemm_mode is None else gemm_mode))
 
 
 @on_device_of
@@ -842,69 +859,21 @@ def static_infer_rings_fwd(x, edge_attr, edge_index, plan_parts, n_dst, layers, 
     """One rank's part of a partitioned scene, rings of halo cells recomputed instead of exchanged (dgnn_static_infer_rings_fwd; arguments as
     static_infer_fwd): x [n_loc, F] local rows (owned cells, ring 1, ring 2, ...), `edge_index` the local list (in-edges of the first n_dst[0] cells),
     n_dst[l] = destinations of layer l.  -> (logits [n_dst[-1], n_logits], plan parts) or None (nothing launched)."""
-    import ctypes as C
-    _req(x, "x", dim=2)
-    _req(edge_attr, "edge_attr", dim=2)
-    n_loc, dev = x.size(0), x.device
-    L, w_arr, cols, prep, dec, n_out = _infer_tables(x.size(1), layers, decoder, prepared, cache)
-    assert len(n_dst) == L
-    nd_arr = (C.c_int64 * L)(*[int(v) for v in n_dst])
-    E = edge_index.size(1) if edge_index is not None else plan_parts[1].numel()
-    build = plan_parts is None
-    if build:
-        rowptr = torch.empty(n_dst[0] + 1, dtype=torch.int32, device=dev)
-        src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-        eid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-        scratch = torch.empty(int(lib().dgnn_plan_scratch_elems(E, n_dst[0])), dtype=torch.int32, device=dev)
-        plan_parts = (rowptr, src, eid)
-    else:
-        rowptr, src, eid = plan_parts
-        scratch = None
-    logits = torch.empty((n_dst[-1], n_out), dtype=torch.float32, device=dev)
-    work = torch.empty(int(lib().dgnn_static_infer_workspace_bytes(n_dst[0], L, w_arr)), dtype=torch.uint8, device=dev)
-    rc = lib().dgnn_static_infer_rings_fwd(
-        ptr(edge_index) if build else None, edge_index.stride(0) if build else 0, edge_index.stride(1) if build else 0, E, hint, ptr(rowptr), ptr(src),
-        ptr(eid), ptr(scratch), int(bool(attr_in_plan_order)), n_loc, nd_arr, ptr(x), _ld(x), ptr(edge_attr), _ld(edge_attr), edge_attr.size(1),
-        L, w_arr, *cols, prep, *dec, int(bool(fuse_decoder)), GEMM_MODE if gemm_mode is None else gemm_mode, ptr(work), ptr(logits), stream_ptr())
-    if rc == DGNN_E_UNSUPPORTED:
-        return None
-    check(rc, "dgnn_static_infer_rings_fwd", poll=build)
-    return logits, plan_parts
+    t = _infer_tables(x.size(1), layers, decoder, prepared, cache)
+    return _one_call("dgnn_static_infer_rings_fwd", x, edge_attr, edge_index, plan_parts, hint, n_dst[0], n_dst[0], n_dst[-1],
+                     (int(bool(attr_in_plan_order)), x.size(0), _n_dst_array(n_dst, t[0])), t,
+                     (t[3], *t[4], int(bool(fuse_decoder)), GEMM_MODE if gemm_mode is None else gemm_mode))
 
 
 @on_device_of
 def static_infer_rings_fwd_bf16(x, edge_attr, edge_index, plan_parts, n_dst, layers, decoder, hint=PLAN_HINT_GROUPED, attr_in_plan_order=True, cache=None):
     """static_infer_rings_fwd in bf16 STORAGE (dgnn_static_infer_rings_fwd_bf16): fp32 input rows read in place by the first layer, 16-bit rows (unsigned
     with BF16_UNSIGNED_ROWS) between the layers, the decoder inside the last launch.  A whole scene is n_dst = [n] * L.  None: nothing launched."""
-    import ctypes as C
-    _req(x, "x", dim=2)
-    _req(edge_attr, "edge_attr", dim=2)
-    n_loc, dev = x.size(0), x.device
-    L, w_arr, cols, _, dec, n_out = _infer_tables(x.size(1), layers, decoder, None, cache)
-    assert len(n_dst) == L and decoder is not None
-    nd_arr = (C.c_int64 * L)(*[int(v) for v in n_dst])
-    E = edge_index.size(1) if edge_index is not None else plan_parts[1].numel()
-    build = plan_parts is None
-    if build:
-        rowptr = torch.empty(n_dst[0] + 1, dtype=torch.int32, device=dev)
-        src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-        eid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-        scratch = torch.empty(int(lib().dgnn_plan_scratch_elems(E, n_dst[0])), dtype=torch.int32, device=dev)
-        plan_parts = (rowptr, src, eid)
-    else:
-        rowptr, src, eid = plan_parts
-        scratch = None
-    logits = torch.empty((n_dst[-1], n_out), dtype=torch.float32, device=dev)
-    work = torch.empty(int(lib().dgnn_static_infer_workspace_bytes(n_dst[0], L, w_arr)), dtype=torch.uint8, device=dev)
-    mode = BF16_MODE | (BF16_ROWS_OUT_UNSIGNED if BF16_UNSIGNED_ROWS else 0)
-    rc = lib().dgnn_static_infer_rings_fwd_bf16(
-        ptr(edge_index) if build else None, edge_index.stride(0) if build else 0, edge_index.stride(1) if build else 0, E, hint, ptr(rowptr), ptr(src),
-        ptr(eid), ptr(scratch), int(bool(attr_in_plan_order)), n_loc, nd_arr, ptr(x), _ld(x), ptr(edge_attr), _ld(edge_attr), edge_attr.size(1),
-        L, w_arr, *cols, *dec, mode, ptr(work), ptr(logits), stream_ptr())
-    if rc == DGNN_E_UNSUPPORTED:
-        return None
-    check(rc, "dgnn_static_infer_rings_fwd_bf16", poll=build)
-    return logits, plan_parts
+    assert decoder is not None
+    t = _infer_tables(x.size(1), layers, decoder, None, cache)
+    return _one_call("dgnn_static_infer_rings_fwd_bf16", x, edge_attr, edge_index, plan_parts, hint, n_dst[0], n_dst[0], n_dst[-1],
+                     (int(bool(attr_in_plan_order)), x.size(0), _n_dst_array(n_dst, t[0])), t,
+                     (*t[4], BF16_MODE | (BF16_ROWS_OUT_UNSIGNED if BF16_UNSIGNED_ROWS else 0)))
 
 
 @on_device_of
@@ -913,33 +882,10 @@ def static_infer_partitioned_fwd(x, edge_attr, edge_index, plan_parts, n_own, n_
     """One rank's part of a partitioned scene in one library call (dgnn_static_infer_partitioned_fwd; arguments as static_infer_fwd): x [n_own + n_halo, F]
     local rows, `edge_index` the local list (destinations < n_own), `halo` / `comm` the library's halo plan and communicator (None: a single-rank
     part), `send_buf` a uint8 buffer of n_send * max hidden width * 4 bytes.  -> (logits [n_own, n_logits], plan parts) or None (nothing launched)."""
-    _req(x, "x", dim=2)
-    _req(edge_attr, "edge_attr", dim=2)
-    n_loc, dev = x.size(0), x.device
-    n_halo = n_loc - n_own
-    L, w_arr, cols, prep, dec, n_out = _infer_tables(x.size(1), layers, decoder, prepared, cache)
-    E = edge_index.size(1) if edge_index is not None else plan_parts[1].numel()
-    build = plan_parts is None
-    if build:
-        rowptr = torch.empty(n_own + 1, dtype=torch.int32, device=dev)
-        src = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-        eid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)[:E]
-        scratch = torch.empty(int(lib().dgnn_plan_scratch_elems(E, n_own)), dtype=torch.int32, device=dev)
-        plan_parts = (rowptr, src, eid)
-    else:
-        rowptr, src, eid = plan_parts
-        scratch = None
-    logits = torch.empty((n_own, n_out), dtype=torch.float32, device=dev)
-    work = torch.empty(int(lib().dgnn_static_infer_workspace_bytes(n_loc, L, w_arr)), dtype=torch.uint8, device=dev)
-    rc = lib().dgnn_static_infer_partitioned_fwd(
-        ptr(edge_index) if build else None, edge_index.stride(0) if build else 0, edge_index.stride(1) if build else 0, E, hint, ptr(rowptr), ptr(src),
-        ptr(eid), ptr(scratch), int(bool(attr_in_plan_order)), n_own, n_interior, n_halo, ptr(x), _ld(x), ptr(edge_attr), _ld(edge_attr), edge_attr.size(1),
-        L, w_arr, *cols, prep, *dec, int(bool(fuse_decoder)), GEMM_MODE if gemm_mode is None else gemm_mode, halo, comm, ptr(send_buf), ptr(work), ptr(logits),
-        stream_ptr())
-    if rc == DGNN_E_UNSUPPORTED:
-        return None
-    check(rc, "dgnn_static_infer_partitioned_fwd", poll=build)
-    return logits, plan_parts
+    t = _infer_tables(x.size(1), layers, decoder, prepared, cache)
+    return _one_call("dgnn_static_infer_partitioned_fwd", x, edge_attr, edge_index, plan_parts, hint, n_own, x.size(0), n_own,
+                     (int(bool(attr_in_plan_order)), n_own, n_interior, x.size(0) - n_own), t,
+                     (t[3], *t[4], int(bool(fuse_decoder)), GEMM_MODE if gemm_mode is None else gemm_mode, halo, comm, ptr(send_buf)))
 
 
 def decoder_fused_supported(k: int, hidden: int, n_out: int) -> bool:
@@ -1004,7 +950,7 @@ def cast_to_f32(x: torch.Tensor) -> torch.Tensor:
 
 
 def fused_layer_supported_bf16(c_in: int, c_out: int, f_e: int, x: torch.Tensor = None) -> bool:
-    """Mirrors the shape dispatch of dgnn_sage_layer_fused_fwd_bf16 (csrc/fused_bf16.hip).  `x` fp32: the first layer reading the
+    """Mirrors the shape dispatch of dgnn_sage_layer_fused_fwd_bf16 (the rule is fused::takes_bf16_rows in csrc/fused_common.h).  `x` fp32: the first layer reading the
     caller's fp32 features in place (c_in <= 32)."""
     if not FUSED_ENABLED or f_e != 20 or c_in > 128 or c_out not in (64, 128):
         return False
@@ -1026,12 +972,7 @@ def sage_layer_fused_fwd_bf16(rowptr, src, n_dst, x_src, c_in, edge_attr, We, be
     _req(x_src, "x_src", ACT + (UROWS,), dim=2)
     _same(x_dst, x_src, "x_dst")
     c_out = Wj.size(0)
-    if out is None:
-        out = torch.empty((n_dst, c_out), dtype=UROWS if rows_out_unsigned else BF16, device=x_src.device)
-    else:
-        _req(out, "out", (BF16, UROWS), dim=2)      # the buffer's dtype names the row format it receives
-        if out.size(0) < n_dst or out.size(1) != c_out or out.stride(0) != c_out:
-            raise ValueError("out must be a contiguous [>= n_dst, c_out] buffer")
+    out = _out_rows(out, n_dst, c_out, "c_out", UROWS if rows_out_unsigned else BF16, x_src, (BF16, UROWS))      # a given buffer's dtype names the row format it receives
     fmt = (BF16_ROWS_IN_UNSIGNED if x_src.dtype == UROWS else 0) | (BF16_ROWS_OUT_UNSIGNED if out.dtype == UROWS else 0)
     check(lib().dgnn_sage_layer_fused_fwd_bf16(
         ptr(rowptr), ptr(src), ptr(eid), n_dst, ptr(x_src), int(x_src.dtype == torch.float32), ptr(x_dst), _ld(x_src), c_in, ptr(edge_attr),
@@ -1056,12 +997,7 @@ def sage_layer_fused_decoder_fwd_bf16(rowptr, src, n_dst, x_src, c_in, edge_attr
     """Last conv layer (bf16 storage) + decoder, one launch -> fp32 logits [n_dst, 2]; the layer's output is never rounded to bf16."""
     _req(x_src, "x_src", (BF16, UROWS), dim=2)
     _same(x_dst, x_src, "x_dst")
-    if out is None:
-        out = torch.empty((n_dst, 2), dtype=torch.float32, device=x_src.device)
-    else:
-        _req(out, "out", dim=2)
-        if out.size(0) < n_dst or out.size(1) != 2 or out.stride(0) != 2:
-            raise ValueError("out must be a contiguous [>= n_dst, 2] buffer")
+    out = _out_rows(out, n_dst, 2, "2", torch.float32, x_src)
     check(lib().dgnn_sage_layer_fused_decoder_fwd_bf16(
         ptr(rowptr), ptr(src), ptr(eid), n_dst, ptr(x_src), ptr(x_dst), _ld(x_src), c_in, ptr(edge_attr), _ld(edge_attr), We.size(1), ptr(We), ptr(be),
         ptr(Wj), ptr(bj), ptr(Wi), ptr(scale), ptr(shift), int(bool(relu)), Wj.size(0), ptr(W0.contiguous()), ptr(b0), ptr(scale1), ptr(shift1), W0.size(0),

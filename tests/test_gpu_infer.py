@@ -377,6 +377,44 @@ def test_static_infer_rings_c_abi_rejects_growing_destination_counts():
     assert rc == -1      # DGNN_E_INVALID (include/dgnn_hip.h)
 
 
+def test_one_call_c_abi_refusals_launch_nothing():
+    """the refusal paths of the ring, bf16-storage and partitioned calls as a C caller meets them: DGNN_E_INVALID for a plan without eid whose edge rows are
+    not in plan order and for halo rows without a halo plan, DGNN_E_UNSUPPORTED for a width table outside the fused kernels -- each decided on the host
+    before anything is launched, so the logits buffer keeps what it held"""
+    from dgnn_amd import ops
+    from dgnn_amd._lib import lib, ptr
+    INVALID = -1         # DGNN_E_INVALID (include/dgnn_hip.h)
+    L = 4
+    good = (C.c_int32 * (L + 1))(28, 64, 128, 128, 128)
+    bad = (C.c_int32 * (L + 1))(28, 64, 128, 256, 128)
+    nd = (C.c_int64 * L)(8, 8, 8, 8)
+    t = torch.zeros(8192, device=DEV)
+    i32 = torch.zeros(64, dtype=torch.int32, device=DEV)
+    logits = torch.full((16, 2), 7.0, device=DEV)
+    arr = (C.c_void_p * L)(*[t.data_ptr()] * L)
+    tabs = (arr,) * 7
+    no_dec = (None, None, None, None, 0, None, None, 0)
+    dec = (ptr(t), ptr(t), None, None, 64, ptr(t), ptr(t), 2)
+    plan = lambda eid, attr: (None, 0, 0, 32, 1, ptr(i32), ptr(i32), eid, None, attr)
+    rows = lambda w: (ptr(t), 28, ptr(t), 20, 20, L, w)
+    rings = lambda eid, attr, w: lib().dgnn_static_infer_rings_fwd(*plan(eid, attr), 16, nd, *rows(w), *tabs, None, *no_dec, 1, ops.GEMM_F16X2, ptr(t), ptr(logits), None)
+    bf16 = lambda eid, attr, w: lib().dgnn_static_infer_rings_fwd_bf16(*plan(eid, attr), 16, nd, *rows(w), *tabs, *dec, ops.BF16_COMPENSATED, ptr(t), ptr(logits), None)
+    part = lambda eid, attr, w, n_halo: lib().dgnn_static_infer_partitioned_fwd(*plan(eid, attr), 8, 4, n_halo, *rows(w), *tabs, None, *no_dec, 1, ops.GEMM_F16X2,
+                                                                                 None, None, None, ptr(t), ptr(logits), None)
+    # edge rows in the caller's order (attr_in_plan_order = 0) need the plan's eid
+    assert rings(None, 0, good) == INVALID
+    assert bf16(None, 0, good) == INVALID
+    assert part(None, 0, good, 0) == INVALID
+    # a width the fused kernels do not have (128 -> 256)
+    assert rings(ptr(i32), 0, bad) == ops.DGNN_E_UNSUPPORTED
+    assert bf16(None, 1, bad) == ops.DGNN_E_UNSUPPORTED
+    assert part(None, 1, bad, 0) == ops.DGNN_E_UNSUPPORTED
+    # halo rows nobody sends
+    assert part(None, 1, good, 8) == INVALID
+    torch.cuda.synchronize()
+    assert (logits == 7.0).all()
+
+
 @pytest.mark.parametrize("points,unsigned", [(7, True), (600, True), (9000, True), (9000, False)])
 def test_one_call_bf16_storage_equals_the_per_layer_path(points, unsigned):
     """dgnn_static_infer_rings_fwd_bf16 on a whole scene: the chain of the per-layer bf16 entry points (fp32 input rows read in place, 16-bit rows between
