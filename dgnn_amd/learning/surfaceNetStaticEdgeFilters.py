@@ -27,7 +27,7 @@ from torch.nn import Linear
 
 from .. import functional as Fn
 from .. import ops
-from ..graph import GraphPlan, plan_for
+from ..graph import GraphPlan, plan_for, register_plan
 
 
 class BatchNorm(nn.Module):
@@ -207,9 +207,7 @@ class SurfaceNet(nn.Module):
             return torch.bfloat16
         for j in range(i + 1):
             conv = self.convs[j][0]
-            le = conv.lin_e
-            fused = isinstance(le, Linear) and le.in_features == 20 and ops.fused_layer_supported_bf16(conv.lin_j.in_features, conv.lin_j.out_features, 20)
-            if not fused or (j == 0 and conv.lin_j.in_features > 32) or not isinstance(self.convs[j][2], nn.ReLU):
+            if not self._fuses_bf16(conv) or (j == 0 and conv.lin_j.in_features > 32) or not isinstance(self.convs[j][2], nn.ReLU):
                 return torch.bfloat16
         return ops.UROWS
 
@@ -231,11 +229,7 @@ class SurfaceNet(nn.Module):
         reads the fp32 features in place (they are never rounded), any other first layer gets a bf16 copy."""
         if self.storage_dtype != torch.bfloat16 or x.dtype == torch.bfloat16:
             return x
-        c0 = self.convs[0][0]
-        if isinstance(c0.lin_e, Linear) and c0.lin_e.in_features == 20 and \
-                ops.fused_layer_supported_bf16(c0.lin_j.in_features, c0.lin_j.out_features, 20, x):
-            return x
-        return ops.cast_to_bf16(x)
+        return x if self._fuses_bf16(self.convs[0][0], x) else ops.cast_to_bf16(x)
 
     def _norm_act(self, layer, x):
         """convs[i][1] then convs[i][2] (reference :218-219): BatchNorm / LayerNorm (if any) + ReLU, one kernel chain."""
@@ -305,7 +299,6 @@ class SurfaceNet(nn.Module):
     def _train_spec(self, x, data, dev):
         """-> (per-layer spec for Fn.static_train_model / ops.static_train_fwd, the decoder's output Linear when it does NOT ride in the call | None),
         or None when a layer does not qualify (see _train_whole_model)"""
-        from .. import ops
         if not (ops.TRAIN_COMPOSITE and ops.TRAIN_WHOLE_MODEL) or x.dtype != torch.float32 or self.num_layers + 2 > 8:
             return None
         # the module tree is read once per model (nn.Module.__getattr__ / Sequential.__getitem__ for every layer were a sixth of the step's host
@@ -351,7 +344,6 @@ class SurfaceNet(nn.Module):
         `loss_fn(logits) -> (loss, dlogits)`, the parameters' .grad are SET to the fresh gradients (what zero_grad + backward leave).  Same kernels,
         same order as the autograd node (functional._StaticTrainModel): same numbers.  Returns the detached loss, or None when the model does not
         take the whole-model calls with logits out of the call (the caller then runs the autograd path)."""
-        from .. import ops
         dev = self._device()
         x_all = data.all.x
         n_id = data.batch_n_id.to(x_all.device)
@@ -406,15 +398,126 @@ class SurfaceNet(nn.Module):
                 p_.grad = None
         return loss.detach()
 
+    # ---- eval-mode rules that several paths share: each is said here once ---------------------
+    def _scene_inputs(self, data_all, dev, first_layer=False):
+        """(x, xe) of a whole scene on `dev` without their regularisation column 0 (reference :329-337); `first_layer`: x as conv layer 0 takes it
+        (`_storage_input`)"""
+        x = self._input_rows(_dev_f32(data_all.x, dev))
+        if first_layer:
+            x = self._storage_input(x)
+        xe = _dev_f32(data_all.edge_attr, dev)
+        return x, (xe[:, 1:] if self.clf.regularization.edge_type else xe)
+
+    @staticmethod
+    def _fused_filter(conv):
+        """lin_e in the form the fused and the wide kernels take: one Linear over the 20 edge attributes"""
+        le = conv.lin_e
+        return isinstance(le, Linear) and le.in_features == 20
+
+    def _fuses_bf16(self, conv, x=None):
+        """the fused bf16-storage kernel takes this conv (and, when given, the rows x)"""
+        return self._fused_filter(conv) and ops.fused_layer_supported_bf16(conv.lin_j.in_features, conv.lin_j.out_features, 20, x)
+
+    def _fuses_f32(self, conv, x):
+        """the fused fp32 kernel takes this conv on the rows x"""
+        return self._fused_filter(conv) and ops.fused_layer_supported(x.size(1), conv.lin_j.out_features, 20, x)
+
+    def _carries_decoder(self, conv, x=None):
+        """the fused launch of `conv` can also carry the decoder in this model's storage type: by the widths alone, or -- with `x` -- on these rows"""
+        dec, bf16 = self.decoder, self.storage_dtype == torch.bfloat16
+        if x is not None and not (self._fuses_bf16(conv, x) if bf16 else x.dtype == torch.float32 and self._fuses_f32(conv, x)):
+            return False
+        sup = ops.fused_layer_decoder_supported_bf16 if bf16 else ops.fused_layer_decoder_supported
+        return sup(conv.lin_j.in_features if (bf16 or x is None) else x.size(1), conv.lin_j.out_features, 20, dec[0].out_features, dec[3].out_features, x)
+
+    @staticmethod
+    def _edge_rows(xe, plan, sorted_attr):
+        """(edge_attr, eid) of a fused / wide launch.  sorted_attr: xe is in the caller's edge order -- either the kernel gathers each row by eid (no
+        staging copy of the edge features), or the rows are staged into plan order once (the plan keeps them for all layers).  Rows that are still not
+        packed and 16-byte aligned, e.g. a [:, 1:] view of 21-column rows (regularization.edge_type), are copied."""
+        if sorted_attr and ops.EDGE_GATHER_IN_KERNEL and xe.stride(0) == 20 and xe.data_ptr() % 16 == 0:
+            return xe, plan.eid
+        ea = plan.sorted_edge_attr(xe) if sorted_attr else xe
+        if ea.stride(0) != 20 or ea.data_ptr() % 16:
+            ea = ea.contiguous()
+        return ea, None
+
+    @staticmethod
+    def _dst_range(plan, rows):
+        """(b, e, rowptr of the destinations [b, e)): every destination of the plan, or the sub-range `rows`"""
+        if rows is None:
+            return 0, plan.n_dst, plan.rowptr
+        return rows[0], rows[1], plan.rowptr[rows[0]:rows[1] + 1]
+
+    def _aggregate(self, conv, x, xe, plan, sorted_attr, rows=None, in_kernel=False, bf16=False):
+        """mean_j x_j * lin_e(e_ji) of one conv by the unfused kernels: a Linear over 2 or 20 attributes inside the aggregate (edge rows staged into plan
+        order -- or, `in_kernel`, read through plan.eid), any other filter materialised first (`bf16`: in the bf16 storage type)"""
+        le = conv.lin_e
+        if isinstance(le, Linear) and le.in_features in (2, 20):
+            b, e, rowptr = self._dst_range(plan, rows)
+            ea, eid = (xe, plan.eid) if in_kernel else (plan.sorted_edge_attr(xe) if sorted_attr else xe, None)
+            return ops.aggregate_fwd(rowptr, plan.src, eid, e - b, x, ea, le.weight, le.bias)
+        if rows is not None:
+            raise NotImplementedError("destination sub-ranges need a Linear edge filter")
+        return Fn.aggregate(x, plan, **conv._filter_args(xe, bf16))
+
+    def _cached(self, store, slot, tensors, extra, make):
+        """make(), kept as self.__dict__[store][slot] = (key, value) until one of `tensors` is written to or moved -- the key is their (address, version)
+        pairs: load_state_dict, optimizer steps, .to() and train-mode running statistics all change it -- or `extra` changes"""
+        key = tuple((t.data_ptr(), t._version) for t in tensors) + extra
+        cache = self.__dict__.setdefault(store, {})
+        hit = cache.get(slot)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        val = make()
+        cache[slot] = (key, val)
+        return val
+
+    def _fold(self, norm):
+        """BatchNorm(eval) as a per-channel (scale, shift) pair (`_cached` on its four tensors and eps); (None, None) without one"""
+        if norm is None:
+            return None, None
+        bn = norm.module
+        return self._cached("_fold_cache", id(bn), (bn.weight, bn.bias, bn.running_mean, bn.running_var), (bn.eps,),
+                            lambda: ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps))
+
+    def _layer_fold(self, i):
+        """the folded (scale, shift) behind conv layer i"""
+        norm = self.convs[i][1]
+        return self._fold(norm if isinstance(norm, BatchNorm) else None)
+
+    def _decoder_args(self):
+        """(W0, b0, folded scale, folded shift, W3, b3) of the Linear - norm - ReLU - Linear decoder, as every decoder entry point takes them"""
+        dec = self.decoder
+        s1, h1 = self._fold(dec[1] if isinstance(dec[1], BatchNorm) else None)
+        return dec[0].weight, dec[0].bias, s1, h1, dec[3].weight, dec[3].bias
+
+    def _prepared(self, i, with_decoder):
+        """Prepared parameters of conv layer i for the fused launches (ops.sage_layer_prepare; `_cached` on the tensors they are made from); None when there
+        is no prepared form (other arithmetic, other shapes, DGNN_PREPARED=0)."""
+        conv = self.convs[i][0]
+        if not ops.PREPARED_PARAMS or ops.GEMM_MODE != ops.GEMM_F16X2 or not self._fused_filter(conv):
+            return None
+        le, with_decoder = conv.lin_e, bool(with_decoder)
+        dec_args = self._decoder_args() if with_decoder else None
+        ts = [le.weight, le.bias, conv.lin_j.weight, conv.lin_i.weight] + [t for t in (dec_args or ()) if t is not None]
+        return self._cached("_prep_cache", (i, with_decoder), ts, (with_decoder,),
+                            lambda: ops.sage_layer_prepare(le.weight, le.bias, conv.lin_j.weight, conv.lin_i.weight, dec_args))
+
+    def _wide_prepared(self, key, tensors, make):
+        """what the wide kernels derive from the weights (split weight rows, the filter operand), `_cached` on `tensors`"""
+        return self._cached("_prep_cache", ("wide",) + tuple(key), tensors, (), make)
+
+    def invalidate_caches(self):
+        """Forget everything derived from the parameters (folded BatchNorm, prepared layer blocks, the one-call tables): after replacing a sub-module."""
+        for k in ("_oc_tables", "_fold_cache", "_prep_cache", "_train_mods", "_direct_static", "_param_list", "_grad_keep"):
+            self.__dict__.pop(k, None)
+
     # ---- INFERENCE, whole graph (reference :323-355; the benchmarked path) ---------------------
     @torch.no_grad()
     def inference_layer(self, data_all, plan: GraphPlan = None):
         dev = self._device()
-        x = _dev_f32(data_all.x, dev)
-        x = x[:, 1:] if self.clf.regularization.cell_type else x
-        x = self._storage_input(x)
-        xe = _dev_f32(data_all.edge_attr, dev)
-        xe = xe[:, 1:] if self.clf.regularization.edge_type else xe
+        x, xe = self._scene_inputs(data_all, dev, first_layer=True)
         edge_index = data_all.edge_index.to(dev)
         one = self._infer_one_call(x, xe, edge_index, plan)
         if one is not None:
@@ -460,19 +563,18 @@ class SurfaceNet(nn.Module):
         for i, layer in enumerate(self.convs):
             conv = layer[0]
             le = conv.lin_e
-            if not (isinstance(le, Linear) and le.in_features == 20 and le.bias is not None) or not isinstance(layer[2], nn.ReLU) \
+            if not (self._fused_filter(conv) and le.bias is not None) or not isinstance(layer[2], nn.ReLU) \
                     or not (layer[1] is None or isinstance(layer[1], BatchNorm)):
                 return None
-            if bf16 and not ops.fused_layer_supported_bf16(conv.lin_j.in_features, conv.lin_j.out_features, 20, x if i == 0 else None):
+            if bf16 and not self._fuses_bf16(conv, x if i == 0 else None):
                 return None
-            scale, shift = self._fold(layer[1], conv.lin_j.out_features, x.device)
+            scale, shift = self._layer_fold(i)
             layers.append((le.weight, le.bias, conv.lin_j.weight, conv.lin_j.bias, conv.lin_i.weight, scale, shift))
             prepared.append(None if bf16 else self._prepared(i, with_dec and i == last))
             mods += [le, conv.lin_j, conv.lin_i] + ([layer[1].module] if layer[1] is not None else [])
         decoder = None
         if len(dec) == 4:
-            s1, h1 = self._fold(dec[1], dec[0].out_features, x.device)
-            decoder = (dec[0].weight, dec[0].bias, s1, h1, dec[3].weight, dec[3].bias)
+            decoder = self._decoder_args()
             mods += [dec[0], dec[3]] + ([dec[1].module] if dec[1] is not None else [])
         if bf16 and not with_dec:          # (the bf16 chain has no decoder-apart form)
             return None
@@ -482,28 +584,12 @@ class SurfaceNet(nn.Module):
 
     @staticmethod
     def _oc_key(mods):
-        key = []
-        for m in mods:
-            for t in m._parameters.values():
-                if t is not None:
-                    key.append(t.data_ptr())
-                    key.append(t._version)
-            for t in m._buffers.values():
-                if t is not None:
-                    key.append(t.data_ptr())
-                    key.append(t._version)
-        return key
-
-    def invalidate_caches(self):
-        """Forget everything derived from the parameters (folded BatchNorm, prepared layer blocks, the one-call tables): after replacing a sub-module."""
-        for k in ("_oc_tables", "_fold_cache", "_prep_cache", "_train_mods", "_direct_static", "_param_list", "_grad_keep"):
-            self.__dict__.pop(k, None)
+        return [v for m in mods for ts in (m._parameters, m._buffers) for t in ts.values() if t is not None for v in (t.data_ptr(), t._version)]
 
     def _infer_one_call(self, x, xe, edge_index, plan):
         """The whole eval forward -- plan (unless the caller's or a cached one exists), every conv layer, the decoder -- as ONE library call
         (dgnn_static_infer_fwd issues the launches `_eval_layers` issues, in its order: bit-identical).  Returns the logits, or None when this
         configuration runs layer by layer (`_one_call_tables`)."""
-        from ..graph import register_plan
         if edge_index.dtype != torch.int64:
             return None
         tabs = self._one_call_tables(x, xe)
@@ -531,47 +617,6 @@ class SurfaceNet(nn.Module):
         """the fused launches take packed 20-column fp32 edge rows and 16-byte aligned feature rows; other inputs run layer and decoder apart"""
         return (x.dtype == torch.float32 or self.storage_dtype == torch.bfloat16) and not self.clf.regularization.edge_type
 
-    def _fold(self, norm, c, device):
-        """BatchNorm(eval) as a per-channel (scale, shift) pair, cached until one of its tensors is written to
-        (load_state_dict / optimizer steps / train-mode running statistics all bump the tensors' version counters)."""
-        if norm is None:
-            return None, None
-        bn = norm.module
-        ts = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        key = tuple((t.data_ptr(), t._version) for t in ts) + (bn.eps,)
-        cache = self.__dict__.setdefault("_fold_cache", {})
-        hit = cache.get(id(bn))
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        out = ops.bn_fold(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-        cache[id(bn)] = (key, out)
-        return out
-
-    def _prepared(self, i, with_decoder):
-        """Prepared parameters of conv layer i for the fused launches (ops.sage_layer_prepare), cached until one of the tensors they were made from is
-        written to (same version-counter key as `_fold`); None when there is no prepared form (other arithmetic, other shapes, DGNN_PREPARED=0)."""
-        if not ops.PREPARED_PARAMS or ops.GEMM_MODE != ops.GEMM_F16X2:
-            return None
-        conv = self.convs[i][0]
-        le = conv.lin_e
-        if not isinstance(le, Linear) or le.in_features != 20:
-            return None
-        ts = [le.weight, le.bias, conv.lin_j.weight, conv.lin_i.weight]
-        dec_args = None
-        if with_decoder:
-            dec = self.decoder
-            s1, h1 = self._fold(dec[1] if isinstance(dec[1], BatchNorm) else None, dec[0].out_features, le.weight.device)
-            dec_args = (dec[0].weight, dec[0].bias, s1, h1, dec[3].weight, dec[3].bias)
-            ts += [t for t in dec_args if t is not None]
-        key = (bool(with_decoder),) + tuple((t.data_ptr(), t._version) for t in ts)
-        cache = self.__dict__.setdefault("_prep_cache", {})
-        hit = cache.get((i, bool(with_decoder)))
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        buf = ops.sage_layer_prepare(le.weight, le.bias, conv.lin_j.weight, conv.lin_i.weight, dec_args)
-        cache[(i, bool(with_decoder))] = (key, buf)
-        return buf
-
     def fuses_decoder(self, i):
         """True when layer i's launch also carries the decoder (the last conv layer of the shipped widths, fp32 storage or -- round 4 -- bf16 storage in
         the compensated arithmetic: the finished tile goes through Linear-BN-ReLU-Linear in the same kernel and only the logits are written, reference
@@ -579,14 +624,11 @@ class SurfaceNet(nn.Module):
         if i != self.num_layers - 1 or not self.clf.model.decoder or len(self.decoder) != 4:
             return False
         conv, dec = self.convs[i][0], self.decoder
-        le = conv.lin_e
-        if not (isinstance(le, Linear) and isinstance(dec[0], nn.Linear) and isinstance(dec[3], nn.Linear) and isinstance(dec[2], nn.ReLU)):
+        if not (self._fused_filter(conv) and isinstance(dec[0], nn.Linear) and isinstance(dec[3], nn.Linear) and isinstance(dec[2], nn.ReLU)):
             return False
         if not isinstance(self.convs[i][2], nn.ReLU) or (dec[1] is not None and not isinstance(dec[1], BatchNorm)):
             return False
-        sup = ops.fused_layer_decoder_supported_bf16 if self.storage_dtype == torch.bfloat16 else ops.fused_layer_decoder_supported
-        return sup(conv.lin_j.in_features, conv.lin_j.out_features, le.in_features, dec[0].out_features,
-                   dec[3].out_features) and dec[0].in_features == conv.lin_j.out_features
+        return self._carries_decoder(conv) and dec[0].in_features == conv.lin_j.out_features
 
     def _eval_layers(self, x, n_dst0, xe, plans, sorted_attr, only=None, out=None, rows=None, decode=False):
         """Eval-mode conv stack: per layer one fused launch when the widths allow it, else the
@@ -601,6 +643,7 @@ class SurfaceNet(nn.Module):
             conv_i = self.convs[i][0]
             n_rows = plans[i].n_dst if rows is None else rows[1] - rows[0]
             dec_i = bool(decode) and self.fuses_decoder(i)
+            # (the opening call names the rows' stored width, the closing one the logical width: they differ on zero-padded bf16 rows)
             tok = hook(None, x.size(1), conv_i.lin_j.out_features, n_rows, not dec_i) if hook is not None else None
             x = self._eval_layer(i, x, xe, plans[i], sorted_attr, out, rows, dec_i)
             if hook is not None:
@@ -608,124 +651,87 @@ class SurfaceNet(nn.Module):
         return x
 
     def _eval_layer(self, i, x, xe, plan, sorted_attr, out, rows, decode=False):
-        """One eval-mode conv layer + BN + ReLU (see _eval_layers); `decode`: + the decoder, logits come back."""
-        layer = self.convs[i]
-        conv = layer[0]
-        if isinstance(layer[1], LayerNorm):
+        """One eval-mode conv layer + BN + ReLU (see _eval_layers); `decode`: + the decoder, logits come back.  The routes, in the order they are tried:
+        graph LayerNorm; (decode on rows the one-launch form does not take: layer and decoder apart;) bf16 storage, fused or not; fused fp32; wide
+        split rows; aggregate + GEMM."""
+        conv = self.convs[i][0]
+        if isinstance(self.convs[i][1], LayerNorm):
             return self._eval_layer_ln(i, x, xe, plan, sorted_attr, out, rows, decode)
-        if decode:
-            le_ = conv.lin_e
-            if self.storage_dtype == torch.bfloat16:
-                fusable = (isinstance(le_, Linear) and le_.in_features == 20
-                           and ops.fused_layer_supported_bf16(conv.lin_j.in_features, conv.lin_j.out_features, 20, x)
-                           and ops.fused_layer_decoder_supported_bf16(conv.lin_j.in_features, conv.lin_j.out_features, 20, self.decoder[0].out_features,
-                                                                      self.decoder[3].out_features, x))
-            else:
-                fusable = (x.dtype == torch.float32 and isinstance(le_, Linear) and le_.in_features == 20
-                           and ops.fused_layer_supported(x.size(1), conv.lin_j.out_features, 20, x)
-                           and ops.fused_layer_decoder_supported(x.size(1), conv.lin_j.out_features, 20, self.decoder[0].out_features,
-                                                                 self.decoder[3].out_features, x))
-            if not fusable:     # this input cannot take the one-launch form (alignment, strides ...): layer and decoder apart, same interface
-                lg = self._eval_decoder(self._eval_layer(i, x, xe, plan, sorted_attr, None, rows, False))
-                if out is None:
-                    return lg
-                b_, e_ = (0, plan.n_dst) if rows is None else rows
-                out[b_:e_] = lg
-                return out
-        norm = layer[1] if isinstance(layer[1], BatchNorm) else None
-        scale, shift = self._fold(norm, conv.lin_j.out_features, x.device)
-        le = conv.lin_e
-        b, e = (0, plan.n_dst) if rows is None else rows
-        n, rowptr = e - b, (plan.rowptr if rows is None else plan.rowptr[b:e + 1])
-        x_dst = x[b:e]
-        out_v = out if (out is None or rows is None) else out[b:e]
-        simple = isinstance(le, Linear) and le.in_features in (2, 20)
-        if x.dtype in (torch.bfloat16, ops.UROWS) or (self.storage_dtype == torch.bfloat16 and simple and le.in_features == 20
-                                                      and ops.fused_layer_supported_bf16(conv.lin_j.in_features, conv.lin_j.out_features, 20, x)):
-            c_in = conv.lin_j.in_features    # the logical width: bf16 rows may carry zero padding columns
-            if not (simple and le.in_features == 20 and ops.fused_layer_supported_bf16(c_in, conv.lin_j.out_features, 20, x)):
+        if decode and not self._carries_decoder(conv, x):
+            return self._eval_layer_decoder_apart(i, x, xe, plan, sorted_attr, out, rows)
+        scale, shift = self._layer_fold(i)
+        out_v = out if (out is None or rows is None) else out[rows[0]:rows[1]]
+        if x.dtype in (torch.bfloat16, ops.UROWS) or (self.storage_dtype == torch.bfloat16 and self._fuses_bf16(conv, x)):
+            if not self._fuses_bf16(conv, x):
                 return self._eval_layer_bf16_unfused(conv, scale, shift, x, xe, plan, sorted_attr, out_v, rows)
-            # row format of the output (ops.UROWS): a fused layer on fp32 feature rows starts the unsigned format, one on 16-bit rows keeps its input's;
-            # a caller-supplied buffer names the format by its dtype
-            # (the decoder-carrying launch writes fp32 logits: no row format to agree on)
-            uns = (ops.BF16_UNSIGNED_ROWS and ops.BF16_MODE == ops.BF16_COMPENSATED and x.dtype != torch.bfloat16) if (out_v is None or decode) \
-                else out_v.dtype == ops.UROWS
-            if not decode and x.dtype != torch.float32 and uns != (x.dtype == ops.UROWS):
-                raise ops.DgnnError("bf16 storage: layer %d reads %s rows but is asked to write %s rows" % (i, x.dtype, out_v.dtype))
-            if sorted_attr and ops.EDGE_GATHER_IN_KERNEL and xe.stride(0) == 20 and xe.data_ptr() % 16 == 0:
-                ea, eid = xe, plan.eid
-            else:
-                ea, eid = (plan.sorted_edge_attr(xe) if sorted_attr else xe), None
-                if ea.stride(0) != 20 or ea.data_ptr() % 16:
-                    ea = ea.contiguous()
-            if decode:      # (`fusable` above: the launch carries the decoder and writes fp32 logits)
-                dec = self.decoder
-                s1, h1 = self._fold(dec[1] if isinstance(dec[1], BatchNorm) else None, dec[0].out_features, x.device)
-                return ops.sage_layer_fused_decoder_fwd_bf16(rowptr, plan.src, n, x, c_in, ea, le.weight, le.bias, conv.lin_j.weight, conv.lin_j.bias,
-                                                             conv.lin_i.weight, scale, shift, True, dec[0].weight, dec[0].bias, s1, h1, dec[3].weight,
-                                                             dec[3].bias, out=out_v, eid=eid, x_dst=x_dst if b else None)
-            return ops.sage_layer_fused_fwd_bf16(rowptr, plan.src, n, x, c_in, ea, le.weight, le.bias, conv.lin_j.weight, conv.lin_j.bias,
-                                                 conv.lin_i.weight, scale, shift, True, out=out_v, eid=eid, x_dst=x_dst if b else None,
-                                                 rows_out_unsigned=uns)
-        if simple and le.in_features == 20 and ops.fused_layer_supported(x.size(1), conv.lin_j.out_features, 20, x):
-            # sorted_attr: xe is in the caller's edge order.  Either the kernel gathers each row by eid (no staging
-            # copy of the edge features), or the rows are staged into plan order once and reused by all layers.
-            if sorted_attr and ops.EDGE_GATHER_IN_KERNEL and xe.stride(0) == 20 and xe.data_ptr() % 16 == 0:
-                ea, eid = xe, plan.eid
-            else:
-                ea, eid = (plan.sorted_edge_attr(xe) if sorted_attr else xe), None
-                if ea.stride(0) != 20 or ea.data_ptr() % 16:
-                    ea = ea.contiguous()  # e.g. a [:, 1:] view of 21-column rows (regularization.edge_type)
-            # the kernels address rows with 32-bit element offsets relative to x_dst: beyond 2^31 elements per launch
-            # (16.7M cells at 128 channels) the destinations are processed as consecutive sub-ranges
-            if x.size(0) * x.stride(0) >= (1 << 32):
-                raise ops.DgnnError("fused layer: source rows beyond 2^32 elements (%d x %d); partition the scene "
-                                    "(dgnn_amd.partition)" % (x.size(0), x.stride(0)))
-            chunk = max(1, (ops.FUSED_MAX_ELEMS - 1) // max(x.stride(0), 1))
-            if decode and ops.fused_layer_decoder_supported(x.size(1), conv.lin_j.out_features, 20, self.decoder[0].out_features,
-                                                            self.decoder[3].out_features, x):
-                dec = self.decoder
-                s1, h1 = self._fold(dec[1] if isinstance(dec[1], BatchNorm) else None, dec[0].out_features, x.device)
-                if out_v is None:
-                    out_v = torch.empty((n, 2), dtype=torch.float32, device=x.device)
-                for s0 in range(0, n, chunk):
-                    s1_ = min(n, s0 + chunk)
-                    ops.sage_layer_fused_decoder_fwd(rowptr[s0:s1_ + 1] if (s0 or s1_ < n) else rowptr, plan.src, s1_ - s0, x, ea, le.weight, le.bias,
-                                                     conv.lin_j.weight, conv.lin_j.bias, conv.lin_i.weight, scale, shift, True, dec[0].weight, dec[0].bias,
-                                                     s1, h1, dec[3].weight, dec[3].bias, out=out_v[s0:s1_], eid=eid,
-                                                     x_dst=x_dst[s0:s1_] if (b or s0) else None, prepared=self._prepared(i, True))
-                return out_v
-            if decode:
-                raise ops.DgnnError("decode=True on a layer whose launch cannot carry the decoder (check fuses_decoder first)")
-            if n <= chunk:
-                x = ops.sage_layer_fused_fwd(rowptr, plan.src, n, x, ea, le.weight, le.bias, conv.lin_j.weight,
-                                             conv.lin_j.bias, conv.lin_i.weight, scale, shift, True, out=out_v, eid=eid,
-                                             x_dst=x_dst if b else None, prepared=self._prepared(i, False))
-            else:
-                if out_v is None:
-                    out_v = torch.empty((n, conv.lin_j.out_features), dtype=torch.float32, device=x.device)
-                for s0 in range(0, n, chunk):
-                    s1 = min(n, s0 + chunk)
-                    ops.sage_layer_fused_fwd(rowptr[s0:s1 + 1], plan.src, s1 - s0, x, ea, le.weight, le.bias, conv.lin_j.weight,
-                                             conv.lin_j.bias, conv.lin_i.weight, scale, shift, True, out=out_v[s0:s1], eid=eid,
-                                             x_dst=x_dst[s0:s1], prepared=self._prepared(i, False))
-                x = out_v
-            return x
-        if simple and le.in_features == 20 and out is None and rows is None and self.wide_layer_split_rows(x.size(1), conv.lin_j.out_features):
+            return self._eval_layer_fused_bf16(i, conv, scale, shift, x, xe, plan, sorted_attr, out_v, rows, decode)
+        if self._fuses_f32(conv, x):
+            return self._eval_layer_fused_f32(i, conv, scale, shift, x, xe, plan, sorted_attr, out_v, rows, decode)
+        if self._fused_filter(conv) and out is None and rows is None and self.wide_layer_split_rows(x.size(1), conv.lin_j.out_features):
             y = self._eval_layer_wide(i, conv, scale, shift, x, xe, plan, sorted_attr)
             if y is not None:
                 return y
+        return self._eval_layer_unfused(conv, scale, shift, x, xe, plan, sorted_attr, out_v, rows)
+
+    def _eval_layer_unfused(self, conv, scale, shift, x, xe, plan, sorted_attr, out_v, rows):
+        """fp32 rows, any width: the aggregate + GEMM pair, BatchNorm(eval) and ReLU in the GEMM's epilogue"""
         if isinstance(x, ops.SplitRows):       # a layer the wide kernels do not take behind one they did: back to fp32 rows
             x = x.float()
-            x_dst = x[b:e]
-        if simple:
-            ea = plan.sorted_edge_attr(xe) if sorted_attr else xe
-            a = ops.aggregate_fwd(rowptr, plan.src, None, n, x, ea, le.weight, le.bias)
-        else:
-            if rows is not None:
-                raise NotImplementedError("destination sub-ranges need a Linear edge filter")
-            a = Fn.aggregate(x, plan, **conv._filter_args(xe))
-        return ops.linear_fwd(a, conv.lin_j.weight, x_dst, conv.lin_i.weight, conv.lin_j.bias, scale, shift, True, out=out_v)
+        b, e, _ = self._dst_range(plan, rows)
+        a = self._aggregate(conv, x, xe, plan, sorted_attr, rows)
+        return ops.linear_fwd(a, conv.lin_j.weight, x[b:e], conv.lin_i.weight, conv.lin_j.bias, scale, shift, True, out=out_v)
+
+    def _eval_layer_decoder_apart(self, i, x, xe, plan, sorted_attr, out, rows):
+        """decode=True on an input that cannot take the one-launch form (alignment, strides ...): layer and decoder apart, same interface"""
+        lg = self._eval_decoder(self._eval_layer(i, x, xe, plan, sorted_attr, None, rows, False))
+        if out is None:
+            return lg
+        b, e, _ = self._dst_range(plan, rows)
+        out[b:e] = lg
+        return out
+
+    def _eval_layer_fused_bf16(self, i, conv, scale, shift, x, xe, plan, sorted_attr, out_v, rows, decode):
+        """bf16 storage, one fused launch (`decode`: it carries the decoder and writes fp32 logits).  Unlike the fp32 route it does not split a launch at
+        2^31 elements."""
+        le, c_in = conv.lin_e, conv.lin_j.in_features    # the logical width: bf16 rows may carry zero padding columns
+        b, e, rowptr = self._dst_range(plan, rows)
+        # row format of the output (ops.UROWS): a fused layer on fp32 feature rows starts the unsigned format, one on 16-bit rows keeps its input's;
+        # a caller-supplied buffer names the format by its dtype
+        # (the decoder-carrying launch writes fp32 logits: no row format to agree on)
+        uns = (ops.BF16_UNSIGNED_ROWS and ops.BF16_MODE == ops.BF16_COMPENSATED and x.dtype != torch.bfloat16) if (out_v is None or decode) \
+            else out_v.dtype == ops.UROWS
+        if not decode and x.dtype != torch.float32 and uns != (x.dtype == ops.UROWS):
+            raise ops.DgnnError("bf16 storage: layer %d reads %s rows but is asked to write %s rows" % (i, x.dtype, out_v.dtype))
+        ea, eid = self._edge_rows(xe, plan, sorted_attr)
+        head = (rowptr, plan.src, e - b, x, c_in, ea, le.weight, le.bias, conv.lin_j.weight, conv.lin_j.bias, conv.lin_i.weight, scale, shift, True)
+        x_dst = x[b:e] if b else None
+        if decode:
+            return ops.sage_layer_fused_decoder_fwd_bf16(*head, *self._decoder_args(), out=out_v, eid=eid, x_dst=x_dst)
+        return ops.sage_layer_fused_fwd_bf16(*head, out=out_v, eid=eid, x_dst=x_dst, rows_out_unsigned=uns)
+
+    def _eval_layer_fused_f32(self, i, conv, scale, shift, x, xe, plan, sorted_attr, out_v, rows, decode):
+        """fp32 rows, fused launches (`decode`: they carry the decoder and write the logits).  The kernels address rows with 32-bit element offsets
+        relative to x_dst: beyond 2^31 elements per launch (16.7M cells at 128 channels) the destinations are processed as consecutive sub-ranges."""
+        le = conv.lin_e
+        b, e, rowptr = self._dst_range(plan, rows)
+        n, x_dst = e - b, x[b:e]
+        ea, eid = self._edge_rows(xe, plan, sorted_attr)
+        if x.size(0) * x.stride(0) >= (1 << 32):
+            raise ops.DgnnError("fused layer: source rows beyond 2^32 elements (%d x %d); partition the scene "
+                                "(dgnn_amd.partition)" % (x.size(0), x.stride(0)))
+        if decode and not self._carries_decoder(conv, x):
+            raise ops.DgnnError("decode=True on a layer whose launch cannot carry the decoder (check fuses_decoder first)")
+        launch = ops.sage_layer_fused_decoder_fwd if decode else ops.sage_layer_fused_fwd
+        tail = self._decoder_args() if decode else ()
+        prepared = self._prepared(i, decode)
+        if out_v is None:
+            out_v = torch.empty((n, 2 if decode else conv.lin_j.out_features), dtype=torch.float32, device=x.device)
+        chunk = max(1, (ops.FUSED_MAX_ELEMS - 1) // max(x.stride(0), 1))
+        for s0 in range(0, n, chunk):
+            s1 = min(n, s0 + chunk)
+            launch(rowptr[s0:s1 + 1] if (s0 or s1 < n) else rowptr, plan.src, s1 - s0, x, ea, le.weight, le.bias, conv.lin_j.weight, conv.lin_j.bias,
+                   conv.lin_i.weight, scale, shift, True, *tail, out=out_v[s0:s1], eid=eid, x_dst=x_dst[s0:s1] if (b or s0) else None, prepared=prepared)
+        return out_v
 
     @staticmethod
     def _ln_act(norm, A1, W1, A2=None, W2=None, bias=None):
@@ -742,14 +748,8 @@ class SurfaceNet(nn.Module):
         if isinstance(x, ops.SplitRows):
             x = x.float()
         conv = self.convs[i][0]
-        le = conv.lin_e
-        n = plan.n_dst
-        if isinstance(le, Linear) and le.in_features in (2, 20):
-            ea = plan.sorted_edge_attr(xe) if sorted_attr else xe
-            a = ops.aggregate_fwd(plan.rowptr, plan.src, None, n, x, ea, le.weight, le.bias)
-        else:
-            a = Fn.aggregate(x, plan, **conv._filter_args(xe))
-        return self._ln_act(self.convs[i][1], a, conv.lin_j.weight, x[:n], conv.lin_i.weight, conv.lin_j.bias)
+        a = self._aggregate(conv, x, xe, plan, sorted_attr)
+        return self._ln_act(self.convs[i][1], a, conv.lin_j.weight, x[:plan.n_dst], conv.lin_i.weight, conv.lin_j.bias)
 
     # ---- wide conv layers on split rows (round 5; csrc/wide.hip) -------------------------------------------------------------------------------
     def wide_layer_split_rows(self, c_in, c_out):
@@ -757,27 +757,11 @@ class SurfaceNet(nn.Module):
         of the reference's real configs: configs/eth.yaml:56, aerial.yaml:57, modelnet.yaml:56)"""
         return self.storage_dtype == torch.float32 and ops.wide_layer_supported(int(c_in), int(c_out), 20)
 
-    def _wide_prepared(self, key, tensors, make):
-        """what the wide kernels derive from the weights (split weight rows, the filter operand), cached until one of `tensors` is written to"""
-        k = tuple((t.data_ptr(), t._version) for t in tensors)
-        cache = self.__dict__.setdefault("_prep_cache", {})
-        hit = cache.get(("wide",) + tuple(key))
-        if hit is not None and hit[0] == k:
-            return hit[1]
-        val = make()
-        cache[("wide",) + tuple(key)] = (k, val)
-        return val
-
     def _eval_layer_wide(self, i, conv, scale, shift, x, xe, plan, sorted_attr):
         """conv + BatchNorm(eval) + ReLU of a wide layer: the mean aggregate and the own rows as SPLIT ROWS (ops.SplitRows), the dense product straight on
         them, the output again split rows -- what the next wide layer and the decoder read.  None: the library declined the layout."""
         le = conv.lin_e
-        if sorted_attr and ops.EDGE_GATHER_IN_KERNEL and xe.stride(0) == 20 and xe.data_ptr() % 16 == 0:
-            ea, eid = xe, plan.eid
-        else:
-            ea, eid = (plan.sorted_edge_attr(xe) if sorted_attr else xe), None
-            if ea.stride(0) != 20 or ea.data_ptr() % 16:
-                ea = ea.contiguous()
+        ea, eid = self._edge_rows(xe, plan, sorted_attr)
         prep = self._wide_prepared((i, "filter"), (le.weight, le.bias), lambda: ops.sr_prepare_filter(le.weight, le.bias))
         Wp = self._wide_prepared((i, "dense"), (conv.lin_j.weight, conv.lin_i.weight), lambda: ops.pack_rows(conv.lin_j.weight, conv.lin_i.weight, per_row=True))
         if prep is None:
@@ -799,16 +783,11 @@ class SurfaceNet(nn.Module):
         """bf16 storage, widths the fused bf16 kernel does not cover: the generic bf16 aggregate + bf16-MFMA GEMM pair."""
         if rows is not None:
             raise NotImplementedError("destination sub-ranges in bf16 storage need a fused-kernel width")
-        le = conv.lin_e
         c_in = conv.lin_j.in_features
         if x.dtype == ops.UROWS:      # unsigned rows of a fused layer: the generic kernels take plain bf16
             x = ops.rows_unsigned_to_bf16(x)
         xs = x[:, :c_in] if x.size(1) != c_in else x
-        if isinstance(le, Linear) and le.in_features in (2, 20):
-            ea = plan.sorted_edge_attr(xe) if sorted_attr else xe
-            a = ops.aggregate_fwd(plan.rowptr, plan.src, None, plan.n_dst, xs, ea, le.weight, le.bias)
-        else:
-            a = Fn.aggregate(xs, plan, **conv._filter_args(xe, True))
+        a = self._aggregate(conv, xs, xe, plan, sorted_attr, bf16=True)
         return ops.linear_fwd(a, conv.lin_j.weight, xs[:plan.n_dst], conv.lin_i.weight, conv.lin_j.bias, scale, shift, True, out=out_v,
                               out_dtype=torch.bfloat16)
 
@@ -818,15 +797,15 @@ class SurfaceNet(nn.Module):
             # behind a wide layer: Linear(h3 -> h3/2) + BN + ReLU straight on the split rows (fp32 rows out), then the small output Linear
             if self.clf.model.decoder and len(dec) == 4 and isinstance(dec[0], nn.Linear) and dec[0].out_features % 256 == 0 and isinstance(dec[2], nn.ReLU) \
                     and (dec[1] is None or isinstance(dec[1], BatchNorm)):
-                scale, shift = self._fold(dec[1] if isinstance(dec[1], BatchNorm) else None, dec[0].out_features, x.device)
+                _, b0, scale, shift, W3, b3 = self._decoder_args()
                 Wp = self._wide_prepared(("dec0",), (dec[0].weight,), lambda: ops.pack_rows(dec[0].weight, per_row=True))
                 if isinstance(dec[3], nn.Linear) and dec[3].out_features in (1, 2):      # the output Linear rides in the same launch: only logits leave it
-                    lg = ops.linear_sr(x, Wp, None, dec[0].bias, scale, shift, relu=True, proj=(dec[3].weight, dec[3].bias))
+                    lg = ops.linear_sr(x, Wp, None, b0, scale, shift, relu=True, proj=(W3, b3))
                     if lg is not None:
                         return lg
-                h = ops.linear_sr(x, Wp, None, dec[0].bias, scale, shift, relu=True, out_f32=True)
+                h = ops.linear_sr(x, Wp, None, b0, scale, shift, relu=True, out_f32=True)
                 if h is not None:
-                    return ops.linear_fwd(h, dec[3].weight, bias=dec[3].bias)
+                    return ops.linear_fwd(h, W3, bias=b3)
             x = x.float()
         if x.dtype == ops.UROWS:          # (a last layer that did not carry the decoder left unsigned rows)
             x = ops.rows_unsigned_to_bf16(x)
@@ -837,26 +816,24 @@ class SurfaceNet(nn.Module):
         if isinstance(dec[1], LayerNorm):     # statistics over every row handed to the decoder (reference :185, :314, :351)
             h = self._ln_act(dec[1], x, dec[0].weight, bias=dec[0].bias)
             return ops.linear_fwd(h, dec[3].weight, bias=dec[3].bias)
-        scale, shift = self._fold(dec[1] if isinstance(dec[1], BatchNorm) else None, dec[0].out_features, x.device)
+        W0, b0, scale, shift, W3, b3 = args = self._decoder_args()
+        fused = ops.decoder_fused_supported(dec[0].in_features, dec[0].out_features, dec[3].out_features)
         if x.dtype == torch.bfloat16:
-            if ops.decoder_fused_supported(dec[0].in_features, dec[0].out_features, dec[3].out_features) and x.stride(0) % 8 == 0:
-                return ops.decoder_fused_fwd_bf16(x, dec[0].weight, dec[0].bias, scale, shift, dec[3].weight, dec[3].bias)
-            h = ops.linear_fwd(x, dec[0].weight, bias=dec[0].bias, scale=scale, shift=shift, relu=True, out_dtype=torch.bfloat16)
-            return ops.linear_fwd(h, dec[3].weight, bias=dec[3].bias, out_dtype=torch.float32)
-        if ops.decoder_fused_supported(dec[0].in_features, dec[0].out_features, dec[3].out_features):
-            return ops.decoder_fused_fwd(x, dec[0].weight, dec[0].bias, scale, shift, dec[3].weight, dec[3].bias)
-        h = ops.linear_fwd(x, dec[0].weight, bias=dec[0].bias, scale=scale, shift=shift, relu=True)
-        return ops.linear_fwd(h, dec[3].weight, bias=dec[3].bias)
+            if fused and x.stride(0) % 8 == 0:
+                return ops.decoder_fused_fwd_bf16(x, *args)
+            h = ops.linear_fwd(x, W0, bias=b0, scale=scale, shift=shift, relu=True, out_dtype=torch.bfloat16)
+            return ops.linear_fwd(h, W3, bias=b3, out_dtype=torch.float32)
+        if fused:
+            return ops.decoder_fused_fwd(x, *args)
+        h = ops.linear_fwd(x, W0, bias=b0, scale=scale, shift=shift, relu=True)
+        return ops.linear_fwd(h, W3, bias=b3)
 
     # ---- INFERENCE, batch-major k-hop blocks (reference :232-275) ------------------------------
     @torch.no_grad()
     def inference_batch_layer(self, data_all, batch_loader):
         dev = self._device()
         x_out = torch.zeros([data_all.x.size(0), 2 if self.clf.training.loss == "kl" else 1], dtype=torch.float32, device=dev)
-        x_all = _dev_f32(data_all.x, dev)
-        x_all = x_all[:, 1:] if self.clf.regularization.cell_type else x_all
-        xe_all = _dev_f32(data_all.edge_attr, dev)
-        xe_all = xe_all[:, 1:] if self.clf.regularization.edge_type else xe_all
+        x_all, xe_all = self._scene_inputs(data_all, dev)
         for batch_size, n_id, adjs in batch_loader:
             n_id = n_id.to(dev)
             x = ops.gather_rows(x_all, n_id.to(torch.int32))
@@ -872,28 +849,20 @@ class SurfaceNet(nn.Module):
         return x_out
 
     def _eval_layers_one(self, i, x, ea, plan):
-        """Layer i as the unfused aggregate + GEMM pair (any width; the row-level tests use it as the reference path)."""
-        layer = self.convs[i]
-        conv = layer[0]
-        norm = layer[1] if isinstance(layer[1], BatchNorm) else None
-        scale, shift = self._fold(norm, conv.lin_j.out_features, x.device)
-        le = conv.lin_e
-        if isinstance(le, Linear) and le.in_features in (2, 20):
-            a = ops.aggregate_fwd(plan.rowptr, plan.src, plan.eid, plan.n_dst, x, ea, le.weight, le.bias)
-        else:
-            a = Fn.aggregate(x, plan, **conv._filter_args(ea))
-        if isinstance(layer[1], LayerNorm):
-            return self._ln_act(layer[1], a, conv.lin_j.weight, x[:plan.n_dst], conv.lin_i.weight, conv.lin_j.bias)
+        """Layer i as the unfused aggregate + GEMM pair (any width; the row-level tests use it as the reference path).  Unlike `_eval_layer`'s unfused
+        route the aggregate reads the caller-ordered edge rows through plan.eid: no staged copy."""
+        conv = self.convs[i][0]
+        scale, shift = self._layer_fold(i)
+        a = self._aggregate(conv, x, ea, plan, True, in_kernel=True)
+        if isinstance(self.convs[i][1], LayerNorm):
+            return self._ln_act(self.convs[i][1], a, conv.lin_j.weight, x[:plan.n_dst], conv.lin_i.weight, conv.lin_j.bias)
         return ops.linear_fwd(a, conv.lin_j.weight, x[:plan.n_dst], conv.lin_i.weight, conv.lin_j.bias, scale, shift, True)
 
     # ---- INFERENCE, layer-major 1-hop blocks (reference :279-320) -------------------------------
     @torch.no_grad()
     def inference_layer_batch(self, data_all, batch_loader):
         dev = self._device()
-        x_all = _dev_f32(data_all.x, dev)
-        x_all = x_all[:, 1:] if self.clf.regularization.cell_type else x_all
-        xe_all = _dev_f32(data_all.edge_attr, dev)
-        xe_all = xe_all[:, 1:] if self.clf.regularization.edge_type else xe_all
+        x_all, xe_all = self._scene_inputs(data_all, dev)
         for i in range(self.num_layers):
             xs = []
             for batch_size, n_id, adj in batch_loader:

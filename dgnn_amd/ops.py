@@ -682,9 +682,10 @@ EDGE_GATHER_IN_KERNEL = __import__("os").environ.get("DGNN_EDGE_STAGING", "0") !
 
 FUSED_MAX_ELEMS = 1 << 31  # row offsets inside one fused-layer launch are 32-bit element counts (tests lower it)
 
-# optional profiling hook (bench.py): SurfaceNet._eval_layers calls tok = hook(None, c_in, c_out, n_dst) right before the
-# launches of one eval-mode conv layer (fused: one launch; other widths: aggregate + GEMM) and hook(tok, c_in, c_out, n_dst)
-# right after them, on the launching thread / current stream
+# optional profiling hook (bench.py): SurfaceNet._eval_layers calls tok = hook(None, c_in, c_out, n_dst, plain) right before the
+# launches of one eval-mode conv layer (fused: one launch; other widths: aggregate + GEMM) and hook(tok, c_in, c_out, n_dst, plain)
+# right after them, on the launching thread / current stream.  `plain`: False when the layer's launch also carries the decoder (logits
+# leave it instead of rows).  While a hook is set the one-call paths step aside (SurfaceNet._one_call_tables).
 LAYER_HOOK = None
 
 

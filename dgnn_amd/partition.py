@@ -476,7 +476,7 @@ class PartitionedScene:
         _refuse_graph_layer_norm(net)
         n_src = self.n_own + self.n_halo
         x = self.x_local[:, 1:] if net.clf.regularization.cell_type else self.x_local
-        x = net._storage_input(x) if hasattr(net, "_storage_input") else x
+        x = net._storage_input(x)
         if net.clf.regularization.edge_type:
             # column 0 is the regularisation column (reference :334-337): strip it once, the kernels want packed rows
             if self._xe_stripped is None:
@@ -496,7 +496,7 @@ class PartitionedScene:
         last = net.num_layers - 1
         # the last layer's launches carry the decoder when the model can do that (as the whole-graph inference_layer does: same kernel, so a
         # partitioned scene stays bit-identical to the whole graph); they then write logits [n_own, 2] instead of rows
-        fuse = bool(getattr(net, "fuses_decoder", lambda i: False)(last)) and net._fusable_rows(x, last)
+        fuse = net.fuses_decoder(last) and net._fusable_rows(x, last)
 
         def layer_fn(i, h, out, b, e):
             net._eval_layers(h, self.n_own, xe, [plan] * net.num_layers, False, only=i, out=out, rows=(b, e), decode=fuse and i == last)
@@ -505,110 +505,100 @@ class PartitionedScene:
         if fuse:
             widths[last] = 2
 
-        act = getattr(net, "activation_dtype", None)
         n_alloc = [0]
 
         def alloc(r, c):      # layer i's rows in the format the model stores them in; the decoder-carrying last launch writes fp32 logits
             i = n_alloc[0]
             n_alloc[0] += 1
             logits = fuse and i == last
-            dt = torch.float32 if logits else (act(i, x.dtype) if act is not None else getattr(net, "storage_dtype", torch.float32))
+            dt = torch.float32 if logits else net.activation_dtype(i, x.dtype)
             return torch.empty((r, c), dtype=dt, device=self.device)
         return run_partitioned_layers(self.lp, x, net.num_layers, layer_fn, (lambda lg: lg) if fuse else net._eval_decoder, self.exchange, alloc,
                                       widths=widths)
 
-
-def _partitioned_scene_infer_one_call(self, net, x, xe, n_src, rebuild_plan):
-    """The step as ONE library call (dgnn_static_infer_partitioned_fwd: plan, layer 0, [interior | wait | boundary] + exchange start per later layer,
-    decoder-carrying last launches) when the model's configuration has that form and the exchange is the library's own (RCCL; or there is none to
-    do: a single-rank part).  A strong-scaling shard is otherwise host-bound: 0.58 ms of interpreter time per step in front of 0.2 ms of GPU work
-    at 1/8 of the 1M-tet scene (tools/bench_partition_rank.py).  None: the per-layer chain below runs (any other transport, bf16 storage, hooks)."""
-    from . import ops
-    self.used_one_call = False
-    if not getattr(self, "one_call", True) or getattr(net, "_one_call_tables", None) is None:
-        return None
-    ex = self.exchange
-    if type(ex) is not HaloExchange or (ex.active and ex._native is None) or ex._pending:
-        return None
-    tabs = net._one_call_tables(x, xe) if net.storage_dtype == torch.float32 else None
-    if tabs is None:
-        return None
-    layers, decoder, prepared, with_dec, cache = tabs
-    if with_dec and not net._fusable_rows(x, net.num_layers - 1):      # (the per-layer chain runs layer and decoder apart there: stay identical to it)
-        return None
-    halo = comm = sbuf = None
-    if ex.active:
-        _, comm, halo = ex._native
-        maxw = max(int(l[2].size(0)) for l in layers)
-        nbytes = max(1, int(sum(self.lp.send_counts)) * maxw * 4)
-        sbuf = getattr(self, "_one_call_sbuf", None)
-        if sbuf is None or sbuf.numel() < nbytes:
-            sbuf = self._one_call_sbuf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-    build = self.plan is None or rebuild_plan
-    parts = None if build else (self.plan.rowptr, self.plan.src, self.plan.eid)
-    out = ops.static_infer_partitioned_fwd(x, xe, self.edge_index, parts, self.n_own, self.lp.n_interior, layers, decoder, prepared, halo=halo, comm=comm,
-                                           send_buf=sbuf, fuse_decoder=with_dec, cache=cache)
-    if out is None:
-        return None
-    if build:
-        self.plan = self._GraphPlan(self.edge_index, n_src, self.n_own, hint=1, parts=out[1])
-    self.used_one_call = True
-    return out[0]
-
-
-PartitionedScene._infer_one_call = _partitioned_scene_infer_one_call
-
-
-def _partitioned_scene_infer_rings(self, net, x, xe, n_src, rebuild_plan):
-    """Forward of a ring part (build_ring_part): layer l over the owned cells and the rings that later layers still read; no exchange.  One library call
-    (dgnn_static_infer_rings_fwd) where the model's configuration has that form, else the per-layer entry points over the same destination prefixes."""
-    from . import ops
-    lp, L = self.lp, net.num_layers
-    nd = ring_dst(lp, L)
-    self.used_one_call = False
-    # A part built with MORE rings than the model has conv layers (build_synthetic's default hops=4 under a 3-layer net) also lists the in-edges of
-    # rings this stack never computes.  The local list is grouped by ascending destination, so the edges of the cells layer 0 computes are a PREFIX
-    # of it: the plan (n_key = nd[0]) is built over that prefix only -- surplus edges would otherwise be clamped into the last row by the trusted
-    # builder (ADVICE r4).
-    ei = self.edge_index
-    if len(lp.ring_counts) > L:
-        n_e = int(np.searchsorted(lp.edge_index[1], nd[0], side="left"))
-        ei, xe = ei[:, :n_e], xe[:n_e]
-        self._ring_ei = ei         # (a plan holds its edge list weakly)
-    if self.plan is not None and (self.plan.n_dst != nd[0] or self.plan.E != ei.size(1)):
-        self.plan = None           # (another model depth was run on this part before)
-    build = self.plan is None or rebuild_plan
-    last = L - 1
-    fuse = bool(getattr(net, "fuses_decoder", lambda i: False)(last)) and net._fusable_rows(x, last)
-    tabs = net._one_call_tables(x, xe) if (getattr(self, "one_call", True) and getattr(net, "_one_call_tables", None) is not None) else None
-    if tabs is not None and (not tabs[3] or fuse):
+    def _infer_one_call(self, net, x, xe, n_src, rebuild_plan):
+        """The step as ONE library call (dgnn_static_infer_partitioned_fwd: plan, layer 0, [interior | wait | boundary] + exchange start per later layer,
+        decoder-carrying last launches) when the model's configuration has that form and the exchange is the library's own (RCCL; or there is none to
+        do: a single-rank part).  A strong-scaling shard is otherwise host-bound: 0.58 ms of interpreter time per step in front of 0.2 ms of GPU work
+        at 1/8 of the 1M-tet scene (tools/bench_partition_rank.py).  None: the per-layer chain below runs (any other transport, bf16 storage, hooks)."""
+        from . import ops
+        self.used_one_call = False
+        if not getattr(self, "one_call", True):
+            return None
+        ex = self.exchange
+        if type(ex) is not HaloExchange or (ex.active and ex._native is None) or ex._pending:
+            return None
+        tabs = net._one_call_tables(x, xe) if net.storage_dtype == torch.float32 else None
+        if tabs is None:
+            return None
         layers, decoder, prepared, with_dec, cache = tabs
+        if with_dec and not net._fusable_rows(x, net.num_layers - 1):      # (the per-layer chain runs layer and decoder apart there: stay identical to it)
+            return None
+        halo = comm = sbuf = None
+        if ex.active:
+            _, comm, halo = ex._native
+            maxw = max(int(l[2].size(0)) for l in layers)
+            nbytes = max(1, int(sum(self.lp.send_counts)) * maxw * 4)
+            sbuf = getattr(self, "_one_call_sbuf", None)
+            if sbuf is None or sbuf.numel() < nbytes:
+                sbuf = self._one_call_sbuf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        build = self.plan is None or rebuild_plan
         parts = None if build else (self.plan.rowptr, self.plan.src, self.plan.eid)
-        # (the local list was laid out grouped by destination by build_ring_part: its plan is ONE launch, nothing to verify -- lp.trusted_grouped)
-        hint = ops.PLAN_HINT_GROUPED_TRUSTED if (getattr(lp, "trusted_grouped", False) and RING_TRUSTED_PLAN) else ops.PLAN_HINT_GROUPED
-        if net.storage_dtype == torch.bfloat16:
-            out = ops.static_infer_rings_fwd_bf16(x, xe, ei, parts, nd, layers, decoder, hint=hint, cache=cache)
-        else:
-            out = ops.static_infer_rings_fwd(x, xe, ei, parts, nd, layers, decoder, prepared, hint=hint, fuse_decoder=with_dec, cache=cache)
-        if out is not None:
-            if build:
-                self.plan = self._GraphPlan(ei, n_src, nd[0], hint=1, parts=out[1])
-            self.used_one_call = True
-            return out[0]
-    if build:
-        self.plan = self._GraphPlan(ei, n_src, nd[0], hint=1)
-    plan = self.plan
-    act = getattr(net, "activation_dtype", None)
-    h = x
-    for i in range(L):
-        dec = fuse and i == last
-        dt = torch.float32 if dec else (act(i, x.dtype) if act is not None else getattr(net, "storage_dtype", torch.float32))
-        out = torch.empty((nd[i], 2 if dec else net.clf.model.convs[i]), dtype=dt, device=self.device)
-        h = net._eval_layers(h, nd[i], xe, [plan] * L, False, only=i, out=out, rows=(0, nd[i]), decode=dec)
-    return h if fuse else net._eval_decoder(h[:self.n_own])
+        out = ops.static_infer_partitioned_fwd(x, xe, self.edge_index, parts, self.n_own, self.lp.n_interior, layers, decoder, prepared, halo=halo, comm=comm,
+                                               send_buf=sbuf, fuse_decoder=with_dec, cache=cache)
+        if out is None:
+            return None
+        if build:
+            self.plan = self._GraphPlan(self.edge_index, n_src, self.n_own, hint=1, parts=out[1])
+        self.used_one_call = True
+        return out[0]
 
-
-PartitionedScene._infer_rings = _partitioned_scene_infer_rings
+    def _infer_rings(self, net, x, xe, n_src, rebuild_plan):
+        """Forward of a ring part (build_ring_part): layer l over the owned cells and the rings that later layers still read; no exchange.  One library call
+        (dgnn_static_infer_rings_fwd) where the model's configuration has that form, else the per-layer entry points over the same destination prefixes."""
+        from . import ops
+        lp, L = self.lp, net.num_layers
+        nd = ring_dst(lp, L)
+        self.used_one_call = False
+        # A part built with MORE rings than the model has conv layers (build_synthetic's default hops=4 under a 3-layer net) also lists the in-edges of
+        # rings this stack never computes.  The local list is grouped by ascending destination, so the edges of the cells layer 0 computes are a PREFIX
+        # of it: the plan (n_key = nd[0]) is built over that prefix only -- surplus edges would otherwise be clamped into the last row by the trusted
+        # builder (ADVICE r4).
+        ei = self.edge_index
+        if len(lp.ring_counts) > L:
+            n_e = int(np.searchsorted(lp.edge_index[1], nd[0], side="left"))
+            ei, xe = ei[:, :n_e], xe[:n_e]
+            self._ring_ei = ei         # (a plan holds its edge list weakly)
+        if self.plan is not None and (self.plan.n_dst != nd[0] or self.plan.E != ei.size(1)):
+            self.plan = None           # (another model depth was run on this part before)
+        build = self.plan is None or rebuild_plan
+        last = L - 1
+        fuse = net.fuses_decoder(last) and net._fusable_rows(x, last)
+        tabs = net._one_call_tables(x, xe) if getattr(self, "one_call", True) else None
+        if tabs is not None and (not tabs[3] or fuse):
+            layers, decoder, prepared, with_dec, cache = tabs
+            parts = None if build else (self.plan.rowptr, self.plan.src, self.plan.eid)
+            # (the local list was laid out grouped by destination by build_ring_part: its plan is ONE launch, nothing to verify -- lp.trusted_grouped)
+            hint = ops.PLAN_HINT_GROUPED_TRUSTED if (getattr(lp, "trusted_grouped", False) and RING_TRUSTED_PLAN) else ops.PLAN_HINT_GROUPED
+            if net.storage_dtype == torch.bfloat16:
+                out = ops.static_infer_rings_fwd_bf16(x, xe, ei, parts, nd, layers, decoder, hint=hint, cache=cache)
+            else:
+                out = ops.static_infer_rings_fwd(x, xe, ei, parts, nd, layers, decoder, prepared, hint=hint, fuse_decoder=with_dec, cache=cache)
+            if out is not None:
+                if build:
+                    self.plan = self._GraphPlan(ei, n_src, nd[0], hint=1, parts=out[1])
+                self.used_one_call = True
+                return out[0]
+        if build:
+            self.plan = self._GraphPlan(ei, n_src, nd[0], hint=1)
+        plan = self.plan
+        h = x
+        for i in range(L):
+            dec = fuse and i == last
+            dt = torch.float32 if dec else net.activation_dtype(i, x.dtype)
+            out = torch.empty((nd[i], 2 if dec else net.clf.model.convs[i]), dtype=dt, device=self.device)
+            h = net._eval_layers(h, nd[i], xe, [plan] * L, False, only=i, out=out, rows=(0, nd[i]), decode=dec)
+        return h if fuse else net._eval_decoder(h[:self.n_own])
 
 
 def build_self_halo_part(edge_index: np.ndarray, n: int, remote: np.ndarray) -> LocalPart:
