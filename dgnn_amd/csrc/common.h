@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/dgnn_hip.h"
 
@@ -21,6 +22,12 @@ void dgnn_set_error(const char* fmt, ...);
             return (code);            \
         }                             \
     } while (0)
+
+// A DGNN_* switch between kept forms: on unless the variable is set and starts with '0'
+static inline bool dgnn_env_on(const char* name) {
+    const char* v = getenv(name);
+    return !(v && v[0] == '0');
+}
 
 static inline int dgnn_check_launch(const char* what) {
     hipError_t e = hipGetLastError();

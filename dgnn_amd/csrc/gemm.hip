@@ -12,14 +12,25 @@
 // fragment reads (ds_read_b128) bank-conflict free for the 16-lane groups of that instruction.
 // k-permutation: within a chunk, half-wave h of MFMA step (S,j) multiplies k = 8S + 4h + j, so one
 // b128 read per operand feeds 4 MFMAs; A and B use the same map, hence every k is used exactly once.
-#include <cstdlib>
-
 #include "common.h"
 #include "reduce_common.h"
 
 namespace {
 
 constexpr int BM = 128, BN = 64, BK = 32, LDT = BK + 4;
+
+// The parameters of a forward kernel, in the order of the C entry points: the operand pairs (A1, W1) and (A2, W2; A2 = nullptr: none), each with its permission
+// for 16-byte loads (one flag for both operands in the fp32 kernels, one each in bf16 storage), the epilogue terms, the output.
+#define LINEAR_FWD_TAIL(TO)                                                                                                                  \
+    const float *__restrict__ bias, const float *__restrict__ scale, const float *__restrict__ shift, int relu, int64_t M, int n_out,         \
+        TO *__restrict__ out, int64_t ldo
+#define LINEAR_FWD_PARAMS                                                                                                                    \
+    const float *__restrict__ A1, int64_t lda1, int k1, const float *__restrict__ W1, int64_t ldw1, bool vec1, const float *__restrict__ A2,  \
+        int64_t lda2, int k2, const float *__restrict__ W2, int64_t ldw2, bool vec2, LINEAR_FWD_TAIL(float)
+#define LINEAR_FWD_PARAMS_B(TO)                                                                                                              \
+    const uint16_t *__restrict__ A1, int64_t lda1, int k1, const float *__restrict__ W1, int64_t ldw1, bool va1, bool vw1,                    \
+        const uint16_t *__restrict__ A2, int64_t lda2, int k2, const float *__restrict__ W2, int64_t ldw2, bool va2, bool vw2,                \
+        LINEAR_FWD_TAIL(TO)
 
 // stage a [rows x BK] tile of a row-major matrix into LDS (zero-filled outside [nrows) x [kmax))
 template <int ROWS>
@@ -47,13 +58,7 @@ __device__ __forceinline__ void stage_tile(float* __restrict__ dst, const float*
     }
 }
 
-__global__ void __launch_bounds__(256) k_linear_fwd(const float* __restrict__ A1, int64_t lda1, int k1,
-                                                    const float* __restrict__ W1, int64_t ldw1, bool vec1,
-                                                    const float* __restrict__ A2, int64_t lda2, int k2,
-                                                    const float* __restrict__ W2, int64_t ldw2, bool vec2,
-                                                    const float* __restrict__ bias, const float* __restrict__ scale,
-                                                    const float* __restrict__ shift, int relu, int64_t M, int n_out,
-                                                    float* __restrict__ out, int64_t ldo) {
+__global__ void __launch_bounds__(256) k_linear_fwd(LINEAR_FWD_PARAMS) {
     __shared__ __attribute__((aligned(16))) float As[BM * LDT];
     __shared__ __attribute__((aligned(16))) float Ws[BN * LDT];
     const int lane = lane_id(), w = wave_id_uniform();
@@ -250,12 +255,7 @@ __device__ __forceinline__ void stage_w_bf16(char* __restrict__ dst, const float
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 
 template <typename TO>
-__global__ void __launch_bounds__(256) k_linear_fwd_b(const uint16_t* __restrict__ A1, int64_t lda1, int k1, const float* __restrict__ W1,
-                                                      int64_t ldw1, bool va1, bool vw1, const uint16_t* __restrict__ A2, int64_t lda2, int k2,
-                                                      const float* __restrict__ W2, int64_t ldw2, bool va2, bool vw2,
-                                                      const float* __restrict__ bias, const float* __restrict__ scale,
-                                                      const float* __restrict__ shift, int relu, int64_t M, int n_out, TO* __restrict__ out,
-                                                      int64_t ldo) {
+__global__ void __launch_bounds__(256) k_linear_fwd_b(LINEAR_FWD_PARAMS_B(TO)) {
     __shared__ __attribute__((aligned(16))) char As[BM * LDB];
     __shared__ __attribute__((aligned(16))) char Ws[BN * LDB];
     const int lane = lane_id(), w = wave_id_uniform();
@@ -313,12 +313,7 @@ __global__ void __launch_bounds__(256) k_linear_fwd_b(const uint16_t* __restrict
 // at batch 1024, see k_linear_fwd_x3_mid.  k-steps in k_linear_fwd_b's order: bit-identical results.
 // KS = 4: four groups of four wavefronts walk a quarter of the chunks each (see k_linear_fwd_x3_mid<4>).
 template <typename TO, int KS>
-__global__ void __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) k_linear_fwd_b_mid(const uint16_t* __restrict__ A1, int64_t lda1, int k1, const float* __restrict__ W1,
-                                                                            int64_t ldw1, bool va1, bool vw1, const uint16_t* __restrict__ A2, int64_t lda2, int k2,
-                                                                            const float* __restrict__ W2, int64_t ldw2, bool va2, bool vw2,
-                                                                            const float* __restrict__ bias, const float* __restrict__ scale,
-                                                                            const float* __restrict__ shift, int relu, int64_t M, int n_out, TO* __restrict__ out,
-                                                                            int64_t ldo) {
+__global__ void __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) k_linear_fwd_b_mid(LINEAR_FWD_PARAMS_B(TO)) {
     constexpr int TM = 64, TN = 64;
     extern __shared__ __attribute__((aligned(16))) char midb_smem[];     // per group: As [TM][LDB] | Ws [TN][LDB]
     const int lane = lane_id(), w = wave_id_uniform();
@@ -445,12 +440,7 @@ __global__ void __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) k_linear_fwd_b_mid(
 // wavefront walking 64+ k-steps behind four loads in flight was a 25-50 us dependent chain per launch at M <= 16k whatever the chip had free (the
 // modelnet-width step spent 280-350 us in these launches).  Another summation order than the tiled kernels' -- fp32 rounding level, used only for K >= 1024.
 template <typename TO, bool SPLITK = false>
-__global__ void __launch_bounds__(256) k_linear_fwd_b_small(const uint16_t* __restrict__ A1, int64_t lda1, int k1, const float* __restrict__ W1,
-                                                            int64_t ldw1, bool va1, bool vw1, const uint16_t* __restrict__ A2, int64_t lda2, int k2,
-                                                            const float* __restrict__ W2, int64_t ldw2, bool va2, bool vw2,
-                                                            const float* __restrict__ bias, const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, int relu, int64_t M, int n_out, TO* __restrict__ out,
-                                                            int64_t ldo) {
+__global__ void __launch_bounds__(256) k_linear_fwd_b_small(LINEAR_FWD_PARAMS_B(TO)) {
     __shared__ float splitk_red[SPLITK ? 3 * 16 * 64 : 1];
     const int lane = lane_id(), w = wave_id_uniform();
     const int h = lane >> 5, l31 = lane & 31;
@@ -802,6 +792,20 @@ __device__ __forceinline__ void x3_store(char* __restrict__ dst, const f32x4 (&v
     }
 }
 
+// The six products of an x3 k-step on one accumulator block each of acc[0 .. NB); af / bf[b]: the (hi, mid, lo) fragments.  THE product order of
+// every x3 kernel, forward and weight gradient -- small terms first: lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi -- which their "bit-identical
+// to k_linear_fwd_x3" claims rest on.  With NB > 1 the blocks alternate product by product: consecutive matrix instructions never wait for each
+// other's result, and every accumulator still sees its six products in this order.
+template <int NB>
+__device__ __forceinline__ void x3_mma6(f32x16* acc, const bf16x8_t (&af)[3], const bf16x8_t (*bf)[3]) {
+    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[q]], bf[b][PB[q]], acc[b], 0, 0, 0);
+}
+__device__ __forceinline__ void x3_mma6(f32x16& acc, const bf16x8_t (&af)[3], const bf16x8_t (&bf)[3]) { x3_mma6<1>(&acc, af, &bf); }
+
 // BatchNorm batch statistics from the GEMM that produces z (training forward): every wavefront adds the 32 x 32 accumulator block it is
 // about to store (bias included) into fp64 column sums / sums of squares and writes them as partial row `row / 32` of
 // colstats[ceil(M / 32)][2][n_out] -- the layout k_stats_finalize reads; the launch that used to read z back for them is gone.
@@ -820,12 +824,7 @@ __device__ __forceinline__ void stats_block_store(double* __restrict__ colstats,
     }
 }
 
-__global__ void __launch_bounds__(256, 2) k_linear_fwd_x3(const float* __restrict__ A1, int64_t lda1, int k1, const float* __restrict__ W1,
-                                                          int64_t ldw1, bool vec1, const float* __restrict__ A2, int64_t lda2, int k2,
-                                                          const float* __restrict__ W2, int64_t ldw2, bool vec2,
-                                                          const float* __restrict__ bias, const float* __restrict__ scale,
-                                                          const float* __restrict__ shift, int relu, int64_t M, int n_out,
-                                                          float* __restrict__ out, int64_t ldo, double* __restrict__ colstats) {
+__global__ void __launch_bounds__(256, 2) k_linear_fwd_x3(LINEAR_FWD_PARAMS, double* __restrict__ colstats) {
     __shared__ __attribute__((aligned(16))) char As[XM * XLD];
     __shared__ __attribute__((aligned(16))) char Ws[XN * XLD];
     const int lane = lane_id(), w = wave_id_uniform();
@@ -876,16 +875,7 @@ __global__ void __launch_bounds__(256, 2) k_linear_fwd_x3(const float* __restric
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    f32x16 c = acc[a][b];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][2], bf[b][0], c, 0, 0, 0);   // small terms first
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][0], bf[b][2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][1], bf[b][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][1], bf[b][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][0], bf[b][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][0], bf[b][0], c, 0, 0, 0);
-                    acc[a][b] = c;
-                }
+                for (int b = 0; b < 2; ++b) x3_mma6(acc[a][b], af[a], bf[b]);
         }
     }
 #pragma unroll
@@ -929,12 +919,7 @@ __global__ void __launch_bounds__(256, 2) k_linear_fwd_x3(const float* __restric
 // chunks of loads in flight instead of one changed nothing; four per SIMD hide them behind each other.  (Another summation order than the KS = 1
 // form: fp32 rounding level.)
 template <int KS>
-__global__ void __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) k_linear_fwd_x3_mid(const float* __restrict__ A1, int64_t lda1, int k1, const float* __restrict__ W1,
-                                                                             int64_t ldw1, bool vec1, const float* __restrict__ A2, int64_t lda2, int k2,
-                                                                             const float* __restrict__ W2, int64_t ldw2, bool vec2,
-                                                                             const float* __restrict__ bias, const float* __restrict__ scale,
-                                                                             const float* __restrict__ shift, int relu, int64_t M, int n_out,
-                                                                             float* __restrict__ out, int64_t ldo, double* __restrict__ colstats) {
+__global__ void __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) k_linear_fwd_x3_mid(LINEAR_FWD_PARAMS, double* __restrict__ colstats) {
     constexpr int TM = 64, TN = 64;
     extern __shared__ __attribute__((aligned(16))) char mid_smem[];      // per group: As [TM][XLD] | Ws [TN][XLD]
     const int lane = lane_id(), w = wave_id_uniform();
@@ -982,12 +967,7 @@ __global__ void __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) k_linear_fwd_x3_mid
                 af[p] = *reinterpret_cast<const bf16x8_t*>(ap + p * 64 + S * 32);
                 bf[p] = *reinterpret_cast<const bf16x8_t*>(bp + p * 64 + S * 32);
             }
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2], bf[0], acc, 0, 0, 0);   // small terms first
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[0], acc, 0, 0, 0);
+            x3_mma6(acc, af, bf);
         }
     }
     if (KS > 1) {      // the groups' partial blocks -> group 0, in group order (16 KB per group: [wavefront][register][lane], over the chunk buffers)
@@ -1033,12 +1013,7 @@ __global__ void __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) k_linear_fwd_x3_mid
 // owns 64 x 32 blocks (2 accumulators each) -- the 128-wide tile computes 64..100 % padding columns there.  Same chunk and product
 // order per output element as k_linear_fwd_x3.
 constexpr int ZN = 64;
-__global__ void __launch_bounds__(256, 2) k_linear_fwd_x3_n64(const float* __restrict__ A1, int64_t lda1, int k1, const float* __restrict__ W1,
-                                                              int64_t ldw1, bool vec1, const float* __restrict__ A2, int64_t lda2, int k2,
-                                                              const float* __restrict__ W2, int64_t ldw2, bool vec2,
-                                                              const float* __restrict__ bias, const float* __restrict__ scale,
-                                                              const float* __restrict__ shift, int relu, int64_t M, int n_out,
-                                                              float* __restrict__ out, int64_t ldo, double* __restrict__ colstats) {
+__global__ void __launch_bounds__(256, 2) k_linear_fwd_x3_n64(LINEAR_FWD_PARAMS, double* __restrict__ colstats) {
     __shared__ __attribute__((aligned(16))) char As[XM * XLD];
     __shared__ __attribute__((aligned(16))) char Ws[ZN * XLD];
     const int lane = lane_id(), w = wave_id_uniform();
@@ -1108,16 +1083,7 @@ __global__ void __launch_bounds__(256, 2) k_linear_fwd_x3_n64(const float* __res
                 for (int m = 0; m < 2; ++m) af[m][p] = *reinterpret_cast<const bf16x8_t*>(ap + m * 32 * XLD + p * 64 + S * 32);
             }
 #pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                f32x16 c = acc[a];
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][2], bf[0], c, 0, 0, 0);   // small terms first
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][0], bf[2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][1], bf[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][1], bf[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][0], bf[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][0], bf[0], c, 0, 0, 0);
-                acc[a] = c;
-            }
+            for (int a = 0; a < 2; ++a) x3_mma6(acc[a], af[a], bf);
         }
     }
     const int col = wc * 32 + l31;
@@ -1155,12 +1121,7 @@ __global__ void __launch_bounds__(256, 2) k_linear_fwd_x3_n64(const float* __res
 // independent workgroup slots.  k-steps and products in the order of k_linear_fwd_x3: bit-identical results.
 // SPLITK: as k_linear_fwd_b_small<., true> -- the workgroup's four wavefronts share one output block, a quarter of the k-steps each (K >= 1024 only)
 template <bool SPLITK>
-__global__ void __launch_bounds__(256) k_linear_fwd_x3_small(const float* __restrict__ A1, int64_t lda1, int k1, const float* __restrict__ W1,
-                                                             int64_t ldw1, bool vec1, const float* __restrict__ A2, int64_t lda2, int k2,
-                                                             const float* __restrict__ W2, int64_t ldw2, bool vec2,
-                                                             const float* __restrict__ bias, const float* __restrict__ scale,
-                                                             const float* __restrict__ shift, int relu, int64_t M, int n_out,
-                                                             float* __restrict__ out, int64_t ldo, double* __restrict__ colstats) {
+__global__ void __launch_bounds__(256) k_linear_fwd_x3_small(LINEAR_FWD_PARAMS, double* __restrict__ colstats) {
     __shared__ float splitk_red[SPLITK ? 3 * 16 * 64 : 1];
     const int lane = lane_id(), w = wave_id_uniform();
     const int h = lane >> 5, l31 = lane & 31;
@@ -1216,18 +1177,13 @@ __global__ void __launch_bounds__(256) k_linear_fwd_x3_small(const float* __rest
             x3_split(v[2][2], v[2][3], qh[1], qm[1], ql[1]);
             x3_split(v[3][0], v[3][1], qh[2], qm[2], ql[2]);
             x3_split(v[3][2], v[3][3], qh[3], qm[3], ql[3]);
-            const bf16x8_t a0 = __builtin_bit_cast(bf16x8_t, make_uint4(ph[0], ph[1], ph[2], ph[3])),
-                           a1 = __builtin_bit_cast(bf16x8_t, make_uint4(pm[0], pm[1], pm[2], pm[3])),
-                           a2 = __builtin_bit_cast(bf16x8_t, make_uint4(pl[0], pl[1], pl[2], pl[3])),
-                           b0 = __builtin_bit_cast(bf16x8_t, make_uint4(qh[0], qh[1], qh[2], qh[3])),
-                           b1 = __builtin_bit_cast(bf16x8_t, make_uint4(qm[0], qm[1], qm[2], qm[3])),
-                           b2 = __builtin_bit_cast(bf16x8_t, make_uint4(ql[0], ql[1], ql[2], ql[3]));
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc, 0, 0, 0);   // small terms first
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc, 0, 0, 0);
+            const bf16x8_t af[3] = {__builtin_bit_cast(bf16x8_t, make_uint4(ph[0], ph[1], ph[2], ph[3])),
+                                    __builtin_bit_cast(bf16x8_t, make_uint4(pm[0], pm[1], pm[2], pm[3])),
+                                    __builtin_bit_cast(bf16x8_t, make_uint4(pl[0], pl[1], pl[2], pl[3]))},
+                           bf[3] = {__builtin_bit_cast(bf16x8_t, make_uint4(qh[0], qh[1], qh[2], qh[3])),
+                                    __builtin_bit_cast(bf16x8_t, make_uint4(qm[0], qm[1], qm[2], qm[3])),
+                                    __builtin_bit_cast(bf16x8_t, make_uint4(ql[0], ql[1], ql[2], ql[3]))};
+            x3_mma6(acc, af, bf);
         };
         // four k-steps of loads in flight
         f32x4 r0[4], r1[4], r2[4], r3[4];
@@ -1325,12 +1281,7 @@ __device__ __forceinline__ void y3_store(char* __restrict__ dst, const f32x4 (&v
     }
 }
 
-__global__ void __launch_bounds__(YT, 1) k_linear_fwd_x3_big(const float* __restrict__ A1, int64_t lda1, int k1, const float* __restrict__ W1,
-                                                             int64_t ldw1, bool vec1, const float* __restrict__ A2, int64_t lda2, int k2,
-                                                             const float* __restrict__ W2, int64_t ldw2, bool vec2,
-                                                             const float* __restrict__ bias, const float* __restrict__ scale,
-                                                             const float* __restrict__ shift, int relu, int64_t M, int n_out,
-                                                             float* __restrict__ out, int64_t ldo) {
+__global__ void __launch_bounds__(YT, 1) k_linear_fwd_x3_big(LINEAR_FWD_PARAMS) {
     extern __shared__ __attribute__((aligned(16))) char y3_smem[];
     char* const As = y3_smem;
     char* const Ws = y3_smem + YM * XLD;
@@ -1378,13 +1329,7 @@ __global__ void __launch_bounds__(YT, 1) k_linear_fwd_x3_big(const float* __rest
                 bf16x8_t af[3];
 #pragma unroll
                 for (int p = 0; p < 3; ++p) af[p] = *reinterpret_cast<const bf16x8_t*>(ap + a * 32 * XLD + p * 64 + S * 32);
-                // the two column blocks alternate product by product: consecutive MFMAs never wait for each other's result, and every
-                // accumulator still sees its six products in the same order (small terms first)
-                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-                for (int q = 0; q < 6; ++q)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[q]], bf[b][PB[q]], acc[a][b], 0, 0, 0);
+                x3_mma6<2>(acc[a], af, bf);   // the two column blocks alternate product by product
             }
         }
     }
@@ -1518,12 +1463,7 @@ __device__ __forceinline__ void y2h_store(char* __restrict__ dst, const f32x4 (&
     }
 }
 
-__global__ void __launch_bounds__(YT, 1) k_linear_fwd_x2h_big(const float* __restrict__ A1, int64_t lda1, int k1, const float* __restrict__ W1,
-                                                              int64_t ldw1, bool vec1, const float* __restrict__ A2, int64_t lda2, int k2,
-                                                              const float* __restrict__ W2, int64_t ldw2, bool vec2,
-                                                              const float* __restrict__ bias, const float* __restrict__ scale,
-                                                              const float* __restrict__ shift, int relu, int64_t M, int n_out,
-                                                              float* __restrict__ out, int64_t ldo, const float* __restrict__ scales) {
+__global__ void __launch_bounds__(YT, 1) k_linear_fwd_x2h_big(LINEAR_FWD_PARAMS, const float* __restrict__ scales) {
     extern __shared__ __attribute__((aligned(16))) char y2h_smem[];
     char* const As = y2h_smem;
     char* const Ws = y2h_smem + YM * HLD;
@@ -1818,12 +1758,7 @@ __global__ void __launch_bounds__(256) k_linear_wgrad_x3(const float* __restrict
                 af[p] = *reinterpret_cast<const bf16x8_t*>(ap + p * 64 + S * 32);
                 bf[p] = *reinterpret_cast<const bf16x8_t*>(bp + p * 64 + S * 32);
             }
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2], bf[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[0], acc, 0, 0, 0);
+            x3_mma6(acc, af, bf);
         }
     }
     float* P = partials + (int64_t)blockIdx.z * na * nb;
@@ -1929,12 +1864,7 @@ __global__ void __launch_bounds__(256) k_linear_wgrad_x3_cat(const float* __rest
                 af[p] = *reinterpret_cast<const bf16x8_t*>(ap + p * 64 + S * 32);
                 bf[p] = *reinterpret_cast<const bf16x8_t*>(bp + p * 64 + S * 32);
             }
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2], bf[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[0], acc, 0, 0, 0);
+            x3_mma6(acc, af, bf);
         }
     }
     float* P = partials + (int64_t)blockIdx.z * na * nbt;
@@ -1983,24 +1913,85 @@ int wgrad_splits(int64_t M, int n_a = 0) {
     return (int)(s < 1 ? 1 : s);
 }
 
-bool vec_ok(const float* p, int64_t ld) { return ((uintptr_t)p % 16 == 0) && (ld % 4 == 0); }
+// p may be read by 16-byte loads along rows of ld elements
+bool vec16(const void* p, int64_t ld_elems, size_t elem) { return ((uintptr_t)p % 16 == 0) && ((ld_elems * (int64_t)elem) % 16 == 0); }
+
+// The arguments of a forward call (LINEAR_FWD_PARAMS / LINEAR_FWD_PARAMS_B): filled once per entry point, checked by fwd_validate, expanded
+// into a kernel's parameters by launch.  TA: float or uint16_t (bf16 storage) activations.
+template <typename TA>
+struct FwdArgs {
+    const char* name;   // the entry point, for messages
+    const TA* A1;
+    int64_t lda1;
+    int k1;
+    const float* W1;
+    int64_t ldw1;
+    const TA* A2;
+    int64_t lda2;
+    int k2;
+    const float* W2;
+    int64_t ldw2;
+    const float *bias, *scale, *shift;
+    int relu;
+    int64_t M;
+    int n_out;
+    void* out;
+    int64_t ldo;
+    hipStream_t stream;
+    bool va1, vw1, va2, vw2;   // 16-byte loads allowed; set by fwd_validate
+
+    int K() const { return k1 + (A2 ? k2 : 0); }
+    int64_t tiles(int tm, int tn) const { return dgnn_cdiv(M, tm) * dgnn_cdiv(n_out, tn); }
+    // the grid of the XCD-aware tile map (k_linear_fwd_x3): the row blocks padded to a multiple of 8
+    int64_t tiles_xcd(int tm, int tn) const { return dgnn_cdiv(dgnn_cdiv(M, tm), 8) * 8 * dgnn_cdiv(n_out, tn); }
+};
+
+// The argument rules all forward entry points share; *empty: M == 0, nothing to launch
+template <typename TA>
+int fwd_validate(FwdArgs<TA>& a, bool* empty) {
+    *empty = true;
+    DGNN_REQUIRE(a.M >= 0 && a.n_out > 0 && a.k1 > 0, DGNN_E_INVALID, "%s: bad sizes M=%lld n_out=%d k1=%d", a.name, (long long)a.M, a.n_out, a.k1);
+    if (a.M == 0) return DGNN_OK;
+    DGNN_REQUIRE(a.A1 && a.W1 && a.out, DGNN_E_INVALID, "%s: null pointer", a.name);
+    DGNN_REQUIRE((a.A2 == nullptr) == (a.W2 == nullptr) && (!a.A2 || a.k2 > 0), DGNN_E_INVALID, "%s: A2/W2 must come together", a.name);
+    DGNN_REQUIRE((a.scale == nullptr) == (a.shift == nullptr), DGNN_E_INVALID, "%s: scale/shift must come together", a.name);
+    a.va1 = vec16(a.A1, a.lda1, sizeof(TA)), a.vw1 = vec16(a.W1, a.ldw1, 4);
+    a.va2 = a.A2 && vec16(a.A2, a.lda2, sizeof(TA)), a.vw2 = a.W2 && vec16(a.W2, a.ldw2, 4);
+    *empty = false;
+    return DGNN_OK;
+}
+
+// TO: the kernel's output type; extra: what the kernel takes after ldo (colstats, row scales)
+template <typename TO = float, typename Kern, typename... Extra>
+void launch(Kern kernel, int64_t grid, int block, size_t lds, const FwdArgs<float>& a, Extra... extra) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), lds, a.stream, a.A1, a.lda1, a.k1, a.W1, a.ldw1, a.va1 && a.vw1, a.A2, a.lda2, a.k2, a.W2, a.ldw2,
+                       a.va2 && a.vw2, a.bias, a.scale, a.shift, a.relu, a.M, a.n_out, (TO*)a.out, a.ldo, extra...);
+}
+template <typename TO, typename Kern>
+void launch(Kern kernel, int64_t grid, int block, size_t lds, const FwdArgs<uint16_t>& a) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), lds, a.stream, a.A1, a.lda1, a.k1, a.W1, a.ldw1, a.va1, a.vw1, a.A2, a.lda2, a.k2, a.W2, a.ldw2,
+                       a.va2, a.vw2, a.bias, a.scale, a.shift, a.relu, a.M, a.n_out, (TO*)a.out, a.ldo);
+}
+
+// f(float{}) or f(uint16_t{}): the instantiation for fp32 or bf16 storage, chosen per call
+template <typename F>
+void by_storage(bool is_f32, F f) {
+    if (is_f32)
+        f(float{});
+    else
+        f(uint16_t{});
+}
 
 }  // namespace
 
 extern "C" int dgnn_linear_fwd(const float* A1, int64_t lda1, int k1, const float* W1, int64_t ldw1, const float* A2,
                                int64_t lda2, int k2, const float* W2, int64_t ldw2, const float* bias, const float* scale,
                                const float* shift, int relu, int64_t M, int n_out, float* out, int64_t ldo, void* stream) {
-    DGNN_REQUIRE(M >= 0 && n_out > 0 && k1 > 0, DGNN_E_INVALID, "linear_fwd: bad sizes M=%lld n_out=%d k1=%d", (long long)M, n_out, k1);
-    if (M == 0) return DGNN_OK;
-    DGNN_REQUIRE(A1 && W1 && out, DGNN_E_INVALID, "linear_fwd: null pointer");
-    DGNN_REQUIRE((A2 == nullptr) == (W2 == nullptr) && (!A2 || k2 > 0), DGNN_E_INVALID, "linear_fwd: A2/W2 must come together");
-    DGNN_REQUIRE((scale == nullptr) == (shift == nullptr), DGNN_E_INVALID, "linear_fwd: scale/shift must come together");
-    const bool v1 = vec_ok(A1, lda1) && vec_ok(W1, ldw1);
-    const bool v2 = A2 && vec_ok(A2, lda2) && vec_ok(W2, ldw2);
-    dim3 grid((unsigned)(dgnn_cdiv(M, BM) * dgnn_cdiv(n_out, BN)));
-    hipLaunchKernelGGL(k_linear_fwd, grid, dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, v1, A2, lda2, k2, W2,
-                       ldw2, v2, bias, scale, shift, relu, M, n_out, out, ldo);
-    return dgnn_check_launch("linear_fwd");
+    FwdArgs<float> a{"linear_fwd", A1, lda1, k1, W1, ldw1, A2, lda2, k2, W2, ldw2, bias, scale, shift, relu, M, n_out, out, ldo, (hipStream_t)stream};
+    bool empty;
+    if (const int rc = fwd_validate(a, &empty); rc != DGNN_OK || empty) return rc;
+    launch(k_linear_fwd, a.tiles(BM, BN), 256, 0, a);
+    return dgnn_check_launch(a.name);
 }
 
 extern "C" int64_t dgnn_linear_wgrad_scratch_elems(int64_t M, int n_a, int n_b) {
@@ -2024,78 +2015,42 @@ extern "C" int dgnn_linear_wgrad(const float* A, int64_t lda, int n_a, const flo
 
 
 // ---- bf16 storage entry points ----------------------------------------------------------------------------------------------
-static bool vec16(const void* p, int64_t ld_elems, size_t elem) { return ((uintptr_t)p % 16 == 0) && ((ld_elems * (int64_t)elem) % 16 == 0); }
-
 extern "C" int dgnn_linear_fwd_bf16(const uint16_t* A1, int64_t lda1, int k1, const float* W1, int64_t ldw1, const uint16_t* A2, int64_t lda2,
                                     int k2, const float* W2, int64_t ldw2, const float* bias, const float* scale, const float* shift, int relu,
                                     int64_t M, int n_out, void* out, int64_t ldo, int out_f32, void* stream) {
-    DGNN_REQUIRE(M >= 0 && n_out > 0 && k1 > 0, DGNN_E_INVALID, "linear_fwd_bf16: bad sizes M=%lld n_out=%d k1=%d", (long long)M, n_out, k1);
-    if (M == 0) return DGNN_OK;
-    DGNN_REQUIRE(A1 && W1 && out, DGNN_E_INVALID, "linear_fwd_bf16: null pointer");
-    DGNN_REQUIRE((A2 == nullptr) == (W2 == nullptr) && (!A2 || k2 > 0), DGNN_E_INVALID, "linear_fwd_bf16: A2/W2 must come together");
-    DGNN_REQUIRE((scale == nullptr) == (shift == nullptr), DGNN_E_INVALID, "linear_fwd_bf16: scale/shift must come together");
-    const bool va1 = vec16(A1, lda1, 2), vw1 = vec16(W1, ldw1, 4);
-    const bool va2 = A2 && vec16(A2, lda2, 2), vw2 = W2 && vec16(W2, ldw2, 4);
-    static const bool small_ok = !(getenv("DGNN_BF16_SMALL") && getenv("DGNN_BF16_SMALL")[0] == '0');
-    static const bool splitk_ok = !(getenv("DGNN_SMALL_SPLITK") && getenv("DGNN_SMALL_SPLITK")[0] == '0');
+    FwdArgs<uint16_t> a{"linear_fwd_bf16", A1, lda1, k1, W1, ldw1, A2, lda2, k2, W2, ldw2, bias, scale, shift, relu, M, n_out, out, ldo, (hipStream_t)stream};
+    bool empty;
+    if (const int rc = fwd_validate(a, &empty); rc != DGNN_OK || empty) return rc;
+    const int K = a.K();
+    const int64_t tiles128 = a.tiles(BM, BN), tiles64 = a.tiles(64, 64), tiles32 = a.tiles(32, 32);
+    static const bool small_ok = dgnn_env_on("DGNN_BF16_SMALL"), splitk_ok = dgnn_env_on("DGNN_SMALL_SPLITK");
     // Round 6: the small-problem kernel re-reads its operands once per 32 x 32 output block -- fine for the shipped widths' inner blocks, not for the
     // reference's training widths (M = 6 000, K = N = 512: 38 us against the tiled kernel's 28; M = 12 000, K = N = 1024: 249 against 100,
     // tools/bench_gemm_train_shapes.py).  It keeps the problems whose 128 x 64 tiles would leave most of the chip idle (fewer than 150 of them).
-    static const bool by_tiles = !(getenv("DGNN_SMALL_BY_TILES") && getenv("DGNN_SMALL_BY_TILES")[0] == '0');
-    const bool tiles_fill = by_tiles && k1 + (A2 ? k2 : 0) >= 128 && dgnn_cdiv(M, BM) * dgnn_cdiv(n_out, BN) >= 150;
-    static const bool mid_ok = !(getenv("DGNN_GEMM_MID") && getenv("DGNN_GEMM_MID")[0] == '0');
-    if (mid_ok && !tiles_fill && M <= 16384 && k1 + (A2 ? k2 : 0) >= 512 && dgnn_cdiv(M, 64) * dgnn_cdiv(n_out, 64) >= 128) {   // 64 x 64 tiles (see the kernel)
-        dim3 mgrid((unsigned)(dgnn_cdiv(M, 64) * dgnn_cdiv(n_out, 64)));
+    static const bool by_tiles = dgnn_env_on("DGNN_SMALL_BY_TILES"), mid_ok = dgnn_env_on("DGNN_GEMM_MID"), ks_ok = dgnn_env_on("DGNN_GEMM_MID_KS");
+    const bool tiles_fill = by_tiles && K >= 128 && tiles128 >= 150;
+    if (mid_ok && !tiles_fill && M <= 16384 && K >= 512 && tiles64 >= 128) {   // 64 x 64 tiles (see the kernel)
         constexpr size_t lds1 = (size_t)(64 + 64) * LDB;
-        static const bool ks_ok = !(getenv("DGNN_GEMM_MID_KS") && getenv("DGNN_GEMM_MID_KS")[0] == '0');
-        const bool ks4 = ks_ok && k1 + (A2 ? k2 : 0) >= 1024 && dgnn_cdiv(M, 64) * dgnn_cdiv(n_out, 64) <= 2 * DGNN_NUM_CU;
         static_assert(4 * lds1 >= 3 * 4 * 16 * 64 * sizeof(float), "the groups' partial blocks fit the chunk buffers");
-#define DGNN_MIDB(TO_, KS_)                                                                                                                                  \
-        hipLaunchKernelGGL((k_linear_fwd_b_mid<TO_, KS_>), mgrid, dim3(256 * KS_), KS_ * lds1, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, va1, vw1, A2, lda2, k2, \
-                           W2, ldw2, va2, vw2, bias, scale, shift, relu, M, n_out, (TO_*)out, ldo)
-        if (ks4) {
-            static bool attr_f[DGNN_MAX_DEVICES], attr_h[DGNN_MAX_DEVICES];
-            if (out_f32) {
-                dgnn_allow_dynamic_lds((const void*)k_linear_fwd_b_mid<float, 4>, 4 * lds1, attr_f);
-                DGNN_MIDB(float, 4);
+        const bool ks4 = ks_ok && K >= 1024 && tiles64 <= 2 * DGNN_NUM_CU;
+        by_storage(out_f32, [&](auto to) {
+            using TO = decltype(to);
+            if (ks4) {
+                static bool attr_set[DGNN_MAX_DEVICES];   // one per output type
+                dgnn_allow_dynamic_lds((const void*)k_linear_fwd_b_mid<TO, 4>, 4 * lds1, attr_set);
+                launch<TO>(k_linear_fwd_b_mid<TO, 4>, tiles64, 1024, 4 * lds1, a);
             } else {
-                dgnn_allow_dynamic_lds((const void*)k_linear_fwd_b_mid<uint16_t, 4>, 4 * lds1, attr_h);
-                DGNN_MIDB(uint16_t, 4);
+                launch<TO>(k_linear_fwd_b_mid<TO, 1>, tiles64, 256, lds1, a);
             }
-        } else {
-            if (out_f32) DGNN_MIDB(float, 1); else DGNN_MIDB(uint16_t, 1);
-        }
-#undef DGNN_MIDB
-        return dgnn_check_launch("linear_fwd_bf16");
+        });
+    } else if (small_ok && !tiles_fill && splitk_ok && M <= 16384 && K >= 1024) {   // four wavefronts per output block, a quarter of K each (see the kernel)
+        by_storage(out_f32, [&](auto to) { launch<decltype(to)>(k_linear_fwd_b_small<decltype(to), true>, tiles32, 256, 0, a); });
+    } else if (small_ok && !tiles_fill && M <= 16384) {   // same k order per output element: identical results
+        by_storage(out_f32, [&](auto to) { launch<decltype(to)>(k_linear_fwd_b_small<decltype(to)>, dgnn_cdiv(tiles32, 4), 256, 0, a); });
+    } else {
+        by_storage(out_f32, [&](auto to) { launch<decltype(to)>(k_linear_fwd_b<decltype(to)>, tiles128, 256, 0, a); });
     }
-    if (small_ok && !tiles_fill && splitk_ok && M <= 16384 && k1 + (A2 ? k2 : 0) >= 1024) {   // four wavefronts per output block, a quarter of K each (see the kernel)
-        dim3 sgrid((unsigned)(dgnn_cdiv(M, 32) * dgnn_cdiv(n_out, 32)));
-        if (out_f32)
-            hipLaunchKernelGGL((k_linear_fwd_b_small<float, true>), sgrid, dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, va1, vw1, A2, lda2, k2, W2,
-                               ldw2, va2, vw2, bias, scale, shift, relu, M, n_out, (float*)out, ldo);
-        else
-            hipLaunchKernelGGL((k_linear_fwd_b_small<uint16_t, true>), sgrid, dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, va1, vw1, A2, lda2, k2,
-                               W2, ldw2, va2, vw2, bias, scale, shift, relu, M, n_out, (uint16_t*)out, ldo);
-        return dgnn_check_launch("linear_fwd_bf16");
-    }
-    if (small_ok && !tiles_fill && M <= 16384) {   // same k order per output element: identical results
-        dim3 sgrid((unsigned)dgnn_cdiv(dgnn_cdiv(M, 32) * dgnn_cdiv(n_out, 32), 4));
-        if (out_f32)
-            hipLaunchKernelGGL((k_linear_fwd_b_small<float>), sgrid, dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, va1, vw1, A2, lda2, k2, W2,
-                               ldw2, va2, vw2, bias, scale, shift, relu, M, n_out, (float*)out, ldo);
-        else
-            hipLaunchKernelGGL((k_linear_fwd_b_small<uint16_t>), sgrid, dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, va1, vw1, A2, lda2, k2,
-                               W2, ldw2, va2, vw2, bias, scale, shift, relu, M, n_out, (uint16_t*)out, ldo);
-        return dgnn_check_launch("linear_fwd_bf16");
-    }
-    dim3 grid((unsigned)(dgnn_cdiv(M, BM) * dgnn_cdiv(n_out, BN)));
-    if (out_f32)
-        hipLaunchKernelGGL((k_linear_fwd_b<float>), grid, dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, va1, vw1, A2, lda2, k2, W2, ldw2,
-                           va2, vw2, bias, scale, shift, relu, M, n_out, (float*)out, ldo);
-    else
-        hipLaunchKernelGGL((k_linear_fwd_b<uint16_t>), grid, dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, va1, vw1, A2, lda2, k2, W2,
-                           ldw2, va2, vw2, bias, scale, shift, relu, M, n_out, (uint16_t*)out, ldo);
-    return dgnn_check_launch("linear_fwd_bf16");
+    return dgnn_check_launch(a.name);
 }
 
 extern "C" int dgnn_linear_wgrad_bf16(const void* A, int a_f32, int64_t lda, int n_a, const void* B, int b_f32, int64_t ldb, int n_b, int64_t M,
@@ -2107,12 +2062,13 @@ extern "C" int dgnn_linear_wgrad_bf16(const void* A, int a_f32, int64_t lda, int
     int64_t rps = dgnn_cdiv(dgnn_cdiv(M, splits), RKB) * RKB;
     if (rps < RKB) rps = RKB;
     dim3 grid((unsigned)dgnn_cdiv(n_a, WT), (unsigned)dgnn_cdiv(n_b, WT), splits);
-#define WG(TA, TB) hipLaunchKernelGGL((k_linear_wgrad_b<TA, TB>), grid, dim3(256), 0, stream, (const TA*)A, lda, n_a, (const TB*)B, ldb, n_b, M, rps, partials)
-    if (a_f32 && b_f32) WG(float, float);
-    else if (a_f32) WG(float, uint16_t);
-    else if (b_f32) WG(uint16_t, float);
-    else WG(uint16_t, uint16_t);
-#undef WG
+    by_storage(a_f32, [&](auto ta) {
+        by_storage(b_f32, [&](auto tb) {
+            using TA = decltype(ta);
+            using TB = decltype(tb);
+            hipLaunchKernelGGL((k_linear_wgrad_b<TA, TB>), grid, dim3(256), 0, stream, (const TA*)A, lda, n_a, (const TB*)B, ldb, n_b, M, rps, partials);
+        });
+    });
     hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)dgnn_cdiv((int64_t)n_a * n_b, 16)), dim3(256), 0, stream, partials, splits, n_a, n_b, dW, lddw,
                        accumulate);
     return dgnn_check_launch("linear_wgrad_bf16");
@@ -2121,82 +2077,58 @@ extern "C" int dgnn_linear_wgrad_bf16(const void* A, int a_f32, int64_t lda, int
 
 // ---- fp32-class GEMMs on the bf16 matrix cores (3-way exact split, 6 products) ---------------------------------------------
 namespace {
-int linear_fwd_x3_impl(const float* A1, int64_t lda1, int k1, const float* W1, int64_t ldw1, const float* A2, int64_t lda2, int k2, const float* W2,
-                       int64_t ldw2, const float* bias, const float* scale, const float* shift, int relu, int64_t M, int n_out, float* out, int64_t ldo,
-                       double* colstats, void* stream) {
-    DGNN_REQUIRE(M >= 0 && n_out > 0 && k1 > 0, DGNN_E_INVALID, "linear_fwd_x3: bad sizes M=%lld n_out=%d k1=%d", (long long)M, n_out, k1);
-    if (M == 0) return DGNN_OK;
-    DGNN_REQUIRE(A1 && W1 && out, DGNN_E_INVALID, "linear_fwd_x3: null pointer");
-    DGNN_REQUIRE((A2 == nullptr) == (W2 == nullptr) && (!A2 || k2 > 0), DGNN_E_INVALID, "linear_fwd_x3: A2/W2 must come together");
-    DGNN_REQUIRE((scale == nullptr) == (shift == nullptr), DGNN_E_INVALID, "linear_fwd_x3: scale/shift must come together");
-    const bool v1 = vec_ok(A1, lda1) && vec_ok(W1, ldw1);
-    const bool v2 = A2 && vec_ok(A2, lda2) && vec_ok(W2, ldw2);
-    static const bool big_ok = !(getenv("DGNN_X3_BIG") && getenv("DGNN_X3_BIG")[0] == '0');
+int linear_fwd_x3_impl(FwdArgs<float> a, double* colstats) {
+    bool empty;
+    if (const int rc = fwd_validate(a, &empty); rc != DGNN_OK || empty) return rc;
+    const int64_t M = a.M;
+    const int n_out = a.n_out, K = a.K();
+    const int64_t tiles256 = a.tiles(YM, YN), tiles128 = a.tiles(XM, XN), tiles64 = a.tiles(64, 64), tiles32 = a.tiles(32, 32);
+    static const bool big_ok = dgnn_env_on("DGNN_X3_BIG"), small_ok = dgnn_env_on("DGNN_X3_SMALL"), by_tiles = dgnn_env_on("DGNN_SMALL_BY_TILES"),
+                      mid_ok = dgnn_env_on("DGNN_GEMM_MID"), ks_ok = dgnn_env_on("DGNN_GEMM_MID_KS"), splitk_ok = dgnn_env_on("DGNN_SMALL_SPLITK"),
+                      n64_ok = dgnn_env_on("DGNN_X3_N64");
+    constexpr int64_t small_m = 16384;
+    // (round 6: ... unless the 128 x 128 tiles of the tiled kernels would fill the chip anyway -- 150 of them -- where the small-problem kernel's operand
+    // re-reads cost more than its barrier-free walk saves: M = 6 000, K = N = 512 57 -> 44 us, M = 12 000, K = N = 1024 356 -> 172 us)
+    const bool tiles_fill = by_tiles && K >= 128 && n_out > ZN && tiles128 >= 150;
     // the 256 x 256 tile pays once its grid fills most of the chip (192 tiles; the merged input-gradient GEMM of a training block, M = 10k,
     // n_out = 256, has 40: 42 us there against 29 us for the small tiles); same arithmetic per output element (chunk order, product
     // order) in every variant: identical results
-    if (big_ok && M >= 8192 && n_out > XN && dgnn_cdiv(M, YM) * dgnn_cdiv(n_out, YN) >= 192) {
+    if (big_ok && M >= 8192 && n_out > XN && tiles256 >= 192) {
         if (colstats) return DGNN_E_UNSUPPORTED;   // the wide tile has no statistics epilogue: the caller reduces z in a launch of its own
         static bool attr_set[DGNN_MAX_DEVICES];
         constexpr size_t lds = (size_t)(YM + YN) * XLD;
         dgnn_allow_dynamic_lds((const void*)k_linear_fwd_x3_big, lds, attr_set);
-        dim3 grid((unsigned)(dgnn_cdiv(dgnn_cdiv(M, YM), 8) * 8 * dgnn_cdiv(n_out, YN)));
-        hipLaunchKernelGGL(k_linear_fwd_x3_big, grid, dim3(YT), lds, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, v1, A2, lda2, k2, W2, ldw2, v2,
-                           bias, scale, shift, relu, M, n_out, out, ldo);
-        return dgnn_check_launch("linear_fwd_x3");
-    }
-    static const bool small_ok = !(getenv("DGNN_X3_SMALL") && getenv("DGNN_X3_SMALL")[0] == '0');
-    constexpr int64_t small_m = 16384;
-    // (round 6: ... unless the 128 x 128 tiles of the tiled kernels would fill the chip anyway -- 150 of them -- where the small-problem kernel's operand
-    // re-reads cost more than its barrier-free walk saves: M = 6 000, K = N = 512 57 -> 44 us, M = 12 000, K = N = 1024 356 -> 172 us)
-    static const bool by_tiles = !(getenv("DGNN_SMALL_BY_TILES") && getenv("DGNN_SMALL_BY_TILES")[0] == '0');
-    const bool tiles_fill = by_tiles && k1 + (A2 ? k2 : 0) >= 128 && n_out > ZN && dgnn_cdiv(M, XM) * dgnn_cdiv(n_out, XN) >= 150;
-    // ... and between the two: 64 x 64 tiles when THEY fill the chip and the inner dimension is long enough for the operand re-reads of the
-    // small-problem kernel to matter (k_linear_fwd_x3_mid)
-    static const bool mid_ok = !(getenv("DGNN_GEMM_MID") && getenv("DGNN_GEMM_MID")[0] == '0');
-    if (mid_ok && !tiles_fill && M <= small_m && n_out > ZN && k1 + (A2 ? k2 : 0) >= 512 && dgnn_cdiv(M, 64) * dgnn_cdiv(n_out, 64) >= 128) {
-        dim3 grid((unsigned)(dgnn_cdiv(dgnn_cdiv(M, 64), 8) * 8 * dgnn_cdiv(n_out, 64)));
+        launch(k_linear_fwd_x3_big, a.tiles_xcd(YM, YN), YT, lds, a);
+    } else if (mid_ok && !tiles_fill && M <= small_m && n_out > ZN && K >= 512 && tiles64 >= 128) {
+        // ... and between the two: 64 x 64 tiles when THEY fill the chip and the inner dimension is long enough for the operand re-reads of the
+        // small-problem kernel to matter (k_linear_fwd_x3_mid)
         constexpr size_t lds1 = (size_t)(64 + 64) * XLD;
-        static const bool ks_ok = !(getenv("DGNN_GEMM_MID_KS") && getenv("DGNN_GEMM_MID_KS")[0] == '0');
-        if (ks_ok && k1 + (A2 ? k2 : 0) >= 1024 && dgnn_cdiv(M, 64) * dgnn_cdiv(n_out, 64) <= 2 * DGNN_NUM_CU) {
+        if (ks_ok && K >= 1024 && tiles64 <= 2 * DGNN_NUM_CU) {
             static bool attr_set[DGNN_MAX_DEVICES];
             dgnn_allow_dynamic_lds((const void*)k_linear_fwd_x3_mid<4>, 4 * lds1, attr_set);
-            hipLaunchKernelGGL(k_linear_fwd_x3_mid<4>, grid, dim3(1024), 4 * lds1, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, v1, A2, lda2, k2, W2, ldw2, v2, bias,
-                               scale, shift, relu, M, n_out, out, ldo, colstats);
+            launch(k_linear_fwd_x3_mid<4>, a.tiles_xcd(64, 64), 1024, 4 * lds1, a, colstats);
         } else {
-            hipLaunchKernelGGL(k_linear_fwd_x3_mid<1>, grid, dim3(256), lds1, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, v1, A2, lda2, k2, W2, ldw2, v2, bias, scale,
-                               shift, relu, M, n_out, out, ldo, colstats);
+            launch(k_linear_fwd_x3_mid<1>, a.tiles_xcd(64, 64), 256, lds1, a, colstats);
         }
-        return dgnn_check_launch("linear_fwd_x3");
-    }
-    if (small_ok && !tiles_fill && M <= small_m) {
-        const int64_t tiles = dgnn_cdiv(M, 32) * dgnn_cdiv(n_out, 32);
-        static const bool splitk_ok = !(getenv("DGNN_SMALL_SPLITK") && getenv("DGNN_SMALL_SPLITK")[0] == '0');
-        if (splitk_ok && k1 + (A2 ? k2 : 0) >= 1024)
-            hipLaunchKernelGGL(k_linear_fwd_x3_small<true>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, v1, A2, lda2,
-                               k2, W2, ldw2, v2, bias, scale, shift, relu, M, n_out, out, ldo, colstats);
+    } else if (small_ok && !tiles_fill && M <= small_m) {
+        if (splitk_ok && K >= 1024)
+            launch(k_linear_fwd_x3_small<true>, tiles32, 256, 0, a, colstats);
         else
-            hipLaunchKernelGGL(k_linear_fwd_x3_small<false>, dim3((unsigned)dgnn_cdiv(tiles, 4)), dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, v1, A2,
-                               lda2, k2, W2, ldw2, v2, bias, scale, shift, relu, M, n_out, out, ldo, colstats);
-        return dgnn_check_launch("linear_fwd_x3");
+            launch(k_linear_fwd_x3_small<false>, dgnn_cdiv(tiles32, 4), 256, 0, a, colstats);
+    } else if (n64_ok && n_out <= ZN) {
+        launch(k_linear_fwd_x3_n64, dgnn_cdiv(M, XM), 256, 0, a, colstats);
+    } else {
+        launch(k_linear_fwd_x3, a.tiles_xcd(XM, XN), 256, 0, a, colstats);
     }
-    static const bool n64_ok = !(getenv("DGNN_X3_N64") && getenv("DGNN_X3_N64")[0] == '0');
-    if (n64_ok && n_out <= ZN) {
-        hipLaunchKernelGGL(k_linear_fwd_x3_n64, dim3((unsigned)dgnn_cdiv(M, XM)), dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, v1, A2, lda2, k2,
-                           W2, ldw2, v2, bias, scale, shift, relu, M, n_out, out, ldo, colstats);
-        return dgnn_check_launch("linear_fwd_x3");
-    }
-    dim3 grid((unsigned)(dgnn_cdiv(dgnn_cdiv(M, XM), 8) * 8 * dgnn_cdiv(n_out, XN)));
-    hipLaunchKernelGGL(k_linear_fwd_x3, grid, dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, v1, A2, lda2, k2, W2, ldw2, v2, bias,
-                       scale, shift, relu, M, n_out, out, ldo, colstats);
-    return dgnn_check_launch("linear_fwd_x3");
+    return dgnn_check_launch(a.name);
 }
 }  // namespace
 
 extern "C" int dgnn_linear_fwd_x3(const float* A1, int64_t lda1, int k1, const float* W1, int64_t ldw1, const float* A2, int64_t lda2, int k2,
                                   const float* W2, int64_t ldw2, const float* bias, const float* scale, const float* shift, int relu,
                                   int64_t M, int n_out, float* out, int64_t ldo, void* stream) {
-    return linear_fwd_x3_impl(A1, lda1, k1, W1, ldw1, A2, lda2, k2, W2, ldw2, bias, scale, shift, relu, M, n_out, out, ldo, nullptr, stream);
+    return linear_fwd_x3_impl({"linear_fwd_x3", A1, lda1, k1, W1, ldw1, A2, lda2, k2, W2, ldw2, bias, scale, shift, relu, M, n_out, out, ldo, (hipStream_t)stream},
+                              nullptr);
 }
 
 // dgnn_linear_fwd_x3 that also leaves the fp64 column sums and sums of squares of `out` per block of 32 rows in
@@ -2206,7 +2138,8 @@ extern "C" int dgnn_linear_fwd_x3_stats(const float* A1, int64_t lda1, int k1, c
                                         const float* W2, int64_t ldw2, const float* bias, int64_t M, int n_out, float* out, int64_t ldo,
                                         double* colstats, void* stream) {
     DGNN_REQUIRE(colstats && ((uintptr_t)colstats & 7) == 0, DGNN_E_INVALID, "linear_fwd_x3_stats: colstats missing or unaligned");
-    return linear_fwd_x3_impl(A1, lda1, k1, W1, ldw1, A2, lda2, k2, W2, ldw2, bias, nullptr, nullptr, 0, M, n_out, out, ldo, colstats, stream);
+    return linear_fwd_x3_impl({"linear_fwd_x3", A1, lda1, k1, W1, ldw1, A2, lda2, k2, W2, ldw2, bias, nullptr, nullptr, 0, M, n_out, out, ldo, (hipStream_t)stream},
+                              colstats);
 }
 
 extern "C" int64_t dgnn_linear_fwd_x2h_scratch_elems(int64_t M, int n_out) { return M + n_out; }
@@ -2216,22 +2149,17 @@ extern "C" int64_t dgnn_linear_fwd_x2h_scratch_elems(int64_t M, int n_out) { ret
 extern "C" int dgnn_linear_fwd_x2h(const float* A1, int64_t lda1, int k1, const float* W1, int64_t ldw1, const float* A2, int64_t lda2, int k2,
                                    const float* W2, int64_t ldw2, const float* bias, const float* scale, const float* shift, int relu,
                                    int64_t M, int n_out, float* out, int64_t ldo, float* scratch, void* stream) {
-    DGNN_REQUIRE(M >= 0 && n_out > 0 && k1 > 0, DGNN_E_INVALID, "linear_fwd_x2h: bad sizes M=%lld n_out=%d k1=%d", (long long)M, n_out, k1);
-    if (M == 0) return DGNN_OK;
-    DGNN_REQUIRE(A1 && W1 && out && scratch, DGNN_E_INVALID, "linear_fwd_x2h: null pointer");
-    DGNN_REQUIRE((A2 == nullptr) == (W2 == nullptr) && (!A2 || k2 > 0), DGNN_E_INVALID, "linear_fwd_x2h: A2/W2 must come together");
-    DGNN_REQUIRE((scale == nullptr) == (shift == nullptr), DGNN_E_INVALID, "linear_fwd_x2h: scale/shift must come together");
+    FwdArgs<float> a{"linear_fwd_x2h", A1, lda1, k1, W1, ldw1, A2, lda2, k2, W2, ldw2, bias, scale, shift, relu, M, n_out, out, ldo, (hipStream_t)stream};
+    bool empty;
+    if (const int rc = fwd_validate(a, &empty); rc != DGNN_OK || empty) return rc;
+    DGNN_REQUIRE(scratch, DGNN_E_INVALID, "linear_fwd_x2h: null pointer");
     if (!(M >= 8192 && n_out > XN)) return DGNN_E_UNSUPPORTED;
-    const bool v1 = vec_ok(A1, lda1) && vec_ok(W1, ldw1);
-    const bool v2 = A2 && vec_ok(A2, lda2) && vec_ok(W2, ldw2);
-    hipLaunchKernelGGL(k_x2h_row_scales, dim3((unsigned)dgnn_grid_cap(dgnn_cdiv(M + n_out, 4), 16)), dim3(256), 0, (hipStream_t)stream, A1, lda1, k1, A2,
-                       lda2, k2, M, W1, ldw1, W2, ldw2, n_out, scratch);
+    hipLaunchKernelGGL(k_x2h_row_scales, dim3((unsigned)dgnn_grid_cap(dgnn_cdiv(M + n_out, 4), 16)), dim3(256), 0, a.stream, A1, lda1, k1, A2, lda2, k2, M, W1,
+                       ldw1, W2, ldw2, n_out, scratch);
     static bool attr_set[DGNN_MAX_DEVICES];
     constexpr size_t lds = (size_t)(YM + YN) * HLD;
     dgnn_allow_dynamic_lds((const void*)k_linear_fwd_x2h_big, lds, attr_set);
-    dim3 grid((unsigned)(dgnn_cdiv(dgnn_cdiv(M, YM), 8) * 8 * dgnn_cdiv(n_out, YN)));
-    hipLaunchKernelGGL(k_linear_fwd_x2h_big, grid, dim3(YT), lds, (hipStream_t)stream, A1, lda1, k1, W1, ldw1, v1, A2, lda2, k2, W2, ldw2, v2, bias,
-                       scale, shift, relu, M, n_out, out, ldo, (const float*)scratch);
+    launch(k_linear_fwd_x2h_big, a.tiles_xcd(YM, YN), YT, lds, a, (const float*)scratch);
     return dgnn_check_launch("linear_fwd_x2h");
 }
 
@@ -2248,11 +2176,10 @@ extern "C" int64_t dgnn_linear_fwd_x2hp_scratch_elems(int64_t M, int n_out, int 
 extern "C" int dgnn_linear_fwd_x2hp(const float* A1, int64_t lda1, int k1, const float* W1, int64_t ldw1, const float* A2, int64_t lda2, int k2,
                                     const float* W2, int64_t ldw2, const float* bias, const float* scale, const float* shift, int relu,
                                     int64_t M, int n_out, float* out, int64_t ldo, float* scratch, void* stream) {
-    DGNN_REQUIRE(M >= 0 && n_out > 0 && k1 > 0, DGNN_E_INVALID, "linear_fwd_x2hp: bad sizes M=%lld n_out=%d k1=%d", (long long)M, n_out, k1);
-    if (M == 0) return DGNN_OK;
-    DGNN_REQUIRE(A1 && W1 && out && scratch && ((uintptr_t)scratch % 16) == 0, DGNN_E_INVALID, "linear_fwd_x2hp: null / unaligned pointer");
-    DGNN_REQUIRE((A2 == nullptr) == (W2 == nullptr) && (!A2 || k2 > 0), DGNN_E_INVALID, "linear_fwd_x2hp: A2/W2 must come together");
-    DGNN_REQUIRE((scale == nullptr) == (shift == nullptr), DGNN_E_INVALID, "linear_fwd_x2hp: scale/shift must come together");
+    FwdArgs<float> a{"linear_fwd_x2hp", A1, lda1, k1, W1, ldw1, A2, lda2, k2, W2, ldw2, bias, scale, shift, relu, M, n_out, out, ldo, (hipStream_t)stream};
+    bool empty;
+    if (const int rc = fwd_validate(a, &empty); rc != DGNN_OK || empty) return rc;
+    DGNN_REQUIRE(scratch && ((uintptr_t)scratch % 16) == 0, DGNN_E_INVALID, "linear_fwd_x2hp: null / unaligned pointer");
     if (!(M >= 8192 && n_out > XN)) return DGNN_E_UNSUPPORTED;
     const int nch = (k1 + HK - 1) / HK + (A2 ? (k2 + HK - 1) / HK : 0);
     float* scales = scratch;
@@ -2337,13 +2264,14 @@ int dgnn_linear_wgrad_bf16_cat_deferred(const void* A, int a_f32, int64_t lda, i
     WgradCatB c;
     c.B[0] = B1, c.B[1] = B2, c.ldb[0] = ldb1, c.ldb[1] = ldb2, c.nb[0] = n_b1, c.nb[1] = n_b2;
     dim3 grid((unsigned)dgnn_cdiv(n_a, WT), (unsigned)(nby1 + nby2), splits);
-#define WG(TA, TB) hipLaunchKernelGGL((k_linear_wgrad_b_cat<TA, TB>), grid, dim3(256), 0, stream, (const TA*)A, lda, n_a, c, nby1, M, rps, partials, \
-                                      dbias ? bias_partials : nullptr)
-    if (a_f32 && b_f32) WG(float, float);
-    else if (a_f32) WG(float, uint16_t);
-    else if (b_f32) WG(uint16_t, float);
-    else WG(uint16_t, uint16_t);
-#undef WG
+    by_storage(a_f32, [&](auto ta) {
+        by_storage(b_f32, [&](auto tb) {
+            using TA = decltype(ta);
+            using TB = decltype(tb);
+            hipLaunchKernelGGL((k_linear_wgrad_b_cat<TA, TB>), grid, dim3(256), 0, stream, (const TA*)A, lda, n_a, c, nby1, M, rps, partials,
+                               dbias ? bias_partials : nullptr);
+        });
+    });
     WgradReduceDesc d;
     d.partials = partials, d.bias_partials = bias_partials, d.splits = splits, d.na = n_a, d.nb1 = n_b1, d.nb2 = n_b2, d.dW1 = dW1, d.dW2 = dW2, d.dbias = dbias;
     if (desc)

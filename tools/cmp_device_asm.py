@@ -1,6 +1,7 @@
 """Compare the gfx950 device code of kernel sources between a git revision and the working tree, kernel by kernel (no GPU needed).
 
     python tools/cmp_device_asm.py [--base REV] [--rename 'REGEX=>REPL' ...] fused_ws.hip wide.hip ...
+    python tools/cmp_device_asm.py gemm.hip                                  # one source against HEAD: "35 kernels", every line `identical`
 
 Each source under dgnn_amd/csrc is compiled twice with the Makefile's flags plus --cuda-device-only -S: once from REV (default HEAD,
 unpacked with git archive) and once from the working tree.  Kernels are paired by demangled name; --rename rewrites base names first
