@@ -89,7 +89,6 @@ int fused_mask() {
     if (v < 0) {
         const char* e = getenv("DGNN_TRAIN_FUSED");
         v = e ? atoi(e) & 3 : 3;
-        if (getenv("DGNN_AGG_CHUNKED") && getenv("DGNN_AGG_CHUNKED")[0] == '0') v &= ~1;   // the addend form lives in the chunked kernel
         __atomic_store_n(&g_fused_on, v, __ATOMIC_RELEASE);
     }
     return v;
@@ -452,7 +451,6 @@ int updated_fwd(const int32_t* rowptr, const int32_t* src, const int32_t* eid, i
 
 }  // namespace
 // library-internal (csrc/aggregate.hip)
-bool dgnn_agg_bwd_can_mask();
 int dgnn_sage_aggregate_bwd_phi_add_masked(const int32_t* t_rowptr, const int32_t* t_dst, const int32_t* t_eid, int64_t n_src, const int32_t* rowptr_dst,
                                            const void* x_src, int64_t ldx, int c_in, const void* phi, int64_t ldphi, const void* da, int64_t ldda,
                                            void* dx_src, int64_t lddx, const void* add, int64_t ldadd, int64_t n_add, void* dphi_out, int64_t lddphi,
@@ -493,7 +491,7 @@ int updated_bwd(const int32_t* t_rowptr, const int32_t* t_dst, const int32_t* t_
         g = dz;
     }
     if (!aux && fused_enabled() && K::can_fuse(mode)) {
-        const int mask_dx = (want_mask && dx && dgnn_agg_bwd_can_mask()) ? 1 : 0;
+        const int mask_dx = (want_mask && dx) ? 1 : 0;
         if (masked) *masked = mask_dx != 0;
         // The launch chain of the Static layer's fused backward (layer_bwd) for this variant: dWl / dWr / dbl from one launch pair, the three
         // transposes from one launch, [da | dz.Wr] from one GEMM against the stacked [Wl^T ; Wr^T] with the second half added where the
@@ -975,9 +973,7 @@ extern "C" int dgnn_updated_tail_bwd(int64_t n, const void* x, int64_t ldx, int 
 // default 3, DGNN_TRAIN_FUSED in the environment).  Returns the previous mask.
 extern "C" int dgnn_train_set_fused(int mask) {
     const int was = fused_mask();
-    int v = mask & 3;
-    if (getenv("DGNN_AGG_CHUNKED") && getenv("DGNN_AGG_CHUNKED")[0] == '0') v &= ~1;
-    __atomic_store_n(&g_fused_on, v, __ATOMIC_RELEASE);
+    __atomic_store_n(&g_fused_on, mask & 3, __ATOMIC_RELEASE);
     return was;
 }
 

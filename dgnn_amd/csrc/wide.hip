@@ -801,7 +801,7 @@ extern "C" int dgnn_sage_aggregate_sr(const int32_t* rowptr, const int32_t* src,
     const dim3 grid((unsigned)nwg_), block(512);
     hipStream_t st = (hipStream_t)stream;
     // the XCDs' group counters of the ticket walk (see the kernel): 8 ints per device, zeroed in stream order before every launch
-    static const bool tickets_on = !(getenv("DGNN_AGG_SR_TICKETS") && getenv("DGNN_AGG_SR_TICKETS")[0] == '0');
+    static const bool tickets_on = dgnn_env_on("DGNN_AGG_SR_TICKETS");
     int* tickets = nullptr;
     // ... for split-row input (C >= 256).  Measured (profiles/r06_wide.md): C = 256 pass FETCH_SIZE 1.53 M -> 0.85 M KiB, L2 hit rate 52 -> 68 %, 802 -> 805 us;
     // the fp32-row form (C = 128, which also writes the own rows) 0.94 M -> 0.78 M KiB but 581 -> 695 us: it keeps the static walk.

@@ -594,8 +594,6 @@ def test_given_phi_aggregate_backward_with_the_two_additions(dtype, c_in, n_src,
     bit; bf16 storage rounds the sums once instead of twice (within one bf16 ulp of the two-step result)"""
     from dgnn_amd import ops
     from dgnn_amd._lib import lib
-    if os.environ.get("DGNN_AGG_CHUNKED") == "0":
-        pytest.skip("the addend form lives in the chunked kernel")
     g = torch.Generator().manual_seed(c_in + n_src)
     E = 4 * n_dst
     ei = torch.stack([torch.randint(0, n_src, (E,), generator=g), torch.arange(n_dst).repeat_interleave(4)])
@@ -651,7 +649,7 @@ def test_lane_group_given_phi_backward_gives_the_bits_of_the_lane_per_channel_ke
     """k_agg_bwd_g (4 channels per lane, 64 / G source rows per wavefront) against k_agg_bwd_c (taken when a row stride is not a multiple of 4
     elements): dx and dphi bit for bit; sources with dozens of out-edges (chunks beyond 64 edges), with none, degree-0 destinations' clamp"""
     from dgnn_amd import ops
-    if os.environ.get("DGNN_AGG_CHUNKED") == "0" or os.environ.get("DGNN_AGG_GROUPED") == "0":
+    if os.environ.get("DGNN_AGG_GROUPED") == "0":
         pytest.skip("compares the two default kernels")
     g = torch.Generator().manual_seed(c_in + n_src)
     E = 4 * n_dst

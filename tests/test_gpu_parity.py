@@ -157,11 +157,11 @@ def test_aggregate_fused_filter(c_in, f_e):
 
 @pytest.mark.parametrize("c_in,n_src,n_dst", [(28, 5000, 1777), (64, 900, 600), (32, 70, 70), (128, 800, 500), (48, 300, 203), (20, 64, 5), (64, 9, 1), (28, 40, 17)])
 def test_lane_group_fused_filter_forward_gives_the_bits_of_the_lane_per_channel_kernel(c_in, n_src, n_dst):
-    """k_agg_fwd_m (round 6: the filter product on the fp32 matrix cores, 4 edge slots per destination row; DGNN_AGG_MFMA=0: k_agg_fwd_g20 -- rows of up
-    to 32 channels, 4 channels per lane, 8 destination rows per wavefront instruction) against k_agg_fwd (taken when the row stride of x is no multiple
+    """k_agg_fwd_m (round 6: the filter product on the fp32 matrix cores, 4 edge slots per destination row; DGNN_AGG_MFMA=0: k_agg_fwd on both
+    sides) against k_agg_fwd (taken when the row stride of x is no multiple
     of 4): the aggregate bit for bit; regular, ragged (a row of more than 4 in-edges sends its step to the per-edge path) and thinned in-degrees"""
     from dgnn_amd import ops
-    if os.environ.get("DGNN_AGG_CHUNKED") == "0" or os.environ.get("DGNN_AGG_GROUPED") == "0":
+    if os.environ.get("DGNN_AGG_GROUPED") == "0":
         pytest.skip("compares the two default kernels")
     g = torch.Generator().manual_seed(c_in + n_src)
     E = 4 * n_dst
@@ -271,8 +271,6 @@ def test_aggregate_backward_with_addend_matches_the_two_steps(c_in, n_src, n_dst
     """dgnn_sage_aggregate_bwd_add: dx = aggregate backward, then dx[:n_add] += add in one fp32 addition per element -- bit for bit; dWe / dbe
     untouched by the addend"""
     from dgnn_amd import ops
-    if os.environ.get("DGNN_AGG_CHUNKED") == "0":
-        pytest.skip("the addend form lives in the chunked kernel")
     g = torch.Generator().manual_seed(c_in + n_src)
     E = 4 * n_dst
     ei = torch.stack([torch.randint(0, n_src, (E,), generator=g), torch.arange(n_dst).repeat_interleave(4)])
@@ -340,12 +338,11 @@ def test_aggregate_backward_on_the_matrix_cores(c_in, graph):
     # no dx (the first layer's form): the same parameter gradients as with dx
     none, dWe_n, dbe_n, _ = ops.aggregate_bwd(t_rowptr, t_dst, t_eid, n_src, rowptr, x_d, da_d, ea_d, We_d, be_d, need_dx=False)
     assert none is None and torch.equal(dWe_n, dWe_m) and torch.equal(dbe_n, dbe_m)
-    # the addend folded into the dx store (DGNN_AGG_CHUNKED=0: the row-at-a-time kernels have no addend form)
-    if os.environ.get("DGNN_AGG_CHUNKED") != "0":
-        dx_a, dWe_a, dbe_a = ops.aggregate_bwd_add(t_rowptr, t_dst, t_eid, n_src, rowptr, x_d, da_d, ea_d, We_d, be_d, add_d)
-        want = dx_m.clone()
-        want[:add_d.size(0)] += add_d
-        assert torch.equal(dx_a, want) and torch.equal(dWe_a, dWe_m) and torch.equal(dbe_a, dbe_m)
+    # the addend folded into the dx store
+    dx_a, dWe_a, dbe_a = ops.aggregate_bwd_add(t_rowptr, t_dst, t_eid, n_src, rowptr, x_d, da_d, ea_d, We_d, be_d, add_d)
+    want = dx_m.clone()
+    want[:add_d.size(0)] += add_d
+    assert torch.equal(dx_a, want) and torch.equal(dWe_a, dWe_m) and torch.equal(dbe_a, dbe_m)
     # twice the same bits (accumulators and slabs in a fixed order)
     dx_2, dWe_2, dbe_2, _ = ops.aggregate_bwd(t_rowptr, t_dst, t_eid, n_src, rowptr, x_d, da_d, ea_d, We_d, be_d)
     assert torch.equal(dx_2, dx_m) and torch.equal(dWe_2, dWe_m) and torch.equal(dbe_2, dbe_m)
