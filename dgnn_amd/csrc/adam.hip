@@ -56,8 +56,10 @@ extern "C" int dgnn_adam_step(int n_tensors, float* const* p, const float* const
         a.nt = n_tensors - t0 < ADAM_MAX ? n_tensors - t0 : ADAM_MAX;
         int blocks = 0;
         for (int t = 0; t < a.nt; ++t) {
-            DGNN_REQUIRE(p[t0 + t] && g[t0 + t] && m[t0 + t] && v[t0 + t] && numel[t0 + t] >= 0 && numel[t0 + t] < ((int64_t)1 << 31), DGNN_E_INVALID,
-                         "adam_step: tensor %d", t0 + t);
+            // an empty tensor has no address (torch gives NULL for it): it takes no block, so nothing reads its entries
+            DGNN_REQUIRE(numel[t0 + t] >= 0 && numel[t0 + t] < ((int64_t)1 << 31), DGNN_E_INVALID, "adam_step: tensor %d has %lld elements", t0 + t,
+                         (long long)numel[t0 + t]);
+            DGNN_REQUIRE(numel[t0 + t] == 0 || (p[t0 + t] && g[t0 + t] && m[t0 + t] && v[t0 + t]), DGNN_E_INVALID, "adam_step: tensor %d", t0 + t);
             a.p[t] = p[t0 + t], a.g[t] = g[t0 + t], a.m[t] = m[t0 + t], a.v[t] = v[t0 + t], a.n[t] = (int)numel[t0 + t];
             blocks += (int)dgnn_cdiv(numel[t0 + t], ADAM_CHUNK);
             a.block_end[t] = blocks;
