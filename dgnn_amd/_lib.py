@@ -183,6 +183,11 @@ SIGNATURES = {
     "dgnn_sage_updated_train_fwd": (i32, [vp, vp, vp, i64, vp, i64, i32, vp, i64, i32, i64, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp]),
     "dgnn_sage_updated_train_bwd": (i32, [vp, vp, vp, vp, i64, i64, i64, vp, i64, i32, vp, i64, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "dgnn_edge_chain_aggregate_supported": (i32, [i32, i32, i32, i32]),
+    "dgnn_edge_chain_aggregate_fwd": (i32, [vp, vp, vp, i64, vp, i64, i32, vp, i64, i32, vp, vp, vp, i64, vp, i64, i32, i32, vp]),
+    "dgnn_updated_infer_workspace_bytes": (i64, [i64, i64, i32, vp, vp, i32, i32]),
+    "dgnn_updated_infer_fwd": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp,
+                                     vp, i32, i32, vp]),
     "dgnn_kl_cell_loss_scratch_doubles": (i64, [i64]),
     "dgnn_kl_cell_loss_fwd": (i32, [vp, i64, vp, i64, vp, i64, i32, i64, vp, vp, vp, vp]),
     "dgnn_kl_cell_loss_bwd": (i32, [vp, i64, vp, i64, vp, i64, i32, i64, vp, vp, vp, i64, vp]),

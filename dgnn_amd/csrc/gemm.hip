@@ -12,7 +12,7 @@
 // fragment reads (ds_read_b128) bank-conflict free for the 16-lane groups of that instruction.
 // k-permutation: within a chunk, half-wave h of MFMA step (S,j) multiplies k = 8S + 4h + j, so one
 // b128 read per operand feeds 4 MFMAs; A and B use the same map, hence every k is used exactly once.
-#include "common.h"
+#include "gemm_x3.h"
 #include "reduce_common.h"
 
 namespace {
@@ -252,7 +252,6 @@ __device__ __forceinline__ void stage_w_bf16(char* __restrict__ dst, const float
     }
 }
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 
 template <typename TO>
 __global__ void __launch_bounds__(256) k_linear_fwd_b(LINEAR_FWD_PARAMS_B(TO)) {
@@ -738,16 +737,6 @@ __global__ void __launch_bounds__(256) k_linear_wgrad_b_cat(const TA* __restrict
 // =====================================================================================================================
 constexpr int XM = 128, XN = 128, XK = 32, XLD = 3 * XK * 2 + 16;
 
-__device__ __forceinline__ void x3_split(float x0, float x1, uint32_t& hi, uint32_t& mid, uint32_t& lo) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{x0, x1}, bf2));
-    const float r0 = x0 - __builtin_bit_cast(float, hi << 16), r1 = x1 - __builtin_bit_cast(float, hi & 0xFFFF0000u);
-    mid = __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{r0, r1}, bf2));
-    const float s0 = r0 - __builtin_bit_cast(float, mid << 16), s1 = r1 - __builtin_bit_cast(float, mid & 0xFFFF0000u);
-    lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(f2{s0, s1}, bf2));
-}
-
 // [128 x 32] fp32 tile -> 3 bf16 parts in LDS; 8 threads per row (4 floats each), 32 rows per pass.  Two steps, so that the next
 // chunk's global loads are in flight while the current chunk is multiplied (register staging, guide T14): x3_load issues the
 // loads into 4 x float4, x3_store splits them and writes the LDS image after the barrier.
@@ -791,20 +780,6 @@ __device__ __forceinline__ void x3_store(char* __restrict__ dst, const f32x4 (&v
         *reinterpret_cast<uint2*>(d + 128) = make_uint2(l0, l1);
     }
 }
-
-// The six products of an x3 k-step on one accumulator block each of acc[0 .. NB); af / bf[b]: the (hi, mid, lo) fragments.  THE product order of
-// every x3 kernel, forward and weight gradient -- small terms first: lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi -- which their "bit-identical
-// to k_linear_fwd_x3" claims rest on.  With NB > 1 the blocks alternate product by product: consecutive matrix instructions never wait for each
-// other's result, and every accumulator still sees its six products in this order.
-template <int NB>
-__device__ __forceinline__ void x3_mma6(f32x16* acc, const bf16x8_t (&af)[3], const bf16x8_t (*bf)[3]) {
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-    for (int q = 0; q < 6; ++q)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[q]], bf[b][PB[q]], acc[b], 0, 0, 0);
-}
-__device__ __forceinline__ void x3_mma6(f32x16& acc, const bf16x8_t (&af)[3], const bf16x8_t (&bf)[3]) { x3_mma6<1>(&acc, af, &bf); }
 
 // BatchNorm batch statistics from the GEMM that produces z (training forward): every wavefront adds the 32 x 32 accumulator block it is
 // about to store (bias included) into fp64 column sums / sums of squares and writes them as partial row `row / 32` of

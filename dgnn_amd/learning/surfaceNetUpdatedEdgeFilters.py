@@ -10,7 +10,13 @@ phi feeds both this layer's aggregation and the next layer's lin_e, so it is mat
 the fp32 MFMA GEMM (its K is 2, F or h_{k-2}) and the aggregation kernel takes phi rows as given.
 
 The reference's three ``inference_*`` methods of this file call the conv without ``edge_attr``
-(:281,:317,:352) and raise there; they are not part of the path and raise here too.
+(:281,:317,:352) and raise there.  Here they run, with the Static model's signatures and the semantics
+of ``forward``: ``inference_layer`` is ``forward`` on ``adjs = [(edge_index, arange(E), (N, N))] * L``
+(every e_id the identity, so the edge chaining is ``ea_{k+1} = relu(phi_k)[:, :k]``) through one
+library call whose conv layers are one launch each where the kernel covers the shape
+(csrc/updated_infer.hip); ``inference_batch_layer`` runs ``forward`` per k-hop block;
+``inference_layer_batch`` walks a 1-hop loader layer by layer.  The model has no normalisation layer,
+so a block's targets equal the whole scene's rows and the three schedules agree.
 """
 from __future__ import annotations
 
@@ -257,8 +263,90 @@ class SurfaceNet(nn.Module):
                 p_.grad = None
         return loss.detach()
 
-    def _unsupported(self, *a, **k):
-        raise NotImplementedError("the reference's surfaceNetUpdatedEdgeFilters.inference_* methods call the conv without "
-                                  "edge_attr and cannot run (reference :281,:317,:352); use forward(data_all)")
+    # ---- INFERENCE (the Static model's three schedules; reference learning/runModel.py:412-451 dispatches to them) ----------------------------
+    def _scene_inputs(self, data_all, dev):
+        """(x [N, F] in the storage type, edge_attr fp32) of a whole scene on `dev`, column 0 of x dropped as forward() does"""
+        if not str(dev).startswith("cuda"):
+            raise RuntimeError("clf.temp.device=%r: dgnn_amd runs on a GPU only (no CPU fallback)" % (dev,))
+        f = self.clf.features
+        x = _dev_f32(data_all.x, dev)
+        if f.normalization_feature and not f.keep_normalization_feature:
+            x = x[:, 1:].contiguous()
+        if self.storage_dtype == torch.bfloat16:
+            x = Fn.to_bf16(x)
+        return x, _dev_f32(data_all.edge_attr, dev)
 
-    inference_batch_layer = inference_layer_batch = inference_layer = _unsupported
+    def _plus(self):
+        return self.clf.training.model_name[-1] == "+"
+
+    def _tail(self, x):
+        """:245-247 behind the last conv layer's ReLU; fp32 logits"""
+        if self._plus():
+            x = Fn.linear2(x, self.out_net[1].weight, bias=self.out_net[1].bias)
+            x = Fn.relu(x)
+            x = Fn.linear2(x, self.out_net[3].weight, bias=self.out_net[3].bias, out_f32=True)
+        return x.float() if x.dtype == torch.bfloat16 else x
+
+    @torch.no_grad()
+    def inference_layer(self, data_all, plan: GraphPlan = None):
+        """The whole graph: forward() on adjs = [(edge_index, arange(E), (N, N))] * num_layers as one library call (ops.updated_infer_fwd)."""
+        from .. import ops
+        dev = self.clf.temp.device
+        x, edge_attr = self._scene_inputs(data_all, dev)
+        if plan is None:
+            plan = plan_for(data_all.edge_index.to(dev), x.size(0), x.size(0), hint=ops.PLAN_HINT_REFERENCE)
+        plus = self._plus()
+        layers = []
+        for i, conv in enumerate(self.convs):
+            if conv.normalize or conv.lin_e.bias is None or conv.lin_l.bias is None:
+                raise NotImplementedError("inference_layer: conv %d is outside the whole-scene call (output normalisation / a Linear without bias)" % i)
+            layers.append(dict(edge_in=conv.edge_in_channels, relu=(i < self.num_layers - 1) or plus, We=conv.lin_e.weight, be=conv.lin_e.bias,
+                               Wl=conv.lin_l.weight, bl=conv.lin_l.bias, Wr=conv.lin_r.weight))
+        tail = (self.out_net[1].weight, self.out_net[1].bias, self.out_net[3].weight, self.out_net[3].bias) if plus else None
+        out, self.fused_layers = ops.updated_infer_fwd(x, edge_attr, (plan.rowptr, plan.src, plan.eid), layers, tail)
+        return out.float() if out.dtype == torch.bfloat16 else out
+
+    @torch.no_grad()
+    def inference_batch_layer(self, data_all, batch_loader):
+        """Batch-major k-hop blocks: every block through forward() (sparse chaining, the conv stack; nothing is saved under no_grad), the targets'
+        logits scattered into [N, out]."""
+        from .. import ops
+        from ..config import Config
+        dev = self.clf.temp.device
+        if not str(dev).startswith("cuda"):
+            raise RuntimeError("clf.temp.device=%r: dgnn_amd runs on a GPU only (no CPU fallback)" % (dev,))
+        x_all, edge_attr = _dev_f32(data_all.x, dev), _dev_f32(data_all.edge_attr, dev)
+        n_out = 2 if self._plus() else self.convs[-1].out_channels
+        out = torch.zeros((x_all.size(0), n_out), dtype=torch.float32, device=dev)
+        for batch_size, n_id, adjs in batch_loader:
+            adjs = [adjs] if isinstance(adjs[0], torch.Tensor) else adjs
+            y = self.forward(Config(x=x_all, n_id=n_id, edge_attr=edge_attr, adjs=adjs))
+            ops.scatter_rows_(out, n_id[:batch_size].to(dev), y.contiguous())
+        return out
+
+    @torch.no_grad()
+    def inference_layer_batch(self, data_all, batch_loader):
+        """Layer-major on a 1-hop loader: per layer the activations of all cells [N, C] and the scene's edge tensor [E_all, C_in] (zeros; every
+        block's phi at its e_id rows; ReLU -- reference :236-241); the batches are concatenated in loader order."""
+        from .. import ops
+        dev = self.clf.temp.device
+        x_all, ea_all = self._scene_inputs(data_all, dev)
+        n_edges = ea_all.size(0)
+        plus = self._plus()
+        for i, conv in enumerate(self.convs):
+            last = i == self.num_layers - 1
+            new_ea = torch.zeros((n_edges, conv.in_channels), dtype=x_all.dtype, device=dev)
+            xs = []
+            for batch_size, n_id, adj in batch_loader:
+                edge_index, e_id, size = adj
+                e_id = e_id.to(dev)
+                x = ops.gather_rows(x_all, n_id.to(dev).to(torch.int32))
+                ea = ops.gather_rows(ea_all, e_id.to(torch.int32), conv.edge_in_channels)           # :237 edge_attr[e_id, :edge_in]
+                y, phi = conv((x, x[:size[1]]), ea, edge_index.to(dev))
+                xs.append(Fn.relu(y) if (not last or plus) else y)
+                if not last:
+                    ops.scatter_rows_(new_ea, e_id, phi)
+            x_all = torch.cat(xs, dim=0)
+            if not last:
+                ea_all = ops.relu(new_ea)
+        return self._tail(x_all)

@@ -1239,6 +1239,73 @@ def updated_tail_bwd(x, W1, W3, h, g):
     return dx, dW1, db1, dW3, db3
 
 
+# ---- Updated variant, whole-scene inference (csrc/updated_infer.hip) -----------------------------------------------------------
+def edge_chain_aggregate_supported(c_in: int, k_e: int, dtype=torch.float32) -> bool:
+    """the layer shapes the one-launch form takes (dgnn_edge_chain_aggregate_supported) in the current GEMM mode"""
+    return bool(lib().dgnn_edge_chain_aggregate_supported(int(c_in), int(k_e), int(dtype == torch.bfloat16), GEMM_MODE))
+
+
+@on_device_of
+def edge_chain_aggregate_fwd(rowptr, src, eid, n_dst, x, ea, We, be, ea_next=None, write_next=True):
+    """lin_e + mean aggregate + the next layer's edge rows of one Updated conv layer in ONE launch (dgnn_edge_chain_aggregate_fwd):
+    -> (a [n_dst, c_in], ea_next).  ea [E, >= k_e] in the order eid indexes (eid None: plan order); ea_next [E, >= c_in] receives relu(phi) at
+    the same rows (allocated when None and write_next; left untouched when not write_next)."""
+    _req(x, "x", dim=2)
+    _req(ea, "ea", dim=2)
+    We = _req(We, "We", dim=2).contiguous()
+    be = _req(be, "be").contiguous()
+    c_in, k_e = x.size(1), We.size(1)
+    if We.size(0) != c_in or ea.size(1) < k_e:
+        raise ValueError("lin_e weight %s does not match c_in=%d / edge rows %s" % (tuple(We.shape), c_in, tuple(ea.shape)))
+    if write_next and ea_next is None:
+        ea_next = torch.empty((ea.size(0), c_in), dtype=torch.float32, device=x.device)
+    if ea_next is not None:
+        _req(ea_next, "ea_next", dim=2)
+        if ea_next.size(0) < ea.size(0) or ea_next.size(1) < c_in:
+            raise ValueError("ea_next %s is smaller than [%d, %d]" % (tuple(ea_next.shape), ea.size(0), c_in))
+    a = torch.empty((n_dst, c_in), dtype=torch.float32, device=x.device)
+    check(lib().dgnn_edge_chain_aggregate_fwd(ptr(rowptr), ptr(src), ptr(eid), n_dst, ptr(x), _ld(x), c_in, ptr(ea), _ld(ea), k_e, ptr(We), ptr(be), ptr(a), c_in,
+                                              ptr(ea_next), _ld(ea_next) if ea_next is not None else 0, int(bool(write_next)), GEMM_MODE, stream_ptr()),
+          "dgnn_edge_chain_aggregate_fwd")
+    return a, ea_next
+
+
+@on_device_of
+def updated_infer_fwd(x, edge_attr, plan_parts, layers, tail=None):
+    """Every conv layer of a whole scene and the "sage+" output network in one library call (dgnn_updated_infer_fwd).  x [n, F] fp32 or bf16 rows,
+    edge_attr fp32 [E, >= edge_in_0] in scene edge order, plan_parts = (rowptr, src, eid) of the scene's destination-sorted plan; `layers`: per conv
+    layer a dict with edge_in, relu, We, be, Wl, bl, Wr; `tail` = (W1, b1, W3, b3) or None.
+    -> (fp32 logits [n, n_out] | the last layer's rows in x's type, bit mask of the layers that ran through the one-launch form)."""
+    import ctypes as C
+    _req(x, "x", ACT, dim=2)
+    _req(edge_attr, "edge_attr", dim=2)
+    dev, bf, L = x.device, x.dtype == torch.bfloat16, len(layers)
+    rowptr, src, eid = plan_parts
+    n, E = x.size(0), edge_attr.size(0)
+    widths = [x.size(1)] + [l["Wl"].size(0) for l in layers]
+    for i, l in enumerate(layers):
+        if l["Wl"].size(1) != widths[i] or l["We"].size(0) != widths[i] or l["We"].size(1) != l["edge_in"]:
+            raise ValueError("Updated conv %d: lin_e %s / lin_l %s do not match %d input channels, %d edge columns"
+                             % (i, tuple(l["We"].shape), tuple(l["Wl"].shape), widths[i], l["edge_in"]))
+    w_arr = _iarr(widths, C.c_int32)
+    k_arr = _iarr([l["edge_in"] for l in layers], C.c_int32)
+    r_arr = _iarr([int(bool(l["relu"])) for l in layers], C.c_int32)
+    arr = lambda k: _parr([l[k] for l in layers])
+    hdim = tail[0].size(0) if tail is not None else 0
+    n_out = tail[2].size(0) if tail is not None else 0
+    ea_cols = max(widths[:L])
+    ea_buf = torch.empty((2, max(E, 1), ea_cols), dtype=x.dtype, device=dev)
+    work = torch.empty(int(lib().dgnn_updated_infer_workspace_bytes(n, E, L, w_arr, k_arr, hdim, int(bf))), dtype=torch.uint8, device=dev)
+    out = torch.empty((n, n_out), dtype=torch.float32, device=dev) if tail is not None else torch.empty((n, widths[-1]), dtype=x.dtype, device=dev)
+    fused = C.c_int32(0)
+    t = tail if tail is not None else (None,) * 4
+    check(lib().dgnn_updated_infer_fwd(ptr(rowptr), ptr(src), ptr(eid), n, E, ptr(x), _ld(x), ptr(edge_attr), _ld(edge_attr), L, w_arr, k_arr,
+                                       arr("We"), arr("be"), arr("Wl"), arr("bl"), arr("Wr"), r_arr, ptr(t[0]), ptr(t[1]), hdim, ptr(t[2]), ptr(t[3]), n_out,
+                                       ptr(ea_buf[0]), ptr(ea_buf[1]), ptr(work), ptr(out), C.byref(fused), int(bf), GEMM_MODE, stream_ptr()),
+          "dgnn_updated_infer_fwd")
+    return out, int(fused.value)
+
+
 # ---- edge-embedding chaining of the Updated variant (csrc/chain.hip) ---------------------------------------------------------
 @on_device_of
 def edge_chain_fwd(phi, e_id_cur, e_id_next, c, pos, relu):

@@ -546,6 +546,38 @@ int dgnn_updated_tail_bwd(int64_t n, const void* x, int64_t ldx, int c, const fl
                           const float* g, float* dW1, float* db1, float* dW3, float* db3, void* dx, void* dh, float* scratch, int bf16,
                           int gemm_mode, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Updated variant, whole-scene inference (csrc/updated_infer.hip).  On a whole graph every layer's e_id is the identity and the reference's edge
+ * chaining is ea_{l+1} = relu(phi_l)[:, :edge_in_{l+1}].
+ *
+ * dgnn_edge_chain_aggregate_fwd: lin_e, the mean aggregate and the next layer's edge rows of ONE conv layer in one launch, fp32 rows:
+ *   phi = ea[eid[k], :k_e] . We^T + be per plan position k (never stored), a [n_dst, c_in] = mean over each destination's segment of x[src[k]] * phi
+ *   (plan order, from 0, / max(deg, 1); any in-degree, 0 included), ea_next[eid[k]] = relu(phi) (row stride ldn >= c_in; write_next = 0: nothing is
+ *   stored per edge and ea_next may be NULL).  eid NULL: the identity.  The filter product follows gemm_mode as the GEMM entry points do: DGNN_GEMM_F32 =
+ *   per (edge, channel) the fmaf chain over ascending k that starts at the bias; any other mode = the bits of dgnn_linear_fwd_x3.
+ *   c_in in {64, 128}, k_e <= 128 (dgnn_edge_chain_aggregate_supported), x / a / ea_next rows 16-byte aligned with strides % 4 == 0; anything else:
+ *   DGNN_E_UNSUPPORTED, nothing launched.  A workgroup walks 16 destinations' plan positions in tiles of 64.
+ *
+ * dgnn_updated_infer_fwd: every conv layer of a scene on ONE plan (n sources = n destinations) and the "sage+" output network, one call.  Layer l maps
+ *   widths[l] -> widths[l + 1] channels and reads edge_in[l] edge columns: of edge_attr (fp32 [E, >= edge_in[0]], scene edge order) for l = 0, of
+ *   relu(phi_{l-1}) behind it.  A layer the launch above takes runs through it and dgnn_linear_fwd / _x3; any other (layer 0, widths >= 256, bf16 = 1:
+ *   x and every intermediate in bf16) through dgnn_sage_updated_train_fwd with the ReLU applied in place.  ea_buf0 / ea_buf1: two [E, max_l widths[l]]
+ *   edge buffers of the storage type, 16-byte aligned; workspace: dgnn_updated_infer_workspace_bytes bytes, 16-byte aligned.  relu[l]: the ReLU behind
+ *   conv l.  W1 NULL: no output network and `out` receives the last layer's rows [n, widths[n_layers]] in the storage type; else (W1 [hdim, widths[L]],
+ *   W3 [n_out, hdim]) fp32 logits [n, n_out] as dgnn_updated_tail_fwd writes them.  fused_layers (host memory, may be NULL): bit l is set when
+ *   layer l ran through dgnn_edge_chain_aggregate_fwd.  Nothing allocates or synchronises.
+ * ---------------------------------------------------------------------------------------------- */
+int dgnn_edge_chain_aggregate_supported(int c_in, int k_e, int bf16, int gemm_mode);
+int dgnn_edge_chain_aggregate_fwd(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n_dst, const float* x, int64_t ldx, int c_in,
+                                  const float* ea, int64_t lde, int k_e, const float* We, const float* be, float* a, int64_t lda, float* ea_next,
+                                  int64_t ldn, int write_next, int gemm_mode, void* stream);
+int64_t dgnn_updated_infer_workspace_bytes(int64_t n, int64_t E, int n_layers, const int32_t* widths, const int32_t* edge_in, int hdim, int bf16);
+int dgnn_updated_infer_fwd(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int64_t n, int64_t E, const void* x, int64_t ldx,
+                           const float* edge_attr, int64_t lde, int n_layers, const int32_t* widths, const int32_t* edge_in, const float* const* We,
+                           const float* const* be, const float* const* Wl, const float* const* bl, const float* const* Wr, const int32_t* relu,
+                           const float* W1, const float* b1, int hdim, const float* W3, const float* b3, int n_out, void* ea_buf0, void* ea_buf1,
+                           void* workspace, void* out, int32_t* fused_layers, int bf16, int gemm_mode, void* stream);
+
 int64_t dgnn_static_train_scratch_elems(int n_layers, const int64_t* n_src, const int64_t* n_dst, const int32_t* widths, int f_e);
 int dgnn_static_train_bwd(int n_layers, const int32_t* const* t_rowptr, const int32_t* const* t_dst, const int32_t* const* t_eid,
                           const int32_t* const* rowptr_dst, const int64_t* n_src, const int64_t* n_dst, const float* x0, int64_t ldx0,
