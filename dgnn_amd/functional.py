@@ -335,6 +335,28 @@ def kl_cell_loss(logits, gt, vol, cell_norm=None):
     return _KLCellLoss.apply(logits, gt, vol, ops.CELL_NORMS.get(cell_norm, 0))
 
 
+class _EdgeTV(torch.autograd.Function):
+    """edge total-variation regulariser on the inside-probabilities (reference learning/runModel.py:109-160) -> (reg, sums[2] = weight * sum tv, E)"""
+
+    @staticmethod
+    def forward(ctx, logits, edge_index, weight):
+        reg, sums, net = ops.edge_tv_fwd(logits, edge_index, weight, need_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(logits, net)
+        ctx.weight, ctx.edges = weight, edge_index.size(1)
+        ctx.mark_non_differentiable(sums)
+        return reg, sums
+
+    @staticmethod
+    def backward(ctx, g, _):
+        logits, net = ctx.saved_tensors
+        return ops.edge_tv_bwd(logits, net, ctx.weight, ctx.edges, g), None, None
+
+
+def edge_tv(logits, edge_index, weight):
+    """weight * mean_e |p(src_e) - p(dst_e)| with p = softmax(logits)[:, 0], and the metric sums, over the kernels of ops.edge_tv_step: the same bits"""
+    return _EdgeTV.apply(logits, edge_index, float(weight))
+
+
 class _SceneBatchNormRelu(torch.autograd.Function):
     """BatchNorm1d (training mode) + ReLU over a scene that is cut across ranks (dgnn_amd/partition.py; SURVEY 8e: one [2 C] all-reduce per layer each
     way): per-row work in the library's kernels -- local column statistics (dgnn_bn_batch_stats), scale / shift + ReLU (dgnn_scale_shift_act), the

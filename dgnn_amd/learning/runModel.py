@@ -58,6 +58,8 @@ class Metrics:
         if name in Metrics._FIELDS:
             if name in Metrics._PACKED:
                 self._flush_packed()
+            if name in Metrics._REG:
+                self._flush_reg()
             acc = self.__dict__.get("_dev", {}).get(name)
             return self._host[name] + (acc.item() if acc is not None else 0)
         raise AttributeError(name)
@@ -91,6 +93,24 @@ class Metrics:
         if acc is not None:
             for name, v in zip(self._PACKED, acc.tolist()):
                 self._host[name] += int(v) if name == "OA_sum" else v
+
+    _REG = ("reg_sum", "edges_sum")
+
+    def _flush_reg(self):
+        acc = self._dev.pop("_reg", None)
+        if acc is not None:
+            reg, edges = acc.tolist()
+            self._host["reg_sum"] += reg
+            self._host["edges_sum"] += int(edges)
+
+    def regAccumulator(self, device):
+        """the device fp64 [reg_sum, edges_sum] accumulator itself, for a kernel that adds a batch's sums into it (ops.edge_tv_step)"""
+        acc = self._dev.get("_reg")
+        if acc is None or acc.device != torch.device(device):
+            if acc is not None:
+                self._flush_reg()
+            acc = self._dev["_reg"] = torch.zeros(2, dtype=torch.float64, device=device)
+        return acc
 
     def addOAItem(self, oa, samples):
         self._add("OA_sum", oa)
@@ -144,7 +164,14 @@ class Trainer:
         self.model = model
 
     def calcRegularization(self, logits_cell, data, clf, metrics):
-        """Edge total-variation term on inside-probabilities, reference :109-160."""
+        """Edge total-variation term on inside-probabilities, reference :109-160.  fp32 logits on a GPU with at least one edge: two library
+        launches each way (csrc/edge_tv.hip: fp64 sum in a fixed order, integer edge counts -- bit-identical reruns), the metric sums stay on the
+        device; anything else, and DGNN_FUSED_LOSS=0, runs the reference's op chain."""
+        tv = self._device_tv(logits_cell, data)
+        if tv is not None:
+            reg, sums = Fn.edge_tv(tv[0], tv[1], clf.regularization.edge_weight)
+            metrics.addRegLossItem(sums[0], sums[1])      # (device values: Metrics._add accumulates them where they are)
+            return reg
         if data.batch_adjs:
             adj = data.batch_adjs[self.model.num_layers]
             inner = F.softmax(logits_cell[:adj.size[0]], dim=-1)
@@ -156,6 +183,22 @@ class Trainer:
         reg_loss = tv * clf.regularization.edge_weight
         metrics.addRegLossItem(reg_loss.sum(), tv.size(0))
         return reg_loss.mean()
+
+    def _device_tv(self, logits_cell, data):
+        """(logits rows, edge_index on their device) of the regulariser when the library's kernels take it -- the batch branch (the extra hop's block)
+        and the whole-graph branch alike --, else None"""
+        if not (FUSED_KL_LOSS and isinstance(logits_cell, torch.Tensor) and logits_cell.is_cuda and logits_cell.dtype == torch.float32
+                and logits_cell.dim() == 2 and logits_cell.size(1) == 2 and logits_cell.stride(1) == 1):
+            return None
+        if data.batch_adjs:
+            adj = data.batch_adjs[self.model.num_layers]
+            logits_cell, ei = logits_cell[:adj.size[0]], adj.edge_index
+        else:
+            ei = data.edge_index
+        if not isinstance(ei, torch.Tensor) or ei.dim() != 2 or ei.size(0) != 2 or ei.size(1) == 0 or ei.dtype not in (torch.int32, torch.int64) \
+                or logits_cell.size(0) == 0:
+            return None
+        return logits_cell, ei.to(logits_cell.device)
 
     def calcLossAndOA(self, logits_cell, logits_edge, data, clf, metrics):
         """Volume-weighted cell loss, reference :163-259 (kl / bce / mse)."""
@@ -277,14 +320,15 @@ class Trainer:
         """The step without the autograd engine (DGNN_TRAIN_DIRECT=0 keeps the autograd path): the Static model's whole-model library calls, the
         fused kl loss and its gradient issued directly (SurfaceNet.train_step_direct) -- the step is bound by the host's issue rate, and the engine's
         bookkeeping, the loss Function and zero_grad were a fifth of it.  Same kernels in the same order: same numbers as the autograd path
-        (tests/test_gpu_train.py).  None = this configuration takes the autograd path (other losses / models, an active edge regulariser)."""
+        (tests/test_gpu_train.py, tests/test_gpu_edge_tv.py).  None = this configuration takes the autograd path (other losses / models)."""
         model = self.model
         step = getattr(model, "train_step_direct", None)
         if step is None or not TRAIN_DIRECT or clf.training.loss != "kl" or not FUSED_KL_LOSS or not clf.regularization.cell_type \
                 or clf.regularization.cell_norm not in Fn.ops.CELL_NORMS:
             return None
-        if clf.regularization.edge_epoch is not None and (clf.temp.current_epoch >= clf.regularization.edge_epoch or clf.graph.additional_num_hops != 1):
-            return None        # (the second clause: `_with_regularization` prints and exits for such a config BEFORE edge_epoch is reached -- reference :250-253)
+        if clf.regularization.edge_epoch is not None and clf.graph.additional_num_hops != 1:
+            return None        # (`_with_regularization` prints and exits for such a config, BEFORE edge_epoch is reached too -- reference :250-253)
+        reg_on = clf.regularization.edge_epoch is not None and clf.temp.current_epoch >= clf.regularization.edge_epoch
         x_all, y_all = data_train.all.x, data_train.all.y
         if not (x_all.is_cuda and y_all.is_cuda and x_all.dtype == torch.float32 and y_all.dtype == torch.float32):
             return None
@@ -294,6 +338,15 @@ class Trainer:
             return None        # (the fused kl loss is guarded by logits.size(0) > 0 on the autograd path; an empty batch takes that path)
         data_train.batch_x, data_train.batch_gt = self._batch_rows(data_train, n_sup)     # (the reference leaves these on the data object, :273-274)
         metrics, norm = clf.training.metrics, Fn.ops.CELL_NORMS[clf.regularization.cell_norm]
+        tv_ei = tv_rows = None
+        if reg_on:
+            # the edge regulariser on the extra hop's block (reference :112-119): its value, gradient and metric sums are two more launches
+            adj = data_train.batch_adjs[model.num_layers] if len(data_train.batch_adjs) > model.num_layers else None
+            tv_ei = getattr(adj, "edge_index", None)
+            if not (isinstance(tv_ei, torch.Tensor) and tv_ei.device == x_all.device and tv_ei.dim() == 2 and tv_ei.size(0) == 2 and tv_ei.size(1) > 0
+                    and tv_ei.dtype in (torch.int32, torch.int64) and 0 < adj.size[0] <= n_sup):
+                return None    # (no edges, indices elsewhere: the autograd path decides, as calcRegularization does)
+            tv_rows, tv_weight = adj.size[0], clf.regularization.edge_weight
         one = self.__dict__.get("_one")
         if one is None or one.device != x_all.device:
             one = self._one = torch.ones((), dtype=torch.float32, device=x_all.device)
@@ -307,10 +360,17 @@ class Trainer:
                 got = Fn.ops.kl_cell_loss_step(logits, data_train.batch_gt, vol, norm, running=metrics.packedAccumulator(logits.device, 0))
                 if got is not None:
                     metrics.packedAccumulator(logits.device, n_sup)
-                    return got[0], got[2]
+                    return with_tv(logits, got[0], got[2])
             loss, sums = Fn.ops.kl_cell_loss_fwd(logits, data_train.batch_gt, vol, norm)
             metrics.addPacked(sums, n_sup)
-            return loss, Fn.ops.kl_cell_loss_bwd(logits, data_train.batch_gt, vol, norm, sums, one)
+            return with_tv(logits, loss, Fn.ops.kl_cell_loss_bwd(logits, data_train.batch_gt, vol, norm, sums, one))
+
+        def with_tv(logits, loss, dlogits):
+            if tv_ei is None:
+                return loss, dlogits
+            # loss + reg, the regulariser's gradient added into the KL loss's rows and its metric sums: the edge pass and the finish pass
+            got = Fn.ops.edge_tv_step(logits[:tv_rows], tv_ei, tv_weight, add_loss=loss, running=metrics.regAccumulator(logits.device), dlogits=dlogits[:tv_rows])
+            return got[3], dlogits
         loss = step(data_train, loss_fn)
         if loss is None:
             return None

@@ -5,6 +5,8 @@ current torch stream and returns torch tensors.  No CPU path exists: a CPU tenso
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from ._lib import DgnnError, check, lib, on_device_of, ptr, stream_ptr
@@ -1388,6 +1390,106 @@ def kl_cell_loss_step(logits, gt, vol, norm: int, running=None, grad_loss=None, 
         return None
     check(rc, "dgnn_kl_cell_loss_step")
     return loss, out[:3], dl
+
+
+# ---- edge total-variation regulariser (csrc/edge_tv.hip) -------------------------------------------------------------------------
+def _edge_tv_args(logits, edge_index, what):
+    """-> (src pointer, dst pointer, element stride, idx64, E) of a PyG-style [2, E] int32 / int64 edge_index as it lies in memory (a column slice of
+    a larger one and the transposed view of an [E, 2] array included); nothing is converted or copied"""
+    _req(logits, "logits", dim=2)
+    if logits.size(1) != 2 or logits.size(0) == 0:
+        raise ValueError("%s: logits [n, 2] with n >= 1 expected, got %s" % (what, tuple(logits.shape)))
+    if not isinstance(edge_index, torch.Tensor):
+        raise TypeError("edge_index must be a tensor")
+    if edge_index.device != logits.device:
+        raise DgnnError("edge_index is on %s, the logits on %s" % (edge_index.device, logits.device))
+    if edge_index.dtype not in (torch.int32, torch.int64):
+        raise TypeError("edge_index must be int32 or int64, got %s" % edge_index.dtype)
+    if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_index.size(1) < 1:
+        raise ValueError("%s: edge_index [2, E] with E >= 1 expected, got %s" % (what, tuple(edge_index.shape)))
+    es = edge_index.stride(1) if edge_index.size(1) > 1 else 1
+    if es < 1 or edge_index.stride(0) < 0:
+        raise ValueError("edge_index must have positive strides (stride %s)" % (edge_index.stride(),))
+    p0 = edge_index.data_ptr()
+    return C.c_void_p(p0), C.c_void_p(p0 + edge_index.stride(0) * edge_index.element_size()), es, int(edge_index.dtype == torch.int64), edge_index.size(1)
+
+
+def _edge_tv_out(device, total):
+    """sums fp64 [2] | reg (| total) fp32 in the third double of one allocation"""
+    out = torch.empty(3, dtype=torch.float64, device=device)
+    f = out[2:].view(torch.float32)
+    return out[:2], f[0], (f[1] if total else None)
+
+
+def _edge_tv_scratch(device):
+    return torch.empty(int(lib().dgnn_edge_tv_scratch_doubles()), dtype=torch.float64, device=device)
+
+
+@on_device_of
+def edge_tv_fwd(logits, edge_index, weight: float, need_grad=True, max_blocks=None):
+    """-> (reg fp32 0-dim = weight * sum_e |p(src_e) - p(dst_e)| / E, sums fp64 [2] = (weight * sum tv, E), net int32 [n] | None) with
+    p = softmax(logits)[:, 0]; `net` (need_grad) holds the signed edge counts edge_tv_bwd turns into the gradient.  Indices are < n by contract.
+    max_blocks: a cap on the edge pass's workgroups (None: the library's)."""
+    src, dst, es, idx64, E = _edge_tv_args(logits, edge_index, "edge_tv_fwd")
+    n = logits.size(0)
+    sums, reg, _ = _edge_tv_out(logits.device, False)
+    net = torch.empty(n, dtype=torch.int32, device=logits.device) if need_grad else None
+    check(lib().dgnn_edge_tv_fwd(ptr(logits), _ld(logits), n, src, dst, es, idx64, E, float(weight), ptr(net), ptr(sums), ptr(reg), ptr(_edge_tv_scratch(logits.device)),
+                                 int(max_blocks or 0), stream_ptr()), "dgnn_edge_tv_fwd", poll=True)
+    return reg, sums, net
+
+
+@on_device_of
+def edge_tv_bwd(logits, net, weight: float, E: int, grad_loss=None, out=None):
+    """dlogits [n, 2] of edge_tv_fwd's `reg` (times the 0-dim `grad_loss`, None = 1) from its `net`; `out`: fp32 [n, 2] rows the gradient is ADDED to"""
+    _req(logits, "logits", dim=2)
+    n = logits.size(0)
+    if logits.size(1) != 2 or net.dtype != torch.int32 or net.numel() < n or not net.is_contiguous() or net.device != logits.device or E < 1:
+        raise ValueError("edge_tv_bwd: logits [n, 2], net int32 [n] of edge_tv_fwd and its E expected")
+    if out is not None and (_req(out, "out", dim=2).shape != logits.shape):
+        raise ValueError("edge_tv_bwd: `out` must have the logits' shape")
+    if grad_loss is not None:
+        grad_loss = grad_loss.to(torch.float32).contiguous()
+    dl = out if out is not None else torch.empty((n, 2), dtype=torch.float32, device=logits.device)
+    check(lib().dgnn_edge_tv_bwd(ptr(logits), _ld(logits), n, ptr(net), float(weight), int(E), ptr(grad_loss), ptr(dl), _ld(dl), int(out is not None), stream_ptr()),
+          "dgnn_edge_tv_bwd")
+    return dl
+
+
+_tv_net = {}      # (device, stream) -> zeroed int32 table of edge_tv_step (the finish pass hands it back zeroed: no memset launch per step)
+
+
+@on_device_of
+def edge_tv_step(logits, edge_index, weight: float, grad_loss=None, add_loss=None, running=None, dlogits=None, max_blocks=None):
+    """edge_tv_fwd + edge_tv_bwd as TWO launches -> (reg, sums, dlogits, total): the same bits as the two calls.  `dlogits`: fp32 [n, 2] rows the
+    gradient is ADDED to (the KL loss's; None: a fresh tensor is written); `add_loss`: fp32 0-dim, total = add_loss + reg comes back (else None);
+    `running`: fp64 [2] accumulator, += sums in the same launch.  The signed-count table is kept per device AND stream between calls: calls on one
+    stream are ordered, calls on different streams use different tables."""
+    src, dst, es, idx64, E = _edge_tv_args(logits, edge_index, "edge_tv_step")
+    n, dev = logits.size(0), logits.device
+    if dlogits is not None and _req(dlogits, "dlogits", dim=2).shape != logits.shape:
+        raise ValueError("edge_tv_step: `dlogits` must have the logits' shape")
+    if running is not None and (running.dtype != torch.float64 or running.numel() < 2 or not running.is_contiguous() or running.device != dev):
+        raise ValueError("edge_tv_step: `running` must be a contiguous fp64 [2] tensor on the logits' device")
+    if add_loss is not None and (add_loss.dtype != torch.float32 or add_loss.numel() != 1 or add_loss.device != dev):
+        raise ValueError("edge_tv_step: `add_loss` must be one fp32 value on the logits' device")
+    if grad_loss is not None:
+        grad_loss = grad_loss.to(torch.float32).contiguous()
+    stream = stream_ptr()
+    key = (dev, stream.value)
+    net = _tv_net.get(key)
+    if net is None or net.numel() < n:
+        net = _tv_net[key] = torch.zeros(max(1 << 16, 1 << (n - 1).bit_length()), dtype=torch.int32, device=dev)
+    sums, reg, total = _edge_tv_out(dev, add_loss is not None)
+    dl = dlogits if dlogits is not None else torch.empty((n, 2), dtype=torch.float32, device=dev)
+    try:
+        check(lib().dgnn_edge_tv_step(ptr(logits), _ld(logits), n, src, dst, es, idx64, E, float(weight), ptr(grad_loss), ptr(net), 1, ptr(sums), ptr(reg), ptr(add_loss),
+                                      ptr(total), ptr(running), ptr(dl), _ld(dl), int(dlogits is not None), ptr(_edge_tv_scratch(dev)), int(max_blocks or 0),
+                                      stream), "dgnn_edge_tv_step", poll=True)
+    except Exception:
+        _tv_net.pop(key, None)      # (a failed call may leave counts behind: the next one starts from a fresh zeroed table)
+        raise
+    return reg, sums, dl, total
 
 
 # ---- Updated variant: one conv layer per call each way (csrc/train.hip) --------------------------------------------------------

@@ -627,6 +627,32 @@ int dgnn_kl_cell_loss_bwd(const float* logits, int64_t ldl, const float* gt, int
 int dgnn_kl_cell_loss_step(const float* logits, int64_t ldl, const float* gt, int64_t ldg, const float* vol, int64_t ldv, int norm, int64_t n,
                            const float* grad_loss, double* sums, float* loss, double* running, float* dlogits, int64_t ldd, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Edge total-variation regulariser of the training objective (learning/runModel.py:109-160, :250-256), csrc/edge_tv.hip:
+ *   p(v) = softmax(logits_v)_0;  tv_e = |p(src_e) - p(dst_e)|;  reg = weight * sum_e tv_e / E;  sums[2] (fp64) = weight * sum_e tv_e, E
+ *   backward: dlogits_v = grad * (weight / E) * c(v) * p(v) (1 - p(v)) * (+1, -1),  c(v) = sum_{src_e = v} sgn_e - sum_{dst_e = v} sgn_e,
+ *   sgn_e = sign(p(src_e) - p(dst_e)) with sign(0) = 0.  c(v) is accumulated in `net` (int32 [n]) with integer atomics and the sum of tv in fp64
+ *   in a fixed order: results do not depend on the order of the edges' arrival, reruns are bit-identical.
+ * logits: n rows of two leading columns, row stride ldl.  src / dst: E indices in [0, n) each, element stride estride, int64 (idx64 != 0) or int32,
+ * any alignment of their type (16-byte aligned rows of stride 1, and the (src, dst) pairs of a transposed [E, 2] array, are read 16 bytes a load);
+ * any other layout -- a contiguous [2, E] tensor whose second row is not 16-byte aligned, i.e. E odd (int64) or E % 4 != 0 (int32), included -- is
+ * read one index a load, four loads of each row in flight); an index outside [0, n) is skipped and reported by dgnn_poll_async_error.  scratch:
+ * dgnn_edge_tv_scratch_doubles() doubles.  max_blocks: 0, or a cap on the edge pass's workgroups (each call of a fwd / step pair the same).
+ *   _fwd:  edge pass + finish (two launches).  net NULL: no gradient wanted; else it is zeroed here and filled with c(v) for _bwd.
+ *   _bwd:  one launch; dlogits rows are written, or added to (accumulate != 0).  grad: device pointer to the upstream scalar, NULL = 1.
+ *   _step: _fwd + _bwd as two launches: the finish pass also writes dlogits, *total = *add_loss + reg (total / add_loss may be NULL) and
+ *          running[2] += sums (may be NULL), and leaves net ZEROED.  net_is_zero != 0: the caller hands in a zeroed net (one that an earlier
+ *          _step left); otherwise it is zeroed here first.  Same bits as _fwd followed by _bwd.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_edge_tv_scratch_doubles(void);
+int dgnn_edge_tv_fwd(const float* logits, int64_t ldl, int64_t n, const void* src, const void* dst, int64_t estride, int idx64, int64_t E, float weight, int32_t* net,
+                     double* sums, float* reg, double* scratch, int max_blocks, void* stream);
+int dgnn_edge_tv_bwd(const float* logits, int64_t ldl, int64_t n, const int32_t* net, float weight, int64_t E, const float* grad, float* dlogits,
+                     int64_t ldd, int accumulate, void* stream);
+int dgnn_edge_tv_step(const float* logits, int64_t ldl, int64_t n, const void* src, const void* dst, int64_t estride, int idx64, int64_t E, float weight,
+                      const float* grad, int32_t* net, int net_is_zero, double* sums, float* reg, const float* add_loss, float* total,
+                      double* running, float* dlogits, int64_t ldd, int accumulate, double* scratch, int max_blocks, void* stream);
+
 /* Fused decoder, eval mode (reference :180-187 applied at :350-351):
  *   logits = W3 . relu((W0 . y + b0) * scale + shift) + b3,   y [M,k] -> out [M,n_out]
  * Supports k == 128, hidden == 64, n_out in {1,2}; DGNN_E_UNSUPPORTED otherwise (use dgnn_linear_fwd twice). */

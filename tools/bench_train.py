@@ -3,7 +3,7 @@
 cell volume) on the synthetic 150k-point scene, everything on the GPU: k-hop block builder (dgnn_amd.sampler) ->
 SurfaceNet.forward (BN in train mode) -> loss -> backward through the HIP kernels -> Adam.
 
-    python tools/bench_train.py [--updated] [--dtype bf16] [--points P] [--batch B] [--steps K]
+    python tools/bench_train.py [--updated] [--dtype bf16] [--points P] [--batch B] [--steps K] [--edge-reg]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         tools/bench_train.py --gpus N ...
 
@@ -41,6 +41,8 @@ ap.add_argument("--prefetch", choices=["none", "stream", "thread"], default="str
                 help="block builder: in line | one block ahead on a side stream, issued by the library's builder thread (default) | "
                      "ahead in a Python worker thread")
 ap.add_argument("--fresh-blocks", action="store_true", help="fresh tensors for every block instead of the builder's ring of three buffer sets")
+ap.add_argument("--edge-reg", action="store_true", help="the edge total-variation regulariser on from the first step (regularization.edge_epoch 0, edge_weight "
+                                                        "0.4): blocks of num_hops + 1 hops as run.py:68 builds them, the extra hop's block carries its edges")
 ap.add_argument("--no-roofline", action="store_true", help="skip the GEMM / aggregate replays behind the `roofline` object")
 args = ap.parse_args()
 
@@ -72,6 +74,12 @@ widths = [int(v) for v in args.widths.split(",")] if args.widths else [64, 128, 
 clf = reconbench_pretrained(device=dev, convs=tuple(widths))
 clf.temp.current_epoch = 0
 clf.training.metrics = Metrics()
+hops = 4
+if args.edge_reg:
+    if args.updated:
+        raise SystemExit("--edge-reg: the Updated model's bench step computes its loss itself; the regulariser is measured on the Static model")
+    clf.regularization.edge_epoch, clf.graph.additional_num_hops = 0, 1
+    hops = clf.graph.num_hops + clf.graph.additional_num_hops
 torch.manual_seed(0)
 if args.updated:
     import torch.nn.functional as F
@@ -129,7 +137,7 @@ g = torch.Generator().manual_seed(rank)
 per = (n // batch) * batch     # whole batches per permutation: no duplicate targets inside a batch
 need = batch * (steps + args.warmup)
 idx = torch.cat([torch.randperm(n, generator=g)[:per] for _ in range(need // per + 1)])[:need]
-loader = NeighborSampler(ei, sizes=[-1] * 4, node_idx=idx.to(dev), num_nodes=n, batch_size=batch,
+loader = NeighborSampler(ei, sizes=[-1] * hops, node_idx=idx.to(dev), num_nodes=n, batch_size=batch,
                          prefetch={"none": False, "stream": True, "thread": "thread"}[args.prefetch], reuse_buffers=not args.fresh_blocks)
 if os.environ.get("DGNN_BLOCK_ROWS", "1") != "0":
     tr.attach_block_rows(loader, all_, net)      # x[n_id, 1:], x[ids], y[ids] gathered by the block builder behind every block (as Trainer.train_test does)
@@ -200,7 +208,7 @@ def replay_roofline():
                 "frac": round(bytes_b / t_b / 1e6 / 8000.0, 4), "traffic": None, "algorithmic_bytes_per_launch": bytes_b, "avg_launch_ms": round(t_b, 4),
                 "timing": "the launch replayed 10x at the last block's shapes, HIP events on the launching stream"}
     gemms, flops, ms = [], 0.0, 0.0
-    for i, (e, e_id, size) in enumerate(adjs):
+    for i, (e, e_id, size) in enumerate(adjs[:4]):      # (--edge-reg: the fifth block carries the regulariser's edges, no conv layer)
         n_src, n_dst = size
         gemms.append((n_dst, w[i], w[i], w[i + 1]))                      # z = a.Wj^T + x_dst.Wi^T
         gemms += [(n_dst, w[i + 1], 0, w[i])] * (2 if i > 0 else 1)      # da = dz.Wj (+ dx_dst += dz.Wi)
@@ -246,10 +254,10 @@ if rank == 0 and not args.no_roofline and (args.updated or args.dtype == "f32"):
     roof = replay_roofline()
 if rank == 0:
     print(json.dumps({"metric": "training step (block builder + fwd + bwd + %sAdam), %d x MI355X" % ("gradient all-reduce + " if world > 1 else "", world),
-                      "model": "UpdatedEdgeFilters sage+" if args.updated else "StaticEdgeFilters", "dtype": args.dtype, "n_gpus": world,
+                      "model": "UpdatedEdgeFilters sage+" if args.updated else "StaticEdgeFilters", "edge_regulariser": bool(args.edge_reg), "dtype": args.dtype, "n_gpus": world,
                       "parallelism": "data-parallel replicas, one scene shard per GPU, flat RCCL all-reduce" if world > 1 else "single GPU",
                       "targets_per_s": round(batch * steps * world / dt, 1), "block_tets_per_s": round(block / dt, 1),
                       "ms_per_step": round(dt / steps * 1e3, 3), "host_issue_ms_per_step": round(host_dt / steps * 1e3, 3), "batch_targets_per_gpu": batch,
-                      "avg_block_tets": round(block / steps / world, 1), "steps": steps, "block_builder": args.prefetch, "scene_tets_per_gpu": n, "final_loss": float(loss), "replicas": replicas, "roofline": roof}))
+                      "avg_block_tets": round(block / steps / world, 1), "steps": steps, "block_builder": args.prefetch, "scene_tets_per_gpu": n, "final_loss": float(loss), "train_loss_reg": clf.training.metrics.getRegLoss(), "replicas": replicas, "roofline": roof}))
 if world > 1:
     dist.destroy_process_group()
