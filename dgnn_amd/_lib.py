@@ -175,7 +175,6 @@ SIGNATURES = {
     "dgnn_sage_layer_train_bwd_bf16": (i32, [vp, vp, vp, vp, i64, i64, vp, i64, i32, vp, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, f32, i32,
                                              vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dgnn_static_train_fwd": (i32, [i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
-    "dgnn_train_set_aux_stream": (i32, [i32]),
     "dgnn_static_train_scratch_elems": (i64, [i32, vp, vp, vp, i32]),
     "dgnn_static_train_bwd": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                     vp, vp, vp, vp, i32, vp]),

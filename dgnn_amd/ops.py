@@ -787,7 +787,6 @@ INFER_ONE_CALL = __import__("os").environ.get("DGNN_INFER_ONE_CALL", "1") != "0"
 def _infer_tables(x_width, layers, decoder, prepared, cache):
     """ctypes argument tables of the one-call entry points: (L, widths, 7 per-layer pointer arrays, prepared, the decoder's 8 scalars / addresses,
     n_out); kept in `cache` (the model's, valid as long as the tensors are: SurfaceNet._one_call_tables) when one is given."""
-    import ctypes as C
     if cache is not None:
         hit = cache.get(x_width)
         if hit is not None:
@@ -838,7 +837,6 @@ def _one_call(name, x, edge_attr, edge_index, plan_parts, hint, n_key, n_work, n
 
 
 def _n_dst_array(n_dst, L):
-    import ctypes as C
     assert len(n_dst) == L
     return (C.c_int64 * L)(*[int(v) for v in n_dst])
 
@@ -1029,6 +1027,24 @@ TRAIN_DECODER_OUTPUT_IN_CALL = __import__("os").environ.get("DGNN_TRAIN_DECODER_
 TRAIN_KEEP_GRADS = __import__("os").environ.get("DGNN_TRAIN_KEEP_GRADS", "1") != "0"
 
 
+def _grad_buffer(rows, dev):
+    """The parameter gradients of a backward call as views of ONE fp32 buffer.  `rows`: per layer the gradients' shapes, (r, c) | (n,), None or an
+    empty shape where the layer has no such parameter.  -> (flat, offs, views): element offsets and views per layer in the order of `rows`, None
+    where there is no gradient.  One allocation and one view op per gradient (a slice + .view pair costs 2.5 x as much on the host)."""
+    offs, off = [], 0
+    for row in rows:
+        o = []
+        for sh in row:
+            n = 0 if sh is None else sh[0] * sh[1] if len(sh) == 2 else sh[0]
+            o.append(off if n else None)
+            off += n
+        offs.append(o)
+    flat = torch.empty(off, dtype=torch.float32, device=dev)
+    st = torch.as_strided
+    views = [tuple(None if o is None else st(flat, sh, (sh[1], 1) if len(sh) == 2 else (1,), o) for sh, o in zip(row, oo)) for row, oo in zip(rows, offs)]
+    return flat, offs, views
+
+
 @on_device_of
 def sage_layer_train_fwd(plan_parts, n_dst, x, edge_attr, We, be, Wj, bj, Wi, gamma, beta, running_mean, running_var, momentum, eps, relu):
     """conv (aggregate + lin_j + lin_i) -> BatchNorm(batch statistics, running buffers updated) -> ReLU as ONE library call; fp32 or
@@ -1072,14 +1088,8 @@ def sage_layer_train_bwd(t_parts, rowptr_dst, n_src, n_dst, x, edge_attr, We, be
     dev, dt = x.device, x.dtype
     agg = t_parts is not None
     f_e = We.size(1) if (agg and We is not None) else 0
-    sizes = [c_in * f_e, c_in if f_e else 0, c_out * c_in, c_out if has_bias else 0, c_out * c_in if (agg and Wi is not None) else 0, c_out, c_out]
-    flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-    shapes = [(c_in, f_e), (c_in,), (c_out, c_in), (c_out,), (c_out, c_in), (c_out,), (c_out,)]
-    parts, o = [], 0
-    for s, sh in zip(sizes, shapes):       # one view op per gradient, already in its final shape
-        parts.append(torch.as_strided(flat, sh, (sh[1], 1) if len(sh) == 2 else (1,), o) if s else None)
-        o += s
-    dWe, dbe, dWj, dbj, dWi, dgamma, dbeta = parts
+    _, _, ((dWe, dbe, dWj, dbj, dWi, dgamma, dbeta),) = _grad_buffer([[(c_in, f_e), (c_in,) if f_e else None, (c_out, c_in), (c_out,) if has_bias else None,
+                                                                       (c_out, c_in) if (agg and Wi is not None) else None, (c_out,), (c_out,)]], dev)
     dx = torch.empty((n_src if agg else n_dst, c_in), dtype=dt, device=dev) if need_dx else None
     scratch = _f32(lib().dgnn_sage_layer_train_scratch_elems(n_src, n_dst, c_in, c_out, f_e), dev)
     t_rowptr, t_dst, t_eid = t_parts if agg else (None, None, None)
@@ -1105,7 +1115,6 @@ UPDATED_TAIL_IN_CALL = __import__("os").environ.get("DGNN_UPDATED_TAIL_IN_CALL",
 def updated_stack_fwd(x0, edge_attr_all, pos, layers):
     """`layers`: per conv layer a dict with plan (GraphPlan), e_id (int64 [E_l], rows of the scene's edge tensor), rows0 (int32 form of e_id, layer 0),
     edge_in, relu, We, be, Wl, bl, Wr.  -> (y_last, saved): every layer's ea / phi / a / y (+ the chaining's inverse maps) in one buffer."""
-    import ctypes as C
     _req(x0, "x", ACT, dim=2)
     _req(edge_attr_all, "edge_attr", dim=2)
     dev, dt, L = x0.device, x0.dtype, len(layers)
@@ -1159,23 +1168,15 @@ def updated_stack_fwd(x0, edge_attr_all, pos, layers):
 @on_device_of
 def updated_stack_bwd(x0, layers, saved, dy):
     """-> per layer (dWe, dbe, dWl, dbl | None, dWr | None): views of one fp32 buffer"""
-    import ctypes as C
     buf, offs, widths, pa = saved
     dev, dt, L = x0.device, x0.dtype, len(layers)
     bf = dt == torch.bfloat16
     base = buf.data_ptr()
     at = lambda o: None if o is None else base + o
-    sizes, off = [], 0
-    for i, l in enumerate(layers):
-        ci, co, k = widths[i], widths[i + 1], l["edge_in"]
-        row = []
-        for sz in (ci * k, ci, co * ci, co if l["bl"] is not None else 0, co * ci if l["Wr"] is not None else 0):
-            row.append((off, sz) if sz else None)
-            off += sz
-        sizes.append(row)
-    flat = torch.empty(off, dtype=torch.float32, device=dev)
+    flat, goffs, grads = _grad_buffer([[(widths[i], l["edge_in"]), (widths[i],), (widths[i + 1], widths[i]), (widths[i + 1],) if l["bl"] is not None else None,
+                                        (widths[i + 1], widths[i]) if l["Wr"] is not None else None] for i, l in enumerate(layers)], dev)
     gbase = flat.data_ptr()
-    gat = lambda e: None if e is None else gbase + 4 * e[0]
+    gat = lambda o: None if o is None else gbase + 4 * o
     P = [l["plan"] for l in layers]
     mx = lambda vals: max(list(vals) + [1])
     # the seven work buffers of the backward (storage type) as pieces of one allocation, 16-byte aligned
@@ -1196,7 +1197,7 @@ def updated_stack_bwd(x0, layers, saved, dy):
     arr = lambda k: _parr([l[k] for l in layers])
     i64 = lambda v: _iarr(v, C.c_int64)
     i32 = lambda v: _iarr(v, C.c_int32)
-    col = lambda j: _parr([gat(r[j]) for r in sizes])
+    col = lambda j: _parr([gat(r[j]) for r in goffs])
     check(lib().dgnn_updated_stack_bwd(
         L, _parr([t[0] for t in tps]), _parr([t[1] for t in tps]), _parr([t[2] for t in tps]), _parr([p.part_ptrs(False)[0] for p in P]),
         i64([p.n_src for p in P]), i64([p.n_dst for p in P]), i64([p.E for p in P]), ptr(x0), _ld(x0), pa["widths"], pa["edge_in"],
@@ -1204,13 +1205,6 @@ def updated_stack_bwd(x0, layers, saved, dy):
         _parr([at(o["phi"]) for o in offs]), _parr([at(o["a"]) for o in offs]), _parr([at(o["y"]) for o in offs]), _parr([at(o["inv"]) for o in offs]),
         ptr(dy), col(0), col(1), col(2), col(3), col(4), _parr(dxb), d_ea, dphi_ext, dz, da, dphi, ptr(scratch), int(bf), GEMM_MODE,
         stream_ptr()), "dgnn_updated_stack_bwd")
-    st = torch.as_strided
-    grads = []
-    for i, (l, row) in enumerate(zip(layers, sizes)):
-        ci, co, k = widths[i], widths[i + 1], l["edge_in"]
-        m = lambda e, r, c: None if e is None else st(flat, (r, c), (c, 1), e[0])
-        v = lambda e, n: None if e is None else st(flat, (n,), (1,), e[0])
-        grads.append((m(row[0], ci, k), v(row[1], ci), m(row[2], co, ci), v(row[3], co), m(row[4], co, ci)))
     return grads
 
 
@@ -1229,10 +1223,7 @@ def updated_tail_fwd(x, W1, b1, W3, b3):
 def updated_tail_bwd(x, W1, W3, h, g):
     """-> (dx [n, c] in x's type, dW1, db1, dW3, db3)"""
     n, c, hd, no = x.size(0), x.size(1), W1.size(0), W3.size(0)
-    flat = torch.empty(hd * c + hd + no * hd + no, dtype=torch.float32, device=x.device)
-    st = torch.as_strided
-    dW1, db1 = st(flat, (hd, c), (c, 1), 0), st(flat, (hd,), (1,), hd * c)
-    dW3, db3 = st(flat, (no, hd), (hd, 1), hd * c + hd), st(flat, (no,), (1,), hd * c + hd + no * hd)
+    _, _, ((dW1, db1, dW3, db3),) = _grad_buffer([[(hd, c), (hd,), (no, hd), (no,)]], x.device)
     dx = torch.empty((n, c), dtype=x.dtype, device=x.device)
     dh = torch.empty((n, hd), dtype=x.dtype, device=x.device)
     scratch = _f32(lib().dgnn_updated_tail_scratch_elems(n, c, hd, no), x.device)
@@ -1278,7 +1269,6 @@ def updated_infer_fwd(x, edge_attr, plan_parts, layers, tail=None):
     edge_attr fp32 [E, >= edge_in_0] in scene edge order, plan_parts = (rowptr, src, eid) of the scene's destination-sorted plan; `layers`: per conv
     layer a dict with edge_in, relu, We, be, Wl, bl, Wr; `tail` = (W1, b1, W3, b3) or None.
     -> (fp32 logits [n, n_out] | the last layer's rows in x's type, bit mask of the layers that ran through the one-launch form)."""
-    import ctypes as C
     _req(x, "x", ACT, dim=2)
     _req(edge_attr, "edge_attr", dim=2)
     dev, bf, L = x.device, x.dtype == torch.bfloat16, len(layers)
@@ -1516,14 +1506,8 @@ def sage_updated_train_bwd(t_parts, rowptr_dst, n_src, n_dst, x, ea, We, Wl, Wr,
     """-> (dx | None, d_ea | None, dWe, dbe, dWl, dbl | None, dWr | None); parameter gradients are views of one fp32 buffer"""
     c_in, c_out, k_e, E = x.size(1), Wl.size(0), We.size(1), ea.size(0)
     dev, dt = x.device, x.dtype
-    sizes = [c_in * k_e, c_in, c_out * c_in, c_out if has_bias else 0, c_out * c_in if Wr is not None else 0]
-    flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-    shapes = [(c_in, k_e), (c_in,), (c_out, c_in), (c_out,), (c_out, c_in)]
-    parts, o = [], 0
-    for sz, sh in zip(sizes, shapes):      # one view op per gradient, already in its final shape
-        parts.append(torch.as_strided(flat, sh, (sh[1], 1) if len(sh) == 2 else (1,), o) if sz else None)
-        o += sz
-    dWe, dbe, dWl, dbl, dWr = parts
+    _, _, ((dWe, dbe, dWl, dbl, dWr),) = _grad_buffer([[(c_in, k_e), (c_in,), (c_out, c_in), (c_out,) if has_bias else None,
+                                                         (c_out, c_in) if Wr is not None else None]], dev)
     dx = torch.empty((n_src, c_in), dtype=dt, device=dev) if need_dx else None
     d_ea = torch.empty((E, k_e), dtype=dt, device=dev) if need_dea else None
     dz = torch.empty((n_dst, c_out), dtype=dt, device=dev) if relu else None
@@ -1540,7 +1524,6 @@ def sage_updated_train_bwd(t_parts, rowptr_dst, n_src, n_dst, x, ea, We, Wl, Wr,
 
 # ---- Static model in training mode, all layers per call (csrc/train.hip) -------------------------------------------------------
 def _parr(vals):
-    import ctypes as C
     return (C.c_void_p * len(vals))(*[(v.data_ptr() if isinstance(v, torch.Tensor) else v) for v in vals])
 
 
@@ -1554,7 +1537,6 @@ _PARAM_ARRAYS = {}      # pointer tables of a model's parameters and BatchNorm b
 def _param_arrays(layers):
     """ctypes tables (one entry per layer) of everything in `layers` that belongs to the MODEL, not to the batch: built once and reused while
     the tensors keep their addresses (40 data_ptr() reads a step instead of a dozen table constructions)."""
-    import ctypes as C
     names = ("We", "be", "Wj", "bj", "Wi", "gamma", "beta")
     key = tuple((l[k].data_ptr() if l[k] is not None else 0) for l in layers for k in names) + tuple(
         ((bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr() if bn.track_running_stats else 0, bn.momentum, bn.eps)
@@ -1578,7 +1560,6 @@ def static_train_fwd(x0, layers):
     """`layers`: list of dicts (one per conv layer, then optionally the decoder's Linear + BN block with plan None) with keys
     plan_parts (rowptr, src, eid) | None, n_dst, edge_attr | None, We, be, Wj, bj, Wi, gamma, beta, bn.
     -> (y_last, buf, meta): one fp32 buffer holding every layer's a / z / y / stats, `meta` the element offsets."""
-    import ctypes as C
     _req(x0, "x", dim=2)
     dev, L = x0.device, len(layers)
     widths = [x0.size(1)] + [l["Wj"].size(0) for l in layers]
@@ -1622,7 +1603,6 @@ def static_train_bwd(x0, layers, buf, meta_widths, dy, keep=None):
     """-> per-layer parameter gradients [(dWe, dbe, dWj, dbj, dWi, dgamma, dbeta), ...] (views of one buffer; None where the layer has
     no such parameter).  `keep`: a dict owned by the caller (the model) -- the gradient buffer and its views are then made ONCE and every step writes
     into the same tensors (round 6: one allocation and 34 view ops a step less; what the optimizer reads through p.grad stays at one address)."""
-    import ctypes as C
     meta, widths, pa = meta_widths
     dev, L = x0.device, len(layers)
     base = buf.data_ptr()
@@ -1630,22 +1610,19 @@ def static_train_bwd(x0, layers, buf, meta_widths, dy, keep=None):
     kept = keep.get("static_bwd") if keep is not None else None
     sig = (dev, tuple(widths), tuple((l["We"].size(1) if l["We"] is not None else 0, l["bj"] is not None, l["Wi"] is not None, l["bn"] is not None) for l in layers))
     if kept is not None and kept[0] == sig:
-        _, sizes, flat, grads_kept = kept
+        _, goffs, flat, grads = kept
     else:
-        sizes, off = [], 0
+        rows = []
         for i, l in enumerate(layers):
             ci, co = widths[i], widths[i + 1]
             fe = l["We"].size(1) if l["We"] is not None else 0
-            row = []
-            nbn = co if l["bn"] is not None else 0
-            for sz in (ci * fe, ci if fe else 0, co * ci, co if l["bj"] is not None else 0, co * ci if l["Wi"] is not None else 0, nbn, nbn):
-                row.append((off, sz) if sz else None)
-                off += sz
-            sizes.append(row)
-        flat = torch.empty(off, dtype=torch.float32, device=dev)
-        grads_kept = None
+            bn = (co,) if l["bn"] is not None else None
+            rows.append([(ci, fe), (ci,) if fe else None, (co, ci), (co,) if l["bj"] is not None else None, (co, ci) if l["Wi"] is not None else None, bn, bn])
+        flat, goffs, grads = _grad_buffer(rows, dev)
+        if keep is not None:
+            keep["static_bwd"] = (sig, goffs, flat, grads)
     gbase = flat.data_ptr()
-    gat = lambda e: None if e is None else gbase + 4 * e[0]
+    gat = lambda o: None if o is None else gbase + 4 * o
     n_src = [(l["n_src"] if l["plan_parts"] is not None else l["n_dst"]) for l in layers]
     dxn = max([n_src[i] * widths[i] for i in range(1, L)] or [1])
     dxn = (dxn + (1 << 20) - 1) >> 20 << 20
@@ -1655,7 +1632,7 @@ def static_train_bwd(x0, layers, buf, meta_widths, dy, keep=None):
                                                               _iarr(widths, C.c_int32), f_e), dev)
     tp = lambda k: _parr([(l["t_parts"][k] if l["plan_parts"] is not None else None) for l in layers])
     key = lambda k: _parr([l[k] for l in layers])
-    col = lambda j: _parr([gat(r[j]) for r in sizes])
+    col = lambda j: _parr([gat(r[j]) for r in goffs])
     check(lib().dgnn_static_train_bwd(
         L, tp(0), tp(1), tp(2), _parr([(l["plan_parts"][0] if l["plan_parts"] is not None else None) for l in layers]), _iarr(n_src, C.c_int64),
         _iarr([l["n_dst"] for l in layers], C.c_int64), ptr(x0), _ld(x0), _iarr(widths, C.c_int32), key("edge_attr"),
@@ -1663,18 +1640,6 @@ def static_train_bwd(x0, layers, buf, meta_widths, dy, keep=None):
         pa["gamma"], _parr([at(m["stats"]) for m in meta]), pa["eps"], _parr([at(m["a"]) for m in meta]),
         _parr([at(m["z"]) for m in meta]), _parr([at(m["y"]) for m in meta]), ptr(dy), col(0), col(1), col(2), col(3), col(4), col(5), col(6),
         _parr([dxb[0], dxb[1]]), ptr(scratch), GEMM_MODE, stream_ptr()), "dgnn_static_train_bwd")
-    if grads_kept is not None:
-        return grads_kept
-    grads = []
-    st = torch.as_strided      # one view op per gradient (a slice + .view pair costs 2.5 x as much on the host, 34 times a step)
-    for i, (l, row) in enumerate(zip(layers, sizes)):
-        ci, co = widths[i], widths[i + 1]
-        fe = l["We"].size(1) if l["We"] is not None else 0
-        m = lambda e, r, c: None if e is None else st(flat, (r, c), (c, 1), e[0])
-        v = lambda e, n: None if e is None else st(flat, (n,), (1,), e[0])
-        grads.append((m(row[0], ci, fe), v(row[1], ci), m(row[2], co, ci), v(row[3], co), m(row[4], co, ci), v(row[5], co), v(row[6], co)))
-    if keep is not None:
-        keep["static_bwd"] = (sig, sizes, flat, grads)
     return grads
 
 
@@ -1701,7 +1666,6 @@ def binary_graph_cut(logits, edges, unary_weight, binary_weight, return_stats=Fa
     -> (labels int32 [n] on the GPU: 0 inside / 1 outside, the minimiser with the fewest outside cells; energy int; max-flow value int)
     (+ {"steps", "relabels"} with return_stats).  Raises ValueError for a negative weight, DgnnError for an edge id outside [0, n),
     non-finite logits, |cost| >= 2^30 or capacities that overflow int32."""
-    import ctypes as C
 
     w = potts_weight(binary_weight)
     dev = logits.device if isinstance(logits, torch.Tensor) and logits.is_cuda else torch.device("cuda", torch.cuda.current_device())

@@ -487,9 +487,7 @@ int dgnn_sage_layer_train_bwd_bf16(const int32_t* t_rowptr, const int32_t* t_dst
  * HOST arrays [n_layers] of device pointers / sizes (widths [n_layers+1]); rowptr[l] == NULL marks a plain Linear + BatchNorm +
  * ReLU block (the decoder's).  Layer l reads y[l-1] (layer 0: x0); stats[l] = [4, widths[l+1]] (mean, var, scale, shift).
  * Forward scratch: max_l dgnn_colstats_scratch_elems(n_dst[l], widths[l+1]); backward scratch: dgnn_static_train_scratch_elems
- * (host arrays); dx_buf[0..1]: max_l n_src[l] * widths[l] floats each.  The backward runs the weight gradients (dWj, dbj, dWi: they
- * depend on dz only) on a second, library-owned stream beside the dx chain when dgnn_train_set_aux_stream(1) / DGNN_TRAIN_AUX_STREAM=1
- * is in effect, and makes `stream` wait for them before it returns; default: one stream.  Results are the same either way.
+ * (host arrays); dx_buf[0..1]: max_l n_src[l] * widths[l] floats each.  Everything runs on `stream`.
  * num_batches_tracked (may be NULL): device int64 counters of the BatchNorm modules, incremented once.
  * ---------------------------------------------------------------------------------------------- */
 int dgnn_static_train_fwd(int n_layers, const int32_t* const* rowptr, const int32_t* const* src, const int32_t* const* eid, const int64_t* n_dst,
@@ -498,10 +496,6 @@ int dgnn_static_train_fwd(int n_layers, const int32_t* const* rowptr, const int3
                           const float* const* gamma, const float* const* beta, float* const* running_mean, float* const* running_var,
                           int64_t* const* num_batches_tracked, const float* momentum, const float* eps, float* const* a, float* const* z,
                           float* const* stats, float* const* y, float* scratch, int gemm_mode, void* stream);
-/* Whether the composite backward entry points (dgnn_sage_layer_train_bwd, dgnn_sage_updated_train_bwd, dgnn_static_train_bwd) run the
- * weight gradients on the library's second stream (default 0 -- measured 2-8 % slower than one stream at the reference's block sizes;
- * environment DGNN_TRAIN_AUX_STREAM=1 starts with 1).  Returns the previous setting.  Results do not depend on it. */
-int dgnn_train_set_aux_stream(int on);
 /* The training step's fused launch chains: bit 0 = backward (dgnn_linear_wgrad_x3_cat, the stacked input-gradient GEMM with
  * dgnn_sage_aggregate_bwd_add, one transpose launch per pass), bit 1 = BatchNorm statistics from the forward GEMM's epilogue
  * (dgnn_linear_fwd_x3_stats).  Default 3 (environment: DGNN_TRAIN_FUSED=<mask>); 0 = the launch chain of the separate entry points.

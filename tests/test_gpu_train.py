@@ -1,4 +1,5 @@
 """GPU twins of tests/test_trainer_cpu.py (HIP SurfaceNet instead of the oracle) + the RCCL smoke test + generate()."""
+import contextlib
 import os
 import socket
 
@@ -238,9 +239,7 @@ def _same_grad(k, a, b):
     return torch.equal(a, b)
 
 
-def test_composite_train_layer_is_bit_identical_to_the_separate_calls(monkeypatch):
-    """dgnn_sage_layer_train_fwd / _bwd (one library call per layer each way) issue the kernels of the separate entry points in
-    the same order: logits, every gradient and every BatchNorm buffer must match bit for bit."""
+def _static_composite_vs_separate(monkeypatch, cases):
     from dgnn_amd import ops
     from dgnn_amd.sampler import NeighborSampler
     from dgnn_amd.synthetic import delaunay_tet_graph, hashed_normal
@@ -259,7 +258,7 @@ def test_composite_train_layer_is_bit_identical_to_the_separate_calls(monkeypatc
         (logits * G).sum().backward()
         return logits.detach().clone(), {k: p.grad.clone() for k, p in net.named_parameters()}, {k: b.clone() for k, b in net.named_buffers()}
 
-    for case in range(2):
+    for case in cases:
         if case == 1:   # a 4-hop block of the GPU block builder on a larger scene (sampler-made plans, ragged last tiles)
             adj, _, _ = delaunay_tet_graph(3000, seed=4)
             n = adj.shape[0] // 4
@@ -277,6 +276,36 @@ def test_composite_train_layer_is_bit_identical_to_the_separate_calls(monkeypatc
                 assert _same_grad(k, ga[k], gb[k]), (case, whole, k, (ga[k] - gb[k]).abs().max().item())
             for k in ba:
                 assert torch.equal(ba[k], bb[k]), (case, whole, k)
+
+
+def test_composite_train_layer_is_bit_identical_to_the_separate_calls(monkeypatch):
+    """dgnn_sage_layer_train_fwd / _bwd (one library call per layer each way) issue the kernels of the separate entry points in
+    the same order: logits, every gradient and every BatchNorm buffer must match bit for bit."""
+    _static_composite_vs_separate(monkeypatch, range(2))
+
+
+@contextlib.contextmanager
+def _train_chain(mode, mask):
+    """the arithmetic (a name of ops.GEMM_MODE_NAMES, None: as it is) and the fused-chain mask (dgnn_train_set_fused) for the block, then as before"""
+    from dgnn_amd import ops
+    from dgnn_amd._lib import lib
+    mode_was, mask_was = ops.GEMM_MODE, lib().dgnn_train_set_fused(mask)
+    try:
+        if mode is not None:
+            ops.GEMM_MODE = ops.GEMM_MODE_NAMES[mode]
+        yield
+    finally:
+        ops.GEMM_MODE = mode_was
+        lib().dgnn_train_set_fused(mask_was)
+
+
+@pytest.mark.parametrize("mode,mask", [("f32", 3), ("f16x2", 0), ("f16x2", 1), ("f16x2", 2)])
+def test_composite_train_layer_matches_the_separate_calls_in_every_chain(monkeypatch, mode, mask):
+    """the chains a default run never enters -- fp32 products (no fused chain at all), and each half of the fused chain switched off (bit 0: the
+    backward, bit 1: the statistics from the forward GEMM's epilogue): whole-model and per-layer calls against the separate entry points on the
+    fixture's blocks, with the assertions of the default run"""
+    with _train_chain(mode, mask):
+        _static_composite_vs_separate(monkeypatch, [0])
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -404,12 +433,7 @@ def test_prefetching_block_builder_yields_the_same_blocks_and_plans(mode):
             assert torch.equal(plan.edge_rows.long(), i2) and torch.equal(plan.transposed_edge_rows.long(), i2[t_ref[2].long()])
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("name", ["sage+", "sage"])
-def test_updated_composite_layer_matches_the_separate_calls(monkeypatch, dtype, name):
-    """dgnn_sage_updated_train_fwd / _bwd (one library call per conv each way) vs the chain of separate Functions: fp32 is
-    bit-identical (same kernels, same order); bf16 storage differs only where the composite adds dz.Wr into dx before rounding
-    to bf16 instead of after (one rounding instead of two), so it is compared at bf16 resolution."""
+def _updated_composite_vs_separate(monkeypatch, dtype, name):
     from dgnn_amd import ops
     from dgnn_amd.learning import surfaceNetUpdatedEdgeFilters as U
     from dgnn_amd.sampler import NeighborSampler
@@ -442,12 +466,25 @@ def test_updated_composite_layer_matches_the_separate_calls(monkeypatch, dtype, 
         else:
             assert (ga[k] - gb[k]).abs().max().item() <= 2e-2 * gb[k].abs().max().item() + 1e-6, (k, (ga[k] - gb[k]).abs().max().item(), gb[k].abs().max().item())
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("name", ["sage+", "sage"])
+def test_updated_composite_layer_matches_the_separate_calls(monkeypatch, dtype, name):
+    """dgnn_sage_updated_train_fwd / _bwd (one library call per conv each way) vs the chain of separate Functions: fp32 is
+    bit-identical (same kernels, same order); bf16 storage differs only where the composite adds dz.Wr into dx before rounding
+    to bf16 instead of after (one rounding instead of two), so it is compared at bf16 resolution."""
+    _updated_composite_vs_separate(monkeypatch, dtype, name)
+
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("name", ["sage+", "sage"])
-def test_updated_conv_stack_call_is_bit_identical_to_the_per_layer_calls(monkeypatch, dtype, name):
-    """dgnn_updated_stack_fwd / _bwd (all conv layers and the edge chaining per call) issue the per-layer composite calls and the chaining kernels
-    in the per-layer path's order: logits and every gradient bit for bit, fp32 and bf16 storage; the chaining table is left all -1."""
+def test_updated_composite_layer_matches_the_separate_calls_in_the_unfused_chain(monkeypatch, dtype, name):
+    """the same under dgnn_train_set_fused(0): the launch chain of the separate entry points, which a default run never enters"""
+    with _train_chain(None, 0):
+        _updated_composite_vs_separate(monkeypatch, dtype, name)
+
+
+
+def _updated_stack_vs_per_layer(monkeypatch, dtype, name):
     from dgnn_amd import ops
     from dgnn_amd.learning import surfaceNetUpdatedEdgeFilters as U
     from dgnn_amd.sampler import NeighborSampler
@@ -486,6 +523,22 @@ def test_updated_conv_stack_call_is_bit_identical_to_the_per_layer_calls(monkeyp
             assert (ga[k] - gb[k]).abs().max().item() <= 1e-6 * gb[k].abs().max().item(), k
         else:
             assert torch.equal(ga[k], gb[k]), (k, (ga[k] - gb[k]).abs().max().item())
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("name", ["sage+", "sage"])
+def test_updated_conv_stack_call_is_bit_identical_to_the_per_layer_calls(monkeypatch, dtype, name):
+    """dgnn_updated_stack_fwd / _bwd (all conv layers and the edge chaining per call) issue the per-layer composite calls and the chaining kernels
+    in the per-layer path's order: logits and every gradient bit for bit, fp32 and bf16 storage; the chaining table is left all -1."""
+    _updated_stack_vs_per_layer(monkeypatch, dtype, name)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("name", ["sage+", "sage"])
+def test_updated_conv_stack_call_is_bit_identical_to_the_per_layer_calls_in_the_unfused_chain(monkeypatch, dtype, name):
+    """the same under dgnn_train_set_fused(0): the launch chain of the separate entry points, which a default run never enters"""
+    with _train_chain(None, 0):
+        _updated_stack_vs_per_layer(monkeypatch, dtype, name)
+
 
 
 def test_eval_after_training_forwards_sees_the_new_running_statistics():
@@ -772,30 +825,6 @@ def test_block_builder_gathers_the_step_rows_and_the_run_is_the_same(model):
     assert out[True][0] == out[False][0]
     for k in out[False][1]:
         assert torch.equal(out[True][1][k], out[False][1][k]), k
-
-
-def test_aux_stream_backward_gives_identical_gradients():
-    """dgnn_train_set_aux_stream(1): weight gradients on the library's second stream beside the dx chain -- same numbers"""
-    from dgnn_amd._lib import lib
-    from test_gpu_parity import gold, f3_data
-    g = gold("static_f3_train_blocks.npz")
-    d = f3_data(g)
-    data = Config(all=Config(x=d.all.x.to(DEV), edge_attr=d.all.edge_attr.to(DEV)), batch_n_id=d.batch_n_id.to(DEV),
-                  batch_adjs=[(a.to(DEV), e.to(DEV), s) for a, e, s in d.batch_adjs])
-    G = torch.from_numpy(g["G"]).to(DEV)
-    res = []
-    was = lib().dgnn_train_set_aux_stream(0)
-    try:
-        for on in (0, 1, 1):
-            lib().dgnn_train_set_aux_stream(on)
-            net = hip_static(train=True)
-            (net(data) * G).sum().backward()
-            torch.cuda.synchronize()
-            res.append({k: p.grad.clone() for k, p in net.named_parameters()})
-    finally:
-        lib().dgnn_train_set_aux_stream(was)
-    for k in res[0]:
-        assert _same_grad(k, res[0][k], res[1][k]) and torch.equal(res[1][k], res[2][k]), k
 
 
 def test_block_builder_buffer_ring_gives_the_same_training_run():
