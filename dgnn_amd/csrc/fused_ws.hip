@@ -55,29 +55,45 @@ template <int CIN, int RING> struct WsL {
     static constexpr int OFF_BP = RING * WsC<CIN>::SLOT;
     static constexpr int OFF_ROWF = OFF_BP + WsC<CIN>::BP;          // [RING][32] inverse row scales
     static constexpr int OFF_CST = OFF_ROWF + RING * WS_TILE * 4;   // bias | scale | shift [128]
-    static constexpr int OFF_SC = OFF_CST + 3 * WS_C * 4;           // max |We|, |be|; then ready[RING], done[RING], ycnt[2], yfree[2], lcnt[2]
+    static constexpr int OFF_SC = OFF_CST + 3 * WS_C * 4;           // max |We|, |be|; then ready[RING], done[RING], ycnt[2], yfree[2], lcnt[2], ccnt[2]
     static constexpr int OFF_DC = OFF_SC + 16 + 2 * RING * 4 + 16 + 16;   // decoder constants: A1 | B1 [64], W3 [2][64], b3 [2] (+2 pad)
     static constexpr int OFF_PLOG = OFF_DC + (64 + 64 + 128 + 4) * 4;     // partial logits [2 tiles][4 hidden blocks][32 cells][2]
-    static constexpr int OFF_YS = OFF_PLOG + 2 * 4 * 32 * 8;              // inverse scales of the parked rows [2 tiles][8 slices][32 cells]
-    static constexpr int OFF_W0 = (OFF_YS + 2 * 8 * 32 * 4 + 255) & ~255; // W0 as A-operand fragments [4 hidden blocks][8 slices][64 lanes] x 16 B (hi x 4 | lo x 4)
-    static constexpr int OFF_YT = OFF_W0 + 4 * 8 * 64 * 16;               // the layer's finished tile as B-operand fragments [2 tiles][8 slices][2 blocks][64 lanes] x 16 B
+    static constexpr int OFF_YS = OFF_PLOG + 2 * 4 * 32 * 8;              // inverse scales of the parked tiles [2 tiles][32 cells]
+    static constexpr int OFF_CMAX = OFF_YS + 2 * 32 * 4;                  // largest exponent of a cell's 128 channels, tagged [4 tiles][32 cells]
+    static constexpr int OFF_W0S = OFF_CMAX + 4 * 32 * 4;                 // W0's scaling groups: max |W0| [4 hidden blocks], inverse scale [4]
+    static constexpr int OFF_W0 = (OFF_W0S + 32 + 255) & ~255;            // W0 as A-operand fragments [4 hidden blocks][4 k-steps][hi | lo][64 lanes] x 16 B
+    static constexpr int OFF_YT = OFF_W0 + 4 * 4 * 2 * 64 * 16;           // the layer's finished tile as B-operand fragments [2 tiles][4 k-steps][2 blocks][hi | lo][64 lanes] x 16 B
     static constexpr int SMEM = OFF_SC + 16 + 2 * RING * 4 + 16 + 16;
-    static constexpr int SMEM_DEC = OFF_YT + 2 * 8 * 2 * 64 * 16;
+    static constexpr int SMEM_DEC = OFF_YT + 2 * 4 * 2 * 2 * 64 * 16;
+    static_assert(SMEM_DEC <= 160 * 1024, "the LDS of one CU");
 };
 
 // the decoder behind the last conv layer (reference learning/surfaceNetStaticEdgeFilters.py:180-187, applied at :350-351): Linear(128 -> 64) - BatchNorm(eval) -
-// ReLU - Linear(64 -> 2).  In the DEC instantiation the consumers do not store the layer's rows.  Three stages, each one tile behind the one before it, so
+// ReLU - Linear(64 -> 2).  In the DEC instantiation the consumers do not store the layer's rows.  Four stages, each one tile behind the one before it, so
 // that no wavefront ever waits for data another one has only just produced (the first form of this kernel exchanged fp32 partial hidden rows of the SAME
 // tile -- three lock-step meetings of the eight consumers per tile, 1.1 us of a tile's 4.4):
-//   A(t)    consumer s: its 16 finished channels of the 32 cells, one power-of-two scale per cell and slice, split (hi, lo) -- a lane's 4 channels of one
-//           cell ARE a B-operand fragment of v_mfma_f32_16x16x16_f16 -- parked in LDS (16 bytes per lane and row block, linear);
-//   B(t-1)  job (hb, b) of 8: hidden units 16 hb .. + 15 of cells 16 b .. + 15 = 8 slices x 3 products against W0's fragments (LDS, laid out once per
-//           workgroup), every slice scaled back and added in slice order; BatchNorm / ReLU / W3 over the lane's 4 units, the 4 lanes of a cell added in
-//           one order: partial logits per cell and hidden block.  A tile's 8 jobs go to the 8 wavefronts of ONE role: the consumers on three tiles of
-//           four, the producers -- between issuing a tile's gathers and using them -- on the fourth (measured: producers always 0.54 ms, half 0.507,
-//           three of four 0.493, consumers always 0.525 on one box; the producers are the busier role but have the gather latency to fill);
-//   C(t-2)  consumer 0 adds the four partial logits of a cell in one order and stores 8 bytes per cell.
+//   A1(t)   consumer s keeps its 16 finished channels of the 32 cells in registers (yv, 8 VGPRs, alive for one iteration) and folds the largest exponent of
+//           each cell's 16 channels into cmax[t & 3][cell]: one LDS atomic unsigned max per lane and row block on the word (t / 4 + 1) << 8 | exponent.  The
+//           maximum does not depend on the order the eight consumers arrive in, the tag in the upper bits makes a tile's word beat whatever the buffer's
+//           previous tile left there (no clearing), and pow2_scales reads nothing but the exponent; then ccnt[t & 1] += 1;
+//   A2(t-1) waits for ccnt at 8 per tile, takes ONE power-of-two scale per cell from the word's low byte (the cell's 128 channels: every consumer derives
+//           the same scale), scales and splits (hi, lo) its yv and parks them as its share of the B operands of v_mfma_f32_16x16x32_f16: a k-step is 32
+//           channels = the slices of consumers 2 ks and 2 ks + 1, a fragment lane (cell n, group g) holds channels 32 ks + 8 g .. + 7, so consumer s, lane
+//           (n, tq) writes the 8 bytes [4 (tq & 1) .. + 3] of lane (n, g = 2 (s & 1) + (tq >> 1)) of k-step s >> 1, hi and lo fragments apart; consumer 0
+//           writes the cell's inverse scale (ysc); then ycnt[t & 1] += 1;
+//   B(t-2)  job (hb, b) of 8: hidden units 16 hb .. + 15 of cells 16 b .. + 15 = 4 k-steps x 3 products (lo.hi, hi.lo, hi.hi: small terms first, as in
+//           the consumers' loop) against W0's fragments (LDS, laid out once per workgroup, one power-of-two scale per hidden block), all twelve in ONE
+//           accumulator, scaled back once by the cell's and the hidden block's inverse scales; BatchNorm / ReLU / W3 over the lane's 4 units, the 4
+//           lanes of a cell added in one order: partial logits per cell and hidden block.  A tile's 8 jobs go to the 8 wavefronts of ONE role (see
+//           b_on_consumers): the producers, between issuing a tile's gathers and using them;
+//   C(t-3)  consumer 0 adds the four partial logits of a cell in one order and stores 8 bytes per cell.
 // Every sum has one order and touches one cell's values only (sub-ranges and ring parts give the same bits).
+// Why cmax has FOUR buffers and needs no wait: a consumer writes cmax[t & 3] for tile t + 4 only after its own A2(t + 2), which waited for all eight A1(t + 2);
+// a consumer that has run A1(t + 2) (iteration t + 3) has finished iteration t + 2 and with it A2(t), the last read of tile t's words.  With two buffers a
+// consumer one iteration ahead of the slowest (the ring allows that) could overwrite a word the slowest has not read yet.  The same argument shows that
+// every A1(t + 2) count lands in ccnt[t & 1] after that counter reached its target for tile t (the adder itself waited for it in A2(t)).
+// LDS banks: stage B reads every fragment as 64 lanes x 16 contiguous bytes (ds_read_b128: four groups of 16 lanes, each group's 64 dwords on 64 different
+// banks): conflict-free.  A2's 8-byte stores (16 lanes of one tq: the same half of 16 neighbouring 16-byte pieces) are 2-way, four stores per tile.
 struct WsDec {
     const float* W0;      // [64, 128]
     const float* b0;      // [64]
@@ -87,7 +103,6 @@ struct WsDec {
     const float* b3;      // [2]
     float* logits;        // [n_dst, 2]
 };
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
 
 
 __device__ __forceinline__ void st_nt16(float* p, f32x4_t v) { __builtin_nontemporal_store(v, reinterpret_cast<f32x4_t*>(p)); }
@@ -104,7 +119,7 @@ __device__ __forceinline__ uint32_t bits(float f) { return __builtin_bit_cast(ui
 
 // knobs (a launch argument, though every launch passes WS_KNOBS: with the value folded into the kernel the compiler schedules the loop differently and the
 // layers ran 4-5 % slower): bit 0 = non-temporal row stores, bits 4-5 = who runs the decoder's stage B (see b_on_consumers)
-constexpr int WS_KNOBS = 1 | (2 << 4);
+constexpr int WS_KNOBS = 1 | (0 << 4);
 template <int CIN, int RING, bool DEC, bool IO16 = false>
 __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src, const int32_t* __restrict__ eid,
                                                         int64_t n_dst, const float* __restrict__ x, const float* __restrict__ xdst, int64_t ldx,
@@ -132,12 +147,16 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
     volatile uint32_t* const done = ready + RING;
     // DEC: one counter per buffer (tile parity), like ready / done per ring slot.  A single running counter is NOT enough: a fast consumer's count for the
     // next tile can stand in for a slow consumer's count of this one wherever nothing else holds the fast one back (the first tiles, the drain)
-    volatile uint32_t* const ycnt = done + RING;          // [2] +1 per consumer whose 16 channels of a finished tile are parked (stage A)
-    volatile uint32_t* const yfree = ycnt + 2;            // [2] +1 per consumer that has read a parked tile (stage B)
-    volatile uint32_t* const lcnt = ycnt + 4;             // [2] +1 per consumer whose partial logits of a tile are parked (stage B)
+    volatile uint32_t* const ycnt = done + RING;          // [2] +1 per consumer whose 16 channels of a finished tile are parked (stage A2)
+    volatile uint32_t* const yfree = ycnt + 2;            // [2] +1 per wavefront that has read a parked tile (stage B)
+    volatile uint32_t* const lcnt = ycnt + 4;             // [2] +1 per wavefront whose partial logits of a tile are parked (stage B)
+    volatile uint32_t* const ccnt = ycnt + 6;             // [2] +1 per consumer whose exponents of a finished tile are in cmax (stage A1)
     float* const dcst = reinterpret_cast<float*>(ws_smem + L::OFF_DC);
     float* const plog = reinterpret_cast<float*>(ws_smem + L::OFF_PLOG);
     float* const ysc = reinterpret_cast<float*>(ws_smem + L::OFF_YS);
+    uint32_t* const cmax = reinterpret_cast<uint32_t*>(ws_smem + L::OFF_CMAX);
+    uint32_t* const w0max = reinterpret_cast<uint32_t*>(ws_smem + L::OFF_W0S);
+    float* const w0inv = reinterpret_cast<float*>(ws_smem + L::OFF_W0S + 16);
     char* const w0buf = ws_smem + L::OFF_W0;
     char* const ytile = ws_smem + L::OFF_YT;
     // wait until *ctr >= target (LDS word, wave-uniform): a short sleep between polls keeps the LDS and the issue slots for the working wavefronts
@@ -175,8 +194,20 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
             dcst[192 + n_] = dec.W3[64 + n_];
         }
         if (threadIdx.x < 2) dcst[256 + threadIdx.x] = dec.b3[threadIdx.x];
+        if (threadIdx.x < 4 * WS_TILE) cmax[threadIdx.x] = 0u;      // tag 0: below every tile's word
+        if (threadIdx.x < 4) w0max[threadIdx.x] = 0u;
     }
     __syncthreads();
+    if constexpr (DEC) {
+        // W0's scaling groups: the 16 rows of a hidden block (what one accumulator of stage B covers)
+#pragma unroll
+        for (int hb = 0; hb < 4; ++hb) {
+            uint32_t m0 = 0u;
+            for (int e = threadIdx.x; e < 16 * WS_C; e += blockDim.x) m0 = umax(m0, absbits(dec.W0[hb * 16 * WS_C + e]));
+            m0 = wave_umax(m0);
+            if ((threadIdx.x & 63) == 0) atomicMax(&w0max[hb], m0);
+        }
+    }
     {
         uint32_t me = 0u;
         for (int e = threadIdx.x; e < CIN * FE; e += blockDim.x) me = umax(me, absbits(We[e]));
@@ -225,25 +256,22 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
         wait_for(ycnt + (t & 1), 8u * (t / 2 + 1));
         int ln = lane;
         asm volatile("" : "+v"(ln));                            // (addresses recomputed per tile, see `key` below)
-        const char* yt = ytile + ((t & 1) << 14) + ((b * 64 + ln) << 4);
-        const char* wp = w0buf + ((hb * 512 + ln) << 4);
-        const float* sp = ysc + (t & 1) * 8 * WS_TILE + 16 * b + (ln & 15);
+        const char* yt = ytile + ((t & 1) << 14) + ((b * 128 + ln) << 4);       // [k-step: 4 KB][row block: 2 KB][hi | lo: 1 KB]
+        const char* wp = w0buf + ((hb * 512 + ln) << 4);                        // [hidden block: 8 KB][k-step: 2 KB][hi | lo: 1 KB]
+        const float inv = ysc[(t & 1) * WS_TILE + 16 * b + (ln & 15)] * w0inv[hb];
         f32x4_t hs = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const uint4 wa = *reinterpret_cast<const uint4*>(wp + (s << 10)), ya = *reinterpret_cast<const uint4*>(yt + (s << 11));
-            const float inv = sp[s * WS_TILE];
-            const f16x4_t w0h = __builtin_bit_cast(f16x4_t, make_uint2(wa.x, wa.y)), w0l = __builtin_bit_cast(f16x4_t, make_uint2(wa.z, wa.w));
-            const f16x4_t yh = __builtin_bit_cast(f16x4_t, make_uint2(ya.x, ya.y)), yl = __builtin_bit_cast(f16x4_t, make_uint2(ya.z, ya.w));
-            f32x4_t d = {0.f, 0.f, 0.f, 0.f};
-            d = __builtin_amdgcn_mfma_f32_16x16x16f16(w0l, yh, d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_16x16x16f16(w0h, yl, d, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_16x16x16f16(w0h, yh, d, 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) hs[i] += d[i] * inv;     // slices 0 .. 7 in order (the scale is a power of two: exact)
+        for (int s = 0; s < 4; ++s) {
+            const f16x8 w0h = H8(*reinterpret_cast<const uint4*>(wp + (s << 11))), w0l = H8(*reinterpret_cast<const uint4*>(wp + (s << 11) + 1024));
+            const f16x8 yh = H8(*reinterpret_cast<const uint4*>(yt + (s << 12))), yl = H8(*reinterpret_cast<const uint4*>(yt + (s << 12) + 1024));
+            hs = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0l, yh, hs, 0, 0, 0);     // small terms first
+            hs = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0h, yl, hs, 0, 0, 0);
+            hs = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0h, yh, hs, 0, 0, 0);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (lane == 0) atomicAdd(const_cast<uint32_t*>(yfree + (t & 1)), 1u);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hs[i] *= inv;                // one scale per cell and hidden block, powers of two: exact
         const int u0 = 16 * hb + 4 * (ln >> 4);
         float l0 = 0.f, l1 = 0.f;
 #pragma unroll
@@ -252,18 +280,18 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
             l0 = __fmaf_rn(hv, dcst[128 + u0 + i], l0);
             l1 = __fmaf_rn(hv, dcst[192 + u0 + i], l1);
         }
-        // the cell's 4 lanes (16 apart): (q0 + q1) + (q2 + q3) in every one of them
-        l0 += __shfl_xor(l0, 16);
-        l1 += __shfl_xor(l1, 16);
-        l0 += __shfl_xor(l0, 32);
-        l1 += __shfl_xor(l1, 32);
+        // the cell's 4 lanes (16 apart): (q0 + q1) + (q2 + q3) in every one of them, on the row-swap instructions (no LDS round trips)
+        l0 = cross_row_sum(l0);
+        l1 = cross_row_sum(l1);
         if (ln < 16) *reinterpret_cast<float2*>(plog + (((t & 1) * 4 + hb) * WS_TILE + 16 * b + ln) * 2) = make_float2(l0, l1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (lane == 0) atomicAdd(const_cast<uint32_t*>(lcnt + (t & 1)), 1u);
     };
 
     // who runs stage B of tile t: every wavefront of one role takes one of the tile's 8 jobs.  (knobs bits 4-5: 0 = producers always, 1 = consumers on even
-    // tiles, 2 = consumers on three tiles of four, 3 = consumers always)
+    // tiles, 2 = consumers on three tiles of four, 3 = consumers always.  With the K = 16 products and a scale per slice, 2 was the best; with half the
+    // products, one scale per cell and the consumers carrying A1 / A2, the job is cheapest between a producer's gathers and their use: 0 -- measured
+    // 0.472 / 0.495 / 0.510 / 0.524 ms for 0 / 1 / 2 / 3, profiles/r08_dec_cellscale.md)
     const int bsel = (knobs >> 4) & 3;
     auto b_on_consumers = [&](uint32_t t) { return bsel == 0 ? false : bsel == 1 ? (t & 1) == 0 : bsel == 2 ? (t & 3) != 3 : true; };
 
@@ -295,37 +323,37 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
             wh[s] = pack8h(ph);
             wl[s] = pack8h(pl);
         }
-        // DEC: W0[:, 16 cw .. 16 cw + 15] (slice cw) as A-operand fragments of v_mfma_f32_16x16x16_f16, for everybody: lane (m = jcol, kg = tq) of hidden block hb
-        // holds hidden unit 16 hb + m, channels 16 cw + 4 kg .. + 3; one power-of-two scale per slice
-        float inv_sW0 = 1.f;
+        // DEC: W0 as A-operand fragments of v_mfma_f32_16x16x32_f16, for everybody: lane (m = jcol, g = tq) of hidden block hb and k-step ks holds hidden
+        // unit 16 hb + m, channels 32 ks + 8 g .. + 7, hi and lo fragments apart.  This consumer lays out k-step cw >> 1 of hidden blocks 2 (cw & 1), + 1.
         if constexpr (DEC) {
-            uint32_t m0 = 0u;
-            f32x4_t raw[4];
 #pragma unroll
-            for (int hb = 0; hb < 4; ++hb) {
-                raw[hb] = *reinterpret_cast<const f32x4_t*>(dec.W0 + (int64_t)(16 * hb + jcol) * WS_C + 16 * cw + 4 * tq);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) m0 = umax(m0, absbits(raw[hb][i]));
-            }
-            float sW0;
-            pow2_scales(wave_umax(m0), sW0, inv_sW0);
-#pragma unroll
-            for (int hb = 0; hb < 4; ++hb) {
-                uint32_t ph[2], pl[2];
-                split2h(raw[hb][0] * sW0, raw[hb][1] * sW0, ph[0], pl[0]);
-                split2h(raw[hb][2] * sW0, raw[hb][3] * sW0, ph[1], pl[1]);
-                *reinterpret_cast<uint4*>(w0buf + (((hb * 8 + cw) * 64 + lane) << 4)) = make_uint4(ph[0], ph[1], pl[0], pl[1]);
+            for (int u = 0; u < 2; ++u) {
+                const int hb = 2 * (cw & 1) + u, ks = cw >> 1;
+                float sW0, inv_sW0;
+                pow2_scales(w0max[hb], sW0, inv_sW0);
+                if (ks == 0 && lane == 0) w0inv[hb] = inv_sW0;
+                const float* wr = dec.W0 + (int64_t)(16 * hb + jcol) * WS_C + 32 * ks + 8 * tq;
+                const f32x4_t r0 = *reinterpret_cast<const f32x4_t*>(wr), r1 = *reinterpret_cast<const f32x4_t*>(wr + 4);
+                uint32_t ph[4], pl[4];
+                split2h(r0[0] * sW0, r0[1] * sW0, ph[0], pl[0]);
+                split2h(r0[2] * sW0, r0[3] * sW0, ph[1], pl[1]);
+                split2h(r1[0] * sW0, r1[1] * sW0, ph[2], pl[2]);
+                split2h(r1[2] * sW0, r1[3] * sW0, ph[3], pl[3]);
+                uint4* dst = reinterpret_cast<uint4*>(w0buf + (((hb * 4 + ks) * 128 + lane) << 4));
+                dst[0] = make_uint4(ph[0], ph[1], ph[2], ph[3]);
+                dst[64] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
             }
         }
         __syncthreads();   // (the producers' prologue barrier)
         const int c0 = 16 * cw + 4 * tq;          // this lane's 4 consecutive output channels
-        const int64_t n_it = my_n + (DEC ? 2 : 0);       // DEC: stage B runs one tile behind the product, stage C two
+        const int64_t n_it = my_n + (DEC ? 3 : 0);       // DEC: stage A2 runs one tile behind the product, stage B two, stage C three
+        f32x4_t yp[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, yn[2] = {yp[0], yp[1]};     // DEC: the previous tile's finished channels, between A1 and A2
         for (int64_t it = 1; it <= n_it; ++it) {
             if constexpr (DEC) {
-                // C(it - 3): consumer 0 adds the four partial logits of a cell in one order and stores them.  (First in the iteration: the others' B(it - 1)
-                // -- next iteration -- reuses this buffer, and they get there only behind this wavefront's A(it - 1) below.)
-                if (cw == 0 && it >= 3) {
-                    const uint32_t t = (uint32_t)(it - 3);
+                // C(it - 4): consumer 0 adds the four partial logits of a cell in one order and stores them.  (First in the iteration: the others' B(it - 2)
+                // -- next iteration -- reuses this buffer, and they get there only behind this wavefront's A2(it - 2) below.)
+                if (cw == 0 && it >= 4) {
+                    const uint32_t t = (uint32_t)(it - 4);
                     wait_for(lcnt + (t & 1), 8u * (t / 2 + 1));
                     if (lane < WS_TILE) {
                         float s0 = dcst[256], s1 = dcst[257];
@@ -411,29 +439,46 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
                         }
                     }
                 } else {
-                    // A(it - 1): this consumer's 16 channels of the tile, one scale per cell and slice (the cell's 4 lanes are 16 apart), parked as B-operand
-                    // fragments; the buffer's previous tile (two back) has been read by everybody
+                    // A1(it - 1): the largest exponent of this lane's 4 channels of each cell into the cell's word (header comment: tag, four buffers)
                     const uint32_t t = (uint32_t)(it - 1);
-                    wait_for(yfree + (t & 1), 8u * (t / 2));
-                    char* yt = ytile + ((t & 1) << 14) + ((cw * 128 + lane) << 4);
-                    float* ys = ysc + ((t & 1) * 8 + cw) * WS_TILE + jcol;
+                    uint32_t* cm = cmax + (t & 3) * WS_TILE + jcol;
 #pragma unroll
                     for (int b = 0; b < 2; ++b) {
                         const float my = fmaxf(fmaxf(fabsf(yv[b][0]), fabsf(yv[b][1])), fmaxf(fabsf(yv[b][2]), fabsf(yv[b][3])));
+                        atomicMax(cm + 16 * b, ((t / 4 + 1) << 8) | (bits(my) >> 23));
+                    }
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if (lane == 0) atomicAdd(const_cast<uint32_t*>(ccnt + (t & 1)), 1u);
+                    yn[0] = yv[0], yn[1] = yv[1];
+                }
+            }
+            if constexpr (DEC) {
+                if (it >= 2 && it <= my_n + 1) {
+                    // A2(it - 2): all eight consumers' exponents of the tile are in; the buffer's previous tile (two back) has been read by everybody.
+                    // One scale per cell (an all-zero cell: exponent 0 -> a finite scale, zeros parked, inverse scale 0)
+                    const uint32_t t = (uint32_t)(it - 2);
+                    wait_for(ccnt + (t & 1), 8u * (t / 2 + 1));
+                    wait_for(yfree + (t & 1), 8u * (t / 2));
+                    int ln = lane;
+                    asm volatile("" : "+v"(ln));
+                    const uint32_t* cm = cmax + (t & 3) * WS_TILE + (ln & 15);
+                    char* yt = ytile + ((t & 1) << 14) + ((cw >> 1) << 12) + (((ln & 15) + 16 * (2 * (cw & 1) + (ln >> 5))) << 4) + (((ln >> 4) & 1) << 3);
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
                         float sY, inv_sY;
-                        pow2_scales(cross_row_umax(bits(my)), sY, inv_sY);
+                        pow2_scales((cm[16 * b] & 255u) << 23, sY, inv_sY);
                         uint32_t ph[2], pl[2];
-                        split2h(yv[b][0] * sY, yv[b][1] * sY, ph[0], pl[0]);
-                        split2h(yv[b][2] * sY, yv[b][3] * sY, ph[1], pl[1]);
-                        *reinterpret_cast<uint4*>(yt + (b << 10)) = make_uint4(ph[0], ph[1], pl[0], pl[1]);
-                        if (tq == 0) ys[16 * b] = inv_sY * inv_sW0;
+                        split2h(yp[b][0] * sY, yp[b][1] * sY, ph[0], pl[0]);
+                        split2h(yp[b][2] * sY, yp[b][3] * sY, ph[1], pl[1]);
+                        *reinterpret_cast<uint2*>(yt + (b << 11)) = make_uint2(ph[0], ph[1]);
+                        *reinterpret_cast<uint2*>(yt + (b << 11) + 1024) = make_uint2(pl[0], pl[1]);
+                        if (cw == 0 && ln < 16) ysc[(t & 1) * WS_TILE + 16 * b + ln] = inv_sY;
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     if (lane == 0) atomicAdd(const_cast<uint32_t*>(ycnt + (t & 1)), 1u);
                 }
-            }
-            if constexpr (DEC) {
-                if (it >= 2 && it <= my_n + 1 && b_on_consumers((uint32_t)(it - 2))) stage_b((uint32_t)(it - 2), cw & 3, cw >> 2);
+                yp[0] = yn[0], yp[1] = yn[1];
+                if (it >= 3 && it <= my_n + 2 && b_on_consumers((uint32_t)(it - 3))) stage_b((uint32_t)(it - 3), cw & 3, cw >> 2);
             }
         }
         return;
@@ -473,10 +518,11 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
     load_rp(1, vb2);
     load_idx(0, vb1, reg1, vsrc1, veid1);
 
-    // DEC: on the tiles the rule gives to the producers (b_on_consumers) this wavefront also runs stage B of tile it - 2 (hidden block p & 3 of row block
-    // p >> 2) -- BETWEEN issuing its gathers for tile `it` and using them: the job fills the gather latency, and its data (the consumers' stage A of tile
-    // it - 2) is complete about when the slot the producer is going to write is handed back anyway.  Two more iterations drain the last two tiles.
-    for (int64_t it = 0; it < my_n + (DEC ? 2 : 0); ++it) {
+    // DEC: on the tiles the rule gives to the producers (b_on_consumers) this wavefront also runs stage B of tile it - 3 (hidden block p & 3 of row block
+    // p >> 2) -- BETWEEN issuing its gathers for tile `it` and using them: the job fills the gather latency, and its data (the consumers' stage A2 of tile
+    // it - 3, behind their product of tile it - 2) is complete about when the slot the producer is going to write is handed back anyway.  Three more
+    // iterations drain the last three tiles.
+    for (int64_t it = 0; it < my_n + (DEC ? 3 : 0); ++it) {
         int nv = 0, sl = 0, tl = 0, vsrc = 0, veid = 0;
         bool regular = false;
         f32x4_t xo[NV], q0, q1, rr[4][NV];              // the gathered rows (DEC: in flight across stage B); read only on the path that loaded them
@@ -540,7 +586,7 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
                 own_row();
                 if (regular) neighbour_rows();
             }
-            if (it >= 2 && !b_on_consumers((uint32_t)(it - 2))) stage_b((uint32_t)(it - 2), p & 3, p >> 2);
+            if (it >= 3 && !b_on_consumers((uint32_t)(it - 3))) stage_b((uint32_t)(it - 3), p & 3, p >> 2);
         }
         if (it < my_n) {
             if (nv > 0) {
