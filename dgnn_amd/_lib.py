@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DGNN_LIB_PATH: another build of the same library (e.g. for whole-library A/B measurements, tools/gpu_ab_libs.sh) -- never a fallback
 LIB_PATH = os.environ.get("DGNN_LIB_PATH") or os.path.join(_HERE, "libdgnn_hip.so")
 
-i64, i32, f32, vp = C.c_int64, C.c_int, C.c_float, C.c_void_p
+i64, i32, f32, f64, vp = C.c_int64, C.c_int, C.c_float, C.c_double, C.c_void_p
 
 # name -> (restype, argtypes); mirrors include/dgnn_hip.h one to one
 SIGNATURES = {
@@ -74,6 +74,8 @@ SIGNATURES = {
     "dgnn_fill_i32": (i32, [vp, i64, i32, vp]),
     "dgnn_standardize_scratch_doubles": (i64, [i32]),
     "dgnn_standardize_f64": (i32, [vp, i64, i64, i32, i32, vp, i64, vp, vp]),
+    "dgnn_scale_features_scratch_bytes": (i64, [i32]),
+    "dgnn_scale_features_f64": (i32, [vp, i64, i64, i32, i32, i32, f64, f64, i32, i32, i32, i32, i32, f64, i32, i32, vp, i64, vp, vp, vp]),
     "dgnn_cell_centroids_scratch_elems": (i64, [i64]),
     "dgnn_cell_centroids_3dt": (i32, [vp, i64, vp, i64, vp, vp, i64, i64, i64, vp, vp, vp]),
     "dgnn_cell_order_morton_scratch_elems": (i64, [i64]),

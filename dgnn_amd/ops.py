@@ -1875,3 +1875,47 @@ def mesh_topology(faces, n_vertices):
     out = dict(zip(MESH_TOPOLOGY_KEYS, (int(c) for c in counts.cpu())))
     out["watertight"] = int(k > 0 and out["boundary_edges"] == 0 and out["nonmanifold_edges"] == 0 and out["nonmanifold_vertices"] == 0)
     return out
+
+
+# ---- ingest: feature scaling (csrc/ingest.hip) ------------------------------------------------------------------------------------
+SCALE_KINDS = {"none": 0, "standard": 1, "minmax": 2, "robust": 3}
+
+
+def _col_range(r, c, name):
+    if r is None:
+        return 0, 0
+    a, b = int(r[0]), int(r[1])
+    if not 0 <= a <= b <= c:
+        raise ValueError("%s=%r outside the frame's columns [0, %d]" % (name, r, c))
+    return a, b
+
+
+@on_device_of
+def scale_features(x64, c_first: int, kind: str, feature_range=(0, 1), sum_cols=None, div_col=None, div_cols=None, div_scalar=None, scalar_cols=None,
+                   return_stats=False):
+    """fp64 [n, c] frame (rows may be strided) -> fp32 [n, c]: the reference's feature scaling (processing/data.py:444-506 + the float32 cast).
+    Pre-steps, in this order, in fp64, each over a column range (c0, c1) or None: `sum_cols` x*1000/colsum; `div_cols` x/(x[:, div_col] + 1e-4)
+    with the divisor taken after the sum step; `scalar_cols` x/div_scalar.  Then the scaler `kind` -- "none", "standard", "minmax" (onto
+    `feature_range`) or "robust" -- fitted on the pre-transformed columns >= c_first; columns below are only pre-transformed and cast.
+    return_stats: -> (out, stats fp64 [2, c]): what was subtracted and what was divided by (minmax: data_min and the zero-handled range)."""
+    _req(x64, "x64", torch.float64, dim=2)
+    if kind not in SCALE_KINDS:
+        raise ValueError("kind=%r: one of %s" % (kind, sorted(SCALE_KINDS)))
+    n, c = x64.shape
+    if n < 1 or c < 1 or not 0 <= int(c_first) <= c:
+        raise ValueError("scale_features: frame %s, c_first %r" % (tuple(x64.shape), c_first))
+    s0, s1 = _col_range(sum_cols, c, "sum_cols")
+    d0, d1 = _col_range(div_cols, c, "div_cols")
+    k0, k1 = _col_range(scalar_cols, c, "scalar_cols")
+    if d0 < d1 and (div_col is None or not 0 <= int(div_col) < c):
+        raise ValueError("div_cols needs div_col in [0, %d), got %r" % (c, div_col))
+    if k0 < k1 and div_scalar is None:
+        raise ValueError("scalar_cols needs div_scalar")
+    dev = x64.device
+    out = torch.empty((n, c), dtype=torch.float32, device=dev)
+    stats = torch.empty((2, c), dtype=torch.float64, device=dev) if return_stats else None
+    scratch = torch.empty(int(lib().dgnn_scale_features_scratch_bytes(c)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_scale_features_f64(ptr(x64), _ld(x64), n, c, int(c_first), SCALE_KINDS[kind], float(feature_range[0]), float(feature_range[1]),
+                                        s0, s1, int(div_col or 0), d0, d1, float(div_scalar if div_scalar is not None else 1.0), k0, k1,
+                                        ptr(out), c, ptr(stats), ptr(scratch), stream_ptr()), "dgnn_scale_features_f64")
+    return (out, stats) if return_stats else out

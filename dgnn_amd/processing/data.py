@@ -5,8 +5,13 @@
 ``readNodeData_bin`` (:194-284) and ``readEdgeData_bin`` (:353-414) do (same order, same 'last'-column drops, the
 un-scaled ``reg_<cell_type>`` copy in column 0), and leaves ``features`` [N, 1+F] fp32, ``edge_features`` [E, F_e]
 fp32, ``edge_lists`` int64 [2,E], ``gt``, ``infinite`` ON THE GPU.  Column selection is host-side bookkeeping on
-numpy arrays (no pandas); the per-scene StandardScaler (:471-506) runs on the device in fp64
-(dgnn_standardize_f64).  Only scaling 's' (all shipped configs) is implemented; others exit like the reference.
+numpy arrays (no pandas); the per-scene feature scaling (standardizeFeatures, :444-506) runs on the device in fp64.
+
+Scaling: ``scaling_plan`` restates the reference's decision tree line by line -- the 'sum' and 'edge' pre-scalings, the row-wise
+division by a normalisation feature, then StandardScaler ('s'), MinMaxScaler over ``normalization_range`` ('n') or RobustScaler ('r')
+-- and ``scale_features`` runs it (dgnn_scale_features_f64: exact column order statistics by radix selection for 'r').  Plain
+scaling 's' without a normalisation feature, which every shipped config uses, keeps dgnn_standardize_f64.  What the reference cannot
+run stops the same way: 'vol' exits, no valid scaler is an AttributeError, a normalisation feature without its column a KeyError.
 
 Cell order (round 4): the reference builds ``edge_index`` straight from the file (:434-438), i.e. in CGAL's insertion order -- the 4
 neighbours of a cell are tens of thousands of rows apart and every neighbour gather of the conv layers misses L2.  ``run`` relabels the cells
@@ -37,6 +42,74 @@ def standardize(cols64: np.ndarray, c_first: int, device) -> torch.Tensor:
         scratch = torch.empty(int(lib().dgnn_standardize_scratch_doubles(c)), dtype=torch.float64, device=device)
         check(lib().dgnn_standardize_f64(ptr(x), c, n, c, c_first, ptr(out), c, ptr(scratch), stream_ptr()), "dgnn_standardize_f64")
     return out
+
+
+def scale_features(cols64: np.ndarray, c_first: int, kind: str, device, **steps) -> torch.Tensor:
+    """[N,C] float64 (host) -> fp32 [N,C] on `device` through ops.scale_features: the pre-steps `steps` (sum_cols, div_col, div_cols,
+    div_scalar, scalar_cols, feature_range), then the scaler `kind` fitted on columns >= c_first."""
+    with torch.cuda.device(device):
+        return ops.scale_features(torch.from_numpy(np.ascontiguousarray(cols64)).to(device), c_first, kind, **steps)
+
+
+def _scale(cols64, plan, device):
+    plan = dict(plan)
+    c_first, kind = plan.pop("c_first"), plan.pop("kind")
+    if kind == "standard" and not plan:
+        return standardize(cols64, c_first, device)          # plain 's' (every shipped config): the kernels and the bits it always had
+    return scale_features(cols64, c_first, kind, device, **plan)
+
+
+def _c_first(reg_type, kind, plan):
+    """The reference fits the scaler on columns 1: when the regularisation column `is not None` (:485, :501), while the un-scaled reg_
+    copy is inserted when it is truthy (_node_columns / _edge_columns): under '' or 0 it leaves the first real feature unscaled.  The new
+    routes mirror that; plain 's' keeps the test it always had here, the one that inserts the copy."""
+    plain = kind == "standard" and set(plan) <= {"c_first", "kind"}
+    return int(bool(reg_type) if plain else reg_type is not None)
+
+
+def scaling_plan(clf, node_names, edge_names, n_node_cols, n_edge_cols, mean_edge, read_edge_features):
+    """The reference's standardizeFeatures (processing/data.py:446-506), line by line, as the arguments of scale_features for the node
+    frame and for the edge frame (None when the model reads no edge features).  Like the reference it asks `in` of whatever the YAML
+    gave -- a string or a list -- so the string "sum" also selects the StandardScaler ('s' in "sum") and the list ['sum'] does not."""
+    f, reg = clf.features, clf.regularization
+    scaling = f.scaling
+    node = dict(c_first=0, kind="none")
+    edge = dict(c_first=0, kind="none")
+    done = lambda: (node, edge if read_edge_features else None)
+    if not scaling:                                                    # run(): no scaling key, no standardizeFeatures -- the cast alone
+        return done()
+    if "sum" in scaling:                                               # :446-452  columns 1: only under a truthy normalisation feature,
+        node["sum_cols"] = (1 if f.node_normalization_feature else 0, n_node_cols)          # else the loss-weight column too
+        edge["sum_cols"] = (0, n_edge_cols)
+    if "vol" in scaling:                                               # :454-459  exits without a normalisation feature and fails on
+        print("scaling 'vol' is not supported by dgnn_amd: the reference cannot run it either (DataFrame.norm)")          # DataFrame.norm with one
+        sys.exit(1)
+    if f.node_normalization_feature is not None:                       # :461-465  columns 1: by the ORIGINAL column named cell_type
+        if reg.cell_type is None:                                      # (not its reg_ copy); that column itself becomes v/(v+1e-4)
+            raise KeyError("None (node_normalization_feature divides by the column regularization.cell_type names; cell_type is unset)")
+        node["div_col"], node["div_cols"] = node_names.index(reg.cell_type), (1, n_node_cols)
+    if "edge" in scaling:                                              # :467-468  the whole node frame, column 0 included
+        node["div_scalar"], node["scalar_cols"] = mean_edge, (0, n_node_cols)
+    if "s" in scaling:                                                 # :471-483
+        kind = "standard"
+    elif "n" in scaling:
+        kind = "minmax"
+        node["feature_range"] = edge["feature_range"] = tuple(f.normalization_range)          # :474  read under 'n' alone
+    elif "r" in scaling:
+        kind = "robust"
+    elif "sum" not in scaling:                                         # the reference dies on self.clf.feature_scaling while it formats its message
+        raise AttributeError("feature_scaling (%r are no valid scalers: choose 'sum', 's', 'n' or 'r')" % (scaling,))
+    else:
+        return done()                                                  # ['sum']: returns before the edge frame's normalisation and scaler
+    node["kind"], node["c_first"] = kind, _c_first(reg.cell_type, kind, node)          # :485-491
+    if not read_edge_features:
+        return done()
+    if f.edge_normalization_feature is not None:                       # :495-499
+        if reg.edge_type is None:
+            raise KeyError("None (edge_normalization_feature divides by the column regularization.edge_type names; edge_type is unset)")
+        edge["div_col"], edge["div_cols"] = edge_names.index(reg.edge_type), (1, n_edge_cols)
+    edge["kind"], edge["c_first"] = kind, _c_first(reg.edge_type, kind, edge)          # :501-506
+    return done()
 
 
 class dataLoader:
@@ -124,20 +197,17 @@ class dataLoader:
         # the reference's own layout (:437-438): the [E,2] array on the device, handed on as its transposed view (strides (1,2)) -- read in place by the
         # plan builder, whose four-lanes-per-cell pass takes exactly this view
         self.edge_lists = torch.from_numpy(np.ascontiguousarray(adj.astype(np.int64))).to(dev).t()
-        scaling = self.clf.features.scaling
-        if scaling != "s" or self.clf.features.node_normalization_feature is not None \
-                or self.clf.features.edge_normalization_feature is not None:
-            # every shipped config (configs/*.yaml:2-7) uses scaling 's' and no normalisation feature
-            print("scaling {!r} / normalization features are not supported by dgnn_amd; use scaling: s".format(scaling))
-            sys.exit(1)
-        c_first = 1 if self.clf.regularization.cell_type else 0
-        self.features = standardize(nodes, c_first, dev)
-        if self.read_edge_features:
+        read_edges = bool(self.read_edge_features)
+        if read_edges:
             self.edge_feature_names, edges = self._edge_columns(base)
             assert adj.shape[0] == edges.shape[0]
-            self.edge_features = standardize(edges, 1 if self.clf.regularization.edge_type else 0, dev)
         else:
-            self.edge_features = torch.empty(1, 1, dtype=torch.float32, device=dev)
+            self.edge_feature_names, edges = [], np.empty((0, 0))
+        # the reference's decision tree, taken before anything is scaled: a config it cannot run stops here as it stops there
+        node_plan, edge_plan = scaling_plan(self.clf, self.node_feature_names, self.edge_feature_names, nodes.shape[1], edges.shape[1],
+                                            self.mean_edge, read_edges)
+        self.features = _scale(nodes, node_plan, dev)
+        self.edge_features = _scale(edges, edge_plan, dev) if read_edges else torch.empty(1, 1, dtype=torch.float32, device=dev)
         self.n_nodes += self.features.size(0)
         self.cell_order = None
         kind = str(getattr(self.clf.temp, "cell_order", None) or os.environ.get("DGNN_CELL_ORDER", "auto")).lower()

@@ -933,6 +933,23 @@ int dgnn_standardize_f64(const double* x, int64_t ld, int64_t n, int c, int c_fi
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Feature scaling with the reference's pre-steps and all of its scalers (processing/data.py:444-506, then the float32 cast).
+ * Every pass reads v = the pre-transformed value, in fp64, in this order (an empty column range c0 >= c1 switches a step off):
+ *   sum     v = (x*1000)/colsum             columns [sum_c0, sum_c1)
+ *   div     v = v/(x[row, div_col] + 1e-4)  columns [div_c0, div_c1); the divisor is taken after `sum`, before `div`
+ *   scalar  v = v/div_scalar                columns [sc_c0, sc_c1)
+ * kind (fitted on columns >= c_first; columns below are pre-transformed and cast): 0 none, 1 standard (StandardScaler),
+ * 2 minmax (MinMaxScaler onto [range_lo, range_hi]), 3 robust (RobustScaler: exact median and quartiles by radix selection,
+ * numpy's linear quantile rule).  A scale below 10 eps becomes 1.  stats (optional, device fp64 [2][c]): what was subtracted and
+ * what was divided by (minmax: data_min and the zero-handled data_range; columns < c_first: 0 and 1).  Non-finite inputs are out
+ * of scope.  n < 2^32.  Integer counts only: reruns are bit-identical.  scratch: dgnn_scale_features_scratch_bytes(c) bytes.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_scale_features_scratch_bytes(int c);
+int dgnn_scale_features_f64(const double* x, int64_t ld, int64_t n, int c, int c_first, int kind, double range_lo, double range_hi,
+                            int sum_c0, int sum_c1, int div_col, int div_c0, int div_c1, double div_scalar, int sc_c0, int sc_c1,
+                            float* out, int64_t ldo, double* stats, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Ingest-time cell locality order (sits where the reference builds edge_index, processing/data.py:434-438).
  * CGAL writes the cells in insertion order (the 4 neighbours of a cell are tens of thousands of rows apart); the loader relabels them once
  * per scene so that the conv layers' neighbour gathers hit L2, and keeps the permutation for the places where per-cell results leave
