@@ -71,6 +71,7 @@ SIGNATURES = {
     "dgnn_sage_aggregate_bwd": (i32, [vp, vp, vp, i64, vp, vp, i64, i32, vp, i64, i32, vp, vp, vp, i64, vp, i64, vp, i64,
                                       vp, vp, vp, i64, vp, vp]),
     "dgnn_debug_trace_buffer": (i32, [vp, i64]),
+    "dgnn_debug_last_linear_variant": (i32, []),
     "dgnn_fill_i32": (i32, [vp, i64, i32, vp]),
     "dgnn_standardize_scratch_doubles": (i64, [i32]),
     "dgnn_standardize_f64": (i32, [vp, i64, i64, i32, i32, vp, i64, vp, vp]),

@@ -1888,6 +1888,9 @@ int wgrad_splits(int64_t M, int n_a = 0) {
     return (int)(s < 1 ? 1 : s);
 }
 
+// the kernel this thread's last forward call chose (dgnn_debug_last_linear_variant): a host-side record, set where the entry points choose
+thread_local int last_linear_variant = DGNN_LINEAR_VARIANT_NONE;
+
 // p may be read by 16-byte loads along rows of ld elements
 bool vec16(const void* p, int64_t ld_elems, size_t elem) { return ((uintptr_t)p % 16 == 0) && ((ld_elems * (int64_t)elem) % 16 == 0); }
 
@@ -1925,6 +1928,7 @@ struct FwdArgs {
 template <typename TA>
 int fwd_validate(FwdArgs<TA>& a, bool* empty) {
     *empty = true;
+    last_linear_variant = DGNN_LINEAR_VARIANT_NONE;
     DGNN_REQUIRE(a.M >= 0 && a.n_out > 0 && a.k1 > 0, DGNN_E_INVALID, "%s: bad sizes M=%lld n_out=%d k1=%d", a.name, (long long)a.M, a.n_out, a.k1);
     if (a.M == 0) return DGNN_OK;
     DGNN_REQUIRE(a.A1 && a.W1 && a.out, DGNN_E_INVALID, "%s: null pointer", a.name);
@@ -1965,6 +1969,7 @@ extern "C" int dgnn_linear_fwd(const float* A1, int64_t lda1, int k1, const floa
     FwdArgs<float> a{"linear_fwd", A1, lda1, k1, W1, ldw1, A2, lda2, k2, W2, ldw2, bias, scale, shift, relu, M, n_out, out, ldo, (hipStream_t)stream};
     bool empty;
     if (const int rc = fwd_validate(a, &empty); rc != DGNN_OK || empty) return rc;
+    last_linear_variant = DGNN_LINEAR_VARIANT_F32;
     launch(k_linear_fwd, a.tiles(BM, BN), 256, 0, a);
     return dgnn_check_launch(a.name);
 }
@@ -2008,6 +2013,7 @@ extern "C" int dgnn_linear_fwd_bf16(const uint16_t* A1, int64_t lda1, int k1, co
         constexpr size_t lds1 = (size_t)(64 + 64) * LDB;
         static_assert(4 * lds1 >= 3 * 4 * 16 * 64 * sizeof(float), "the groups' partial blocks fit the chunk buffers");
         const bool ks4 = ks_ok && K >= 1024 && tiles64 <= 2 * DGNN_NUM_CU;
+        last_linear_variant = ks4 ? DGNN_LINEAR_VARIANT_B_MID4 : DGNN_LINEAR_VARIANT_B_MID1;
         by_storage(out_f32, [&](auto to) {
             using TO = decltype(to);
             if (ks4) {
@@ -2019,10 +2025,13 @@ extern "C" int dgnn_linear_fwd_bf16(const uint16_t* A1, int64_t lda1, int k1, co
             }
         });
     } else if (small_ok && !tiles_fill && splitk_ok && M <= 16384 && K >= 1024) {   // four wavefronts per output block, a quarter of K each (see the kernel)
+        last_linear_variant = DGNN_LINEAR_VARIANT_B_SMALL_SPLITK;
         by_storage(out_f32, [&](auto to) { launch<decltype(to)>(k_linear_fwd_b_small<decltype(to), true>, tiles32, 256, 0, a); });
     } else if (small_ok && !tiles_fill && M <= 16384) {   // same k order per output element: identical results
+        last_linear_variant = DGNN_LINEAR_VARIANT_B_SMALL;
         by_storage(out_f32, [&](auto to) { launch<decltype(to)>(k_linear_fwd_b_small<decltype(to)>, dgnn_cdiv(tiles32, 4), 256, 0, a); });
     } else {
+        last_linear_variant = DGNN_LINEAR_VARIANT_B;
         by_storage(out_f32, [&](auto to) { launch<decltype(to)>(k_linear_fwd_b<decltype(to)>, tiles128, 256, 0, a); });
     }
     return dgnn_check_launch(a.name);
@@ -2073,6 +2082,7 @@ int linear_fwd_x3_impl(FwdArgs<float> a, double* colstats) {
         static bool attr_set[DGNN_MAX_DEVICES];
         constexpr size_t lds = (size_t)(YM + YN) * XLD;
         dgnn_allow_dynamic_lds((const void*)k_linear_fwd_x3_big, lds, attr_set);
+        last_linear_variant = DGNN_LINEAR_VARIANT_X3_BIG;
         launch(k_linear_fwd_x3_big, a.tiles_xcd(YM, YN), YT, lds, a);
     } else if (mid_ok && !tiles_fill && M <= small_m && n_out > ZN && K >= 512 && tiles64 >= 128) {
         // ... and between the two: 64 x 64 tiles when THEY fill the chip and the inner dimension is long enough for the operand re-reads of the
@@ -2081,18 +2091,25 @@ int linear_fwd_x3_impl(FwdArgs<float> a, double* colstats) {
         if (ks_ok && K >= 1024 && tiles64 <= 2 * DGNN_NUM_CU) {
             static bool attr_set[DGNN_MAX_DEVICES];
             dgnn_allow_dynamic_lds((const void*)k_linear_fwd_x3_mid<4>, 4 * lds1, attr_set);
+            last_linear_variant = DGNN_LINEAR_VARIANT_X3_MID4;
             launch(k_linear_fwd_x3_mid<4>, a.tiles_xcd(64, 64), 1024, 4 * lds1, a, colstats);
         } else {
+            last_linear_variant = DGNN_LINEAR_VARIANT_X3_MID1;
             launch(k_linear_fwd_x3_mid<1>, a.tiles_xcd(64, 64), 256, lds1, a, colstats);
         }
     } else if (small_ok && !tiles_fill && M <= small_m) {
-        if (splitk_ok && K >= 1024)
+        if (splitk_ok && K >= 1024) {
+            last_linear_variant = DGNN_LINEAR_VARIANT_X3_SMALL_SPLITK;
             launch(k_linear_fwd_x3_small<true>, tiles32, 256, 0, a, colstats);
-        else
+        } else {
+            last_linear_variant = DGNN_LINEAR_VARIANT_X3_SMALL;
             launch(k_linear_fwd_x3_small<false>, dgnn_cdiv(tiles32, 4), 256, 0, a, colstats);
+        }
     } else if (n64_ok && n_out <= ZN) {
+        last_linear_variant = DGNN_LINEAR_VARIANT_X3_N64;
         launch(k_linear_fwd_x3_n64, dgnn_cdiv(M, XM), 256, 0, a, colstats);
     } else {
+        last_linear_variant = DGNN_LINEAR_VARIANT_X3;
         launch(k_linear_fwd_x3, a.tiles_xcd(XM, XN), 256, 0, a, colstats);
     }
     return dgnn_check_launch(a.name);
@@ -2117,6 +2134,8 @@ extern "C" int dgnn_linear_fwd_x3_stats(const float* A1, int64_t lda1, int k1, c
                               colstats);
 }
 
+extern "C" int dgnn_debug_last_linear_variant(void) { return last_linear_variant; }
+
 extern "C" int64_t dgnn_linear_fwd_x2h_scratch_elems(int64_t M, int n_out) { return M + n_out; }
 
 // fp16 two-part form of dgnn_linear_fwd_x3 (see k_linear_fwd_x2h_big).  Covers M >= 8192 with n_out > 128 -- the wide conv layers; other shapes
@@ -2129,6 +2148,7 @@ extern "C" int dgnn_linear_fwd_x2h(const float* A1, int64_t lda1, int k1, const 
     if (const int rc = fwd_validate(a, &empty); rc != DGNN_OK || empty) return rc;
     DGNN_REQUIRE(scratch, DGNN_E_INVALID, "linear_fwd_x2h: null pointer");
     if (!(M >= 8192 && n_out > XN)) return DGNN_E_UNSUPPORTED;
+    last_linear_variant = DGNN_LINEAR_VARIANT_X2H;
     hipLaunchKernelGGL(k_x2h_row_scales, dim3((unsigned)dgnn_grid_cap(dgnn_cdiv(M + n_out, 4), 16)), dim3(256), 0, a.stream, A1, lda1, k1, A2, lda2, k2, M, W1,
                        ldw1, W2, ldw2, n_out, scratch);
     static bool attr_set[DGNN_MAX_DEVICES];
@@ -2156,6 +2176,7 @@ extern "C" int dgnn_linear_fwd_x2hp(const float* A1, int64_t lda1, int k1, const
     if (const int rc = fwd_validate(a, &empty); rc != DGNN_OK || empty) return rc;
     DGNN_REQUIRE(scratch && ((uintptr_t)scratch % 16) == 0, DGNN_E_INVALID, "linear_fwd_x2hp: null / unaligned pointer");
     if (!(M >= 8192 && n_out > XN)) return DGNN_E_UNSUPPORTED;
+    last_linear_variant = DGNN_LINEAR_VARIANT_X2HP;
     const int nch = (k1 + HK - 1) / HK + (A2 ? (k2 + HK - 1) / HK : 0);
     float* scales = scratch;
     char* As = reinterpret_cast<char*>(scratch + ((M + n_out + 3) / 4) * 4);

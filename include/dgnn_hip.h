@@ -736,6 +736,29 @@ int dgnn_relu_bwd_bf16(const uint16_t* y, const uint16_t* g, int64_t n, uint16_t
  * wall_clock64() at phase boundaries (slot = (tile_iter*12 + wave)*8 + phase).  NULL disables. */
 int dgnn_debug_trace_buffer(int64_t* dev_buf, int64_t n);
 
+/* Debug only: the kernel the calling thread's last dense forward call chose (dgnn_linear_fwd, _x3, _x3_stats, _bf16, _x2h, _x2hp, and
+ * the composite entry points that go through them); NONE before the first call and after a call that launched nothing (M = 0, an
+ * argument error, DGNN_E_UNSUPPORTED).  A host-side record of the dispatch: the kernels do not know about it. */
+enum dgnn_linear_variant {
+    DGNN_LINEAR_VARIANT_NONE = 0,
+    DGNN_LINEAR_VARIANT_F32 = 1,             /* k_linear_fwd */
+    DGNN_LINEAR_VARIANT_X3 = 2,              /* k_linear_fwd_x3, 128 x 128 tiles */
+    DGNN_LINEAR_VARIANT_X3_N64 = 3,          /* k_linear_fwd_x3_n64 */
+    DGNN_LINEAR_VARIANT_X3_BIG = 4,          /* k_linear_fwd_x3_big, 256 x 256 tiles */
+    DGNN_LINEAR_VARIANT_X3_MID1 = 5,         /* k_linear_fwd_x3_mid<1> */
+    DGNN_LINEAR_VARIANT_X3_MID4 = 6,         /* k_linear_fwd_x3_mid<4> */
+    DGNN_LINEAR_VARIANT_X3_SMALL = 7,        /* k_linear_fwd_x3_small<false> */
+    DGNN_LINEAR_VARIANT_X3_SMALL_SPLITK = 8, /* k_linear_fwd_x3_small<true> */
+    DGNN_LINEAR_VARIANT_B = 9,               /* k_linear_fwd_b */
+    DGNN_LINEAR_VARIANT_B_MID1 = 10,         /* k_linear_fwd_b_mid<., 1> */
+    DGNN_LINEAR_VARIANT_B_MID4 = 11,         /* k_linear_fwd_b_mid<., 4> */
+    DGNN_LINEAR_VARIANT_B_SMALL = 12,        /* k_linear_fwd_b_small<., false> */
+    DGNN_LINEAR_VARIANT_B_SMALL_SPLITK = 13, /* k_linear_fwd_b_small<., true> */
+    DGNN_LINEAR_VARIANT_X2H = 14,            /* k_x2h_row_scales + k_linear_fwd_x2h_big */
+    DGNN_LINEAR_VARIANT_X2HP = 15            /* k_x2hp_presplit + k_linear_fwd_x2hp_big */
+};
+int dgnn_debug_last_linear_variant(void);
+
 /* ------------------------------------------------------------------------------------------------
  * k-hop full-neighbour block builder: GPU replacement of the CPU
  * torch_geometric NeighborSampler(edge_index, sizes=[-1]*k) the reference builds at run.py:72-74,221-223.

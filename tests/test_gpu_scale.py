@@ -273,11 +273,27 @@ def test_fused_predicate_matches_dispatch_128_to_64():
     logit_check(got, ref)
 
 
+def reached(entry, expect, M, n_out, K):
+    """the kernel the last dense forward call of this thread chose (dgnn_debug_last_linear_variant) is `expect` -- what these tests used to trust
+    a comment for.  `expect` holds under the default switches; with a switch set, the mirrored dispatch of tests/gemm_model.py decides."""
+    import gemm_model as gm
+    from dgnn_amd._lib import lib
+    on = gm.env_switches()
+    got = gm.VARIANT_NAMES[lib().dgnn_debug_last_linear_variant()]
+    assert got == gm.expected_variant(entry, M, n_out, K, on), (got, M, n_out, K)
+    if all(on.values()):
+        assert got == expect, (got, expect, M, n_out, K)
+
+
 @pytest.mark.parametrize("k1,k2,n_out", [(256, 256, 512), (128, 128, 256), (70, 0, 300), (512, 512, 1024)])
 def test_x3_gemm_large_tile_equals_the_small_tile_and_fp64(monkeypatch, k1, k2, n_out):
     """dgnn_linear_fwd_x3 takes a 256 x 256 tile for M >= 8192, n_out > 128: per output element the same chunk and product
     order as the 128 x 128 tile (reached here by calling it on row slices below the threshold), so results are bit-identical;
-    and both are fp32-class against an fp64 product."""
+    and both are fp32-class against an fp64 product.
+    What the dispatch observer shows (`whole`, `slices`, `last` below: the kernels of the whole call, the 4096-row slices and the ragged last
+    slice): since the 256 x 256 tile asks for 192 tiles, NONE of these shapes reaches it any more (35 row blocks x 1..4 column blocks) -- they
+    compare the 128 x 128, 64 x 64 and small-problem kernels with each other.  k_linear_fwd_x3_big is held to fp64 in test_gpu_gemm_edges.py."""
+    whole, slices, last = {512: ("X3", "X3_MID1", "X3_SMALL"), 256: ("X3_SMALL",) * 3, 300: ("X3_SMALL",) * 3, 1024: ("X3", "X3", "X3_MID4")}[n_out]
     from dgnn_amd import ops
     monkeypatch.setattr(ops, "GEMM_MODE", ops.GEMM_BF16X3)
     g = torch.Generator().manual_seed(k1 + n_out)
@@ -288,7 +304,12 @@ def test_x3_gemm_large_tile_equals_the_small_tile_and_fp64(monkeypatch, k1, k2, 
     W2 = (torch.randn(n_out, k2, generator=g) / k2 ** 0.5).to(DEV) if k2 else None
     bias = torch.randn(n_out, generator=g).to(DEV)
     big = ops.linear_fwd(A1, W1, A2, W2, bias, relu=True)
-    small = torch.cat([ops.linear_fwd(A1[s:s + 4096], W1, A2[s:s + 4096] if k2 else None, W2, bias, relu=True) for s in range(0, M, 4096)])
+    reached("x3", whole, M, n_out, k1 + k2)
+    parts = []
+    for s in range(0, M, 4096):
+        parts.append(ops.linear_fwd(A1[s:s + 4096], W1, A2[s:s + 4096] if k2 else None, W2, bias, relu=True))
+        reached("x3", slices if s + 4096 <= M else last, min(4096, M - s), n_out, k1 + k2)
+    small = torch.cat(parts)
     ref = A1.double() @ W1.double().t() + bias.double()
     if k2:
         ref = ref + A2.double() @ W2.double().t()
@@ -307,7 +328,10 @@ def test_x3_gemm_large_tile_equals_the_small_tile_and_fp64(monkeypatch, k1, k2, 
 @pytest.mark.parametrize("k1,k2,n_out", [(28, 28, 64), (128, 0, 64), (64, 64, 28), (64, 0, 2), (512, 0, 64), (70, 33, 37)])
 def test_x3_gemm_narrow_tile_equals_the_128_wide_tile(monkeypatch, k1, k2, n_out):
     """n_out <= 64 takes a 128 x 64 tile; per output element it is the 128 x 128 kernel's arithmetic (reached here by padding W with zero
-    rows to 128 outputs), so the shared columns are bit-identical."""
+    rows to 128 outputs), so the shared columns are bit-identical.
+    What the dispatch observer shows: at M = 5077 (below the small-problem threshold of 16384 rows) the narrow call takes the small-problem
+    kernel and the padded one that or, at K = 512, the 64 x 64 tiles -- neither k_linear_fwd_x3_n64 nor the 128 x 128 tile.  The comparison
+    still holds between the kernels it reaches; the narrow and the 128 x 128 tile are held to fp64 in test_gpu_gemm_edges.py."""
     from dgnn_amd import ops
     monkeypatch.setattr(ops, "GEMM_MODE", ops.GEMM_BF16X3)
     g = torch.Generator().manual_seed(k1 * 7 + n_out)
@@ -319,7 +343,9 @@ def test_x3_gemm_narrow_tile_equals_the_128_wide_tile(monkeypatch, k1, k2, n_out
     bias = torch.randn(n_out, generator=g).to(DEV)
     pad = lambda W: torch.cat([W, torch.zeros(128 - n_out, W.size(1), device=DEV)])
     narrow = ops.linear_fwd(A1, W1, A2, W2, bias, relu=True)
+    reached("x3", "X3_SMALL", M, n_out, k1 + k2)
     wide = ops.linear_fwd(A1, pad(W1), A2, pad(W2) if k2 else None, torch.cat([bias, torch.zeros(128 - n_out, device=DEV)]), relu=True)
+    reached("x3", "X3_MID1" if k1 + k2 >= 512 else "X3_SMALL", M, 128, k1 + k2)
     assert torch.equal(narrow, wide[:, :n_out])
     acc = torch.randn(M, n_out, generator=g).to(DEV)      # the accumulate flag of the backward pass
     out = acc.clone()
@@ -516,8 +542,10 @@ def test_x3_gemm_small_problem_kernel_equals_the_tiled_kernels(monkeypatch, k1, 
     W2 = (torch.randn(n_out, k2, generator=g) / k2 ** 0.5).to(DEV) if k2 else None
     bias = torch.randn(n_out, generator=g).to(DEV)
     small = ops.linear_fwd(A1, W1, A2, W2, bias, relu=True)
+    reached("x3", "X3_MID1" if n_out == 512 else "X3_SMALL", M, n_out, k1 + k2)     # (256, 256, 512): the 64 x 64 tiles took this shape over in round 6
     rep = 9                                                                  # 18603 rows: past the small-problem threshold
     big = ops.linear_fwd(A1.repeat(rep, 1), W1, A2.repeat(rep, 1) if k2 else None, W2, bias, relu=True)
+    reached("x3", "X3_N64" if n_out <= 64 else "X3", rep * M, n_out, k1 + k2)
     assert torch.equal(small, big[:M]) and torch.equal(small, big[-M:])
     ref = A1.double() @ W1.double().t() + bias.double()
     if k2:
@@ -536,7 +564,10 @@ def test_small_gemm_split_k_form(monkeypatch, k1, k2, n_out, M):
     1024 -> 512 decoder Linear and their input gradients at batch 1024) take the small-problem kernels in their split-K form -- four wavefronts per
     32 x 32 output block, a quarter of the k-steps each, partial blocks added in wavefront order.  fp32-class arithmetic (x3) against fp64 within the
     tiled kernels' tolerance, bf16 storage against fp64 on the bf16-rounded operands at fp32-accumulation level; the same bits on a second call; ragged
-    K / N / M; bias + BatchNorm + ReLU epilogue."""
+    K / N / M; bias + BatchNorm + ReLU epilogue.
+    What the dispatch observer shows (`form` below): the first two shapes have 128 or more 64 x 64 tiles and take those with four K groups per
+    workgroup (k_linear_fwd_x3_mid<4> / k_linear_fwd_b_mid<., 4>); the last two take the split-K small-problem kernels."""
+    form = "MID4" if M >= 1024 else "SMALL_SPLITK"
     from dgnn_amd import ops
     monkeypatch.setattr(ops, "GEMM_MODE", ops.GEMM_BF16X3)
     g = torch.Generator().manual_seed(k1 + 3 * n_out)
@@ -554,6 +585,7 @@ def test_small_gemm_split_k_form(monkeypatch, k1, k2, n_out, M):
             m = m + a2.double().abs() @ w2.double().abs().t()
         return (r * scale.double() + shift.double()).clamp_min(0), m * scale.double().abs() + shift.double().abs()
     got = ops.linear_fwd(A1, W1, A2, W2, bias, scale, shift, relu=True)
+    reached("x3", "X3_" + form, M, n_out, k1 + k2)
     want, mag = ref(A1, W1, A2, W2)
     assert ((got.double() - want).abs() <= 2e-6 * mag + 1e-30).all(), ((got.double() - want).abs() / mag).max().item()
     assert torch.equal(got, ops.linear_fwd(A1, W1, A2, W2, bias, scale, shift, relu=True))
@@ -561,6 +593,7 @@ def test_small_gemm_split_k_form(monkeypatch, k1, k2, n_out, M):
     bf = lambda t: t.to(torch.bfloat16)
     A1b, A2b = bf(A1), (bf(A2) if k2 else None)
     gotb = ops.linear_fwd(A1b, W1, A2b, W2, bias, scale, shift, relu=True, out_dtype=torch.float32)
+    reached("bf16", "B_" + form, M, n_out, k1 + k2)
     wantb, magb = ref(A1b.float(), bf(W1).float(), A2b.float() if k2 else None, bf(W2).float() if k2 else None)
     assert ((gotb.double() - wantb).abs() <= 4e-6 * magb + 1e-30).all(), ((gotb.double() - wantb).abs() / magb).max().item()
     assert torch.equal(gotb, ops.linear_fwd(A1b, W1, A2b, W2, bias, scale, shift, relu=True, out_dtype=torch.float32))
