@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DGNN_LIB_PATH: another build of the same library (e.g. for whole-library A/B measurements, tools/gpu_ab_libs.sh) -- never a fallback
 LIB_PATH = os.environ.get("DGNN_LIB_PATH") or os.path.join(_HERE, "libdgnn_hip.so")
 
-i64, i32, f32, f64, vp = C.c_int64, C.c_int, C.c_float, C.c_double, C.c_void_p
+i64, u64, i32, f32, f64, vp = C.c_int64, C.c_uint64, C.c_int, C.c_float, C.c_double, C.c_void_p
 
 # name -> (restype, argtypes); mirrors include/dgnn_hip.h one to one
 SIGNATURES = {
@@ -113,6 +113,11 @@ SIGNATURES = {
     "dgnn_khop_blocks_regular_start_rows": (vp, [vp, vp, vp, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                  i32, vp, vp, vp, vp, vp, vp]),
     "dgnn_khop_blocks_regular_wait": (i32, [vp, i32, vp]),
+    "dgnn_khop_count_sampled": (i32, [vp, vp, i64, i32, i32, u64, i64, i32, vp, vp, vp, vp]),
+    "dgnn_khop_expand_sampled": (i32, [vp, vp, vp, vp, i64, vp, i64, i32, u64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dgnn_khop_blocks_sampled": (i32, [vp, vp, vp, i32, vp, i64, i32, vp, u64, i64] + [vp] * 20),
+    "dgnn_khop_blocks_sampled_start": (vp, [vp, vp, vp, i32, vp, i64, i32, vp, u64, i64] + [vp] * 19),
+    "dgnn_khop_blocks_sampled_start_rows": (vp, [vp, vp, vp, i32, vp, i64, i32, vp, u64, i64] + [vp] * 18 + [i32, vp, vp, vp, vp, vp, vp]),
     "dgnn_decoder_fused_fwd": (i32, [vp, i64, i64, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, i64, vp]),
     "dgnn_cast_f32_to_bf16": (i32, [vp, i64, i64, i32, i32, vp, i64, vp]),
     "dgnn_rows_unsigned_to_bf16": (i32, [vp, i64, i64, i32, vp, i64, vp]),

@@ -8,6 +8,12 @@
 // for the reference's adjacency layout equals ascending source id, PyG's order -- relabelled to local ids where
 // targets keep their positions and newly seen sources are appended in order of first appearance.
 // `pos` (int32 [n_nodes], all -1 between batches) carries the global->local map across the hops of a batch.
+//
+// Sampled neighbourhoods (sizes[h] > 0; DESIGN "Sampled neighbourhoods"): the *_sampled entry points keep, of a target with more than
+// `size` in-edges, the `size` of them with the smallest 64-bit keys key(seed, draw, hop, global id, j) -- j = rank of the in-edge in plan
+// order, ties to the smaller j -- and leave them in plan order; everything downstream (local ids, first appearance, e_id) is the
+// construction above applied to the kept edges.  The key is a counter-based hash (khop_select below): no device RNG, no atomics in the
+// selection, so a block is a pure function of (graph, batch, sizes, seed, draw).  The full-neighbourhood entry points are unchanged.
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -98,6 +104,124 @@ __global__ void k_fill_i32(int32_t* p, int64_t n, int32_t v) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
+// ---- sampled neighbourhoods ---------------------------------------------------------------------------------------------------------
+struct KhopDraw {
+    int size;        // in-edges kept per target at most; < 0: all of them
+    uint64_t base;   // mix64(seed + 0x9E3779B97F4A7C15 * (draw + 1))
+    uint64_t hop;    // builder hop << 32
+};
+
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {   // the splitmix64 finaliser
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+inline KhopDraw khop_draw(int size, uint64_t seed, int64_t draw, int hop) {
+    return KhopDraw{size, mix64(seed + 0x9E3779B97F4A7C15ull * ((uint64_t)draw + 1ull)), (uint64_t)(uint32_t)hop << 32};
+}
+
+// THE selection, recomputed identically by the count, first, flags and emit passes: calls keep(j, r) for every kept in-edge j (rank in
+// plan order) of the target with global id g and in-degree d, r = its rank among the kept ones, in ascending j; returns how many.
+// key_j = mix64(mix64(base ^ g) + (hop << 32 | j)); kept = the `size` smallest (key, j) pairs.  d <= 8 (a Delaunay cell: 4): the keys sit
+// in registers and every lane runs the same 8 x 8 compare network, predicated on j < d; longer segments recompute the keys in a loop
+// that is quadratic in d (the convention of graphcut.hip's k_sort_segments).
+template <typename F>
+__device__ __forceinline__ int khop_select(const KhopDraw s, int64_t g, int d, F keep) {
+    if (s.size < 0 || d <= s.size) {
+        for (int j = 0; j < d; ++j) keep(j, j);
+        return d;
+    }
+    const uint64_t b = mix64(s.base ^ (uint64_t)g);
+    int r = 0;
+    if (d <= 8) {
+        uint64_t key[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) key[j] = mix64(b + (s.hop | (uint64_t)j));
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            int smaller = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) smaller += (i < d && (key[i] < key[j] || (key[i] == key[j] && i < j))) ? 1 : 0;
+            if (j < d && smaller < s.size) keep(j, r++);
+        }
+        return r;
+    }
+    for (int j = 0; j < d; ++j) {
+        const uint64_t kj = mix64(b + (s.hop | (uint64_t)(uint32_t)j));
+        int smaller = 0;
+        for (int i = 0; i < d; ++i) {
+            const uint64_t ki = mix64(b + (s.hop | (uint64_t)(uint32_t)i));
+            smaller += (ki < kj || (ki == kj && i < j)) ? 1 : 0;
+        }
+        if (smaller < s.size) keep(j, r++);
+    }
+    return r;
+}
+
+__global__ void k_khop_deg_sampled(const int32_t* __restrict__ rowptr, const int64_t* __restrict__ n_id, int64_t n_t, int first_hop, int size,
+                                   int32_t* __restrict__ deg, int32_t* __restrict__ pos) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_t; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t g = n_id[i];
+        const int d = rowptr[g + 1] - rowptr[g];
+        deg[i] = (size >= 0 && d > size) ? size : d;
+        if (first_hop) pos[g] = (int32_t)i;
+    }
+}
+
+__global__ void k_khop_first_sampled(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src, const int64_t* __restrict__ n_id,
+                                     int64_t n_t, const int32_t* __restrict__ off, const int32_t* __restrict__ pos, KhopDraw draw,
+                                     int32_t* __restrict__ first) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_t; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t g = n_id[i];
+        const int b = rowptr[g], e = rowptr[g + 1], o = off[i];
+        khop_select(draw, g, e - b, [&](int j, int r) {
+            const int s = src[b + j];
+            if (pos[s] < 0) atomicMin(&first[s], o + r);
+        });
+    }
+}
+
+__global__ void k_khop_flags_sampled(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src, const int64_t* __restrict__ n_id,
+                                     int64_t n_t, const int32_t* __restrict__ off, const int32_t* __restrict__ pos,
+                                     const int32_t* __restrict__ first, KhopDraw draw, int32_t* __restrict__ flags) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_t; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t g = n_id[i];
+        const int b = rowptr[g], e = rowptr[g + 1], o = off[i];
+        khop_select(draw, g, e - b, [&](int j, int r) {
+            const int s = src[b + j], q = o + r;
+            flags[q] = (pos[s] < 0 && first[s] == q) ? 1 : 0;
+        });
+    }
+}
+
+__global__ void k_khop_emit_sampled(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src, const int32_t* __restrict__ eid,
+                                    const int64_t* __restrict__ n_id, int64_t n_t, const int32_t* __restrict__ off,
+                                    const int32_t* __restrict__ pos, const int32_t* __restrict__ first, const int32_t* __restrict__ rank,
+                                    KhopDraw draw, int64_t* __restrict__ e_src, int64_t* __restrict__ e_dst, int64_t* __restrict__ e_id,
+                                    int64_t* __restrict__ n_id_out) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_t; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t g = n_id[i];
+        const int b = rowptr[g], e = rowptr[g + 1], o = off[i];
+        n_id_out[i] = g;
+        khop_select(draw, g, e - b, [&](int j, int r) {
+            const int s = src[b + j], q = o + r;
+            const int p = pos[s];
+            int64_t local;
+            if (p >= 0) {
+                local = p;
+            } else {
+                const int fq = first[s];
+                local = n_t + rank[fq];
+                if (fq == q) n_id_out[local] = s;
+            }
+            e_src[q] = local;
+            e_dst[q] = i;
+            e_id[q] = eid[b + j];
+        });
+    }
+}
+
 }  // namespace
 
 int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out /*[n+1]*/, int32_t* sums_scratch, hipStream_t stream);  // plan.hip
@@ -148,6 +272,50 @@ extern "C" int dgnn_khop_expand(const int32_t* rowptr, const int32_t* src, const
         hipLaunchKernelGGL(k_khop_emit, grid, block, 0, stream, rowptr, src, eid, n_id, n_t, off, pos, first, rank, e_src, e_dst, e_id,
                            n_id_out);
     return dgnn_check_launch("khop_expand");
+}
+
+// The sampled twins of dgnn_khop_count / dgnn_khop_expand (same buffers, same protocol): off[i] = exclusive scan of min(d_i, size) and the
+// block of the kept in-edges only.  size = -1 keeps everything (the result of the plain entry points); seed / draw / hop feed the key.
+static bool khop_draw_ok(int size, int64_t draw, int hop) { return (size == -1 || size >= 1) && draw >= 0 && hop >= 0 && hop < 65536; }
+
+extern "C" int dgnn_khop_count_sampled(const int32_t* rowptr, const int64_t* n_id, int64_t n_t, int first_hop, int size, uint64_t seed, int64_t draw,
+                                       int hop, int32_t* pos, int32_t* off, int32_t* scratch, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    (void)seed;   // the COUNT of kept edges depends on the size alone; the arguments mirror dgnn_khop_expand_sampled
+    DGNN_REQUIRE(n_t >= 0 && rowptr && pos && off && scratch && (n_t == 0 || n_id) && khop_draw_ok(size, draw, hop), DGNN_E_INVALID,
+                 "khop_count_sampled: bad args");
+    int32_t* deg = scratch;
+    if (n_t > 0)
+        hipLaunchKernelGGL(k_khop_deg_sampled, dim3(dgnn_grid_cap(dgnn_cdiv(n_t, 256))), dim3(256), 0, stream, rowptr, n_id, n_t, first_hop, size, deg, pos);
+    const int rc = dgnn_exclusive_scan_i32(deg, n_t, off, scratch + n_t + 1, stream);
+    if (rc) return rc;
+    return dgnn_check_launch("khop_count_sampled");
+}
+
+extern "C" int dgnn_khop_expand_sampled(const int32_t* rowptr, const int32_t* src, const int32_t* eid, const int64_t* n_id, int64_t n_t,
+                                        const int32_t* off, int64_t n_edges, int size, uint64_t seed, int64_t draw, int hop, int32_t* pos,
+                                        int32_t* first, int64_t* e_src, int64_t* e_dst, int64_t* e_id, int64_t* n_id_out, int32_t* n_new_out,
+                                        int32_t* scratch, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DGNN_REQUIRE(n_t >= 0 && n_edges >= 0 && rowptr && src && eid && off && pos && first && n_id_out && n_new_out && scratch &&
+                     khop_draw_ok(size, draw, hop),
+                 DGNN_E_INVALID, "khop_expand_sampled: bad args");
+    const KhopDraw kd = khop_draw(size, seed, draw, hop);
+    int32_t* flags = scratch;                 // [n_edges]
+    int32_t* rank = flags + n_edges + 1;      // [n_edges + 1]
+    int32_t* sums = rank + n_edges + 1;
+    const dim3 grid(dgnn_grid_cap(dgnn_cdiv(n_t > 0 ? n_t : 1, 256))), block(256);
+    if (n_t > 0 && n_edges > 0) {
+        hipLaunchKernelGGL(k_khop_first_sampled, grid, block, 0, stream, rowptr, src, n_id, n_t, off, pos, kd, first);
+        hipLaunchKernelGGL(k_khop_flags_sampled, grid, block, 0, stream, rowptr, src, n_id, n_t, off, pos, first, kd, flags);
+    }
+    const int rc = dgnn_exclusive_scan_i32(flags, n_edges, rank, sums, stream);
+    if (rc) return rc;
+    (void)hipMemcpyAsync(n_new_out, rank + n_edges, sizeof(int32_t), hipMemcpyDeviceToDevice, stream);
+    if (n_t > 0)
+        hipLaunchKernelGGL(k_khop_emit_sampled, grid, block, 0, stream, rowptr, src, eid, n_id, n_t, off, pos, first, rank, kd, e_src, e_dst, e_id,
+                           n_id_out);
+    return dgnn_check_launch("khop_expand_sampled");
 }
 
 // step 3 (after the host read n_new): record the new nodes' local ids for the next hop
@@ -292,23 +460,31 @@ bool read_back(const int32_t* dev_value, int32_t* out, const Mailbox& mb, hipStr
 // block.  t_rowptr != NULL: every hop's transposed plan as well (dgnn_plan_build by source: t_rowptr[h] int32 [cap_all[h] + 1],
 // t_dst[h] / t_eid[h] int32 [cap_e[h]]) and t_rows[h] = e_id32[h][t_eid[h]]; plan_scratch = max_h dgnn_plan_scratch_elems(cap_e[h],
 // cap_all[h]).  Returns DGNN_E_INVALID when a capacity is too small (nothing is left half-written in `pos` / `first`).
-extern "C" int dgnn_khop_blocks_regular(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch,
-                                        int64_t n_batch, int hops, int32_t* pos, int32_t* first, int64_t* const* ei, int64_t* const* e_id,
-                                        int32_t* const* src32, int32_t* const* e_id32, int32_t* const* off, int64_t* const* n_id_out, const int64_t* cap_t,
-                                        const int64_t* cap_e, int32_t* scratch, int32_t* n_new_dev, int32_t* const* t_rowptr, int32_t* const* t_dst,
-                                        int32_t* const* t_eid, int32_t* const* t_rows, const int64_t* cap_all, int32_t* plan_scratch,
-                                        int64_t* counts_out, void* stream_) {
+//
+// `sizes` (NULL: full neighbourhoods, dgnn_khop_blocks_regular) makes it the sampled builder, dgnn_khop_blocks_sampled: hop h keeps
+// e_h = min(sizes[h], deg) in-edges per target (deg for sizes[h] = -1), drawn as khop_select says with (seed, draw, h), so its edge count
+// counts[h] * e_h is again known without a read-back; a hop with e_h = deg takes the full-neighbourhood kernels.
+static int khop_blocks(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch, int64_t n_batch, int hops,
+                       const int32_t* sizes, uint64_t seed, int64_t draw, int32_t* pos, int32_t* first, int64_t* const* ei, int64_t* const* e_id,
+                       int32_t* const* src32, int32_t* const* e_id32, int32_t* const* off, int64_t* const* n_id_out, const int64_t* cap_t,
+                       const int64_t* cap_e, int32_t* scratch, int32_t* n_new_dev, int32_t* const* t_rowptr, int32_t* const* t_dst,
+                       int32_t* const* t_eid, int32_t* const* t_rows, const int64_t* cap_all, int32_t* plan_scratch, int64_t* counts_out, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     DGNN_REQUIRE(hops >= 1 && hops <= 16 && deg >= 1 && n_batch >= 0 && rowptr && src && eid && pos && first && ei && e_id && src32 && e_id32 && off && n_id_out &&
                      cap_t && cap_e && scratch && n_new_dev && counts_out && (n_batch == 0 || batch),
                  DGNN_E_INVALID, "khop_blocks_regular: bad args");
+    if (sizes) {
+        DGNN_REQUIRE(draw >= 0, DGNN_E_INVALID, "khop_blocks_sampled: draw < 0");
+        for (int q = 0; q < hops; ++q) DGNN_REQUIRE(sizes[q] == -1 || sizes[q] >= 1, DGNN_E_INVALID, "khop_blocks_sampled: sizes[%d] = %d (-1 or > 0)", q, sizes[q]);
+    }
     const int64_t* n_id = batch;
     int64_t n_t = n_batch;
     int rc = DGNN_OK;
     int h = 0;
     Mailbox mailbox;
     for (; h < hops; ++h) {
-        const int64_t n_e = n_t * deg;
+        const int keep = (sizes && sizes[h] >= 0 && sizes[h] < deg) ? sizes[h] : deg;   // in-edges per target of this hop
+        const int64_t n_e = n_t * keep;
         counts_out[h] = n_t;
         if (n_t > cap_t[h] || n_e > cap_e[h]) {
             dgnn_set_error("khop_blocks_regular: hop %d needs %lld targets / %lld edges, capacity %lld / %lld", h, (long long)n_t, (long long)n_e,
@@ -316,10 +492,17 @@ extern "C" int dgnn_khop_blocks_regular(const int32_t* rowptr, const int32_t* sr
             rc = DGNN_E_INVALID;
             break;
         }
-        if ((rc = dgnn_khop_count(rowptr, n_id, n_t, h == 0, pos, off[h], scratch, stream_)) != DGNN_OK) break;
-        if ((rc = dgnn_khop_expand(rowptr, src, eid, n_id, n_t, off[h], n_e, pos, first, ei[h], ei[h] + cap_e[h], e_id[h], n_id_out[h], n_new_dev, scratch,
-                                   stream_)) != DGNN_OK)
-            break;
+        if (keep == deg) {
+            if ((rc = dgnn_khop_count(rowptr, n_id, n_t, h == 0, pos, off[h], scratch, stream_)) != DGNN_OK) break;
+            if ((rc = dgnn_khop_expand(rowptr, src, eid, n_id, n_t, off[h], n_e, pos, first, ei[h], ei[h] + cap_e[h], e_id[h], n_id_out[h], n_new_dev, scratch,
+                                       stream_)) != DGNN_OK)
+                break;
+        } else {
+            if ((rc = dgnn_khop_count_sampled(rowptr, n_id, n_t, h == 0, keep, seed, draw, h, pos, off[h], scratch, stream_)) != DGNN_OK) break;
+            if ((rc = dgnn_khop_expand_sampled(rowptr, src, eid, n_id, n_t, off[h], n_e, keep, seed, draw, h, pos, first, ei[h], ei[h] + cap_e[h], e_id[h],
+                                               n_id_out[h], n_new_dev, scratch, stream_)) != DGNN_OK)
+                break;
+        }
         int32_t n_new = 0;
         if (!read_back(n_new_dev, &n_new, mailbox, stream)) {
             dgnn_set_error("khop_blocks_regular: reading the new-node count failed: %s", hipGetErrorString(hipGetLastError()));
@@ -361,6 +544,28 @@ extern "C" int dgnn_khop_blocks_regular(const int32_t* rowptr, const int32_t* sr
     return dgnn_check_launch("khop_blocks_regular");
 }
 
+extern "C" int dgnn_khop_blocks_regular(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch,
+                                        int64_t n_batch, int hops, int32_t* pos, int32_t* first, int64_t* const* ei, int64_t* const* e_id,
+                                        int32_t* const* src32, int32_t* const* e_id32, int32_t* const* off, int64_t* const* n_id_out, const int64_t* cap_t,
+                                        const int64_t* cap_e, int32_t* scratch, int32_t* n_new_dev, int32_t* const* t_rowptr, int32_t* const* t_dst,
+                                        int32_t* const* t_eid, int32_t* const* t_rows, const int64_t* cap_all, int32_t* plan_scratch,
+                                        int64_t* counts_out, void* stream) {
+    return khop_blocks(rowptr, src, eid, deg, batch, n_batch, hops, nullptr, 0, 0, pos, first, ei, e_id, src32, e_id32, off, n_id_out, cap_t, cap_e, scratch,
+                       n_new_dev, t_rowptr, t_dst, t_eid, t_rows, cap_all, plan_scratch, counts_out, stream);
+}
+
+// ... with sampled neighbourhoods: sizes int32 [hops] (HOST; -1 or > 0), the loader's seed and the block's draw number
+extern "C" int dgnn_khop_blocks_sampled(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch,
+                                        int64_t n_batch, int hops, const int32_t* sizes, uint64_t seed, int64_t draw, int32_t* pos, int32_t* first,
+                                        int64_t* const* ei, int64_t* const* e_id, int32_t* const* src32, int32_t* const* e_id32, int32_t* const* off,
+                                        int64_t* const* n_id_out, const int64_t* cap_t, const int64_t* cap_e, int32_t* scratch, int32_t* n_new_dev,
+                                        int32_t* const* t_rowptr, int32_t* const* t_dst, int32_t* const* t_eid, int32_t* const* t_rows,
+                                        const int64_t* cap_all, int32_t* plan_scratch, int64_t* counts_out, void* stream) {
+    DGNN_REQUIRE(sizes, DGNN_E_INVALID, "khop_blocks_sampled: sizes is NULL");
+    return khop_blocks(rowptr, src, eid, deg, batch, n_batch, hops, sizes, seed, draw, pos, first, ei, e_id, src32, e_id32, off, n_id_out, cap_t, cap_e, scratch,
+                       n_new_dev, t_rowptr, t_dst, t_eid, t_rows, cap_all, plan_scratch, counts_out, stream);
+}
+
 // ---- the same call on a library-owned host thread ------------------------------------------------------------------------------
 // start() returns at once; a std::thread (no interpreter lock involved) issues the launches on `stream` and waits for the per-hop
 // counts; wait() joins it.  The caller keeps enqueueing the training step on its own stream meanwhile and must not touch
@@ -377,6 +582,7 @@ struct KhopJob {
     std::vector<int64_t*> ei, e_id, n_id_out;
     std::vector<int32_t*> src32, e_id32, off, t_rowptr, t_dst, t_eid, t_rows;
     std::vector<int64_t> cap_t, cap_e, cap_all, counts;
+    std::vector<int32_t> sizes;   // empty: full neighbourhoods
 };
 template <typename T>
 std::vector<T> copy_n(const T* p, int n) {
@@ -403,8 +609,8 @@ __global__ void k_gather_rows_i64(const float* __restrict__ src, int64_t ld, con
 }
 }  // namespace
 
-static void* khop_start(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch, int64_t n_batch, int hops, int32_t* pos,
-                        int32_t* first, int64_t* const* ei, int64_t* const* e_id, int32_t* const* src32, int32_t* const* e_id32, int32_t* const* off,
+static void* khop_start(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch, int64_t n_batch, int hops,
+                        const int32_t* sizes, uint64_t seed, int64_t draw, int32_t* pos, int32_t* first, int64_t* const* ei, int64_t* const* e_id, int32_t* const* src32, int32_t* const* e_id32, int32_t* const* off,
                         int64_t* const* n_id_out, const int64_t* cap_t, const int64_t* cap_e, int32_t* scratch, int32_t* n_new_dev, int32_t* const* t_rowptr,
                         int32_t* const* t_dst, int32_t* const* t_eid, int32_t* const* t_rows, const int64_t* cap_all, int32_t* plan_scratch, KhopRows rows,
                         void* stream) {
@@ -419,19 +625,19 @@ static void* khop_start(const int32_t* rowptr, const int32_t* src, const int32_t
     j->src32 = copy_n(src32, hops), j->e_id32 = copy_n(e_id32, hops), j->off = copy_n(off, hops);
     j->t_rowptr = copy_n(t_rowptr, hops), j->t_dst = copy_n(t_dst, hops), j->t_eid = copy_n(t_eid, hops), j->t_rows = copy_n(t_rows, hops);
     j->cap_t = copy_n(cap_t, hops), j->cap_e = copy_n(cap_e, hops), j->cap_all = copy_n(cap_all, hops);
+    j->sizes = copy_n(sizes, hops);
     j->counts.assign(hops + 1, 0);
-    const bool want_t = t_rowptr != nullptr;
+    const bool want_t = t_rowptr != nullptr, sampled = sizes != nullptr;
     j->th = std::thread([=]() {
         if (hipSetDevice(device) != hipSuccess) {
             j->rc = DGNN_E_LAUNCH;
             j->err = "khop_blocks_regular_start: hipSetDevice failed on the builder thread";
             return;
         }
-        j->rc = dgnn_khop_blocks_regular(rowptr, src, eid, deg, batch, n_batch, hops, pos, first, j->ei.data(), j->e_id.data(), j->src32.data(),
-                                         j->e_id32.data(), j->off.data(), j->n_id_out.data(), j->cap_t.data(), j->cap_e.data(), scratch, n_new_dev,
-                                         want_t ? j->t_rowptr.data() : nullptr, want_t ? j->t_dst.data() : nullptr, want_t ? j->t_eid.data() : nullptr,
-                                         want_t ? j->t_rows.data() : nullptr, want_t ? j->cap_all.data() : nullptr, plan_scratch, j->counts.data(),
-                                         stream);
+        j->rc = khop_blocks(rowptr, src, eid, deg, batch, n_batch, hops, sampled ? j->sizes.data() : nullptr, seed, draw, pos, first, j->ei.data(),
+                            j->e_id.data(), j->src32.data(), j->e_id32.data(), j->off.data(), j->n_id_out.data(), j->cap_t.data(), j->cap_e.data(), scratch,
+                            n_new_dev, want_t ? j->t_rowptr.data() : nullptr, want_t ? j->t_dst.data() : nullptr, want_t ? j->t_eid.data() : nullptr,
+                            want_t ? j->t_rows.data() : nullptr, want_t ? j->cap_all.data() : nullptr, plan_scratch, j->counts.data(), stream);
         if (j->rc != DGNN_OK) {
             j->err = dgnn_last_error_string();   // the error text is per thread: carry it over
             return;
@@ -457,12 +663,29 @@ extern "C" void* dgnn_khop_blocks_regular_start(const int32_t* rowptr, const int
                                                 const int64_t* cap_t, const int64_t* cap_e, int32_t* scratch, int32_t* n_new_dev,
                                                 int32_t* const* t_rowptr, int32_t* const* t_dst, int32_t* const* t_eid, int32_t* const* t_rows,
                                                 const int64_t* cap_all, int32_t* plan_scratch, void* stream) {
-    return khop_start(rowptr, src, eid, deg, batch, n_batch, hops, pos, first, ei, e_id, src32, e_id32, off, n_id_out, cap_t, cap_e, scratch, n_new_dev, t_rowptr,
-                      t_dst, t_eid, t_rows, cap_all, plan_scratch, KhopRows(), stream);
+    return khop_start(rowptr, src, eid, deg, batch, n_batch, hops, nullptr, 0, 0, pos, first, ei, e_id, src32, e_id32, off, n_id_out, cap_t, cap_e, scratch,
+                      n_new_dev, t_rowptr, t_dst, t_eid, t_rows, cap_all, plan_scratch, KhopRows(), stream);
 }
 
 // ... and up to 4 row gathers behind the block: r_src[i] (fp32, already offset to its first column), row stride r_ld[i], r_cols[i] columns, r_which[i]
 // 0 = all nodes of the outermost block (n_id_out[hops-1][:counts[hops]]) / 1 = the batch's targets, r_out[i] [capacity, r_cols[i]] packed rows
+static bool khop_rows(KhopRows& rows, int n_rows, const float* const* r_src, const int64_t* r_ld, const int32_t* r_cols, const int32_t* r_which,
+                      float* const* r_out) {
+    if (n_rows < 0 || n_rows > 4 || (n_rows && !(r_src && r_ld && r_cols && r_which && r_out))) {
+        dgnn_set_error("khop_blocks_regular_start_rows: at most 4 row gathers, all arrays given");
+        return false;
+    }
+    rows.n = n_rows;
+    for (int i = 0; i < n_rows; ++i) {
+        if (!r_src[i] || !r_out[i] || r_cols[i] <= 0 || r_ld[i] < r_cols[i]) {
+            dgnn_set_error("khop_blocks_regular_start_rows: bad row gather %d", i);
+            return false;
+        }
+        rows.src[i] = r_src[i], rows.ld[i] = r_ld[i], rows.cols[i] = r_cols[i], rows.which[i] = r_which[i], rows.out[i] = r_out[i];
+    }
+    return true;
+}
+
 extern "C" void* dgnn_khop_blocks_regular_start_rows(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch,
                                                      int64_t n_batch, int hops, int32_t* pos, int32_t* first, int64_t* const* ei, int64_t* const* e_id,
                                                      int32_t* const* src32, int32_t* const* e_id32, int32_t* const* off, int64_t* const* n_id_out,
@@ -471,20 +694,42 @@ extern "C" void* dgnn_khop_blocks_regular_start_rows(const int32_t* rowptr, cons
                                                      const int64_t* cap_all, int32_t* plan_scratch, int n_rows, const float* const* r_src, const int64_t* r_ld,
                                                      const int32_t* r_cols, const int32_t* r_which, float* const* r_out, void* stream) {
     KhopRows rows;
-    if (n_rows < 0 || n_rows > 4 || (n_rows && !(r_src && r_ld && r_cols && r_which && r_out))) {
-        dgnn_set_error("khop_blocks_regular_start_rows: at most 4 row gathers, all arrays given");
+    if (!khop_rows(rows, n_rows, r_src, r_ld, r_cols, r_which, r_out)) return nullptr;
+    return khop_start(rowptr, src, eid, deg, batch, n_batch, hops, nullptr, 0, 0, pos, first, ei, e_id, src32, e_id32, off, n_id_out, cap_t, cap_e, scratch,
+                      n_new_dev, t_rowptr, t_dst, t_eid, t_rows, cap_all, plan_scratch, rows, stream);
+}
+
+// The sampled builder on the library-owned host thread, without and with the row gathers; dgnn_khop_blocks_regular_wait joins either.
+extern "C" void* dgnn_khop_blocks_sampled_start(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch,
+                                                int64_t n_batch, int hops, const int32_t* sizes, uint64_t seed, int64_t draw, int32_t* pos, int32_t* first,
+                                                int64_t* const* ei, int64_t* const* e_id, int32_t* const* src32, int32_t* const* e_id32, int32_t* const* off,
+                                                int64_t* const* n_id_out, const int64_t* cap_t, const int64_t* cap_e, int32_t* scratch, int32_t* n_new_dev,
+                                                int32_t* const* t_rowptr, int32_t* const* t_dst, int32_t* const* t_eid, int32_t* const* t_rows,
+                                                const int64_t* cap_all, int32_t* plan_scratch, void* stream) {
+    if (!sizes) {
+        dgnn_set_error("khop_blocks_sampled_start: sizes is NULL");
         return nullptr;
     }
-    rows.n = n_rows;
-    for (int i = 0; i < n_rows; ++i) {
-        if (!r_src[i] || !r_out[i] || r_cols[i] <= 0 || r_ld[i] < r_cols[i]) {
-            dgnn_set_error("khop_blocks_regular_start_rows: bad row gather %d", i);
-            return nullptr;
-        }
-        rows.src[i] = r_src[i], rows.ld[i] = r_ld[i], rows.cols[i] = r_cols[i], rows.which[i] = r_which[i], rows.out[i] = r_out[i];
+    return khop_start(rowptr, src, eid, deg, batch, n_batch, hops, sizes, seed, draw, pos, first, ei, e_id, src32, e_id32, off, n_id_out, cap_t, cap_e, scratch,
+                      n_new_dev, t_rowptr, t_dst, t_eid, t_rows, cap_all, plan_scratch, KhopRows(), stream);
+}
+
+extern "C" void* dgnn_khop_blocks_sampled_start_rows(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch,
+                                                     int64_t n_batch, int hops, const int32_t* sizes, uint64_t seed, int64_t draw, int32_t* pos,
+                                                     int32_t* first, int64_t* const* ei, int64_t* const* e_id, int32_t* const* src32, int32_t* const* e_id32,
+                                                     int32_t* const* off, int64_t* const* n_id_out, const int64_t* cap_t, const int64_t* cap_e,
+                                                     int32_t* scratch, int32_t* n_new_dev, int32_t* const* t_rowptr, int32_t* const* t_dst,
+                                                     int32_t* const* t_eid, int32_t* const* t_rows, const int64_t* cap_all, int32_t* plan_scratch, int n_rows,
+                                                     const float* const* r_src, const int64_t* r_ld, const int32_t* r_cols, const int32_t* r_which,
+                                                     float* const* r_out, void* stream) {
+    KhopRows rows;
+    if (!sizes) {
+        dgnn_set_error("khop_blocks_sampled_start_rows: sizes is NULL");
+        return nullptr;
     }
-    return khop_start(rowptr, src, eid, deg, batch, n_batch, hops, pos, first, ei, e_id, src32, e_id32, off, n_id_out, cap_t, cap_e, scratch, n_new_dev, t_rowptr,
-                      t_dst, t_eid, t_rows, cap_all, plan_scratch, rows, stream);
+    if (!khop_rows(rows, n_rows, r_src, r_ld, r_cols, r_which, r_out)) return nullptr;
+    return khop_start(rowptr, src, eid, deg, batch, n_batch, hops, sizes, seed, draw, pos, first, ei, e_id, src32, e_id32, off, n_id_out, cap_t, cap_e, scratch,
+                      n_new_dev, t_rowptr, t_dst, t_eid, t_rows, cap_all, plan_scratch, rows, stream);
 }
 
 extern "C" int dgnn_khop_blocks_regular_wait(void* job, int hops, int64_t* counts_out) {

@@ -1,6 +1,7 @@
-"""GPU k-hop full-neighbour block builder: drop-in for the CPU
-``torch_geometric.data.NeighborSampler(edge_index, sizes=[-1]*k, node_idx, batch_size, shuffle, drop_last,
-return_e_id=True)`` that the reference builds at run.py:72-74 (training) and run.py:221-223 (inference).
+"""GPU k-hop block builder: drop-in for the CPU
+``torch_geometric.data.NeighborSampler(edge_index, sizes, node_idx, batch_size, shuffle, drop_last,
+return_e_id=True)`` that the reference builds at run.py:72-74 (training) and run.py:221-223 (inference) with
+``sizes = graph.clique_sizes * num_hops``: -1 for a full neighbourhood (every shipped config), k > 0 for k sampled neighbours.
 
 Iterating yields ``(batch_size, n_id, adjs)`` exactly as PyG does: ``adjs`` is the list of
 ``(edge_index [2,E_l] local ids, e_id [E_l], size=(n_src, n_dst))`` with the OUTERMOST hop first (a single
@@ -9,6 +10,21 @@ of sources.  Everything stays on the GPU (the reference samples on the CPU with 
 over PCIe).  Per destination, edges come in plan order = ascending edge position; for the reference's adjacency
 layout (4 rows per source tet, distinct neighbours) that is ascending source id, i.e. PyG's order, so blocks are
 identical to the CPU sampler's (tests/test_gpu_parity.py checks this against the oracle's restatement).
+
+Sampled neighbourhoods (the contract; DESIGN.md "Sampled neighbourhoods" gives the reasons).  ``sizes[h]`` applies to builder hop ``h``; hop 0 is
+the batch's own neighbourhood, the INNERMOST block, last in ``adjs`` (PyG: ``for size in self.sizes: sample_adj(n_id, size)``).  A target with
+global id ``g`` and in-degree ``d`` at hop ``h`` keeps all its in-edges when ``sizes[h] == -1`` or ``d <= sizes[h]``; otherwise exactly
+``k = sizes[h]`` distinct ones, uniformly without replacement: its in-edges are ranked ``j = 0..d-1`` in plan order, each gets the 64-bit key
+
+    key = mix(mix(mix(seed + 0x9E3779B97F4A7C15 * (draw + 1)) ^ g) + ((h << 32) | j))        mix = the splitmix64 finaliser, modulo 2^64
+
+and the ``k`` smallest keys are kept, ties to the smaller ``j``.  Kept edges stay in plan order, and everything after that is the construction
+above applied to the kept edges only (targets keep their local positions, new sources are appended in order of first appearance among kept
+edges, ``e_id`` is the graph edge id, targets are a prefix of sources, ``adjs`` is reversed at the end).  Hops draw independently (``h`` is in
+the key), as PyG's do.  The key is a stateless counter-based hash: a block is a pure function of (graph, batch, sizes, seed, draw) --
+``seed`` = the loader's ``sample_seed``, ``draw`` = the number of the block: ``sample(batch, draw)`` pins it, ``sample(batch)`` and iteration
+count it in ``draws``, in batch order whichever path (in line, side stream, worker thread, library thread, buffer ring) builds the block.
+tests/sampled_blocks_model.py restates this in numpy; tests/test_gpu_sampled_blocks.py holds the builder to it, exactly.
 """
 from __future__ import annotations
 
@@ -39,12 +55,16 @@ class EdgeIndex(tuple):
 class NeighborSampler:
     def __init__(self, edge_index, sizes, node_idx=None, num_nodes=None, batch_size=1, shuffle=False, drop_last=False,
                  return_e_id=True, plan: GraphPlan = None, generator=None, prefetch=True, transposed_plans=True, reuse_buffers=False,
-                 **kwargs):
-        if any(int(s) != -1 for s in sizes):
-            raise NotImplementedError("only full neighbourhoods (size -1) are used by the reference (clique_sizes: [-1])")
+                 sample_seed: int = 0, **kwargs):
+        sizes = [int(s) for s in sizes]
+        if any(s == 0 or s < -1 for s in sizes):
+            raise ValueError("NeighborSampler sizes: -1 (all neighbours) or a positive count per hop, got %r" % (sizes,))
         if not edge_index.is_cuda:
             raise RuntimeError("dgnn_amd.sampler.NeighborSampler builds blocks on the GPU: pass a CUDA edge_index")
-        self.sizes = list(sizes)
+        self.sizes = sizes
+        self._sampled = any(s != -1 for s in sizes)     # all -1: the full-neighbourhood entry points, as ever
+        self.sample_seed = int(sample_seed) & (2 ** 64 - 1)
+        self.draws = 0     # blocks handed out so far = the draw number of the next one (the sampling key's `draw`)
         self.device = edge_index.device
         n = int(num_nodes) if num_nodes is not None else int(edge_index.max().item()) + 1
         self.num_nodes = n
@@ -78,6 +98,7 @@ class NeighborSampler:
         # two host round trips per hop (reading the count back) is not needed
         rp = self.plan.rowptr
         self._regular = bool(((rp[1:] - rp[:-1]) == 4).all().item()) if n > 0 else False
+        self._keep = [4 if s < 0 else min(s, 4) for s in sizes]    # ... and with sizes[h] > 0 it is min(sizes[h], 4) x targets
 
     def attach_rows(self, specs):
         """Rows the builder gathers behind every block, on its own stream (prefetching iteration with reuse_buffers over a 4-regular graph; other
@@ -108,14 +129,25 @@ class NeighborSampler:
         return m // self.batch_size if self.drop_last else (m + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
+        # block i of this pass has draw number base + i whichever path builds it, however far ahead; `draws` moves when a block is handed out
+        base = self.draws
+        blocks = self._iter_blocks(base)
+        try:
+            for i, blk in enumerate(blocks):
+                self.draws = base + i + 1
+                yield blk
+        finally:
+            blocks.close()
+
+    def _iter_blocks(self, base):
         idx = self.node_idx
         if self.shuffle:
             idx = idx[torch.randperm(idx.numel(), device=self.device, generator=self.generator)]
         starts = [s for s in range(0, idx.numel(), self.batch_size)
                   if not (self.drop_last and idx.numel() - s < self.batch_size)]
         if not self.prefetch:
-            for s in starts:
-                yield self.sample(idx[s:s + self.batch_size])
+            for i, s in enumerate(starts):
+                yield self.sample(idx[s:s + self.batch_size], base + i)
             return
         with torch.cuda.device(self.device):
             if self._side is None:
@@ -133,7 +165,7 @@ class NeighborSampler:
             free_ev = [torch.cuda.Event() for _ in range(3)]
             self._done_ev, self._done_k = [torch.cuda.Event() for _ in range(4)], 0
             try:
-                for s in starts:
+                for i, s in enumerate(starts):
                     blk = self._finish_on_side(pending) if pending is not None else None
                     pending = None
                     batch = idx[s:s + self.batch_size]      # (a row range of a contiguous vector: contiguous)
@@ -161,14 +193,14 @@ class NeighborSampler:
                         if cur_dev != want_dev:
                             torch._C._cuda_setDevice(want_dev)
                         try:
-                            pending = (self._start_regular(batch, background=True, b=ring[slot], stream=side.cuda_stream), None)
+                            pending = (self._start_regular(batch, background=True, b=ring[slot], stream=side.cuda_stream, draw=base + i), None)
                         finally:
                             if cur_dev != want_dev:
                                 torch._C._cuda_setDevice(cur_dev)
                     else:
                         with torch.cuda.device(self.device), torch.cuda.stream(side):
                             self._escaped = []
-                            pending = (self._start_regular(batch.contiguous(), background=True, b=None), self._escaped)
+                            pending = (self._start_regular(batch.contiguous(), background=True, b=None, draw=base + i), self._escaped)
                             self._escaped = None
                     k += 1
                     if blk is not None:
@@ -193,8 +225,8 @@ class NeighborSampler:
             return
         if self.prefetch != "thread":
             pending = None
-            for s in starts:
-                nxt = self._build_on_side(idx[s:s + self.batch_size])
+            for i, s in enumerate(starts):
+                nxt = self._build_on_side(idx[s:s + self.batch_size], base + i)
                 if pending is not None:
                     yield self._hand_over(pending)
                 pending = nxt
@@ -218,8 +250,8 @@ class NeighborSampler:
 
         def worker():
             try:
-                for s in starts:
-                    if stop.is_set() or not put(self._build_on_side(idx[s:s + self.batch_size])):
+                for i, s in enumerate(starts):
+                    if stop.is_set() or not put(self._build_on_side(idx[s:s + self.batch_size], base + i)):
                         return
                 put(None)
             except BaseException as e:   # surfaces in the consuming thread
@@ -256,10 +288,10 @@ class NeighborSampler:
                 self._escaped = None
             return (out, escaped, self._side.record_event())
 
-    def _build_on_side(self, batch):
+    def _build_on_side(self, batch, draw):
         with torch.cuda.device(self.device), torch.cuda.stream(self._side):
             self._escaped = []
-            out = self._sample(batch)
+            out = self._sample(batch, draw)
             item = (out, self._escaped, self._side.record_event())
             self._escaped = None
         return item
@@ -277,17 +309,24 @@ class NeighborSampler:
                 t.record_stream(cur)   # the allocator must not recycle them for the next block while this stream reads them
         return out
 
-    def sample(self, batch: torch.Tensor):
+    def sample(self, batch: torch.Tensor, draw: int = None):
+        """One block.  `draw` pins the block's draw number (sampled sizes: the block is a pure function of (batch, sizes, sample_seed, draw));
+        None takes the next one, `self.draws`, and counts it."""
+        if draw is None:
+            draw, self.draws = self.draws, self.draws + 1
         with torch.cuda.device(self.device):  # the plan's GPU, whatever the thread's current device is
-            return self._sample(batch)
+            return self._sample(batch, int(draw))
 
     def _alloc_regular(self, nb: int, want_t: bool):
-        """buffers of one batch of `nb` targets, sized by the 5^h growth bound (4-regular graph: 4 new sources per target at most),
-        and the argument arrays that only depend on them"""
+        """buffers of one batch of `nb` targets, sized by the growth bound nb x prod (1 + e_g) (4-regular graph: e_h = 4, or min(sizes[h], 4), new
+        sources per target at most), and the argument arrays that only depend on them"""
         import ctypes as C
         hops, dev = len(self.sizes), self.device
-        cap_t = [min(nb * 5 ** h, self.num_nodes) for h in range(hops)]
-        cap_e = [4 * t for t in cap_t]
+        cap_t, grown = [], nb
+        for e_h in self._keep:
+            cap_t.append(min(grown, self.num_nodes))
+            grown *= 1 + e_h
+        cap_e = [e_h * t for e_h, t in zip(self._keep, cap_t)]
         i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)      # nb > 0: every capacity is positive
         i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
         b = dict(cap_nb=nb, hops=hops, want_t=want_t,
@@ -305,6 +344,7 @@ class NeighborSampler:
             b["t_dst"], b["t_eid"], b["t_rows"] = ([i32(e) for e in cap_e] for _ in range(3))
             b["plan_scratch"] = plan_scratch = i32(max(int(L.dgnn_plan_scratch_elems(e, a)) for e, a in zip(cap_e, cap_all)))
             t_arrs = [arr(b[k]) for k in ("t_rowptr", "t_dst", "t_eid", "t_rows")]
+        b["sizes"] = (C.c_int32 * hops)(*self.sizes) if self._sampled else None
         b["args_tail"] = (arr(b["ei"]), arr(b["e_id"]), arr(b["src32"]), arr(b["e_id32"]), arr(b["off"]), arr(b["n_out"]), caps(cap_t), caps(cap_e),
                           ptr(scratch[:-1]), ptr(scratch[-1:]), *t_arrs, caps(cap_all) if want_t else None, ptr(plan_scratch))
         if self._rows:     # row gathers behind the block (attach_rows): outputs sized by the outermost block's bound / the batch
@@ -318,9 +358,10 @@ class NeighborSampler:
                               (C.c_int32 * k)(*[int(which == "batch") for _, _, _, which in self._rows]), (C.c_void_p * k)(*[o.data_ptr() for o in outs]))
         return b
 
-    def _start_regular(self, n_id: torch.Tensor, background: bool, b=None, stream=None):
+    def _start_regular(self, n_id: torch.Tensor, background: bool, b=None, stream=None, draw=0):
         """every node has exactly 4 in-edges: all hops (and, when iterating with prefetch, the transposed plans) in one library
-        call.  `background`: the call runs on a library-owned host thread (dgnn_khop_blocks_regular_start) and this returns at
+        call (dgnn_khop_blocks_regular*, or with sampled sizes dgnn_khop_blocks_sampled* and the block's `draw`).
+        `background`: the call runs on a library-owned host thread (the _start form) and this returns at
         once; _finish_regular joins it and cuts the views.  `b`: buffers to build into (a slot of the reuse ring), default fresh ones."""
         import ctypes as C
         p, nb = self.plan, n_id.numel()
@@ -329,20 +370,26 @@ class NeighborSampler:
         b["nb"], b["n_id"] = nb, n_id
         b["counts"] = counts = (C.c_int64 * (b["hops"] + 1))()
         L = lib()
-        args = (ptr(p.rowptr), ptr(p.src), ptr(p.eid), 4, ptr(n_id), nb, b["hops"], ptr(self._pos), ptr(self._first)) + b["args_tail"]
+        if self._sampled:
+            name = "dgnn_khop_blocks_sampled"
+            args = (ptr(p.rowptr), ptr(p.src), ptr(p.eid), 4, ptr(n_id), nb, b["hops"], b["sizes"], self.sample_seed, int(draw), ptr(self._pos),
+                    ptr(self._first)) + b["args_tail"]
+        else:
+            name = "dgnn_khop_blocks_regular"
+            args = (ptr(p.rowptr), ptr(p.src), ptr(p.eid), 4, ptr(n_id), nb, b["hops"], ptr(self._pos), ptr(self._first)) + b["args_tail"]
         if background and b.get("rows_args") is not None:
-            b["job"] = L.dgnn_khop_blocks_regular_start_rows(*args, *b["rows_args"], stream if stream is not None else stream_ptr())
+            b["job"] = getattr(L, name + "_start_rows")(*args, *b["rows_args"], stream if stream is not None else stream_ptr())
             if not b["job"]:
-                check(-1, "dgnn_khop_blocks_regular_start_rows")
+                check(-1, name + "_start_rows")
             b["rows_live"] = True
         elif background:
             b["rows_live"] = False
-            b["job"] = L.dgnn_khop_blocks_regular_start(*args, stream if stream is not None else stream_ptr())
+            b["job"] = getattr(L, name + "_start")(*args, stream if stream is not None else stream_ptr())
             if not b["job"]:
-                check(-1, "dgnn_khop_blocks_regular_start")
+                check(-1, name + "_start")
         else:
             b["rows_live"] = False
-            check(L.dgnn_khop_blocks_regular(*args, counts, stream_ptr()), "dgnn_khop_blocks_regular", poll=True)
+            check(getattr(L, name)(*args, counts, stream_ptr()), name, poll=True)
         return b
 
     def _finish_regular(self, b):
@@ -353,7 +400,7 @@ class NeighborSampler:
         adjs = []
         for h in range(hops):
             n_t, n_all = int(counts[h]), int(counts[h + 1])
-            n_e = 4 * n_t
+            n_e = self._keep[h] * n_t
             e = b["ei"][h][:, :n_e]     # a strided view: plans and kernels read edge lists in place
             # (buffer, length) pairs: the plan cuts a view when a tensor is asked for; the training step's library calls take the addresses
             plan = GraphPlan(e, n_all, n_t, parts=((b["off"][h], n_t + 1), (b["src32"][h], n_e), (self._arange_full(n_e), n_e)))
@@ -378,32 +425,42 @@ class NeighborSampler:
                 self._escaped += list(b["rows_out"])
         return b["nb"], n_id, adjs
 
-    def _sample_regular(self, n_id: torch.Tensor):
-        return self._finish_regular(self._start_regular(n_id, background=False))
+    def _sample_regular(self, n_id: torch.Tensor, draw=0):
+        return self._finish_regular(self._start_regular(n_id, background=False, draw=draw))
 
-    def _sample(self, batch: torch.Tensor):
+    def _sample(self, batch: torch.Tensor, draw=0):
         L, st, p = lib(), stream_ptr(), self.plan
         n_id = batch.to(self.device, torch.int64).contiguous()
         batch_size = n_id.numel()
         if self._regular and batch_size > 0 and ONE_CALL:
-            return self._sample_regular(n_id)
+            return self._sample_regular(n_id, draw)
         adjs = []
         for hop in range(len(self.sizes)):
             n_t = n_id.numel()
             off = torch.empty(n_t + 1, dtype=torch.int32, device=self.device)
             scratch = torch.empty(int(L.dgnn_khop_scratch_elems(n_t, 0)), dtype=torch.int32, device=self.device)
-            check(L.dgnn_khop_count(ptr(p.rowptr), ptr(n_id), n_t, int(hop == 0), ptr(self._pos), ptr(off), ptr(scratch), st),
-                  "dgnn_khop_count")
-            n_e = 4 * n_t if self._regular else int(off[n_t].item())  # sizes the block tensors
+            size = self.sizes[hop]
+            if size < 0:
+                check(L.dgnn_khop_count(ptr(p.rowptr), ptr(n_id), n_t, int(hop == 0), ptr(self._pos), ptr(off), ptr(scratch), st),
+                      "dgnn_khop_count")
+            else:
+                check(L.dgnn_khop_count_sampled(ptr(p.rowptr), ptr(n_id), n_t, int(hop == 0), size, self.sample_seed, draw, hop, ptr(self._pos), ptr(off),
+                                                ptr(scratch), st), "dgnn_khop_count_sampled")
+            n_e = self._keep[hop] * n_t if self._regular else int(off[n_t].item())  # sizes the block tensors
             ei = torch.empty((2, n_e), dtype=torch.int64, device=self.device)
             e_src, e_dst = ei[0], ei[1]
             e_id = torch.empty(n_e, dtype=torch.int64, device=self.device)
             n_id_out = torch.empty(n_t + n_e, dtype=torch.int64, device=self.device)
             n_new = torch.zeros(1, dtype=torch.int32, device=self.device)
             scratch = torch.empty(int(L.dgnn_khop_scratch_elems(n_t, n_e)), dtype=torch.int32, device=self.device)
-            check(L.dgnn_khop_expand(ptr(p.rowptr), ptr(p.src), ptr(p.eid), ptr(n_id), n_t, ptr(off), n_e, ptr(self._pos),
-                                     ptr(self._first), ptr(e_src), ptr(e_dst), ptr(e_id), ptr(n_id_out), ptr(n_new), ptr(scratch),
-                                     st), "dgnn_khop_expand")
+            if size < 0:
+                check(L.dgnn_khop_expand(ptr(p.rowptr), ptr(p.src), ptr(p.eid), ptr(n_id), n_t, ptr(off), n_e, ptr(self._pos),
+                                         ptr(self._first), ptr(e_src), ptr(e_dst), ptr(e_id), ptr(n_id_out), ptr(n_new), ptr(scratch),
+                                         st), "dgnn_khop_expand")
+            else:
+                check(L.dgnn_khop_expand_sampled(ptr(p.rowptr), ptr(p.src), ptr(p.eid), ptr(n_id), n_t, ptr(off), n_e, size, self.sample_seed, draw, hop,
+                                                 ptr(self._pos), ptr(self._first), ptr(e_src), ptr(e_dst), ptr(e_id), ptr(n_id_out), ptr(n_new),
+                                                 ptr(scratch), st), "dgnn_khop_expand_sampled")
             n_all = n_t + int(n_new.item())
             check(L.dgnn_khop_commit(ptr(n_id_out), n_t, n_all, ptr(self._pos), ptr(self._first), st), "dgnn_khop_commit")
             n_id = n_id_out[:n_all]

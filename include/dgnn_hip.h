@@ -760,8 +760,8 @@ enum dgnn_linear_variant {
 int dgnn_debug_last_linear_variant(void);
 
 /* ------------------------------------------------------------------------------------------------
- * k-hop full-neighbour block builder: GPU replacement of the CPU
- * torch_geometric NeighborSampler(edge_index, sizes=[-1]*k) the reference builds at run.py:72-74,221-223.
+ * k-hop block builder (full neighbourhoods here, sampled ones below): GPU replacement of the CPU
+ * torch_geometric NeighborSampler(edge_index, sizes) the reference builds at run.py:72-74,221-223.
  * One hop: dgnn_khop_count -> host reads off[n_t] (edge total) -> dgnn_khop_expand -> host reads *n_new ->
  * dgnn_khop_commit; dgnn_khop_reset after the last hop of a batch.  `pos` int32 [n_nodes] all -1 and `first`
  * int32 [n_nodes] all INT32_MAX between batches (dgnn_fill_i32).  rowptr/src/eid: the by-destination plan.
@@ -813,6 +813,42 @@ void* dgnn_khop_blocks_regular_start_rows(const int32_t* rowptr, const int32_t* 
                                           const int64_t* cap_all, int32_t* plan_scratch, int n_rows, const float* const* r_src, const int64_t* r_ld,
                                           const int32_t* r_cols, const int32_t* r_which, float* const* r_out, void* stream);
 int dgnn_khop_blocks_regular_wait(void* job, int hops, int64_t* counts_out);
+/* Sampled neighbourhoods (NeighborSampler sizes[h] > 0).  A target with global id g and d > size in-edges keeps the `size` of them with the
+ * smallest 64-bit keys, ties to the smaller j, and the kept ones stay in plan order:
+ *     mix = the splitmix64 finaliser;   key(j) = mix(mix(mix(seed + 0x9E3779B97F4A7C15 * (draw + 1)) ^ g) + ((hop << 32) | j))
+ * with j = 0..d-1 the rank of the in-edge in plan order -- a counter-based hash, no RNG state and no atomics: the block is a pure function of
+ * (graph, batch, size, seed, draw, hop).  Targets with d <= size, and size = -1, keep everything.  dgnn_khop_count_sampled /
+ * dgnn_khop_expand_sampled replace dgnn_khop_count / dgnn_khop_expand in the per-hop protocol above (off = scan of min(d, size); the same
+ * buffers; hop = 0 for the batch's own neighbourhood); size is -1 or > 0, draw >= 0, 0 <= hop < 65536. */
+int dgnn_khop_count_sampled(const int32_t* rowptr, const int64_t* n_id, int64_t n_t, int first_hop, int size, uint64_t seed, int64_t draw, int hop,
+                            int32_t* pos, int32_t* off, int32_t* scratch, void* stream);
+int dgnn_khop_expand_sampled(const int32_t* rowptr, const int32_t* src, const int32_t* eid, const int64_t* n_id, int64_t n_t, const int32_t* off,
+                             int64_t n_edges, int size, uint64_t seed, int64_t draw, int hop, int32_t* pos, int32_t* first, int64_t* e_src,
+                             int64_t* e_dst, int64_t* e_id, int64_t* n_id_out, int32_t* n_new_out, int32_t* scratch, void* stream);
+/* dgnn_khop_blocks_regular with sampled hops: sizes HOST int32 [hops] (-1 or > 0); hop h emits e_h = min(sizes[h], deg) edges per target (deg
+ * for -1), so its edge count counts[h] * e_h needs no read-back and off[h][i] = e_h * i.  Capacities: cap_t[h] >= targets of hop h (at most
+ * n_batch * prod_{g<h} (1 + e_g)), cap_e[h] >= e_h * cap_t[h]; row 1 of ei[h] starts at ei[h] + cap_e[h].  Everything else -- buffers,
+ * transposed plans, counts_out, DGNN_E_INVALID on a small capacity with pos / first left clean, the _start / _start_rows forms on the
+ * library's host thread, joined by dgnn_khop_blocks_regular_wait -- is as described there. */
+int dgnn_khop_blocks_sampled(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch, int64_t n_batch,
+                             int hops, const int32_t* sizes, uint64_t seed, int64_t draw, int32_t* pos, int32_t* first, int64_t* const* ei,
+                             int64_t* const* e_id, int32_t* const* src32, int32_t* const* e_id32, int32_t* const* off, int64_t* const* n_id_out,
+                             const int64_t* cap_t, const int64_t* cap_e, int32_t* scratch, int32_t* n_new_dev, int32_t* const* t_rowptr,
+                             int32_t* const* t_dst, int32_t* const* t_eid, int32_t* const* t_rows, const int64_t* cap_all, int32_t* plan_scratch,
+                             int64_t* counts_out, void* stream);
+void* dgnn_khop_blocks_sampled_start(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch, int64_t n_batch,
+                                     int hops, const int32_t* sizes, uint64_t seed, int64_t draw, int32_t* pos, int32_t* first, int64_t* const* ei,
+                                     int64_t* const* e_id, int32_t* const* src32, int32_t* const* e_id32, int32_t* const* off,
+                                     int64_t* const* n_id_out, const int64_t* cap_t, const int64_t* cap_e, int32_t* scratch, int32_t* n_new_dev,
+                                     int32_t* const* t_rowptr, int32_t* const* t_dst, int32_t* const* t_eid, int32_t* const* t_rows,
+                                     const int64_t* cap_all, int32_t* plan_scratch, void* stream);
+void* dgnn_khop_blocks_sampled_start_rows(const int32_t* rowptr, const int32_t* src, const int32_t* eid, int deg, const int64_t* batch,
+                                          int64_t n_batch, int hops, const int32_t* sizes, uint64_t seed, int64_t draw, int32_t* pos, int32_t* first,
+                                          int64_t* const* ei, int64_t* const* e_id, int32_t* const* src32, int32_t* const* e_id32,
+                                          int32_t* const* off, int64_t* const* n_id_out, const int64_t* cap_t, const int64_t* cap_e, int32_t* scratch,
+                                          int32_t* n_new_dev, int32_t* const* t_rowptr, int32_t* const* t_dst, int32_t* const* t_eid,
+                                          int32_t* const* t_rows, const int64_t* cap_all, int32_t* plan_scratch, int n_rows, const float* const* r_src,
+                                          const int64_t* r_ld, const int32_t* r_cols, const int32_t* r_which, float* const* r_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Logits -> labels -> interface facets (reference processing/generate_mesh.py:75 and :93-105).

@@ -3,7 +3,7 @@
 cell volume) on the synthetic 150k-point scene, everything on the GPU: k-hop block builder (dgnn_amd.sampler) ->
 SurfaceNet.forward (BN in train mode) -> loss -> backward through the HIP kernels -> Adam.
 
-    python tools/bench_train.py [--updated] [--dtype bf16] [--points P] [--batch B] [--steps K] [--edge-reg]
+    python tools/bench_train.py [--updated] [--dtype bf16] [--points P] [--batch B] [--steps K] [--edge-reg] [--sizes 2,2,2,2]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         tools/bench_train.py --gpus N ...
 
@@ -43,6 +43,9 @@ ap.add_argument("--prefetch", choices=["none", "stream", "thread"], default="str
 ap.add_argument("--fresh-blocks", action="store_true", help="fresh tensors for every block instead of the builder's ring of three buffer sets")
 ap.add_argument("--edge-reg", action="store_true", help="the edge total-variation regulariser on from the first step (regularization.edge_epoch 0, edge_weight "
                                                         "0.4): blocks of num_hops + 1 hops as run.py:68 builds them, the extra hop's block carries its edges")
+ap.add_argument("--sizes", type=str, default=None, help="neighbours kept per target and hop, builder hop 0 (the batch's own neighbourhood) first, e.g. 2,2,2,2 "
+                                                         "(graph.clique_sizes * num_hops of the reference; -1 = all); default: full neighbourhoods, -1 for every hop")
+ap.add_argument("--sample-seed", type=int, default=0, help="NeighborSampler sample_seed (sampled sizes only)")
 ap.add_argument("--no-roofline", action="store_true", help="skip the GEMM / aggregate replays behind the `roofline` object")
 args = ap.parse_args()
 
@@ -137,12 +140,16 @@ g = torch.Generator().manual_seed(rank)
 per = (n // batch) * batch     # whole batches per permutation: no duplicate targets inside a batch
 need = batch * (steps + args.warmup)
 idx = torch.cat([torch.randperm(n, generator=g)[:per] for _ in range(need // per + 1)])[:need]
-loader = NeighborSampler(ei, sizes=[-1] * hops, node_idx=idx.to(dev), num_nodes=n, batch_size=batch,
+sizes = [int(v) for v in args.sizes.split(",")] if args.sizes else [-1] * hops
+if len(sizes) != hops:
+    raise SystemExit("--sizes names %d hops, this configuration builds %d (num_hops%s)" % (len(sizes), hops, " + 1 for --edge-reg" if args.edge_reg else ""))
+loader = NeighborSampler(ei, sizes=sizes, sample_seed=args.sample_seed, node_idx=idx.to(dev), num_nodes=n, batch_size=batch,
                          prefetch={"none": False, "stream": True, "thread": "thread"}[args.prefetch], reuse_buffers=not args.fresh_blocks)
 if os.environ.get("DGNN_BLOCK_ROWS", "1") != "0":
     tr.attach_block_rows(loader, all_, net)      # x[n_id, 1:], x[ids], y[ids] gathered by the block builder behind every block (as Trainer.train_test does)
 it = iter(loader)
 block = 0
+hop_nodes = [0] * (hops + 1)      # targets, then the node count of every block from the innermost out, summed over the timed steps
 for _ in range(args.warmup):
     bs, n_id, adjs = next(it)
     tr.train(Config(all=all_, batch_n_id=n_id, batch_adjs=adjs), opt, clf)
@@ -159,6 +166,9 @@ t0 = time.perf_counter()
 for _ in range(steps):
     bs, n_id, adjs = next(it)
     block += int(n_id.numel())
+    hop_nodes[0] += bs
+    for h, a in enumerate(adjs[::-1]):
+        hop_nodes[h + 1] += a[2][0]
     loss = tr.train(Config(all=all_, batch_n_id=n_id, batch_adjs=adjs), opt, clf)
 host_dt = time.perf_counter() - t0      # the main thread has issued every step; what is left until sync() returns is the GPU's backlog
 sync()
@@ -258,6 +268,7 @@ if rank == 0:
                       "parallelism": "data-parallel replicas, one scene shard per GPU, flat RCCL all-reduce" if world > 1 else "single GPU",
                       "targets_per_s": round(batch * steps * world / dt, 1), "block_tets_per_s": round(block / dt, 1),
                       "ms_per_step": round(dt / steps * 1e3, 3), "host_issue_ms_per_step": round(host_dt / steps * 1e3, 3), "batch_targets_per_gpu": batch,
-                      "avg_block_tets": round(block / steps / world, 1), "steps": steps, "block_builder": args.prefetch, "scene_tets_per_gpu": n, "final_loss": float(loss), "train_loss_reg": clf.training.metrics.getRegLoss(), "replicas": replicas, "roofline": roof}))
+                      "avg_block_tets": round(block / steps / world, 1),
+                      "sizes": sizes, "avg_nodes_per_hop": [round(v / steps, 1) for v in hop_nodes], "steps": steps, "block_builder": args.prefetch, "scene_tets_per_gpu": n, "final_loss": float(loss), "train_loss_reg": clf.training.metrics.getRegLoss(), "replicas": replicas, "roofline": roof}))
 if world > 1:
     dist.destroy_process_group()
