@@ -103,6 +103,12 @@ SIGNATURES = {
     "dgnn_compact_vertices": (i32, [vp, i64, i64, vp, vp, vp, vp, vp]),
     "dgnn_mesh_topology_scratch_bytes": (i64, [i64, i64]),
     "dgnn_mesh_topology": (i32, [vp, i64, i64, vp, vp, vp]),
+    "dgnn_mesh_contains_scratch_bytes": (i64, [i64, i64, i32]),
+    "dgnn_mesh_contains_plan": (i32, [vp, i64, vp, i64, i32, i64, vp, vp, vp, vp]),
+    "dgnn_mesh_contains": (i32, [vp, i64, vp, i64, i32, i64, vp, i64, vp, vp, vp, i64, vp, vp]),
+    "dgnn_box_points": (i32, [i64, f64, u64, vp, vp]),
+    "dgnn_jitter_points": (i32, [vp, i64, f64, u64, vp, vp]),
+    "dgnn_face_normals": (i32, [vp, i64, vp, i64, vp, vp, vp]),
     "dgnn_khop_scratch_elems": (i64, [i64, i64]),
     "dgnn_khop_count": (i32, [vp, vp, i64, i32, vp, vp, vp, vp]),
     "dgnn_khop_expand": (i32, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

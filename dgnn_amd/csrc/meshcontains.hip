@@ -1,0 +1,370 @@
+// Point-in-mesh occupancy of an arbitrary triangle mesh (reference utils/libmesh: inside_mesh.py MeshIntersector.query with
+// triangle_hash.pyx as its candidate generator) and the three small generators of the evaluation-sample builder.  DESIGN §21.
+//
+//   rescale    vertices and points go to the hash frame in fp64: r(a) = scale * a + translate, two roundings, with scale = (R - 1) /
+//              (max - min) and translate = 0.5 - scale * min over the vertices the faces reference (host fp64, the same two expressions).
+//   candidates a uniform xy grid of ((R - 1) >> shift) + 1 cells per axis on int(coord) >> shift: a triangle is entered in every cell its
+//              xy bounding box touches (cells clamped to [0, R - 1] before the shift), a point reads the list of its own cell.  A point
+//              that passes the strict barycentric test of a triangle lies inside that triangle's box, so any shift offers a superset of
+//              the triangles that count and the answer is the all-pairs answer; shift = the smallest with at most max_entries entries.
+//              Built by count / scan / fill with ONE WORK ITEM PER (triangle, cell) ENTRY, so a triangle over the whole grid costs what
+//              its entries cost, spread over the machine.
+//   query      one lane per point (DESIGN §21 says why), every loop bounded by a list length; per candidate the reference's 2D test and
+//              depth, operand for operand; the two parities are integer counts, so the order inside a cell does not matter.
+//   generators box points, Gaussian jitter (Box-Muller) and face normals, all fp64, randomness from mm_hash (mesh_common.h).
+#include <math.h>
+
+#include "common.h"
+#include "mesh_common.h"
+
+int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* sums_scratch, hipStream_t stream);  // plan.hip
+
+namespace {
+
+constexpr int MC_THREADS = 256;
+constexpr int MC_MAX_R = 4096;     // hash_resolution; (MC_MAX_R - 1) >> (MC_SHIFTS - 1) == 0: the coarsest grid is one cell
+constexpr int MC_SHIFTS = 13;
+constexpr int32_t MC_BAD_ID = 1, MC_NONFINITE = 2;
+
+struct McState {
+    int32_t err, pad;
+    unsigned long long lo[3], hi[3];          // bbox of the referenced vertices (f64_key)
+    unsigned long long totals[MC_SHIFTS];     // (triangle, cell) entries at every shift
+    unsigned long long n_disagree;
+};
+
+struct Frame {          // by value to the kernels
+    double scale[3], translate[3];
+    int32_t R, shift, G;   // G cells per axis at `shift`
+};
+
+dim3 mc_grid(int64_t items) { return dim3(dgnn_grid_cap(dgnn_cdiv(items > 0 ? items : 1, MC_THREADS))); }
+
+// ---- validation and bounding box ----------------------------------------------------------------------------------------------
+__global__ void k_mc_check_faces(const int32_t* __restrict__ faces, int64_t n3, int64_t nv, McState* st) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x)
+        if (faces[i] < 0 || faces[i] >= nv) atomicOr(&st->err, MC_BAD_ID);
+}
+
+// faces are validated: min / max over the vertices they reference (integer keys: order-free)
+__global__ void k_mc_bbox(const double* __restrict__ v, const int32_t* __restrict__ faces, int64_t n3, McState* st) {
+    unsigned long long lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0, 0, 0};
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t id = faces[i];
+        for (int a = 0; a < 3; ++a) {
+            const double x = v[3 * id + a];
+            if (!isfinite(x)) { atomicOr(&st->err, MC_NONFINITE); continue; }
+            const unsigned long long k = f64_key(x);
+            lo[a] = k < lo[a] ? k : lo[a];
+            hi[a] = k > hi[a] ? k : hi[a];
+        }
+    }
+    for (int a = 0; a < 3; ++a) wave_minmax_atomic(lo[a], hi[a], &st->lo[a], &st->hi[a]);
+}
+
+// rv = scale * v + translate (a multiply, then an add: the library is built without contraction)
+__global__ void k_mc_rescale(const double* __restrict__ v, int64_t nv, Frame f, double* __restrict__ rv) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < 3 * nv; i += (int64_t)gridDim.x * blockDim.x) {
+        const int a = (int)(i % 3);
+        const double m = f.scale[a] * v[i];
+        rv[i] = m + f.translate[a];
+    }
+}
+
+// the reference's int(coord) clamped to [0, R - 1]; clamping first keeps the cast defined for any value
+__device__ __forceinline__ int32_t mc_cell(double x, int32_t R) { return !(x > 0) ? 0 : (x >= (double)(R - 1) ? R - 1 : (int32_t)x); }
+
+// tbox[t] = (x0, y0, x1, y1): the cells at full resolution of the triangle's xy bounding box; entries at every shift -> totals
+__global__ void __launch_bounds__(MC_THREADS) k_mc_tri_box(const double* __restrict__ rv, const int32_t* __restrict__ faces, int64_t nf, int32_t R,
+                                                           int4* __restrict__ tbox, McState* st) {
+    long long tot[MC_SHIFTS];
+#pragma unroll
+    for (int s = 0; s < MC_SHIFTS; ++s) tot[s] = 0;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nf; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t a = faces[3 * t], b = faces[3 * t + 1], c = faces[3 * t + 2];
+        const double ax = rv[3 * a], ay = rv[3 * a + 1], bx = rv[3 * b], by = rv[3 * b + 1], cx = rv[3 * c], cy = rv[3 * c + 1];
+        const int32_t x0 = mc_cell(fmin(fmin(ax, bx), cx), R), x1 = mc_cell(fmax(fmax(ax, bx), cx), R);
+        const int32_t y0 = mc_cell(fmin(fmin(ay, by), cy), R), y1 = mc_cell(fmax(fmax(ay, by), cy), R);
+        tbox[t] = make_int4(x0, y0, x1, y1);
+#pragma unroll
+        for (int s = 0; s < MC_SHIFTS; ++s) tot[s] += (long long)((x1 >> s) - (x0 >> s) + 1) * ((y1 >> s) - (y0 >> s) + 1);
+    }
+#pragma unroll
+    for (int s = 0; s < MC_SHIFTS; ++s) {
+        long long x = tot[s];
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+        if (lane_id() == 0 && x) atomicAdd(&st->totals[s], (unsigned long long)x);   // integer sums: order-free
+    }
+}
+
+// ---- the grid: count / scan / fill, one work item per (triangle, cell) entry ------------------------------------------------------
+__global__ void k_mc_tri_count(const int4* __restrict__ tbox, int64_t nf, int32_t shift, int32_t* __restrict__ tcnt) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nf; t += (int64_t)gridDim.x * blockDim.x) {
+        const int4 b = tbox[t];
+        tcnt[t] = ((b.z >> shift) - (b.x >> shift) + 1) * ((b.w >> shift) - (b.y >> shift) + 1);
+    }
+}
+
+// entry e belongs to the triangle t with toff[t] <= e < toff[t + 1] (toff ascending, toff[nf] = n_entries: the search ends inside
+// [0, nf)); its cell is the (e - toff[t])-th of the triangle's box, row-major
+__device__ __forceinline__ int32_t mc_entry(const int32_t* __restrict__ toff, const int4* __restrict__ tbox, int64_t nf, int32_t shift, int32_t G,
+                                            int32_t e, int32_t* cell) {
+    int64_t lo = 0, hi = nf - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (toff[mid] <= e) lo = mid;
+        else hi = mid - 1;
+    }
+    const int4 b = tbox[lo];
+    const int32_t y0 = b.y >> shift, ny = (b.w >> shift) - y0 + 1, k = e - toff[lo];
+    *cell = G * ((b.x >> shift) + k / ny) + y0 + k % ny;
+    return (int32_t)lo;
+}
+
+// fill == 0: ccnt[cell] += 1; fill != 0: entries[cursor[cell]++] = t (the order inside a cell is whatever the atomics give: the query
+// only counts)
+__global__ void k_mc_entries(const int32_t* __restrict__ toff, const int4* __restrict__ tbox, int64_t nf, int32_t shift, int32_t G, int64_t n_entries,
+                             int fill, int32_t* __restrict__ ccnt, int32_t* __restrict__ entries) {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n_entries; e += (int64_t)gridDim.x * blockDim.x) {
+        int32_t cell;
+        const int32_t t = mc_entry(toff, tbox, nf, shift, G, (int32_t)e, &cell);
+        const int32_t slot = atomicAdd(ccnt + cell, 1);
+        if (fill) entries[slot] = t;
+    }
+}
+
+// ---- the query -----------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(MC_THREADS) k_mc_query(const double* __restrict__ rv, const int32_t* __restrict__ faces,
+                                                         const int32_t* __restrict__ rowptr, const int32_t* __restrict__ entries, Frame f,
+                                                         const double* __restrict__ pts, int64_t np, uint8_t* __restrict__ out, McState* st) {
+    long long dis = 0;
+    const double Rd = (double)f.R;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < np; i += (int64_t)gridDim.x * blockDim.x) {
+        double p[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double m = f.scale[a] * pts[3 * i + a];
+            p[a] = m + f.translate[a];
+        }
+        uint32_t above = 0, below = 0;
+        // the box test is false for NaN; x, y < R as the hash's own test (a coordinate equal to R is in no cell)
+        if (0 <= p[0] && p[0] < Rd && 0 <= p[1] && p[1] < Rd && 0 <= p[2] && p[2] <= Rd) {
+            const int32_t cell = f.G * ((int32_t)p[0] >> f.shift) + ((int32_t)p[1] >> f.shift);
+            for (int32_t s = rowptr[cell], e = rowptr[cell + 1]; s < e; ++s) {
+                const int64_t t = entries[s];
+                const double* t1 = rv + 3 * (int64_t)faces[3 * t];
+                const double* t2 = rv + 3 * (int64_t)faces[3 * t + 1];
+                const double* t3 = rv + 3 * (int64_t)faces[3 * t + 2];
+                const double t1x = t1[0], t1y = t1[1], t1z = t1[2], t2x = t2[0], t2y = t2[1], t2z = t2[2], t3x = t3[0], t3y = t3[1], t3z = t3[2];
+                // check_triangles: A = [t1 - t3, t2 - t3] as columns, y = p - t3
+                const double a00 = t1x - t3x, a01 = t2x - t3x, a10 = t1y - t3y, a11 = t2y - t3y;
+                const double y0 = p[0] - t3x, y1 = p[1] - t3y;
+                const double det = a00 * a11 - a01 * a10;
+                if (!(fabs(det) != 0.)) continue;
+                const double sd = det > 0 ? 1.0 : (det < 0 ? -1.0 : det), ad = fabs(det);   // np.sign (nan stays nan)
+                const double u = (a11 * y0 - a01 * y1) * sd;
+                const double v = (-a10 * y0 + a00 * y1) * sd;
+                const double uv = u + v;
+                if (!(0 < u && u < ad && 0 < v && v < ad && 0 < uv && uv < ad)) continue;
+                // compute_intersection_depth: normals = cross(t3 - t1, t2 - t1)
+                const double v1x = t3x - t1x, v1y = t3y - t1y, v1z = t3z - t1z, v2x = t2x - t1x, v2y = t2y - t1y, v2z = t2z - t1z;
+                const double n0 = v1y * v2z - v1z * v2y, n1 = v1z * v2x - v1x * v2z, n2 = v1x * v2y - v1y * v2x;
+                const double alpha = n0 * (t1x - p[0]) + n1 * (t1y - p[1]);
+                const double an = fabs(n2);
+                if (!(an != 0)) continue;                                 // depth = nan: neither above nor below
+                const double sn = n2 > 0 ? 1.0 : (n2 < 0 ? -1.0 : n2);
+                const double depth = t1z * an + alpha * sn, rhs = p[2] * an;
+                above += depth >= rhs;
+                below += depth < rhs;
+            }
+        }
+        const uint32_t c1 = above & 1, c2 = below & 1;
+        out[i] = (uint8_t)(c1 & c2);
+        dis += c1 != c2;
+    }
+    for (int o = 32; o > 0; o >>= 1) dis += __shfl_xor(dis, o);
+    if (lane_id() == 0 && dis) atomicAdd(&st->n_disagree, (unsigned long long)dis);   // integer sum: order-free
+}
+
+__global__ void k_mc_disagree_out(const McState* st, int64_t* out) {
+    if (threadIdx.x == 0) *out = (int64_t)st->n_disagree;
+}
+
+// ---- generators ------------------------------------------------------------------------------------------------------------------
+__global__ void k_box_points(int64_t n3, double boxsize, uint64_t seed, double* __restrict__ out) {
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n3; j += (int64_t)gridDim.x * blockDim.x)
+        out[j] = boxsize * (mm_u01(mm_hash(seed, (uint64_t)j + 1)) - 0.5);
+}
+
+// out[j] = pts[j] + sigma * (sqrt(-2 log u1) cos(2 pi u2)), u1 in (0, 1] from counter 2 j + 1, u2 in [0, 1) from 2 j + 2
+__global__ void k_jitter_points(const double* __restrict__ pts, int64_t n3, double sigma, uint64_t seed, double* __restrict__ out) {
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n3; j += (int64_t)gridDim.x * blockDim.x) {
+        const double u1 = mm_u01_open0(mm_hash(seed, 2 * (uint64_t)j + 1)), u2 = mm_u01(mm_hash(seed, 2 * (uint64_t)j + 2));
+        const double z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+        out[j] = pts[j] + sigma * z;
+    }
+}
+
+__global__ void k_face_normals(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ faces, int64_t nf, double* __restrict__ out,
+                               McState* st) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nf; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t a = faces[3 * t], b = faces[3 * t + 1], c = faces[3 * t + 2];
+        double nx = 0, ny = 0, nz = 0;
+        if (a < 0 || a >= nv || b < 0 || b >= nv || c < 0 || c >= nv) {
+            atomicOr(&st->err, MC_BAD_ID);
+        } else {
+            const double ux = v[3 * b] - v[3 * a], uy = v[3 * b + 1] - v[3 * a + 1], uz = v[3 * b + 2] - v[3 * a + 2];
+            const double wx = v[3 * c] - v[3 * a], wy = v[3 * c + 1] - v[3 * a + 1], wz = v[3 * c + 2] - v[3 * a + 2];
+            const double cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
+            const double len = sqrt(cx * cx + cy * cy + cz * cz);
+            if (len > 0 && isfinite(len)) { nx = cx / len; ny = cy / len; nz = cz / len; }   // a degenerate face: zeros
+        }
+        out[3 * t] = nx; out[3 * t + 1] = ny; out[3 * t + 2] = nz;
+    }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------
+struct McLayout { McState* st; double* rv; int4* tbox; int32_t *tcnt, *toff, *ccnt, *rowptr, *sums; int64_t bytes; };
+McLayout mc_layout(void* base, int64_t nv, int64_t nf, int64_t R) {
+    Take t{(char*)base, 256};
+    McLayout L{};
+    L.st = (McState*)base;
+    const int64_t cells = R * R, m = nf > cells ? nf : cells;
+    L.rv = t.take<double>(3 * nv);
+    L.tbox = t.take<int4>(nf);
+    L.tcnt = t.take<int32_t>(nf + 1);
+    L.toff = t.take<int32_t>(nf + 1);
+    L.ccnt = t.take<int32_t>(cells + 1);
+    L.rowptr = t.take<int32_t>(cells + 1);
+    L.sums = t.take<int32_t>(dgnn_cdiv(m + 1, 2048) + 2);
+    L.bytes = t.off;
+    return L;
+}
+
+int mc_status(const McState& hs, const char* what) {
+    if (!hs.err) return DGNN_OK;
+    dgnn_set_error("%s: %s%s", what, hs.err & MC_BAD_ID ? "a face's vertex id out of range; " : "",
+                   hs.err & MC_NONFINITE ? "a non-finite coordinate of a referenced vertex; " : "");
+    return DGNN_E_INVALID;
+}
+
+// validation, bounding box, rescaled vertices, per-triangle boxes and the choice of the shift.  On success rv / tbox of L are filled, *fr is
+// the frame and *n_entries the entries at fr->shift.  Synchronises three times.
+int mc_plan(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf, int32_t R, int64_t max_entries, const McLayout& L, Frame* fr,
+            int64_t* n_entries, hipStream_t stream, const char* what) {
+    DGNN_REQUIRE(nv >= 0 && nf >= 0 && (nv == 0 || vertices) && (nf == 0 || faces) && L.st, DGNN_E_INVALID, "%s: bad args", what);
+    DGNN_REQUIRE(nf > 0, DGNN_E_INVALID, "%s: a mesh without faces", what);
+    DGNN_REQUIRE(R >= 2, DGNN_E_INVALID, "%s: hash_resolution %d < 2", what, R);
+    DGNN_REQUIRE(R <= MC_MAX_R, DGNN_E_UNSUPPORTED, "%s: hash_resolution %d above %d", what, R, MC_MAX_R);
+    DGNN_REQUIRE(max_entries >= 1, DGNN_E_INVALID, "%s: max_entries < 1", what);
+    DGNN_REQUIRE(nf < INT32_MAX / 4 && nv < INT32_MAX, DGNN_E_UNSUPPORTED, "%s: sizes exceed the int32 indexing", what);
+    const dim3 block(MC_THREADS);
+    McState hs{};
+    hs.lo[0] = hs.lo[1] = hs.lo[2] = ~0ull;
+    (void)hipMemcpyAsync(L.st, &hs, sizeof(McState), hipMemcpyHostToDevice, stream);
+    hipLaunchKernelGGL(k_mc_check_faces, mc_grid(3 * nf), block, 0, stream, faces, 3 * nf, nv, L.st);
+    int rc = dgnn_check_launch(what);
+    if (rc || (rc = mm_read(&hs, L.st, sizeof(McState), stream, what)) || (rc = mc_status(hs, what))) return rc;   // ids are read below: checked first
+    hipLaunchKernelGGL(k_mc_bbox, mc_grid(3 * nf), block, 0, stream, vertices, faces, 3 * nf, L.st);
+    if ((rc = dgnn_check_launch(what)) || (rc = mm_read(&hs, L.st, sizeof(McState), stream, what)) || (rc = mc_status(hs, what))) return rc;
+    Frame f{};
+    f.R = R;
+    for (int a = 0; a < 3; ++a) {
+        const double lo = f64_unkey(hs.lo[a]), hi = f64_unkey(hs.hi[a]);
+        const double ext = hi - lo;
+        DGNN_REQUIRE(ext > 0, DGNN_E_INVALID, "%s: the mesh has no extent on axis %d", what, a);
+        f.scale[a] = (double)(R - 1) / ext;
+        const double m = f.scale[a] * lo;
+        f.translate[a] = 0.5 - m;
+        DGNN_REQUIRE(isfinite(f.scale[a]) && isfinite(f.translate[a]), DGNN_E_INVALID, "%s: the extent %g of axis %d does not rescale", what, ext, a);
+    }
+    hipLaunchKernelGGL(k_mc_rescale, mc_grid(3 * nv), block, 0, stream, vertices, nv, f, L.rv);
+    hipLaunchKernelGGL(k_mc_tri_box, mc_grid(nf), block, 0, stream, L.rv, faces, nf, R, L.tbox, L.st);
+    if ((rc = dgnn_check_launch(what)) || (rc = mm_read(&hs, L.st, sizeof(McState), stream, what))) return rc;
+    int s = 0;
+    while (s < MC_SHIFTS && hs.totals[s] > (unsigned long long)max_entries) ++s;
+    DGNN_REQUIRE(s < MC_SHIFTS, DGNN_E_UNSUPPORTED, "%s: max_entries %lld is below the number of faces %lld", what, (long long)max_entries, (long long)nf);
+    DGNN_REQUIRE(hs.totals[s] < (unsigned long long)INT32_MAX, DGNN_E_UNSUPPORTED, "%s: %llu hash entries exceed the int32 indexing", what, hs.totals[s]);
+    f.shift = s;
+    f.G = ((R - 1) >> s) + 1;
+    *fr = f;
+    *n_entries = (int64_t)hs.totals[s];
+    return DGNN_OK;
+}
+
+}  // namespace
+
+// ================================================================================================================================
+extern "C" int64_t dgnn_mesh_contains_scratch_bytes(int64_t n_vertices, int64_t n_faces, int32_t hash_resolution) {
+    if (n_vertices < 0 || n_faces < 0 || hash_resolution < 2 || hash_resolution > MC_MAX_R) return 256;
+    return mc_layout(nullptr, n_vertices, n_faces, hash_resolution).bytes;
+}
+
+extern "C" int dgnn_mesh_contains_plan(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t hash_resolution,
+                                       int64_t max_entries, int32_t* shift_out, int64_t* n_entries_out, void* scratch, void* stream_) {
+    DGNN_REQUIRE(scratch && shift_out && n_entries_out, DGNN_E_INVALID, "mesh_contains_plan: bad args");
+    Frame f{};
+    const McLayout L = mc_layout(scratch, n_vertices > 0 ? n_vertices : 0, n_faces > 0 ? n_faces : 0,
+                                 hash_resolution >= 2 && hash_resolution <= MC_MAX_R ? hash_resolution : 2);
+    const int rc = mc_plan(vertices, n_vertices, faces, n_faces, hash_resolution, max_entries, L, &f, n_entries_out, (hipStream_t)stream_, "mesh_contains_plan");
+    if (rc) return rc;
+    *shift_out = f.shift;
+    return DGNN_OK;
+}
+
+extern "C" int dgnn_mesh_contains(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t hash_resolution,
+                                  int64_t max_entries, const double* points, int64_t n_points, uint8_t* contains_out, int64_t* n_disagree_out,
+                                  int32_t* entries, int64_t entry_capacity, void* scratch, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DGNN_REQUIRE(scratch && n_points >= 0 && entry_capacity >= 0 && (n_points == 0 || (points && contains_out)), DGNN_E_INVALID, "mesh_contains: bad args");
+    DGNN_REQUIRE(n_points < INT32_MAX, DGNN_E_UNSUPPORTED, "mesh_contains: sizes exceed the int32 indexing");
+    Frame f{};
+    int64_t ne = 0;
+    const McLayout L = mc_layout(scratch, n_vertices > 0 ? n_vertices : 0, n_faces > 0 ? n_faces : 0,
+                                 hash_resolution >= 2 && hash_resolution <= MC_MAX_R ? hash_resolution : 2);
+    int rc = mc_plan(vertices, n_vertices, faces, n_faces, hash_resolution, max_entries, L, &f, &ne, stream, "mesh_contains");
+    if (rc) return rc;
+    DGNN_REQUIRE(entries && ne <= entry_capacity, DGNN_E_INVALID, "mesh_contains: %lld hash entries, room for %lld (dgnn_mesh_contains_plan gives the number)",
+                 (long long)ne, (long long)entry_capacity);
+    if (n_disagree_out) (void)hipMemsetAsync(n_disagree_out, 0, sizeof(int64_t), stream);
+    if (n_points == 0) return dgnn_check_launch("mesh_contains");
+    const dim3 block(MC_THREADS);
+    const int64_t cells = (int64_t)f.G * f.G;
+    hipLaunchKernelGGL(k_mc_tri_count, mc_grid(n_faces), block, 0, stream, L.tbox, n_faces, f.shift, L.tcnt);
+    if ((rc = dgnn_exclusive_scan_i32(L.tcnt, n_faces, L.toff, L.sums, stream))) return rc;
+    (void)hipMemsetAsync(L.ccnt, 0, sizeof(int32_t) * (cells + 1), stream);
+    hipLaunchKernelGGL(k_mc_entries, mc_grid(ne), block, 0, stream, L.toff, L.tbox, n_faces, f.shift, f.G, ne, 0, L.ccnt, (int32_t*)nullptr);
+    if ((rc = dgnn_exclusive_scan_i32(L.ccnt, cells, L.rowptr, L.sums, stream))) return rc;
+    (void)hipMemcpyAsync(L.ccnt, L.rowptr, sizeof(int32_t) * (cells + 1), hipMemcpyDeviceToDevice, stream);   // the fill's cursors
+    hipLaunchKernelGGL(k_mc_entries, mc_grid(ne), block, 0, stream, L.toff, L.tbox, n_faces, f.shift, f.G, ne, 1, L.ccnt, entries);
+    hipLaunchKernelGGL(k_mc_query, mc_grid(n_points), block, 0, stream, L.rv, faces, L.rowptr, entries, f, points, n_points, contains_out, L.st);
+    if (n_disagree_out) hipLaunchKernelGGL(k_mc_disagree_out, dim3(1), dim3(64), 0, stream, L.st, n_disagree_out);
+    return dgnn_check_launch("mesh_contains");
+}
+
+extern "C" int dgnn_box_points(int64_t n_points, double boxsize, uint64_t seed, double* points_out, void* stream_) {
+    DGNN_REQUIRE(n_points >= 0 && (n_points == 0 || points_out), DGNN_E_INVALID, "box_points: bad args");
+    if (n_points > 0) hipLaunchKernelGGL(k_box_points, mc_grid(3 * n_points), dim3(MC_THREADS), 0, (hipStream_t)stream_, 3 * n_points, boxsize, seed, points_out);
+    return dgnn_check_launch("box_points");
+}
+
+extern "C" int dgnn_jitter_points(const double* points, int64_t n_points, double sigma, uint64_t seed, double* points_out, void* stream_) {
+    DGNN_REQUIRE(n_points >= 0 && (n_points == 0 || (points && points_out)), DGNN_E_INVALID, "jitter_points: bad args");
+    if (n_points > 0)
+        hipLaunchKernelGGL(k_jitter_points, mc_grid(3 * n_points), dim3(MC_THREADS), 0, (hipStream_t)stream_, points, 3 * n_points, sigma, seed, points_out);
+    return dgnn_check_launch("jitter_points");
+}
+
+extern "C" int dgnn_face_normals(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, double* normals_out, void* scratch,
+                                 void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    DGNN_REQUIRE(n_vertices >= 0 && n_faces >= 0 && scratch && (n_faces == 0 || (faces && normals_out)) && (n_vertices == 0 || vertices), DGNN_E_INVALID,
+                 "face_normals: bad args");
+    McState* st = (McState*)scratch;
+    McState hs{};
+    (void)hipMemsetAsync(st, 0, sizeof(McState), stream);
+    if (n_faces > 0) hipLaunchKernelGGL(k_face_normals, mc_grid(n_faces), dim3(MC_THREADS), 0, stream, vertices, n_vertices, faces, n_faces, normals_out, st);
+    int rc = dgnn_check_launch("face_normals");
+    if (rc || (rc = mm_read(&hs, st, sizeof(McState), stream, "face_normals"))) return rc;
+    return mc_status(hs, "face_normals");
+}

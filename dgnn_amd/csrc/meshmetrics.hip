@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "mesh_common.h"
 
 int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* sums_scratch, hipStream_t stream);  // plan.hip
 
@@ -47,16 +48,6 @@ inline float f32_unkey(unsigned int k) {
     float f;
     memcpy(&f, &u, 4);
     return f;
-}
-__device__ __forceinline__ unsigned long long f64_key(double x) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-inline double f64_unkey(unsigned long long k) {
-    const unsigned long long u = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
-    double d;
-    memcpy(&d, &u, 8);
-    return d;
 }
 
 __device__ __forceinline__ void mm_block_add(unsigned long long* dst, long long v) {
@@ -144,20 +135,6 @@ __global__ void k_fill_i32(int32_t* __restrict__ x, int64_t n, int32_t v) {
 }
 
 // ---- neighbour table ---------------------------------------------------------------------------------------------------------
-// min / max keys: per thread, then per wave, then one atomic per wave and axis
-template <typename K>
-__device__ __forceinline__ void wave_minmax_atomic(K lo, K hi, K* dlo, K* dhi) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const K a = __shfl_xor(lo, o), b = __shfl_xor(hi, o);
-        lo = a < lo ? a : lo;
-        hi = b > hi ? b : hi;
-    }
-    if (lane_id() == 0) {
-        if (lo != (K)~(K)0) atomicMin(dlo, lo);
-        if (hi != (K)0) atomicMax(dhi, hi);
-    }
-}
-
 __global__ void k_check_vertices(const double* __restrict__ v, int64_t nv, MmState* st) {
     unsigned long long lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0, 0, 0};
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
@@ -353,13 +330,6 @@ __global__ void k_chunk_add(double* __restrict__ x, int64_t n, const double* __r
 }
 
 // ---- sampler -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mm_hash(uint64_t seed, uint64_t ctr) {
-    uint64_t z = seed + ctr * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 __global__ void k_face_area(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ facets, int64_t n_facets,
                             const int32_t* __restrict__ face_ids, int64_t nfc, double* __restrict__ area, MmState* st) {
     for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < nfc; j += (int64_t)gridDim.x * blockDim.x) {
@@ -504,17 +474,6 @@ __global__ void k_nn_query(const int32_t* __restrict__ rowptr, const float4* __r
 }
 
 // ---- scratch layouts -----------------------------------------------------------------------------------------------------------
-struct Take {
-    char* p;
-    int64_t off;
-    template <typename T>
-    T* take(int64_t elems) {
-        T* q = (T*)(p ? p + off : nullptr);
-        off += (((elems > 0 ? elems : 1) * (int64_t)sizeof(T) + 255) / 256) * 256;
-        return q;
-    }
-};
-
 int64_t start_bins(int64_t nc) { return nc / 2 > 1 ? nc / 2 : 1; }
 int64_t nn_bins(int64_t nr) { return nr > 1 ? nr : 1; }
 
@@ -555,14 +514,6 @@ NnLayout nn_layout(void* base, int64_t nr, int64_t nq) {
     L.part = t.take<double>(dgnn_cdiv(nq, MM_SUM_CHUNK) + 1);
     L.bytes = t.off;
     return L;
-}
-
-int mm_read(void* dst, const void* src, size_t bytes, hipStream_t stream, const char* what) {
-    if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-        dgnn_set_error("%s: %s", what, hipGetErrorString(hipGetLastError()));
-        return DGNN_E_LAUNCH;
-    }
-    return DGNN_OK;
 }
 
 int mm_status(const MmState& hs, const char* what) {

@@ -1877,6 +1877,108 @@ def mesh_topology(faces, n_vertices):
     return out
 
 
+# ---- occupancy of any triangle mesh and the evaluation-sample generators (csrc/meshcontains.hip; reference utils/libmesh) ----------
+def _check_value(code, what):
+    """`check`, with the library's "bad input" status as the ValueError a Python caller expects for bad data"""
+    if code == -1:
+        raise ValueError("%s: %s" % (what, lib().dgnn_last_error_string().decode()))
+    check(code, what)
+
+
+def _points64(points, dev):
+    t = torch.as_tensor(points)
+    if t.dtype not in (torch.float16, torch.float32, torch.float64):
+        raise ValueError("points must be fp16, fp32 or fp64, got %s" % t.dtype)
+    return _on(t, dev, torch.float64, 3)     # every fp16 / fp32 value is an fp64 value: exact
+
+
+@on_device_of
+def mesh_contains(vertices, faces, points, hash_resolution=512, max_entries=2 ** 30):
+    """check_mesh_contains(mesh, points, hash_resolution) of the reference's utils/libmesh on the device (dgnn_mesh_contains; the
+    arithmetic is in include/dgnn_hip.h): vertices [V, 3] and points [n, 3] (fp16 / fp32 / fp64, tensor or ndarray) are promoted to fp64,
+    faces int [F, 3].  -> (contains bool [n] on the GPU, n_disagree: the points whose two ray parities differ, for which the reference
+    prints its warning).  max_entries caps the (triangle, cell) entries of the candidate grid, which is coarsened to fit; the answer does
+    not depend on it.  ValueError for a mesh without faces or without extent on an axis, a face id out of range or a non-finite
+    referenced vertex; DgnnError for hash_resolution above 4096 or max_entries below the number of faces."""
+    dev = _dev_of(points, vertices, faces)
+    v = _on(vertices, dev, torch.float64, 3)
+    f = _on(faces, dev, torch.int32, 3)
+    pts = _points64(points, dev)
+    nv, nf, n, R = v.size(0), f.size(0), pts.size(0), int(hash_resolution)
+    if nf == 0:
+        raise ValueError("mesh_contains: a mesh without faces")
+    out = torch.empty(max(n, 1), dtype=torch.bool, device=dev)[:n]
+    if n == 0:
+        return out, 0
+    scratch = torch.empty(int(lib().dgnn_mesh_contains_scratch_bytes(nv, nf, R)), dtype=torch.uint8, device=dev)
+    shift, n_entries = C.c_int32(0), C.c_int64(0)
+    _check_value(lib().dgnn_mesh_contains_plan(ptr(v), nv, ptr(f), nf, R, int(max_entries), C.byref(shift), C.byref(n_entries), ptr(scratch),
+                                               stream_ptr()), "dgnn_mesh_contains_plan")
+    cap = max(int(n_entries.value), 1)
+    entries = torch.empty(cap, dtype=torch.int32, device=dev)
+    dis = torch.zeros(1, dtype=torch.int64, device=dev)
+    _check_value(lib().dgnn_mesh_contains(ptr(v), nv, ptr(f), nf, R, int(max_entries), ptr(pts), n, ptr(out), ptr(dis), ptr(entries), cap,
+                                          ptr(scratch), stream_ptr()), "dgnn_mesh_contains")
+    return out, int(dis.item())
+
+
+def mesh_occupancy_iou(vertices, faces, points, occ_gt):
+    """IoU of the mesh's occupancy at `points` (mesh_contains) with the ground-truth occupancies occ_gt [n] (non-zero = inside), as
+    compute_iou computes it (the integer counts of iou_counts, float32 ratio; nan for an empty union): the reference's `iou` metric
+    (processing/generate_mesh.py:139-141) for a mesh from anywhere.  -> (iou float, occupancy bool [n] on the GPU, |A n B|, |A u B|)."""
+    import numpy as np
+
+    occ, n_disagree = mesh_contains(vertices, faces, points)
+    if n_disagree:
+        print("Warning: contains1 != contains2 for some points.")
+    cells = occ.to(torch.int32) - 1                                  # "cell 0, labelled inside" or "no cell"
+    _, inter, union = iou_counts(cells, torch.zeros(1, dtype=torch.int32, device=occ.device), occ_gt)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        iou = float(np.float32(inter) / np.float32(union))
+    return iou, occ, inter, union
+
+
+@on_device_of
+def face_normals(vertices, faces):
+    """Unit normals fp64 [F, 3] on the GPU of the faces (v0, v1, v2): (v1 - v0) x (v2 - v0), normalised; zeros for a face without area
+    (dgnn_face_normals).  ValueError for a face id out of range."""
+    dev = _dev_of(vertices, faces)
+    v = _on(vertices, dev, torch.float64, 3)
+    f = _on(faces, dev, torch.int32, 3)
+    nf = f.size(0)
+    out = torch.empty(max(nf, 1), 3, dtype=torch.float64, device=dev)[:nf]
+    scratch = torch.empty(256, dtype=torch.uint8, device=dev)
+    _check_value(lib().dgnn_face_normals(ptr(v), v.size(0), ptr(f), nf, ptr(out), ptr(scratch), stream_ptr()), "dgnn_face_normals")
+    return out
+
+
+def _seed64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def box_points(n, boxsize, seed=0, device=None):
+    """n points fp64 [n, 3] on the GPU, uniform in the cube of edge `boxsize` about the origin: boxsize * (u - 0.5) with u in [0, 1) from
+    mm_hash(seed, .) (dgnn_box_points; include/dgnn_hip.h)."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    n = int(n)
+    with torch.cuda.device(dev):
+        out = torch.empty(max(n, 1), 3, dtype=torch.float64, device=dev)[:n]
+        check(lib().dgnn_box_points(n, float(boxsize), _seed64(seed), ptr(out), stream_ptr()), "dgnn_box_points")
+    return out
+
+
+@on_device_of
+def jitter_points(points64, sigma, seed=0):
+    """points64 (fp64 [n, 3]) + sigma * N(0, 1) per coordinate, Box-Muller in fp64 on two mm_hash draws (dgnn_jitter_points) -> a new
+    fp64 tensor on the GPU."""
+    dev = _dev_of(points64)
+    p = _on(points64, dev, torch.float64, 3)
+    n = p.size(0)
+    out = torch.empty(max(n, 1), 3, dtype=torch.float64, device=dev)[:n]
+    check(lib().dgnn_jitter_points(ptr(p), n, float(sigma), _seed64(seed), ptr(out), stream_ptr()), "dgnn_jitter_points")
+    return out
+
+
 # ---- ingest: feature scaling (csrc/ingest.hip) ------------------------------------------------------------------------------------
 SCALE_KINDS = {"none": 0, "standard": 1, "minmax": 2, "robust": 3}
 

@@ -149,6 +149,28 @@ def iou_gpu(data, mdata, labels):
     return iou
 
 
+def load_occupancy(path):
+    """ONet's points.npz -> (points as stored: fp16 / fp32 / fp64 [n, 3], ground-truth occupancies uint8 [n]: the bit-packed
+    `occupancies` unpacked and cut to len(points), the reference's :138-139)"""
+    occ = np.load(path)
+    points = np.asarray(occ["points"])
+    if points.dtype not in (np.float16, np.float32, np.float64):
+        points = points.astype(np.float32)
+    return points, np.unpackbits(occ["occupancies"])[:len(points)]
+
+
+def iou_mesh_gpu(data, vertices, faces, device=None):
+    """The reference's `iou` by its literal method (:139-141): check_mesh_contains of the MESH (vertices [V, 3], faces [F, 3]: any mesh,
+    not only an interface of the tetrahedralization) at the points of points.npz, on the device (ops.mesh_occupancy_iou), against the
+    file's occupancies.  Selected in `generate` by ``evaluation.occupancy: mesh`` next to ``evaluation.solver: gpu``."""
+    from ..ops import mesh_occupancy_iou
+
+    points, gt = load_occupancy(_occupancy_file(data))
+    if device is not None:
+        points = torch.from_numpy(points).to(device)
+    return mesh_occupancy_iou(vertices, faces, points, gt)[0]
+
+
 def chamfer_gpu(data, mdata, interfaces, clf):
     """The reference's `chamfer` (:147-159, compute_chamfer) on the device: len(gt) points sampled on the interface facets by area
     (seed clf.evaluation.seed, default 0) against eval/<id or category>/pointcloud.npz, exact nearest neighbours both ways.  An interface
@@ -213,7 +235,8 @@ def generate(data, prediction, clf):
       InterfaceMesh with the same vertices / faces and an ``export``; the evaluation metrics (watertight / iou / chamfer,
       :115-163) need trimesh + utils/libmesh and are computed only when those import -- otherwise eval_dict stays empty;
     * with ``clf.evaluation.solver == "gpu"`` iou and chamfer come from the device (iou_gpu / chamfer_gpu, no trimesh needed), from the
-      labels and interface facets above; the mesh object is the same;
+      labels and interface facets above; the mesh object is the same; with ``clf.evaluation.occupancy == "mesh"`` as well, iou is the
+      reference's literal check_mesh_contains of the generated mesh (iou_mesh_gpu) instead of the walk in the tetrahedralization;
     * with ``clf.mesh.solver == "gpu"`` the mesh object is built on the device whether or not trimesh imports (mesh_gpu: exact outward
       orientation under ``fix_orientation``, only the referenced vertices) and watertight comes from the device (watertight_gpu).
     """
@@ -304,7 +327,11 @@ def _generate_gpu_metrics(data, clf, mdata, labels, interfaces, faces, trimesh):
 def _gpu_iou_chamfer(data, clf, mdata, labels, interfaces, metrics, eval_dict):
     if "iou" in metrics:
         try:
-            eval_dict["iou"] = iou_gpu(data, mdata, labels)
+            if getattr(getattr(clf, "evaluation", None), "occupancy", None) == "mesh":
+                faces = torch.from_numpy(np.ascontiguousarray(mdata["facets"], dtype=np.int32)).to(interfaces.device)[interfaces.long()]
+                eval_dict["iou"] = iou_mesh_gpu(data, mdata["vertices"], faces, device=interfaces.device)
+            else:
+                eval_dict["iou"] = iou_gpu(data, mdata, labels)
         except Exception:  # noqa: BLE001  (the reference: bare except, :142-145)
             print("WARNING: Could not calculate IoU for mesh ", data['filename'])
             eval_dict["iou"] = 0.0

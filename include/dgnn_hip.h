@@ -983,6 +983,44 @@ int64_t dgnn_mesh_topology_scratch_bytes(int64_t n_faces, int64_t n_vertices);
 int dgnn_mesh_topology(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int64_t* counts_out, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Occupancy of points in an arbitrary triangle mesh (reference utils/libmesh check_mesh_contains) and the generators of the
+ * evaluation-sample builder (reference processing/<dataset>/sample_mesh.py).  DESIGN.md section 21.
+ *
+ * dgnn_mesh_contains: contains_out uint8 [n_points] = (above odd) & (below odd), n_disagree_out DEVICE int64 [1] = the points whose two
+ *   parities differ (NULL: not written), for vertices fp64 [n_vertices, 3], faces int32 [n_faces, 3], points fp64 [n_points, 3].
+ *   frame     per axis, over the vertices the faces reference: scale = (R - 1) / (max - min), translate = 0.5 - scale * min, R =
+ *             hash_resolution in [2, 4096]; vertices and points are rescaled as scale * a + translate (a product, then a sum).
+ *   rule      a rescaled point outside 0 <= p <= R on an axis (NaN included) is not contained.  Otherwise, over the triangles
+ *             (t1, t2, t3) whose xy projection passes det = a00 a11 - a01 a10 != 0 with a00 = t1x - t3x, a01 = t2x - t3x, a10 = t1y - t3y,
+ *             a11 = t2y - t3y, y = p - t3, u = (a11 y0 - a01 y1) sign(det), v = (-a10 y0 + a00 y1) sign(det), 0 < u, v, u + v < |det|:
+ *             n = (t3 - t1) x (t2 - t1), depth = t1z |n2| + (n0 (t1x - px) + n1 (t1y - py)) sign(n2) (none when n2 == 0); the triangle
+ *             is above when depth >= pz |n2|, below when depth < pz |n2|.
+ *   grid      candidates come from an xy grid on int(coord) >> shift (cells clamped to [0, R - 1]); shift = the smallest for which the
+ *             (triangle, cell) entries number at most max_entries.  The answer does not depend on it.  `entries` int32
+ *             [entry_capacity] holds them: dgnn_mesh_contains_plan returns the number (n_entries_out, shift_out: HOST values).
+ *   scratch   dgnn_mesh_contains_scratch_bytes(n_vertices, n_faces, hash_resolution) bytes for either call.
+ * DGNN_E_INVALID: no faces, a face id out of range, a non-finite referenced vertex, no extent on an axis, entry_capacity too small;
+ * DGNN_E_UNSUPPORTED: hash_resolution above 4096, max_entries below n_faces.  Ids are validated before any kernel indexes with them.
+ * Both calls SYNCHRONISE `stream` three times (ids, box, entry totals).  Integer counts: bit-identical from run to run.
+ *
+ * dgnn_box_points:    points_out fp64 [n, 3], element j = boxsize * (u - 0.5), u = (mm_hash(seed, j + 1) >> 11) 2^-53.
+ * dgnn_jitter_points: points_out[j] = points[j] + sigma * sqrt(-2 log u1) cos(2 pi u2) per element j (fp64), u1 = ((mm_hash(seed, 2 j + 1)
+ *                     >> 11) + 1) 2^-53, u2 = (mm_hash(seed, 2 j + 2) >> 11) 2^-53.  In place allowed.
+ * dgnn_face_normals:  normals_out fp64 [n_faces, 3] = (v1 - v0) x (v2 - v0) / its length; zeros for a face without area.  scratch: 256
+ *                     bytes.  DGNN_E_INVALID: a face id out of range.  SYNCHRONISES `stream` once.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_mesh_contains_scratch_bytes(int64_t n_vertices, int64_t n_faces, int32_t hash_resolution);
+int dgnn_mesh_contains_plan(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t hash_resolution,
+                            int64_t max_entries, int32_t* shift_out, int64_t* n_entries_out, void* scratch, void* stream);
+int dgnn_mesh_contains(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t hash_resolution,
+                       int64_t max_entries, const double* points, int64_t n_points, uint8_t* contains_out, int64_t* n_disagree_out,
+                       int32_t* entries, int64_t entry_capacity, void* scratch, void* stream);
+int dgnn_box_points(int64_t n_points, double boxsize, uint64_t seed, double* points_out, void* stream);
+int dgnn_jitter_points(const double* points, int64_t n_points, double sigma, uint64_t seed, double* points_out, void* stream);
+int dgnn_face_normals(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, double* normals_out, void* scratch,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-scene standardisation (reference processing/data.py:444-506 sklearn StandardScaler + :512-519
  * float32 cast): out[i,c] = float((x[i,c] - mean_c) / std_c) for c >= c_first, plain cast for c < c_first;
  * fp64 statistics (population variance, zero scale -> 1).  scratch: dgnn_standardize_scratch_doubles(c) doubles.
