@@ -103,6 +103,12 @@ SIGNATURES = {
     "dgnn_compact_vertices": (i32, [vp, i64, i64, vp, vp, vp, vp, vp]),
     "dgnn_mesh_topology_scratch_bytes": (i64, [i64, i64]),
     "dgnn_mesh_topology": (i32, [vp, i64, i64, vp, vp, vp]),
+    "dgnn_mesh_components_scratch_bytes": (i64, [i64]),
+    "dgnn_mesh_components": (i32, [vp, i64, i64, vp, vp, vp, vp]),
+    "dgnn_mesh_component_measures_scratch_bytes": (i64, [i64, i64]),
+    "dgnn_mesh_component_measures": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+    "dgnn_mesh_component_keep_scratch_bytes": (i64, []),
+    "dgnn_mesh_component_keep": (i32, [vp, i64, vp, i64, i32, i64, vp, vp, vp, vp]),
     "dgnn_mesh_contains_scratch_bytes": (i64, [i64, i64, i32]),
     "dgnn_mesh_contains_plan": (i32, [vp, i64, vp, i64, i32, i64, vp, vp, vp, vp]),
     "dgnn_mesh_contains": (i32, [vp, i64, vp, i64, i32, i64, vp, i64, vp, vp, vp, i64, vp, vp]),

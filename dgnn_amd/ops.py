@@ -1877,6 +1877,75 @@ def mesh_topology(faces, n_vertices):
     return out
 
 
+# ---- connected components of a triangle mesh (csrc/meshcomp.hip; the reference: trimesh split / body_count) --------------------------
+@on_device_of
+def mesh_components(faces, n_vertices):
+    """Connected components of a triangle mesh (dgnn_mesh_components): faces that share an undirected edge are connected, however many
+    faces meet on it; a shared vertex alone does not connect.  -> (comp int32 [F] on the GPU, K): components 0..K-1 numbered in ascending
+    order of their smallest face id, the same on every run.  DgnnError for ids out of range or a face with a repeated vertex."""
+    dev = _dev_of(faces)
+    f = _on(faces, dev, torch.int32, 3)
+    nv, k = int(n_vertices), f.size(0)
+    comp = torch.empty(max(k, 1), dtype=torch.int32, device=dev)[:k]
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(max(int(lib().dgnn_mesh_components_scratch_bytes(k)), 1), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_mesh_components(ptr(f), k, nv, ptr(comp), ptr(cnt), ptr(scratch), stream_ptr()), "dgnn_mesh_components")
+    return comp, int(cnt.item())
+
+
+@on_device_of
+def mesh_component_measures(vertices, faces, comp, K):
+    """Per component of `comp` (mesh_components): {"n_faces": int64 [K], "area": fp64 [K], "signed_volume": fp64 [K]} on the GPU
+    (dgnn_mesh_component_measures).  signed_volume = sum of v0 . (v1 x v2) / 6 over the component's faces in their stored winding: the
+    enclosed volume of a closed component wound outward, its negative when wound inward.  Sums run in a fixed order (include/dgnn_hip.h):
+    reruns are bit-identical.  DgnnError for a vertex or component id out of range."""
+    dev = _dev_of(comp, faces, vertices)
+    v = _on(vertices, dev, torch.float64, 3)
+    f = _on(faces, dev, torch.int32, 3)
+    c = _on(comp, dev, torch.int32).reshape(-1)
+    nf, k = f.size(0), int(K)
+    if c.numel() != nf:
+        raise ValueError("%d component ids for %d faces" % (c.numel(), nf))
+    n = torch.zeros(max(k, 1), dtype=torch.int64, device=dev)[:k]
+    area = torch.zeros(max(k, 1), dtype=torch.float64, device=dev)[:k]
+    vol = torch.zeros(max(k, 1), dtype=torch.float64, device=dev)[:k]
+    scratch = torch.empty(max(int(lib().dgnn_mesh_component_measures_scratch_bytes(nf, k)), 1), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_mesh_component_measures(ptr(v), v.size(0), ptr(f), nf, ptr(c), k, ptr(n), ptr(area), ptr(vol), ptr(scratch), stream_ptr()),
+          "dgnn_mesh_component_measures")
+    return {"n_faces": n, "area": area, "signed_volume": vol}
+
+
+@on_device_of
+def filter_components(faces, comp, counts, largest=False, min_faces=None):
+    """The faces of the components a rule keeps (dgnn_mesh_component_keep, then dgnn_compact_i32: face order preserved): `largest` = the
+    one component with the most faces (a tie goes to the smaller component id), `min_faces=n` = every component with at least n faces.
+    counts: the "n_faces" of mesh_component_measures.  -> (faces int32 [n_kept, 3], keep bool [F], n_kept), tensors on the GPU."""
+    if bool(largest) == (min_faces is not None):
+        raise ValueError("filter_components: give either largest=True or min_faces=n")
+    if min_faces is not None and int(min_faces) < 1:
+        raise ValueError("filter_components: min_faces=%r, expected an int >= 1" % (min_faces,))
+    dev = _dev_of(comp, faces, counts)
+    f = _on(faces, dev, torch.int32, 3)
+    c = _on(comp, dev, torch.int32).reshape(-1)
+    cnt = _on(counts, dev, torch.int64).reshape(-1)
+    nf = f.size(0)
+    if c.numel() != nf:
+        raise ValueError("%d component ids for %d faces" % (c.numel(), nf))
+    keep = torch.zeros(max(nf, 1), dtype=torch.int32, device=dev)[:nf]
+    n_kept = torch.zeros(1, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(lib().dgnn_mesh_component_keep_scratch_bytes()), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_mesh_component_keep(ptr(c), nf, ptr(cnt), cnt.numel(), 0 if largest else 1, 1 if largest else int(min_faces), ptr(keep),
+                                         ptr(n_kept), ptr(scratch), stream_ptr()), "dgnn_mesh_component_keep")
+    ids = torch.empty(max(nf, 1), dtype=torch.int32, device=dev)
+    got = torch.zeros(1, dtype=torch.int32, device=dev)
+    cscratch = torch.empty(int(lib().dgnn_compact_scratch_elems(nf)), dtype=torch.int32, device=dev)
+    check(lib().dgnn_compact_i32(None, ptr(keep), 0, nf, ptr(ids), ptr(got), ptr(cscratch), stream_ptr()), "dgnn_compact_i32")
+    m = int(n_kept.item())
+    if int(got.item()) != m:
+        raise DgnnError("filter_components: %d faces flagged, %d compacted" % (m, int(got.item())))
+    return f[ids[:m].long()], keep.bool(), m
+
+
 # ---- occupancy of any triangle mesh and the evaluation-sample generators (csrc/meshcontains.hip; reference utils/libmesh) ----------
 def _check_value(code, what):
     """`check`, with the library's "bad input" status as the ValueError a Python caller expects for bad data"""

@@ -5,8 +5,8 @@ and the trimesh call: labels of the finite cells (:75), the infinite cell append
 of facets whose two cells carry different labels (:101-105) -- two Python loops over all facets in the reference,
 three small kernels here.  The optional integer alpha-expansion graph cut (:15-58, third-party ``gco``) runs exactly on
 the device with ``graph_cut.solver: gpu`` (``graph_cut_gpu``), and the iou / chamfer metrics with ``evaluation.solver: gpu``
-(``iou_gpu`` / ``chamfer_gpu``), and the mesh object with its watertight metric with ``mesh.solver: gpu`` (``mesh_gpu`` /
-``watertight_gpu``); without that key the ``trimesh`` mesh object stays a CPU-side third-party step.  ``labels`` can be replaced by the graph-cut labels before ``interface_from_labels``.
+(``iou_gpu`` / ``chamfer_gpu``), and the mesh object with its watertight and components metrics and the small-component filter with
+``mesh.solver: gpu`` (``mesh_gpu`` / ``watertight_gpu`` / ``mesh_components_gpu``); without that key the ``trimesh`` mesh object stays a CPU-side third-party step.  ``labels`` can be replaced by the graph-cut labels before ``interface_from_labels``.
 """
 from __future__ import annotations
 
@@ -187,22 +187,48 @@ def chamfer_gpu(data, mdata, interfaces, clf):
     return chamfer_distance(torch.from_numpy(gt_points).to(recon_points.device), recon_points)
 
 
-def mesh_gpu(mdata, labels, interfaces, fix_orientation):
+def _components_rule(value):
+    """clf.mesh.components -> None (no filter), "largest" or an int n >= 1 (components with at least n faces)"""
+    if value is None:
+        return None
+    if value == "largest":
+        return "largest"
+    if isinstance(value, (int, np.integer)) and not isinstance(value, bool) and int(value) >= 1:
+        return int(value)
+    raise ValueError("mesh.components: %r (expected null, \"largest\" or an int >= 1)" % (value,))
+
+
+def mesh_gpu(mdata, labels, interfaces, fix_orientation, components=None, name=""):
     """The mesh `generate` returns, built on the device: the interface facets `interfaces` (int32 ids into mdata["facets"],
     e.g. interface_from_labels) of the labelled tetrahedralization `mdata` (`_3dt.npz`; labels of the finite cells, 0 = inside), wound so
     that every normal points away from its inside cell when `fix_orientation` is set (ops.orient_interface: exact signs; a facet between
     flat cells keeps its stored winding and is counted), else in the stored winding; then only the vertices the faces reference, in
     ascending id, with the faces renumbered (ops.compact_vertices).  Runs on the device of `labels` / `interfaces`.
-    -> InterfaceMesh, with three more attributes: vertex_ids (the kept original ids, int32 ndarray), n_undetermined, faces_dev (the
-    faces on the device)."""
-    from ..ops import compact_vertices, orient_interface
+    `components` ("largest" or an int n >= 1) drops, before the vertex compaction, every face outside the largest connected
+    component / in a component of fewer than n faces (ops.mesh_components / mesh_component_measures / filter_components; face order kept).
+    Any other value is a ValueError (a configuration mistake); a failing device step warns and leaves the mesh unfiltered.
+    -> InterfaceMesh, with more attributes: vertex_ids (the kept original ids, int32 ndarray), n_undetermined, faces_dev (the faces on
+    the device), n_removed_faces and keep_mask (bool tensor over `interfaces` on the device; None when nothing was filtered)."""
+    from ..ops import compact_vertices, filter_components, mesh_component_measures, mesh_components, orient_interface
 
+    rule = _components_rule(components)
     faces, n_undetermined = orient_interface(mdata["vertices"], mdata["tetrahedra"], mdata["facets"], mdata["nfacets"], labels, interfaces,
                                              orient=bool(fix_orientation))
+    n_removed, keep = 0, None
+    if rule is not None:
+        try:
+            comp, k = mesh_components(faces, len(mdata["vertices"]))
+            counts = mesh_component_measures(mdata["vertices"], faces, comp, k)["n_faces"]
+            kept_faces, keep, n_kept = filter_components(faces, comp, counts, largest=rule == "largest", min_faces=None if rule == "largest" else rule)
+            n_removed, faces = faces.shape[0] - n_kept, kept_faces
+        except Exception:  # noqa: BLE001  (the reference's style: warn and go on)
+            print("WARNING: Could not filter the components of mesh {}. Using the unfiltered mesh.".format(name))
+            n_removed, keep = 0, None
     faces, kept = compact_vertices(faces, len(mdata["vertices"]))
     ids = kept.cpu().numpy()
     mesh = InterfaceMesh(np.asarray(mdata["vertices"], dtype=np.float64)[ids], faces.cpu().numpy())
     mesh.vertex_ids, mesh.n_undetermined, mesh.faces_dev = ids, n_undetermined, faces
+    mesh.n_removed_faces, mesh.keep_mask = n_removed, keep
     return mesh
 
 
@@ -219,6 +245,17 @@ def watertight_gpu(mesh, name=""):
         print("WARNING: Mesh {} has no faces; watertight set to 0".format(name))
         return 0
     return mesh_topology(faces, len(mesh.vertices))["watertight"]
+
+
+def mesh_components_gpu(mesh):
+    """The number of connected components of an InterfaceMesh (faces connected through shared edges; ops.mesh_components):
+    what the reference reports from trimesh's body_count.  A mesh without faces has 0."""
+    from ..ops import mesh_components
+
+    faces = getattr(mesh, "faces_dev", None)
+    if faces is None:
+        faces = torch.from_numpy(np.ascontiguousarray(mesh.faces, dtype=np.int32).reshape(-1, 3))
+    return mesh_components(faces, len(mesh.vertices))[1]
 
 
 def generate(data, prediction, clf):
@@ -239,6 +276,15 @@ def generate(data, prediction, clf):
       reference's literal check_mesh_contains of the generated mesh (iou_mesh_gpu) instead of the walk in the tetrahedralization;
     * with ``clf.mesh.solver == "gpu"`` the mesh object is built on the device whether or not trimesh imports (mesh_gpu: exact outward
       orientation under ``fix_orientation``, only the referenced vertices) and watertight comes from the device (watertight_gpu).
+      On this path only:
+      - ``"components"`` in ``clf.temp.metrics``: ``eval_dict["components"]`` = the number of connected components (faces connected
+        through shared edges, mesh_components_gpu) of the mesh that is returned;
+      - ``clf.mesh.components``: absent / None = no filter; ``"largest"`` = only the component with the most faces is returned; an int
+        n >= 1 = only the components with at least n faces.  The returned mesh, ``watertight`` and ``components`` are those of the
+        filtered mesh, and ``eval_dict["n_removed_faces"]`` (also ``mesh.n_removed_faces``) says how many faces went.  With
+        ``evaluation.solver: gpu`` iou is then check_mesh_contains of the filtered mesh (iou_mesh_gpu: the walk in the labelled
+        tetrahedralization would score the unfiltered labels) and chamfer samples the kept facets only.  Any other value of the
+        key raises ValueError; a failing device step warns and returns the unfiltered mesh.
     """
     dev = prediction.device if prediction.is_cuda else torch.device(getattr(clf.temp, "device", "cuda:0"))
     pred_dev = prediction.to(dev, torch.float32)
@@ -343,24 +389,54 @@ def _gpu_iou_chamfer(data, clf, mdata, labels, interfaces, metrics, eval_dict):
             eval_dict["chamfer"] = float("inf")
 
 
+def _gpu_iou_chamfer_filtered(data, clf, mdata, mesh, kept_interfaces, metrics, eval_dict):
+    """iou / chamfer of a mesh whose small components were dropped (``mesh.components``): iou from the occupancy of the filtered MESH,
+    chamfer from samples on the kept interface facets `kept_interfaces` only (orient_interface keeps the face order, so the keep mask of
+    the faces indexes the interface ids).  The reference's warnings on failure."""
+    if "iou" in metrics:
+        try:
+            eval_dict["iou"] = iou_mesh_gpu(data, mesh.vertices, mesh.faces_dev, device=mesh.faces_dev.device)
+        except Exception:  # noqa: BLE001  (the reference: bare except, :142-145)
+            print("WARNING: Could not calculate IoU for mesh ", data['filename'])
+            eval_dict["iou"] = 0.0
+    if "chamfer" in metrics:
+        try:
+            eval_dict["chamfer"] = chamfer_gpu(data, mdata, kept_interfaces, clf)
+        except Exception:  # noqa: BLE001  (the reference: bare except, :157-159)
+            print("WARNING: Could not calculate Chamfer distance for mesh ", data['filename'])
+            eval_dict["chamfer"] = float("inf")
+
+
 def _generate_gpu_mesh(data, clf, mdata, labels, interfaces, trimesh):
     """`generate`'s tail with ``mesh.solver: gpu``: the mesh from mesh_gpu, watertight from watertight_gpu; iou / chamfer from the device
     with ``evaluation.solver: gpu``, else chamfer by trimesh's sampler when trimesh imports (as without the key).  A facet whose winding
     could not be decided is reported once; a failing metric keeps the reference's warning."""
     metrics = getattr(clf.temp, "metrics", None) or []
     name = getattr(data, "filename", "")
-    mesh = mesh_gpu(mdata, labels, interfaces, getattr(clf.temp, "fix_orientation", None))
+    rule = getattr(getattr(clf, "mesh", None), "components", None)
+    mesh = mesh_gpu(mdata, labels, interfaces, getattr(clf.temp, "fix_orientation", None), components=rule, name=name)
     if mesh.n_undetermined:
         print("WARNING: {} faces of mesh {} lie on flat cells only; they keep their stored winding".format(mesh.n_undetermined, name))
     eval_dict = dict()
+    if rule is not None:
+        eval_dict["n_removed_faces"] = mesh.n_removed_faces
     if "watertight" in metrics:
         try:
             eval_dict["watertight"] = watertight_gpu(mesh, name)
         except Exception:  # noqa: BLE001  (the reference's style: warn and go on)
             print("WARNING: Could not calculate watertightness for mesh ", name)
             eval_dict["watertight"] = 0
+    if "components" in metrics:
+        try:
+            eval_dict["components"] = mesh_components_gpu(mesh)
+        except Exception:  # noqa: BLE001
+            print("WARNING: Could not count the components of mesh ", name)
+            eval_dict["components"] = 0
     if getattr(getattr(clf, "evaluation", None), "solver", None) == "gpu":
-        _gpu_iou_chamfer(data, clf, mdata, labels, interfaces, metrics, eval_dict)
+        if mesh.keep_mask is None:
+            _gpu_iou_chamfer(data, clf, mdata, labels, interfaces, metrics, eval_dict)
+        else:
+            _gpu_iou_chamfer_filtered(data, clf, mdata, mesh, interfaces[mesh.keep_mask], metrics, eval_dict)
         return mesh, eval_dict
     wanted = [m for m in ("iou", "chamfer") if m in metrics]
     if trimesh is None:

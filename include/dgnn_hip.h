@@ -983,6 +983,52 @@ int64_t dgnn_mesh_topology_scratch_bytes(int64_t n_faces, int64_t n_vertices);
 int dgnn_mesh_topology(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int64_t* counts_out, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Connected components of a triangle mesh, their measures and the small-component filter (the reference: trimesh split / body_count).
+ * DESIGN.md section 22.
+ *
+ * dgnn_mesh_components: comp_out int32 [n_faces] = the component of every face of faces int32 [n_faces, 3], n_components_out DEVICE
+ *   int32 [1] = their number K.
+ *   rule      two faces are connected when they share an undirected edge {u, v}, however many faces share it: a non-manifold edge joins
+ *             all of its faces (Open3D's cluster_connected_triangles).  Contact at a vertex alone does not connect.
+ *   numbering components are numbered 0 .. K-1 in ascending order of their smallest face id: comp_out is a function of the mesh alone, the
+ *             same for every schedule and every rerun.
+ *   scratch   dgnn_mesh_components_scratch_bytes(n_faces) bytes.
+ *   n_faces == 0 is valid: K = 0.  DGNN_E_INVALID: an id out of range or a face with a repeated vertex (as dgnn_mesh_topology);
+ *   DGNN_E_UNSUPPORTED: 3 n_faces >= 2^31 - 1.  SYNCHRONISES `stream` once (input check).
+ *
+ * dgnn_mesh_component_measures: per component c of comp int32 [n_faces] (values in [0, n_components)), for vertices fp64 [n_vertices, 3]:
+ *   n_faces_out int64 [K], area_out fp64 [K], volume_out fp64 [K] (a component id without faces gets 0, 0.0, 0.0).
+ *   terms     of face (v0, v1, v2), every operation an fp64 operation rounded on its own (no fused multiply-add), with u = v1 - v0,
+ *             w = v2 - v0, n = (uy wz - uz wy, uz wx - ux wz, ux wy - uy wx):
+ *               area   = 0.5 * sqrt((nx nx + ny ny) + nz nz)
+ *               volume = ((v0x (v1y v2z - v1z v2y) + v0y (v1z v2x - v1x v2z)) + v0z (v1x v2y - v1y v2x)) / 6
+ *             volume_out = the signed volume of the component in its stored winding (positive when a closed component is wound outward).
+ *   order     the faces are sorted stably by component: component c holds positions [s, e) of that order, in ascending face id.  [s, e)
+ *             is cut at the multiples of 256; every piece is summed from 0.0 in ascending position, and the piece sums are added from 0.0
+ *             in ascending position.  Bit-identical from run to run.
+ *   scratch   dgnn_mesh_component_measures_scratch_bytes(n_faces, n_components) bytes.
+ *   DGNN_E_INVALID: a vertex or component id out of range (faces with n_components == 0 included), n_components > n_faces;
+ *   DGNN_E_UNSUPPORTED as above.  Non-finite coordinates give non-finite sums.  SYNCHRONISES `stream` once (input check).
+ *
+ * dgnn_mesh_component_keep: keep_out int32 [n_faces] = 1 for the faces of the components the rule keeps, n_kept_out DEVICE int64 [1] =
+ *   their number; component_faces int64 [n_components] = the n_faces_out above.  Integer logic only.
+ *   rule 0    `largest`: the one component with the most faces; a tie goes to the smaller component id (min_faces is ignored)
+ *   rule 1    `min_faces`: every component with at least min_faces (>= 1) faces
+ *   The kept faces are compacted with dgnn_compact_i32 (face order preserved) and their vertices with dgnn_compact_vertices.
+ *   scratch   dgnn_mesh_component_keep_scratch_bytes() bytes.  DGNN_E_INVALID: a component id out of range, an unknown rule, min_faces < 1.
+ *   SYNCHRONISES `stream` once (status).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_mesh_components_scratch_bytes(int64_t n_faces);
+int dgnn_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int32_t* comp_out, int32_t* n_components_out, void* scratch,
+                         void* stream);
+int64_t dgnn_mesh_component_measures_scratch_bytes(int64_t n_faces, int64_t n_components);
+int dgnn_mesh_component_measures(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, const int32_t* comp,
+                                 int64_t n_components, int64_t* n_faces_out, double* area_out, double* volume_out, void* scratch, void* stream);
+int64_t dgnn_mesh_component_keep_scratch_bytes(void);
+int dgnn_mesh_component_keep(const int32_t* comp, int64_t n_faces, const int64_t* component_faces, int64_t n_components, int rule,
+                             int64_t min_faces, int32_t* keep_out, int64_t* n_kept_out, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Occupancy of points in an arbitrary triangle mesh (reference utils/libmesh check_mesh_contains) and the generators of the
  * evaluation-sample builder (reference processing/<dataset>/sample_mesh.py).  DESIGN.md section 21.
  *
