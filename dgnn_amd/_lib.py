@@ -90,6 +90,10 @@ SIGNATURES = {
     "dgnn_interface_flags": (i32, [vp, vp, i64, vp, vp]),
     "dgnn_graph_cut_scratch_bytes": (i64, [i64, i64]),
     "dgnn_graph_cut_binary": (i32, [vp, i64, i64, vp, i64, f32, i32, vp, vp, vp, vp, vp, vp]),
+    "dgnn_graph_cut_weighted_scratch_bytes": (i64, [i64, i64]),
+    "dgnn_graph_cut_weighted": (i32, [vp, i64, i64, vp, i64, f32, vp, vp, vp, vp, vp, vp, vp]),
+    "dgnn_facet_cut_terms_scratch_bytes": (i64, [i64]),
+    "dgnn_facet_cut_terms": (i32, [vp, i64, vp, i64, vp, vp, i64, i32, f64, vp, vp, vp, vp, vp]),
     "dgnn_locate_scratch_bytes": (i64, [i64]),
     "dgnn_locate_points": (i32, [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp]),
     "dgnn_mesh_iou_counts": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp]),

@@ -14,16 +14,20 @@
 //   stop       an exact BFS from t reaches no node with positive excess: the preflow is maximum, and the nodes that BFS
 //              reached are label 1 (outside) -- the minimal sink side, i.e. the minimiser with the fewest outside cells.
 //              Heights only steer the pushes; the answer comes from the BFS alone.
-//   energy     int64 sums: E = sum D_i(l_i) + w * #{rows with l_i != l_j}; flow = sum of what reached t.  E == flow + sum min D_i
+//   energy     int64 sums: E = sum D_i(l_i) + sum over rows w_r [l_i != l_j]; flow = sum of what reached t.  E == flow + sum min D_i
 //              is checked before returning (the max-flow / min-cut identity).
+//   weights    one Potts weight for every row (dgnn_graph_cut_binary) or one capacity per row (dgnn_graph_cut_weighted): the same body
+//              (gc_solve), the four kernels that read a weight (k_count, k_rev, k_check_caps, k_pair_energy) templated on where it comes from.  A row of weight 0 keeps its arcs
+//              (the CSR does not depend on the weights) and carries nothing.
 #include "common.h"
+#include "mesh_common.h"
 
 int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* sums_scratch, hipStream_t stream);  // plan.hip
 
 namespace {
 
 // error bits of the status word (checked once after the costs and graph are built)
-constexpr int32_t GC_BAD_EDGE = 1, GC_NONFINITE = 2, GC_COST_RANGE = 4, GC_CAP_OVERFLOW = 8;
+constexpr int32_t GC_BAD_EDGE = 1, GC_NONFINITE = 2, GC_COST_RANGE = 4, GC_CAP_OVERFLOW = 8, GC_NEG_WEIGHT = 16;
 constexpr int GC_THREADS = 256;
 constexpr int GC_BFS_GRID = 1024;      // blocks of a BFS level launch (grid-stride over the frontier)
 constexpr int GC_BFS_BATCH = 8;        // BFS levels queued between two reads of the frontier size
@@ -56,9 +60,19 @@ __global__ void k_costs(const float* __restrict__ logits, int64_t ld, int64_t n,
     }
 }
 
-__global__ void k_count(const int32_t* __restrict__ edges, int64_t rows, int64_t n, int32_t* __restrict__ deg, GcState* st) {
+// the weight of row r: PER_ROW ? rw[r] : w (the scalar form never reads rw)
+template <bool PER_ROW>
+__device__ __forceinline__ int32_t row_weight(const int32_t* __restrict__ rw, int32_t w, int64_t r) {
+    if constexpr (PER_ROW) return rw[r];
+    else return w;
+}
+
+template <bool PER_ROW>
+__global__ void k_count(const int32_t* __restrict__ edges, int64_t rows, int64_t n, const int32_t* __restrict__ rw, int32_t* __restrict__ deg,
+                        GcState* st) {
     for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
         const int32_t i = edges[2 * r], j = edges[2 * r + 1];
+        if (PER_ROW && rw[r] < 0) atomicOr(&st->err, GC_NEG_WEIGHT);   // of any row, a self-loop's included
         if (i < 0 || i >= n || j < 0 || j >= n) { atomicOr(&st->err, GC_BAD_EDGE); continue; }
         if (i == j) continue;   // a self-loop never separates its cell from itself
         atomicAdd(deg + i, 1);
@@ -116,24 +130,40 @@ __global__ void k_sort_segments(const int32_t* __restrict__ rowptr, int64_t n, i
     }
 }
 
-// the slots in use are [0, rowptr[n]) (self-loop rows and rows with a bad id have none)
+// the slots in use are [0, rowptr[n]) (self-loop rows and rows with a bad id have none); arc id >> 1 = its row
+template <bool PER_ROW>
 __global__ void k_rev(const int32_t* __restrict__ rowptr, int64_t n, const int32_t* __restrict__ aid, const int32_t* __restrict__ pos_of_arc,
-                      int32_t w, int32_t* __restrict__ rev, int32_t* __restrict__ res, int32_t* __restrict__ push) {
+                      const int32_t* __restrict__ rw, int32_t w, int32_t* __restrict__ rev, int32_t* __restrict__ res, int32_t* __restrict__ push) {
     const int64_t n_arcs = rowptr[n];
     for (int64_t a = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; a < n_arcs; a += (int64_t)gridDim.x * blockDim.x) {
         rev[a] = pos_of_arc[aid[a] ^ 1];
-        res[a] = w;
+        res[a] = row_weight<PER_ROW>(rw, w, aid[a] >> 1);
         push[a] = 0;
     }
 }
 
-// terminal capacity + max(degree, 2) * w must fit int32: bounds the excess (<= cs + deg w) and an arc's residual (<= 2 w)
-__global__ void k_check_caps(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ e, const int32_t* __restrict__ rt, int64_t n,
-                             int32_t w, GcState* st) {
+// terminal capacity + max(sum of the incident weights, 2 * the largest of them) must fit int32: bounds the excess (<= cs + what can flow
+// in) and an arc's residual (<= twice its row's weight).  With one weight w that is max(degree, 2) * w.
+template <bool PER_ROW>
+__global__ void k_check_caps(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ aid, const int32_t* __restrict__ e,
+                             const int32_t* __restrict__ rt, int64_t n, const int32_t* __restrict__ rw, int32_t w, GcState* st) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t deg = rowptr[i + 1] - rowptr[i];
-        if (deg == 0) continue;
-        const int64_t cap = (int64_t)e[i] + rt[i] + (deg < 2 ? 2 : deg) * (int64_t)w;
+        const int32_t b = rowptr[i], end = rowptr[i + 1];
+        if (end == b) continue;
+        int64_t sum, top;
+        if constexpr (PER_ROW) {
+            sum = 0;
+            top = 0;
+            for (int32_t a = b; a < end; ++a) {
+                const int64_t wa = rw[aid[a] >> 1];
+                sum += wa;
+                top = wa > top ? wa : top;
+            }
+        } else {
+            sum = (int64_t)(end - b) * w;
+            top = w;
+        }
+        const int64_t cap = (int64_t)e[i] + rt[i] + (sum > 2 * top ? sum : 2 * top);
         if (cap > INT32_MAX) atomicOr(&st->err, GC_CAP_OVERFLOW);
     }
 }
@@ -269,12 +299,16 @@ __global__ void __launch_bounds__(GC_THREADS) k_labels_energy(const int32_t* __r
     gc_block_add(&st->sums[3], mn);
 }
 
+template <bool PER_ROW>
 __global__ void __launch_bounds__(GC_THREADS) k_pair_energy(const int32_t* __restrict__ edges, int64_t rows, const int32_t* __restrict__ labels,
-                                                            int32_t w, GcState* st) {
+                                                            const int32_t* __restrict__ rw, int32_t w, GcState* st) {
     long long cut = 0;
-    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x)
-        cut += labels[edges[2 * r]] != labels[edges[2 * r + 1]];
-    gc_block_add(&st->sums[1], cut * (long long)w);
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
+        const bool differ = labels[edges[2 * r]] != labels[edges[2 * r + 1]];
+        if constexpr (PER_ROW) cut += differ ? (long long)rw[r] : 0;
+        else cut += differ;
+    }
+    gc_block_add(&st->sums[1], PER_ROW ? cut : cut * (long long)w);
 }
 
 __global__ void k_outputs(const GcState* st, int64_t* energy_out, int64_t* flow_out, int32_t* stats_out, int32_t steps, int32_t relabels) {
@@ -311,11 +345,90 @@ GcLayout gc_layout(void* base, int64_t n, int64_t rows) {
     return L;
 }
 
-int gc_read(void* dst, const void* src, size_t bytes, hipStream_t stream) {
-    if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-        dgnn_set_error("graph_cut_binary: %s", hipGetErrorString(hipGetLastError()));
-        return DGNN_E_LAUNCH;
+// The solver behind both entry points.  PER_ROW: row r weighs row_weights[r]; else every row weighs w.
+template <bool PER_ROW>
+int gc_solve(const char* what, const float* logits, int64_t ld, int64_t n, const int32_t* edges, int64_t n_rows, float unary_weight,
+             const int32_t* row_weights, int32_t w, int32_t* labels_out, int64_t* energy_out, int64_t* flow_out, int32_t* stats_out, void* scratch,
+             hipStream_t stream) {
+    char where[96];
+    auto at = [&](const char* phase) { snprintf(where, sizeof(where), "%s (%s)", what, phase); return where; };
+    DGNN_REQUIRE(n >= 0 && n_rows >= 0 && ld >= 2 && scratch && (n == 0 || (logits && labels_out)) && (n_rows == 0 || edges) &&
+                     (!PER_ROW || n_rows == 0 || row_weights),
+                 DGNN_E_INVALID, "%s: bad args", what);
+    DGNN_REQUIRE(w >= 0, DGNN_E_INVALID, "%s: binary_weight %d < 0 is not a cut problem", what, w);
+    DGNN_REQUIRE(n < INT32_MAX / 2 && n_rows < INT32_MAX / 2, DGNN_E_UNSUPPORTED, "%s: %lld cells / %lld rows exceed the int32 indexing", what,
+                 (long long)n, (long long)n_rows);
+    const GcLayout L = gc_layout(scratch, n, n_rows);
+    const int64_t arcs = 2 * n_rows;
+    const dim3 block(GC_THREADS);
+    auto grid = [](int64_t items) { return dim3(dgnn_grid_cap(dgnn_cdiv(items > 0 ? items : 1, GC_THREADS))); };
+    GcState hs{};
+
+    // costs; graph: degrees counted into `cursor`, scanned into rowptr, cursor = rowptr again as the fill's claim pointers
+    (void)hipMemsetAsync(L.st, 0, sizeof(GcState), stream);
+    (void)hipMemsetAsync(L.cursor, 0, sizeof(int32_t) * (n + 1), stream);
+    (void)hipMemsetAsync(L.touched, 0, sizeof(int32_t) * (n > 0 ? n : 1), stream);
+    hipLaunchKernelGGL(k_costs, grid(n), block, 0, stream, logits, ld, n, unary_weight, L.d0, L.d1, L.e, L.rt, L.st);
+    hipLaunchKernelGGL(k_count<PER_ROW>, grid(n_rows), block, 0, stream, edges, n_rows, n, row_weights, L.cursor, L.st);
+    int rc = dgnn_exclusive_scan_i32(L.cursor, n, L.rowptr, L.sums, stream);
+    if (rc) return rc;
+    (void)hipMemcpyAsync(L.cursor, L.rowptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToDevice, stream);
+    hipLaunchKernelGGL(k_fill, grid(n_rows), block, 0, stream, edges, n_rows, n, L.cursor, L.nbr, L.aid);
+    hipLaunchKernelGGL(k_sort_segments, grid(n), block, 0, stream, L.rowptr, n, L.nbr, L.aid, L.pos);
+    hipLaunchKernelGGL(k_rev<PER_ROW>, grid(arcs), block, 0, stream, L.rowptr, n, L.aid, L.pos, row_weights, w, L.rev, L.res, L.push);
+    hipLaunchKernelGGL(k_check_caps<PER_ROW>, grid(n), block, 0, stream, L.rowptr, L.aid, L.e, L.rt, n, row_weights, w, L.st);
+    if ((rc = dgnn_check_launch(at("build")))) return rc;
+    if ((rc = mm_read(&hs, L.st, sizeof(GcState), stream, what))) return rc;
+    if (hs.err) {
+        dgnn_set_error("%s: %s%s%s%s%s", what, hs.err & GC_BAD_EDGE ? "edge id outside [0, n); " : "",
+                       hs.err & GC_NONFINITE ? "non-finite logits; " : "", hs.err & GC_COST_RANGE ? "|unary cost| >= 2^30; " : "",
+                       hs.err & GC_NEG_WEIGHT ? "a row weight < 0; " : "", hs.err & GC_CAP_OVERFLOW ? "a node's capacities overflow int32; " : "");
+        return DGNN_E_INVALID;
     }
+
+    // phase 1: global relabel, stop test, K synchronous steps; repeat
+    int64_t steps = 0;
+    int relabels = 0;
+    for (;;) {
+        if (relabels >= GC_MAX_RELABELS) {
+            dgnn_set_error("%s: no maximum preflow after %d global relabels / %lld steps (cap)", what, relabels, (long long)steps);
+            return DGNN_E_UNSUPPORTED;
+        }
+        (void)hipMemsetAsync(&L.st->excess_hit, 0, sizeof(int32_t) * 4, stream);   // excess_hit, cnt[0..2]
+        hipLaunchKernelGGL(k_bfs_init, grid(n), block, 0, stream, L.e, L.rt, n, L.h, L.hnew, L.fr0, L.st);
+        int level = 0;
+        for (;;) {   // at most n + 1 non-empty levels
+            for (int b = 0; b < GC_BFS_BATCH; ++b, ++level)
+                hipLaunchKernelGGL(k_bfs_level, dim3(GC_BFS_GRID), block, 0, stream, L.rowptr, L.nbr, L.rev, L.res, L.e, n, level,
+                                   level & 1 ? L.fr1 : L.fr0, level & 1 ? L.fr0 : L.fr1, L.h, L.hnew, L.st);
+            if ((rc = dgnn_check_launch(at("bfs")))) return rc;
+            if ((rc = mm_read(&hs, L.st, sizeof(GcState), stream, what))) return rc;   // synchronises the stream
+            if (hs.cnt[level % 3] == 0) break;
+        }
+        ++relabels;
+        if (!hs.excess_hit) break;   // no excess can reach t: the preflow is maximum, the BFS marks the sink side
+        const int64_t k = level > 16 ? level : 16;   // excess moves one hop per step: about one BFS depth of steps between relabels
+        if (steps + k > GC_MAX_STEPS) {
+            dgnn_set_error("%s: no maximum preflow after %lld steps / %d global relabels (cap)", what, (long long)steps, relabels);
+            return DGNN_E_UNSUPPORTED;
+        }
+        for (int64_t s = 0; s < k; ++s) {
+            hipLaunchKernelGGL(k_push, grid(n), block, 0, stream, L.rowptr, L.nbr, L.h, n, L.e, L.rt, L.res, L.push, L.hnew, L.touched);
+            hipLaunchKernelGGL(k_gather, grid(n), block, 0, stream, L.rowptr, L.rev, n, L.e, L.res, L.push, L.h, L.hnew, L.touched);
+        }
+        steps += k;
+        if ((rc = dgnn_check_launch(at("push-relabel")))) return rc;
+    }
+
+    // labels = reached by the last BFS; energy, flow and the identity between them
+    hipLaunchKernelGGL(k_labels_energy, grid(n), block, 0, stream, L.h, L.d0, L.d1, L.rt, n, labels_out, L.st);
+    hipLaunchKernelGGL(k_pair_energy<PER_ROW>, grid(n_rows), block, 0, stream, edges, n_rows, labels_out, row_weights, w, L.st);
+    hipLaunchKernelGGL(k_outputs, dim3(1), dim3(64), 0, stream, L.st, energy_out, flow_out, stats_out, (int32_t)steps, relabels);
+    if ((rc = dgnn_check_launch(at("energy")))) return rc;
+    if ((rc = mm_read(&hs, L.st, sizeof(GcState), stream, what))) return rc;
+    const int64_t energy = (int64_t)(hs.sums[0] + hs.sums[1]), flow = (int64_t)hs.sums[2], base = (int64_t)hs.sums[3];
+    DGNN_REQUIRE(energy == flow + base, DGNN_E_UNSUPPORTED, "%s: energy %lld != flow %lld + sum min D %lld (not a minimum cut)", what,
+                 (long long)energy, (long long)flow, (long long)base);
     return DGNN_OK;
 }
 
@@ -329,82 +442,15 @@ extern "C" int64_t dgnn_graph_cut_scratch_bytes(int64_t n, int64_t n_rows) {
 extern "C" int dgnn_graph_cut_binary(const float* logits, int64_t ld, int64_t n, const int32_t* edges, int64_t n_rows, float unary_weight,
                                      int32_t binary_weight, int32_t* labels_out, int64_t* energy_out, int64_t* flow_out, int32_t* stats_out,
                                      void* scratch, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    DGNN_REQUIRE(n >= 0 && n_rows >= 0 && ld >= 2 && scratch && (n == 0 || (logits && labels_out)) && (n_rows == 0 || edges),
-                 DGNN_E_INVALID, "graph_cut_binary: bad args");
-    DGNN_REQUIRE(binary_weight >= 0, DGNN_E_INVALID, "graph_cut_binary: binary_weight %d < 0 is not a cut problem", binary_weight);
-    DGNN_REQUIRE(n < INT32_MAX / 2 && n_rows < INT32_MAX / 2, DGNN_E_UNSUPPORTED, "graph_cut_binary: %lld cells / %lld rows exceed the int32 indexing",
-                 (long long)n, (long long)n_rows);
-    const GcLayout L = gc_layout(scratch, n, n_rows);
-    const int64_t arcs = 2 * n_rows;
-    const dim3 block(GC_THREADS);
-    auto grid = [](int64_t items) { return dim3(dgnn_grid_cap(dgnn_cdiv(items > 0 ? items : 1, GC_THREADS))); };
-    GcState hs{};
+    return gc_solve<false>("graph_cut_binary", logits, ld, n, edges, n_rows, unary_weight, nullptr, binary_weight, labels_out, energy_out, flow_out,
+                           stats_out, scratch, (hipStream_t)stream_);
+}
 
-    // costs; graph: degrees counted into `cursor`, scanned into rowptr, cursor = rowptr again as the fill's claim pointers
-    (void)hipMemsetAsync(L.st, 0, sizeof(GcState), stream);
-    (void)hipMemsetAsync(L.cursor, 0, sizeof(int32_t) * (n + 1), stream);
-    (void)hipMemsetAsync(L.touched, 0, sizeof(int32_t) * (n > 0 ? n : 1), stream);
-    hipLaunchKernelGGL(k_costs, grid(n), block, 0, stream, logits, ld, n, unary_weight, L.d0, L.d1, L.e, L.rt, L.st);
-    hipLaunchKernelGGL(k_count, grid(n_rows), block, 0, stream, edges, n_rows, n, L.cursor, L.st);
-    int rc = dgnn_exclusive_scan_i32(L.cursor, n, L.rowptr, L.sums, stream);
-    if (rc) return rc;
-    (void)hipMemcpyAsync(L.cursor, L.rowptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToDevice, stream);
-    hipLaunchKernelGGL(k_fill, grid(n_rows), block, 0, stream, edges, n_rows, n, L.cursor, L.nbr, L.aid);
-    hipLaunchKernelGGL(k_sort_segments, grid(n), block, 0, stream, L.rowptr, n, L.nbr, L.aid, L.pos);
-    hipLaunchKernelGGL(k_rev, grid(arcs), block, 0, stream, L.rowptr, n, L.aid, L.pos, binary_weight, L.rev, L.res, L.push);
-    hipLaunchKernelGGL(k_check_caps, grid(n), block, 0, stream, L.rowptr, L.e, L.rt, n, binary_weight, L.st);
-    if ((rc = dgnn_check_launch("graph_cut_binary (build)"))) return rc;
-    if ((rc = gc_read(&hs, L.st, sizeof(GcState), stream))) return rc;
-    if (hs.err) {
-        dgnn_set_error("graph_cut_binary: %s%s%s%s", hs.err & GC_BAD_EDGE ? "edge id outside [0, n); " : "",
-                       hs.err & GC_NONFINITE ? "non-finite logits; " : "", hs.err & GC_COST_RANGE ? "|unary cost| >= 2^30; " : "",
-                       hs.err & GC_CAP_OVERFLOW ? "a node's capacities overflow int32; " : "");
-        return DGNN_E_INVALID;
-    }
+extern "C" int64_t dgnn_graph_cut_weighted_scratch_bytes(int64_t n, int64_t n_rows) { return dgnn_graph_cut_scratch_bytes(n, n_rows); }
 
-    // phase 1: global relabel, stop test, K synchronous steps; repeat
-    int64_t steps = 0;
-    int relabels = 0;
-    for (;;) {
-        if (relabels >= GC_MAX_RELABELS) {
-            dgnn_set_error("graph_cut_binary: no maximum preflow after %d global relabels / %lld steps (cap)", relabels, (long long)steps);
-            return DGNN_E_UNSUPPORTED;
-        }
-        (void)hipMemsetAsync(&L.st->excess_hit, 0, sizeof(int32_t) * 4, stream);   // excess_hit, cnt[0..2]
-        hipLaunchKernelGGL(k_bfs_init, grid(n), block, 0, stream, L.e, L.rt, n, L.h, L.hnew, L.fr0, L.st);
-        int level = 0;
-        for (;;) {   // at most n + 1 non-empty levels
-            for (int b = 0; b < GC_BFS_BATCH; ++b, ++level)
-                hipLaunchKernelGGL(k_bfs_level, dim3(GC_BFS_GRID), block, 0, stream, L.rowptr, L.nbr, L.rev, L.res, L.e, n, level,
-                                   level & 1 ? L.fr1 : L.fr0, level & 1 ? L.fr0 : L.fr1, L.h, L.hnew, L.st);
-            if ((rc = dgnn_check_launch("graph_cut_binary (bfs)"))) return rc;
-            if ((rc = gc_read(&hs, L.st, sizeof(GcState), stream))) return rc;   // synchronises the stream
-            if (hs.cnt[level % 3] == 0) break;
-        }
-        ++relabels;
-        if (!hs.excess_hit) break;   // no excess can reach t: the preflow is maximum, the BFS marks the sink side
-        const int64_t k = level > 16 ? level : 16;   // excess moves one hop per step: about one BFS depth of steps between relabels
-        if (steps + k > GC_MAX_STEPS) {
-            dgnn_set_error("graph_cut_binary: no maximum preflow after %lld steps / %d global relabels (cap)", (long long)steps, relabels);
-            return DGNN_E_UNSUPPORTED;
-        }
-        for (int64_t s = 0; s < k; ++s) {
-            hipLaunchKernelGGL(k_push, grid(n), block, 0, stream, L.rowptr, L.nbr, L.h, n, L.e, L.rt, L.res, L.push, L.hnew, L.touched);
-            hipLaunchKernelGGL(k_gather, grid(n), block, 0, stream, L.rowptr, L.rev, n, L.e, L.res, L.push, L.h, L.hnew, L.touched);
-        }
-        steps += k;
-        if ((rc = dgnn_check_launch("graph_cut_binary (push-relabel)"))) return rc;
-    }
-
-    // labels = reached by the last BFS; energy, flow and the identity between them
-    hipLaunchKernelGGL(k_labels_energy, grid(n), block, 0, stream, L.h, L.d0, L.d1, L.rt, n, labels_out, L.st);
-    hipLaunchKernelGGL(k_pair_energy, grid(n_rows), block, 0, stream, edges, n_rows, labels_out, binary_weight, L.st);
-    hipLaunchKernelGGL(k_outputs, dim3(1), dim3(64), 0, stream, L.st, energy_out, flow_out, stats_out, (int32_t)steps, relabels);
-    if ((rc = dgnn_check_launch("graph_cut_binary (energy)"))) return rc;
-    if ((rc = gc_read(&hs, L.st, sizeof(GcState), stream))) return rc;
-    const int64_t energy = (int64_t)(hs.sums[0] + hs.sums[1]), flow = (int64_t)hs.sums[2], base = (int64_t)hs.sums[3];
-    DGNN_REQUIRE(energy == flow + base, DGNN_E_UNSUPPORTED, "graph_cut_binary: energy %lld != flow %lld + sum min D %lld (not a minimum cut)",
-                 (long long)energy, (long long)flow, (long long)base);
-    return DGNN_OK;
+extern "C" int dgnn_graph_cut_weighted(const float* logits, int64_t ld, int64_t n, const int32_t* edges, int64_t n_rows, float unary_weight,
+                                       const int32_t* row_weights, int32_t* labels_out, int64_t* energy_out, int64_t* flow_out, int32_t* stats_out,
+                                       void* scratch, void* stream_) {
+    return gc_solve<true>("graph_cut_weighted", logits, ld, n, edges, n_rows, unary_weight, row_weights, 0, labels_out, energy_out, flow_out,
+                          stats_out, scratch, (hipStream_t)stream_);
 }

@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "mesh_common.h"
+#include "fixed_sum.h"
 
 int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* sums_scratch, hipStream_t stream);  // plan.hip
 
@@ -28,7 +29,6 @@ constexpr int MM_THREADS = 256;
 constexpr int32_t MM_MAX_STEPS = 1 << 16;            // walk steps per query
 constexpr int32_t MM_NBR_UNSET = (int32_t)0x80808080;
 constexpr int MM_MAX_DIM = 1024;                      // grid bins per axis
-constexpr int MM_SUM_CHUNK = 256;                     // elements per serial partial sum / scan chunk
 // status bits
 constexpr int32_t MM_BAD_ID = 1, MM_NONFINITE = 2, MM_MALFORMED = 4, MM_CAP = 8;
 
@@ -300,33 +300,10 @@ __global__ void k_counts_out(const MmState* st, int64_t* counts_out) {
     if (threadIdx.x == 0) { counts_out[0] = (int64_t)st->counts[0]; counts_out[1] = (int64_t)st->counts[1]; }
 }
 
-// ---- fixed-order fp64 sums / inclusive scan ------------------------------------------------------------------------------------
-// chunk t = [t C, (t + 1) C): a serial inclusive scan in place (scan != 0) or a serial sum; chunk totals -> part[t]
-template <typename T>
-__global__ void k_chunk(T* __restrict__ x, int64_t n, int scan, double* __restrict__ part) {
-    const int64_t nch = (n + MM_SUM_CHUNK - 1) / MM_SUM_CHUNK;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nch; t += (int64_t)gridDim.x * blockDim.x) {
-        double s = 0;
-        const int64_t e = (t + 1) * MM_SUM_CHUNK < n ? (t + 1) * MM_SUM_CHUNK : n;
-        for (int64_t i = t * MM_SUM_CHUNK; i < e; ++i) {
-            s += (double)x[i];
-            if (scan) x[i] = (T)s;
-        }
-        part[t] = s;
-    }
-}
-
-// part[] -> exclusive offsets in place, serially (so cum is monotone and its last element equals *total bit for bit)
-__global__ void k_chunk_offsets(double* __restrict__ part, int64_t nch, double* __restrict__ total) {
-    if (threadIdx.x != 0) return;
-    double acc = 0;
-    for (int64_t t = 0; t < nch; ++t) { const double r = part[t]; part[t] = acc; acc += r; }
-    *total = acc;
-}
-
+// ---- fixed-order fp64 sums / inclusive scan: fixed_sum (fixed_sum.h); the scan's second pass -------------------------------------
 __global__ void k_chunk_add(double* __restrict__ x, int64_t n, const double* __restrict__ part) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        x[i] += part[i / MM_SUM_CHUNK];
+        x[i] += part[i / FIXED_SUM_CHUNK];
 }
 
 // ---- sampler -----------------------------------------------------------------------------------------------------------------
@@ -495,7 +472,7 @@ SampLayout samp_layout(void* base, int64_t nfc) {
     SampLayout L{};
     L.st = (MmState*)base;
     L.area = t.take<double>(nfc);
-    L.part = t.take<double>(dgnn_cdiv(nfc, MM_SUM_CHUNK) + 1);
+    L.part = t.take<double>(dgnn_cdiv(nfc, FIXED_SUM_CHUNK) + 1);
     L.total = t.take<double>(1);
     L.bytes = t.off;
     return L;
@@ -511,7 +488,7 @@ NnLayout nn_layout(void* base, int64_t nr, int64_t nq) {
     L.rowptr = t.take<int32_t>(nb + 1);
     L.sums = t.take<int32_t>(dgnn_cdiv(nb + 1, 2048) + 2);
     L.cells = t.take<float4>(nr);
-    L.part = t.take<double>(dgnn_cdiv(nq, MM_SUM_CHUNK) + 1);
+    L.part = t.take<double>(dgnn_cdiv(nq, FIXED_SUM_CHUNK) + 1);
     L.bytes = t.off;
     return L;
 }
@@ -525,14 +502,6 @@ int mm_status(const MmState& hs, const char* what) {
 }
 
 dim3 mm_grid(int64_t items) { return dim3(dgnn_grid_cap(dgnn_cdiv(items > 0 ? items : 1, MM_THREADS))); }
-
-// fixed-order fp64 sum of x[0, n) -> *total (device); part: dgnn_cdiv(n, MM_SUM_CHUNK) + 1 doubles
-template <typename T>
-void fixed_sum(T* x, int64_t n, int scan, double* part, double* total, hipStream_t stream) {
-    const int64_t nch = dgnn_cdiv(n, MM_SUM_CHUNK);
-    hipLaunchKernelGGL(k_chunk<T>, mm_grid(nch), dim3(MM_THREADS), 0, stream, x, n, scan, part);
-    hipLaunchKernelGGL(k_chunk_offsets, dim3(1), dim3(64), 0, stream, part, nch, total);
-}
 
 }  // namespace
 

@@ -1693,6 +1693,86 @@ def binary_graph_cut(logits, edges, unary_weight, binary_weight, return_stats=Fa
     return labels, energy, flow
 
 
+@on_device_of
+def weighted_graph_cut(logits, edges, unary_weight, row_weights, return_stats=False):
+    """`binary_graph_cut` with one integer capacity per row of `edges` (dgnn_graph_cut_weighted): the exact minimum of
+    sum_i D_i(l_i) + sum_r row_weights[r] [l_i != l_j].  row_weights int [F], each >= 0 (e.g. from facet_cut_terms, compacted to the
+    finite-finite rows); a row of weight 0 carries nothing, duplicate rows add up, self-loops never count.  Returns what
+    binary_graph_cut returns; with every weight equal to w, exactly what binary_graph_cut(..., w) returns (steps and relabels too).
+    Raises ValueError for a wrong length or shape, DgnnError for a negative weight, capacities that overflow int32 and what
+    binary_graph_cut raises."""
+    dev = logits.device if isinstance(logits, torch.Tensor) and logits.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    logits = torch.as_tensor(logits).to(dev, torch.float32)
+    edges = torch.as_tensor(edges).to(dev, torch.int32).contiguous()
+    if logits.dim() != 2 or logits.size(1) != 2:
+        raise ValueError("logits must be [n, 2], got %s" % (tuple(logits.shape),))
+    if edges.numel() == 0:
+        edges = edges.reshape(0, 2)
+    if edges.dim() != 2 or edges.size(1) != 2:
+        raise ValueError("edges must be [F, 2], got %s" % (tuple(edges.shape),))
+    rw = torch.as_tensor(row_weights)
+    if rw.is_floating_point() or rw.dtype == torch.bool:
+        raise ValueError("row_weights must be integers, got %s" % (rw.dtype,))
+    if rw.dim() != 1 or rw.numel() != edges.size(0):
+        raise ValueError("row_weights must be [%d] (one per row of edges), got %s" % (edges.size(0), tuple(rw.shape)))
+    if rw.dtype == torch.int64 and rw.numel() and (int(rw.max()) > 0x7FFFFFFF or int(rw.min()) < -0x80000000):   # narrower types fit
+        raise ValueError("row_weights do not fit int32")
+    rw = rw.to(dev, torch.int32).contiguous()
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    n, f = logits.size(0), edges.size(0)
+    labels = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    out64 = torch.zeros(2, dtype=torch.int64, device=dev)
+    stats = torch.zeros(2, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib().dgnn_graph_cut_weighted_scratch_bytes(n, f)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_graph_cut_weighted(ptr(logits), max(_ld(logits), 2) if n else 2, n, ptr(edges), f, float(unary_weight), ptr(rw), ptr(labels),
+                                        ptr(out64), C.c_void_p(out64.data_ptr() + 8), ptr(stats), ptr(scratch), stream_ptr()),
+          "dgnn_graph_cut_weighted")
+    energy, flow = (int(v) for v in out64.cpu())
+    if return_stats:
+        s = stats.cpu()
+        return labels, energy, flow, {"steps": int(s[0]), "relabels": int(s[1])}
+    return labels, energy, flow
+
+
+CUT_TERM_KINDS = {"area": 1, "beta": 2}
+
+
+@on_device_of
+def facet_cut_terms(vertices, tetrahedra, facets, nfacets, kind, binary_weight, return_q=False):
+    """Integer graph-cut capacities of the facets of `<scene>_3dt.npz` from their geometry (dgnn_facet_cut_terms):
+    kind "area": q_f = A_f / mean(A); kind "beta": q_f = 1 - min(cos phi, cos psi) of the two cells' circumspheres (Labatut et al. 2009);
+    w_f = rint(binary_weight * q_f).  Only facets between two finite cells (both nfacets entries >= 0) are weighted; the others get 0.
+    vertices fp64 [V, 3], tetrahedra int [N, 4], facets int [F, 3], nfacets int [F, 2].
+    -> (w int32 [F] on the GPU, stats {"rows", "neutral_sides", "zero_weights", "max_weight"}), with return_q (w, q fp64 [F], stats).
+    ValueError for an unknown kind or a binary_weight that is negative or not finite; DgnnError for malformed input, a mean area of 0
+    and weights that reach 2^30."""
+    import numpy as np
+
+    if kind not in CUT_TERM_KINDS:
+        raise ValueError("facet_cut_terms: kind %r (expected \"area\" or \"beta\")" % (kind,))
+    bw = float(binary_weight)
+    if not np.isfinite(bw) or bw < 0:
+        raise ValueError("facet_cut_terms: binary_weight %r must be finite and >= 0" % (binary_weight,))
+    dev = _dev_of(vertices, tetrahedra, facets, nfacets)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    fac = _on(facets, dev, torch.int32, 3)
+    nfac = _on(nfacets, dev, torch.int32, 2)
+    if fac.size(0) != nfac.size(0):
+        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
+    f = fac.size(0)
+    w = torch.empty(max(f, 1), dtype=torch.int32, device=dev)[:f]
+    q = torch.empty(max(f, 1), dtype=torch.float64, device=dev)[:f] if return_q else None
+    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(lib().dgnn_facet_cut_terms_scratch_bytes(f)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_facet_cut_terms(ptr(v), v.size(0), ptr(tets), tets.size(0), ptr(fac), ptr(nfac), f, CUT_TERM_KINDS[kind], bw, ptr(q), ptr(w),
+                                     ptr(stats), ptr(scratch), stream_ptr()), "dgnn_facet_cut_terms")
+    s = [int(x) for x in stats.cpu()]
+    sd = {"rows": s[0], "neutral_sides": s[1], "zero_weights": s[2], "max_weight": s[3]}
+    return (w, q, sd) if return_q else (w, sd)
+
+
 # ---- mesh metrics (reference processing/generate_mesh.py:126-163, processing/evaluate_mesh.py) ----------------------------------
 def _dev_of(*xs):
     for x in xs:

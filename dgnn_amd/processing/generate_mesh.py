@@ -101,15 +101,17 @@ def graph_cut(labels, prediction, edges, clf):
     return gc.get_labels()
 
 
-def graph_cut_gpu(labels, prediction, edges, clf):
+def graph_cut_gpu(labels, prediction, edges, clf, row_weights=None):
     """`graph_cut` solved exactly on the device (dgnn_graph_cut_binary): same arguments, same energy.  With two labels and a
     non-negative Potts weight the energy is submodular and gco's converged alpha-expansion is a global minimum, so the minimum cut
     reaches the energy gco reaches; where several labellings share it, the one with the fewest outside cells is returned.
     `prediction` fp32 [Nf, 2] logits of the finite cells (a GPU tensor is read in place), `edges` [F, 2] finite-finite facets,
     clf.graph_cut.unary_weight / binary_weight as in the reference.  `labels` is only checked for its length (the solver needs no
     initial labelling).  Returns what it was given: an ndarray of int32 labels for an ndarray / list `labels` (as gco's
-    get_labels), an int32 tensor on the device for a tensor."""
-    from ..ops import binary_graph_cut
+    get_labels), an int32 tensor on the device for a tensor.
+    `row_weights` (int [F], one capacity per row of `edges`, e.g. `facet_weights_gpu`): the cut charges row r its own weight instead of
+    clf.graph_cut.binary_weight (dgnn_graph_cut_weighted)."""
+    from ..ops import binary_graph_cut, weighted_graph_cut
 
     n = len(labels)
     if n != len(prediction):
@@ -118,8 +120,33 @@ def graph_cut_gpu(labels, prediction, edges, clf):
         prediction = torch.from_numpy(np.ascontiguousarray(prediction, dtype=np.float32))
     if not isinstance(edges, torch.Tensor):
         edges = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.int32))
-    lab, _, _ = binary_graph_cut(prediction, edges, clf.graph_cut.unary_weight, clf.graph_cut.binary_weight)
+    if row_weights is None:
+        lab, _, _ = binary_graph_cut(prediction, edges, clf.graph_cut.unary_weight, clf.graph_cut.binary_weight)
+    else:
+        lab, _, _ = weighted_graph_cut(prediction, edges, clf.graph_cut.unary_weight, row_weights)
     return lab if isinstance(labels, torch.Tensor) else lab.cpu().numpy()
+
+
+def _binary_term(clf):
+    """clf.graph_cut.binary_term -> None (the reference's uniform weights), "area" or "beta"; the two need ``graph_cut.solver: gpu``"""
+    gc = getattr(clf, "graph_cut", None)
+    term = getattr(gc, "binary_term", None)
+    if term is None or term == "uniform":
+        return None
+    if term not in ("area", "beta"):
+        raise ValueError("graph_cut.binary_term: %r (expected null, \"uniform\", \"area\" or \"beta\")" % (term,))
+    if getattr(gc, "solver", None) != "gpu":
+        raise ValueError("graph_cut.binary_term: %r needs graph_cut.solver: gpu (no weights are passed to the CPU solver)" % (term,))
+    return term
+
+
+def facet_weights_gpu(mdata, term, binary_weight, device=None):
+    """int32 capacities [F] on the device for every facet of the tetrahedralization `mdata` (`_3dt.npz`): ops.facet_cut_terms with
+    kind `term` ("area" / "beta") and clf.graph_cut.binary_weight as the scale; 0 for a facet with an infinite cell."""
+    from ..ops import facet_cut_terms
+
+    vertices = mdata["vertices"] if device is None else torch.from_numpy(np.ascontiguousarray(mdata["vertices"], dtype=np.float64)).to(device)
+    return facet_cut_terms(vertices, mdata["tetrahedra"], mdata["facets"], mdata["nfacets"], term, binary_weight)[0]
 
 
 def _occupancy_file(data):
@@ -267,7 +294,10 @@ def generate(data, prediction, clf):
       the reference) run on the GPU (dgnn_argmax_rows / dgnn_interface_flags / dgnn_compact_i32); integer results, identical;
     * the optional graph cut (``clf.temp.graph_cut``): with ``clf.graph_cut.solver == "gpu"`` the exact device solver
       (graph_cut_gpu, on the device logits); otherwise the reference's CPU solver when `gco` imports.  Either way a failure keeps
-      the raw labels with the reference's warning;
+      the raw labels with the reference's warning.  ``clf.graph_cut.binary_type`` is ignored, as in the reference (:34-40); the key
+      ``clf.graph_cut.binary_term`` (absent / None / "uniform": every facet weighs ``binary_weight``) set to "area" or "beta" weighs
+      each finite-finite facet by its geometry (facet_weights_gpu: rint(binary_weight * q_f), DESIGN §23) and needs the gpu solver;
+      any other value, or "area" / "beta" without the gpu solver, raises ValueError;
     * the mesh object is a trimesh.Trimesh (``process=True``, optional fix_normals) when trimesh imports, else an
       InterfaceMesh with the same vertices / faces and an ``export``; the evaluation metrics (watertight / iou / chamfer,
       :115-163) need trimesh + utils/libmesh and are computed only when those import -- otherwise eval_dict stays empty;
@@ -301,10 +331,15 @@ def generate(data, prediction, clf):
     assert labels_dev.numel() == len(mdata["tetrahedra"])
     if getattr(clf.temp, "graph_cut", None):
         mask = (nfacets >= 0).all(axis=1)
+        term = _binary_term(clf)     # a configuration mistake raises here, outside the try
         try:
             if getattr(getattr(clf, "graph_cut", None), "solver", None) == "gpu":
                 finite = (infinite == 0).to(dev)
-                labels_dev = graph_cut_gpu(labels_dev, pred_dev.detach()[finite], torch.from_numpy(nfacets[mask]), clf)
+                if term is None:
+                    labels_dev = graph_cut_gpu(labels_dev, pred_dev.detach()[finite], torch.from_numpy(nfacets[mask]), clf)
+                else:
+                    weights = facet_weights_gpu(mdata, term, clf.graph_cut.binary_weight, device=dev)[torch.from_numpy(mask).to(dev)]
+                    labels_dev = graph_cut_gpu(labels_dev, pred_dev.detach()[finite], torch.from_numpy(nfacets[mask]), clf, row_weights=weights)
             else:
                 finite = (infinite == 0).to(prediction.device)
                 lab = graph_cut(labels_dev.cpu().numpy(), prediction[finite].detach().cpu().numpy(), nfacets[mask], clf)

@@ -856,6 +856,7 @@ void* dgnn_khop_blocks_sampled_start_rows(const int32_t* rowptr, const int32_t* 
  *   dgnn_compact_i32     order-preserving stream compaction (finite-cell labels; interface facet ids)
  *   dgnn_interface_flags flags[f] = label(nfacets[f,0]) != label(nfacets[f,1]), cell -1 = outside
  *   dgnn_graph_cut_binary the optional graph cut between the two (:84-91), exact, on the device
+ *   dgnn_graph_cut_weighted the same cut with one capacity per facet; dgnn_facet_cut_terms makes the capacities from the geometry
  * ---------------------------------------------------------------------------------------------- */
 int dgnn_argmax_rows(const float* logits, int64_t ld, int64_t n, int c, int32_t* labels, void* stream);
 int64_t dgnn_compact_scratch_elems(int64_t n);
@@ -885,6 +886,51 @@ int64_t dgnn_graph_cut_scratch_bytes(int64_t n, int64_t n_rows);
 int dgnn_graph_cut_binary(const float* logits, int64_t ld, int64_t n, const int32_t* edges, int64_t n_rows, float unary_weight,
                           int32_t binary_weight, int32_t* labels_out, int64_t* energy_out, int64_t* flow_out, int32_t* stats_out,
                           void* scratch, void* stream);
+
+/* The same cut with one capacity per row: E(l) = sum_i D_i(l_i) + sum_r row_weights[r] [l_i != l_j].  Everything else is
+ * dgnn_graph_cut_binary's (the same solver body): costs, labels_out = the minimiser with the fewest outside cells, energy / flow / stats,
+ * scratch (dgnn_graph_cut_weighted_scratch_bytes = dgnn_graph_cut_scratch_bytes), the synchronisation points.
+ *   row_weights int32 [n_rows], each >= 0.  A row of weight 0 stays in the graph with no capacity; duplicate rows add up; a self-loop never
+ *               counts, whatever its weight.  With every weight = w the labels, energy, flow, steps and relabels are those of
+ *               dgnn_graph_cut_binary(w): the same arithmetic in the same order.
+ * DGNN_E_INVALID as above, and: a weight < 0 (of any row); a node with terminal capacity + max(sum of its incident weights, 2 * the
+ * largest of them) > INT32_MAX (the excess is bounded by the terminal capacity plus what can flow in, an arc's residual by twice its row's
+ * weight). */
+int64_t dgnn_graph_cut_weighted_scratch_bytes(int64_t n, int64_t n_rows);
+int dgnn_graph_cut_weighted(const float* logits, int64_t ld, int64_t n, const int32_t* edges, int64_t n_rows, float unary_weight,
+                            const int32_t* row_weights, int32_t* labels_out, int64_t* energy_out, int64_t* flow_out, int32_t* stats_out,
+                            void* scratch, void* stream);
+
+/* Per-facet weights for dgnn_graph_cut_weighted from the geometry of `<scene>_3dt.npz` (the layout of
+ * dgnn_locate_points: vertices fp64 [n_vertices, 3], tets int32 [n_cells, 4], facets int32 [n_facets, 3], nfacets int32 [n_facets, 2]).
+ *   kind 1 (area)  q_f = A_f / mean(A),  A_f = |(b - a) x (c - a)| / 2
+ *   kind 2 (beta)  q_f = 1 - min(cos phi_T1, cos phi_T2) in [0, 2]  (Labatut et al. 2009: phi = the angle between the facet and the
+ *                  circumsphere of the cell on that side; cos > 0 when the circumcentre lies on the cell's own side of the facet)
+ *   w_f = (int32) rint(binary_weight * q_f)   (fp64 product, half to even)
+ * A facet is a graph row iff both entries of its nfacets row are >= 0; every other facet gets q = 0, w = 0 (and is in none of the sums).
+ * q_out DEVICE fp64 [n_facets] (NULL: not written), w_out DEVICE int32 [n_facets], stats_out DEVICE int64 [4] (NULL: not written): graph
+ * rows, neutralised sides, graph rows with w_f == 0, max w_f.  scratch: dgnn_facet_cut_terms_scratch_bytes(n_facets) bytes.
+ *
+ * OPERATION ORDER (fp64, no contraction; tests/graph_cut_weights_model.py restates it).  For 3-vectors
+ *   x - y = componentwise;  x X y = (x.y y.z - x.z y.y,  x.z y.x - x.x y.z,  x.x y.y - x.y y.x);  x . y = (x.x y.x + x.y y.y) + x.z y.z.
+ * With (a, b, c) the facet's vertices as stored:
+ *   n = (b - a) X (c - a);  nn = sqrt(n . n);  A_f = 0.5 * nn.
+ *   mean(A) = S / rows: S = the sum over ALL facets f = 0 .. n_facets-1 of A_f (0 for a facet that is no graph row) taken serially in chunks
+ *   of 256 consecutive facets, the chunk sums then added serially in chunk order, each from 0.0; rows as a double.  q_f = A_f / mean(A).
+ * beta, for the side of cell T = nfacets[f, k] with vertices p0..p3 as stored and d = the one vertex id of T not in the facet:
+ *   u = p1 - p0, v = p2 - p0, w = p3 - p0;  vw = v X w, wu = w X u, uv = u X v;  det = u . vw;  d2 = 2.0 * det;
+ *   c.x = ((|u|^2 vw.x + |v|^2 wu.x) + |w|^2 uv.x) / d2  (y, z alike; |x|^2 = x . x): the circumcentre relative to p0;  R = sqrt(c . c);
+ *   sd = n . (d - a);  g = (p0 + c) - a;  hn = n . g;  h = (sd > 0 ? hn : -hn) / nn;  r = h / R;  cos phi_T = min(max(r, -1), 1).
+ *   The side is NEUTRAL (cos phi_T = 0, counted in stats_out[1]) when det == 0, nn == 0, sd == 0 or one of R, h, r is not finite.
+ *   q_f = 1.0 - (cos phi_T1 < cos phi_T2 ? cos phi_T1 : cos phi_T2), T1 = nfacets[f, 0], T2 = nfacets[f, 1].
+ * DGNN_E_INVALID: kind not 1 / 2; binary_weight < 0 or not finite; a vertex id of any facet, or of a cell named by a graph row, outside
+ * [0, n_vertices), or a cell id >= n_cells; a graph row whose facet is not a face of a cell its nfacets row names (beta); mean(A) that is
+ * 0 or not finite when there are graph rows (area); a w_f that is not below 2^30.  The call SYNCHRONISES `stream` once, at its end.  All
+ * counters are integer atomics and the sum has a fixed order: reruns are bit-identical. */
+int64_t dgnn_facet_cut_terms_scratch_bytes(int64_t n_facets);
+int dgnn_facet_cut_terms(const double* vertices, int64_t n_vertices, const int32_t* tets, int64_t n_cells, const int32_t* facets,
+                         const int32_t* nfacets, int64_t n_facets, int kind, double binary_weight, double* q_out, int32_t* w_out,
+                         int64_t* stats_out, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Mesh metrics of the interface surface (reference processing/generate_mesh.py:126-163, processing/evaluate_mesh.py compute_iou /
