@@ -3,11 +3,17 @@
 //     cell_k = sum_c kl_div(log_softmax(logits_k)_c, gt_kc)           kl_div(x, t) = t * (log t - x), 0 where t == 0
 //     w_k    = vol_k | log(1 + vol_k) | sqrt(vol_k)                     (regularization.cell_norm)
 //     loss   = sum_k cell_k * w_k / sum_k w_k
-//     OA    += #{ k : [gt_k0 > gt_k1] == argmax_c logits_kc }           (the reference's overall-accuracy counter, :178-180)
+//     OA    += #{ k : [gt_k0 > gt_k1] == argmax_c log_softmax(logits_k)_c }   (the reference's overall-accuracy counter, :178-180)
+//
+// The counter takes the argmax of the two fp32 log-softmax values, first index on a tie, as the reference does -- not of the logits: for
+// 0 < l1 - l0 below half an ulp of log 2 (about 3e-8) both values round to the same float and the reference counts class 0.
 //
 // The reference runs this as ~20 elementwise / reduction launches forward and as many backward on a [2048, 2] batch -- pure
-// launch overhead.  Row terms are evaluated in fp32 like the reference's, the three sums accumulate in fp64 in a fixed order
-// (deterministic), so the loss agrees with the reference's fp32 reduction to its last few ulps.
+// launch overhead.  A row's term is built from elementary functions rounded to fp32 -- log t, log(sum exp(x - max)), the weight; each
+// evaluated in fp64 and rounded once, so that no libm's last bits enter -- and combined in fp64: a row is within 2^-23 of its magnitude
+// |t log t| + |t| (|x - max| + |lg|) whatever its values (down to fp32's underflow: a log-sum below 2^-126), and where the reference's fp32 terms are exact (expf(-d) = 0, logf(1) = 0) so
+// are these.  The three sums accumulate in fp64 in a fixed order (deterministic); the loss agrees with the reference's fp32 reduction to its
+// last few ulps.
 #include "common.h"
 
 namespace {
@@ -15,7 +21,25 @@ namespace {
 constexpr int LOSS_THREADS = 1024;
 constexpr int LOSS_MAX_BLOCKS = 256;
 
-__device__ __forceinline__ float weight_of(float vol, int norm) { return norm == 1 ? logf(1.f + vol) : (norm == 2 ? sqrtf(vol) : vol); }
+// log(1 + vol) | sqrt(vol) | vol, rounded once to fp32 (1 + vol is exact in fp64; logf(1.f + vol) would carry the rounding of 1 + vol, 2^-24 of 1
+// and so 6e-5 of the weight at vol = 1e-3)
+__device__ __forceinline__ float weight_of(float vol, int norm) { return norm == 1 ? (float)log(1.0 + (double)vol) : (norm == 2 ? sqrtf(vol) : vol); }
+
+// (cell_k w_k, w_k, OA_k) of one row added to v.  The class is the reference's: argmax of the two fp32 log-softmax values in torch's order,
+// (x - max) - log(sum exp(x - max)), first index on a tie.
+__device__ __forceinline__ void add_row(double (&v)[3], float l0, float l1, float t0, float t1, float vol, int norm) {
+    const float m = fmaxf(l0, l1);
+    const float lg32 = logf(expf(l0 - m) + expf(l1 - m));
+    const float s0 = (l0 - m) - lg32, s1 = (l1 - m) - lg32;
+    const double a0 = (double)l0 - (double)m, a1 = (double)l1 - (double)m;      // exact; one is 0, the other -|l0 - l1|
+    const double lg = (double)(float)log1p(exp(a0 + a1));
+    const double c0 = (t0 > 0.f ? (double)t0 * (double)(float)log((double)t0) : 0.0) - (double)t0 * (a0 - lg);
+    const double c1 = (t1 > 0.f ? (double)t1 * (double)(float)log((double)t1) : 0.0) - (double)t1 * (a1 - lg);
+    const double w = (double)weight_of(vol, norm);
+    v[0] += (c0 + c1) * w;
+    v[1] += w;
+    v[2] += ((t0 > t1 ? 1 : 0) == (s1 > s0 ? 1 : 0)) ? 1.0 : 0.0;
+}
 
 __device__ __forceinline__ void block_sum3(double (&v)[3], double* red /*[3][16]*/) {
 #pragma unroll
@@ -42,16 +66,7 @@ __global__ void __launch_bounds__(LOSS_THREADS) k_kl_loss_fwd(const float* __res
     __shared__ double red[3 * 16];
     double v[3] = {0, 0, 0};
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
-        const float l0 = logits[k * ldl], l1 = logits[k * ldl + 1];
-        const float t0 = gt[k * ldg], t1 = gt[k * ldg + 1];
-        const float m = fmaxf(l0, l1);
-        const float lg = logf(expf(l0 - m) + expf(l1 - m));   // log_softmax = (x - max) - log(sum exp(x - max)), torch's order
-        const float c0 = (t0 > 0.f ? t0 * logf(t0) : 0.f) - t0 * ((l0 - m) - lg);
-        const float c1 = (t1 > 0.f ? t1 * logf(t1) : 0.f) - t1 * ((l1 - m) - lg);
-        const float w = weight_of(vol[k * ldv], norm);
-        v[0] += (double)((c0 + c1) * w);
-        v[1] += (double)w;
-        v[2] += ((t0 > t1 ? 1 : 0) == (l1 > l0 ? 1 : 0)) ? 1.0 : 0.0;
+        add_row(v, logits[k * ldl], logits[k * ldl + 1], gt[k * ldg], gt[k * ldg + 1], vol[k * ldv], norm);
     }
     block_sum3(v, red);
     if (threadIdx.x == 0) {
@@ -106,16 +121,7 @@ __global__ void __launch_bounds__(LOSS_THREADS) k_kl_loss_step(const float* __re
     for (int b = 0; b < nb; ++b) {
         double v[3] = {0, 0, 0};
         for (int64_t k = (int64_t)b * LOSS_THREADS + threadIdx.x; k < n; k += (int64_t)nb * LOSS_THREADS) {
-            const float l0 = logits[k * ldl], l1 = logits[k * ldl + 1];
-            const float t0 = gt[k * ldg], t1 = gt[k * ldg + 1];
-            const float m = fmaxf(l0, l1);
-            const float lg = logf(expf(l0 - m) + expf(l1 - m));
-            const float c0 = (t0 > 0.f ? t0 * logf(t0) : 0.f) - t0 * ((l0 - m) - lg);
-            const float c1 = (t1 > 0.f ? t1 * logf(t1) : 0.f) - t1 * ((l1 - m) - lg);
-            const float w = weight_of(vol[k * ldv], norm);
-            v[0] += (double)((c0 + c1) * w);
-            v[1] += (double)w;
-            v[2] += ((t0 > t1 ? 1 : 0) == (l1 > l0 ? 1 : 0)) ? 1.0 : 0.0;
+            add_row(v, logits[k * ldl], logits[k * ldl + 1], gt[k * ldg], gt[k * ldg + 1], vol[k * ldv], norm);
         }
         block_sum3(v, red);
         if (threadIdx.x == 0) {

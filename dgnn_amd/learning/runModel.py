@@ -217,8 +217,9 @@ class Trainer:
             metrics.addPacked(sums, data.batch_x.shape[0])
             return self._with_regularization(loss, logits_cell, data, clf, metrics)
         if clf.training.loss == "kl":
-            cell_loss = F.kl_div(F.log_softmax(logits_cell, dim=-1), gt[:, :2], reduction='none').sum(dim=1)
-            pred = logits_cell.argmax(1)
+            log_p = F.log_softmax(logits_cell, dim=-1)
+            cell_loss = F.kl_div(log_p, gt[:, :2], reduction='none').sum(dim=1)
+            pred = log_p.argmax(1)                 # of the log-softmax values, as the reference (:179): nearly equal logits tie there
             metrics.addOAItem(((gt[:, 0] > gt[:, 1]).long() == pred).sum(), data.batch_x.shape[0])
         elif clf.training.loss == "bce":
             cell_loss = F.binary_cross_entropy_with_logits(logits_cell.squeeze(-1), gt[:, 3], reduction='none')

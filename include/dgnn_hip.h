@@ -605,7 +605,7 @@ int dgnn_sage_updated_train_bwd(const int32_t* t_rowptr, const int32_t* t_dst, c
 /* ------------------------------------------------------------------------------------------------
  * Volume-weighted KL cell loss of the training step (learning/runModel.py:171-209), one launch each way:
  *   cell_k = sum_c kl_div(log_softmax(logits_k)_c, gt_kc);  w_k = vol_k | log(1+vol_k) | sqrt(vol_k)  (norm 0 | 1 | 2)
- *   loss = sum cell_k w_k / sum w_k;   sums[3] (fp64) = sum cell_k w_k, sum w_k, #{k: [gt_k0 > gt_k1] == argmax logits_k}
+ *   loss = sum cell_k w_k / sum w_k;   sums[3] (fp64) = sum cell_k w_k, sum w_k, #{k: [gt_k0 > gt_k1] == argmax log_softmax(logits_k), fp32, first index on a tie}
  *   backward: dlogits_kc = grad_loss * w_k / sums[1] * (softmax_kc (gt_k0 + gt_k1) - gt_kc)
  * logits / gt: two leading columns of rows with strides ldl / ldg; vol: element stride ldv.  scratch:
  * dgnn_kl_cell_loss_scratch_doubles(n) doubles.  grad_loss: device pointer to the upstream scalar.
