@@ -113,6 +113,14 @@ SIGNATURES = {
     "dgnn_mesh_component_measures": (i32, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
     "dgnn_mesh_component_keep_scratch_bytes": (i64, []),
     "dgnn_mesh_component_keep": (i32, [vp, i64, vp, i64, i32, i64, vp, vp, vp, vp]),
+    "dgnn_tet_neighbors_scratch_bytes": (i64, []),
+    "dgnn_tet_neighbors": (i32, [vp, i64, vp, vp, i64, vp, vp, vp, vp]),
+    "dgnn_cell_geometry_scratch_bytes": (i64, [i64]),
+    "dgnn_cell_geometry": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dgnn_vertex_incidence_scratch_bytes": (i64, [i64]),
+    "dgnn_vertex_incidence": (i32, [vp, i64, i64, vp, vp, vp, vp]),
+    "dgnn_vertex_rays_scratch_bytes": (i64, [i64, i64, i64]),
+    "dgnn_vertex_rays": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dgnn_mesh_contains_scratch_bytes": (i64, [i64, i64, i32]),
     "dgnn_mesh_contains_plan": (i32, [vp, i64, vp, i64, i32, i64, vp, vp, vp, vp]),
     "dgnn_mesh_contains": (i32, [vp, i64, vp, i64, i32, i64, vp, i64, vp, vp, vp, i64, vp, vp]),

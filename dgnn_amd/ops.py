@@ -2026,6 +2026,110 @@ def filter_components(faces, comp, counts, largest=False, min_faces=None):
     return f[ids[:m].long()], keep.bool(), m
 
 
+# ---- the scene front end: adjacency, cell geometry, vertex-ray visibility (csrc/scenefeat.hip) ---------------------------
+def _empty(dev, dtype, *shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return torch.empty(max(n, 1), dtype=dtype, device=dev)[:n].view(*shape)
+
+
+@on_device_of
+def tet_neighbors(facets, nfacets, tetrahedra):
+    """neighbors int32 [T, 4] on the GPU (dgnn_tet_neighbors): slot k = the cell across the facet opposite vertex k of the tet, -1 = the
+    infinite cell; facets int [F, 3], nfacets int [F, 2], tetrahedra int [T, 4] of a `_3dt.npz`.  DgnnError for ids out of range and
+    for a facet that is not a face of a cell nfacets names for it."""
+    dev = _dev_of(tetrahedra, facets, nfacets)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    fac = _on(facets, dev, torch.int32, 3)
+    nfac = _on(nfacets, dev, torch.int32, 2)
+    if fac.size(0) != nfac.size(0):
+        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
+    t = tets.size(0)
+    nbr = _empty(dev, torch.int32, t, 4)
+    bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(lib().dgnn_tet_neighbors_scratch_bytes()), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_tet_neighbors(ptr(tets), t, ptr(fac), ptr(nfac), fac.size(0), ptr(nbr), ptr(bad), ptr(scratch), stream_ptr()), "dgnn_tet_neighbors")
+    if int(bad.item()):
+        raise DgnnError("tet_neighbors: %d (facet, cell) pairs whose facet is not a face of the cell nfacets names" % int(bad.item()))
+    return nbr
+
+
+@on_device_of
+def cell_geometry(vertices, tetrahedra):
+    """The `_cgeom` columns of the finite cells (dgnn_cell_geometry; the expressions are in include/dgnn_hip.h): dict of "radius"
+    (circumradius, +inf for a flat cell), "vol", "longest_edge", "shortest_edge" fp64 [T] on the GPU, "n_flat" int, and "sum_longest",
+    "sum_shortest" floats: the two column sums in a fixed order, from which the loader's mean_edge over n cells is
+    (sum_longest + sum_shortest) / (2 n).  DgnnError for a vertex id out of range."""
+    dev = _dev_of(vertices, tetrahedra)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    t = tets.size(0)
+    cols = [_empty(dev, torch.float64, t) for _ in range(4)]
+    sums = torch.zeros(2, dtype=torch.float64, device=dev)
+    flat = torch.zeros(1, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(lib().dgnn_cell_geometry_scratch_bytes(t)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_cell_geometry(ptr(v), v.size(0), ptr(tets), t, ptr(cols[0]), ptr(cols[1]), ptr(cols[2]), ptr(cols[3]), ptr(sums), ptr(flat),
+                                   ptr(scratch), stream_ptr()), "dgnn_cell_geometry")
+    s = sums.cpu()
+    return {"radius": cols[0], "vol": cols[1], "longest_edge": cols[2], "shortest_edge": cols[3], "n_flat": int(flat.item()),
+            "sum_longest": float(s[0]), "sum_shortest": float(s[1])}
+
+
+@on_device_of
+def vertex_incidence(tetrahedra, n_vertices):
+    """(rowptr int32 [V + 1], entries int32 [4 T]) on the GPU (dgnn_vertex_incidence): row v holds 4 t + k for every corner
+    tetrahedra[t][k] == v.  The order inside a row is not specified.  DgnnError for a vertex id out of range."""
+    dev = _dev_of(tetrahedra)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    t, nv = tets.size(0), int(n_vertices)
+    rowptr = torch.zeros(nv + 1, dtype=torch.int32, device=dev)
+    entries = _empty(dev, torch.int32, 4 * t)
+    scratch = torch.empty(int(lib().dgnn_vertex_incidence_scratch_bytes(nv)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_vertex_incidence(ptr(tets), t, nv, ptr(rowptr), ptr(entries), ptr(scratch), stream_ptr()), "dgnn_vertex_incidence")
+    return rowptr, entries
+
+
+RAY_SIDES = ("outside", "inside")
+RAY_STATS = ("used", "duplicates", "degenerate", "no_outside", "no_inside", "exact_used")
+
+
+@on_device_of
+def vertex_ray_features(vertices, tetrahedra, ray_vertex, sensors, unique=True, incidence=None):
+    """The vertex-ray visibility aggregates (dgnn_vertex_rays; cell choice, tie rule and the distance are in include/dgnn_hip.h): ray r
+    runs from vertices[ray_vertex[r]] towards sensors[r] (fp64 [R, 3]); with `unique` only the lowest-index ray of a vertex is used.
+    incidence: the pair of vertex_incidence (built here when None).  -> dict of tensors on the GPU:
+      "ray_tet", "ray_slot" int32 [R, 2], "ray_dist" fp64 [R, 2]: the chosen cell per side (column 0 outside, 1 inside; -1 / 0.0 = none);
+      "<side>_tet_count" int32 [T], "<side>_tet_{min,max,sum}" fp64 [T], "<side>_slot_count" int32 [T, 4], "<side>_slot_{min,max,sum}"
+      fp64 [T, 4] for <side> in RAY_SIDES; "stats": dict of RAY_STATS -> int.
+    DgnnError for ids out of range and coordinates outside the exact predicate's range."""
+    dev = _dev_of(ray_vertex, sensors, vertices, tetrahedra)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    rv = _on(ray_vertex, dev, torch.int32).reshape(-1)
+    s = _on(sensors, dev, torch.float64, 3)
+    if s.size(0) != rv.numel():
+        raise ValueError("%d sensor positions for %d rays" % (s.size(0), rv.numel()))
+    t, r, nv = tets.size(0), rv.numel(), v.size(0)
+    rowptr, entries = vertex_incidence(tets, nv) if incidence is None else (_on(incidence[0], dev, torch.int32), _on(incidence[1], dev, torch.int32))
+    if rowptr.numel() != nv + 1 or entries.numel() != 4 * t:
+        raise ValueError("incidence of %d vertices and %d corners for %d vertices and %d tets" % (rowptr.numel() - 1, entries.numel(), nv, t))
+    ray_tet, ray_slot, ray_dist = _empty(dev, torch.int32, r, 2), _empty(dev, torch.int32, r, 2), _empty(dev, torch.float64, r, 2)
+    tet_count, tet_stat = _empty(dev, torch.int32, 2, t), _empty(dev, torch.float64, 2, 3, t)
+    slot_count, slot_stat = _empty(dev, torch.int32, 2, t, 4), _empty(dev, torch.float64, 2, 3, t, 4)
+    stats = torch.zeros(len(RAY_STATS), dtype=torch.int64, device=dev)
+    scratch = torch.empty(max(int(lib().dgnn_vertex_rays_scratch_bytes(r, t, nv)), 1), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_vertex_rays(ptr(v), nv, ptr(tets), t, ptr(rowptr), ptr(entries), ptr(rv), ptr(s), r, int(bool(unique)), ptr(ray_tet), ptr(ray_slot),
+                                 ptr(ray_dist), ptr(tet_count), ptr(tet_stat), ptr(slot_count), ptr(slot_stat), ptr(stats), ptr(scratch), stream_ptr()),
+          "dgnn_vertex_rays")
+    out = {"ray_tet": ray_tet, "ray_slot": ray_slot, "ray_dist": ray_dist, "stats": dict(zip(RAY_STATS, (int(x) for x in stats.cpu())))}
+    for i, side in enumerate(RAY_SIDES):
+        out[side + "_tet_count"], out[side + "_slot_count"] = tet_count[i], slot_count[i]
+        for j, stat in enumerate(("min", "max", "sum")):
+            out["%s_tet_%s" % (side, stat)], out["%s_slot_%s" % (side, stat)] = tet_stat[i, j], slot_stat[i, j]
+    return out
+
+
 # ---- occupancy of any triangle mesh and the evaluation-sample generators (csrc/meshcontains.hip; reference utils/libmesh) ----------
 def _check_value(code, what):
     """`check`, with the library's "bad input" status as the ValueError a Python caller expects for bad data"""

@@ -1,0 +1,92 @@
+"""Scene preparation on the device: from a triangulation (`<scene>_3dt.npz`) and a scan (points + sensor positions) to the model's input
+files `<scene>_cgeom.npz`, `<scene>_cbvf.npz`, `<scene>_fbvf.npz`.
+
+The reference gets these files from an external binary; their definitions here are the ones that reproduce its recorded output for
+Ignatius scene 99 (counts and edge lengths exactly, the other columns to the last bits).  The facet-ray files (`_cbff`, `_fbff`), `_fgeom`
+and `_labels` are not built.
+
+Rows: the cells of a scene are its finite tets in `tetrahedra` order with the infinite cells interleaved where `infinite` is 1; finite
+cell number r is tet r.  Infinite cells hold 0 in every column.  Edge row 4 c + k belongs to the facet of cell c opposite its vertex k (the
+row order of `_adjacencies.npz`).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import ops
+
+CGEOM_KEYS = ("radius", "vol", "longest_edge", "shortest_edge")
+VF_GROUPS = ("inside", "outside", "last")          # the files' key order; `last` holds 0 everywhere
+VF_STATS = ("count", "dist_min", "dist_max", "dist_sum")
+
+
+def match_vertices(vertices, points):
+    """vertex id of every point by exact coordinate match (int64 [P], -1 = no vertex; equal vertices: the lowest id).  Host-side bookkeeping
+    on the raw fp64 bits (0.0 and -0.0 are one coordinate)."""
+    v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+    p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    if len(v) == 0:
+        return np.full(len(p), -1, dtype=np.int64)
+    key = lambda x: (x + 0.0).view(np.dtype((np.void, 24))).reshape(-1)
+    kv, kp = key(v), key(p)
+    order = np.argsort(kv, kind="stable")
+    pos = np.minimum(np.searchsorted(kv[order], kp), len(v) - 1)
+    return np.where(kv[order][pos] == kp, order[pos], -1).astype(np.int64)
+
+
+def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base=None, device=None):
+    """mdata: the arrays of `<scene>_3dt.npz` (vertices, tetrahedra, facets, nfacets); infinite [n_cells]: 1 = infinite cell (the
+    `infinite` of `_labels.npz`); scan_points, sensor_position [P, 3]: every point that equals a vertex casts that vertex's ray towards its
+    sensor, points that share a vertex cast one ray (the lowest-index point's).  Runs ops.tet_neighbors / cell_geometry / vertex_ray_features on
+    `device` (default: the current GPU) and returns a dict:
+      "cgeom", "cbvf", "fbvf": key -> fp64 ndarray, with the reference files' keys in their order ([n_cells] / [4 n_cells] rows);
+      "neighbors": int64 ndarray [n_cells, 4], the cell across each facet of the finite cells (-1: an infinite cell; infinite rows: -1);
+      "mean_edge": the loader's mean_edge, "stats": the ray stats plus "points", "unmatched_points", "n_flat".
+    With out_base the three files are written as out_base + "_cgeom.npz" etc., readable by the reference's and this package's dataLoader."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    inf = np.asarray(infinite).astype(bool).reshape(-1)
+    cell_of_tet = np.nonzero(~inf)[0]
+    vertices = np.asarray(mdata["vertices"], dtype=np.float64)
+    n_cells, n_tets = len(inf), len(mdata["tetrahedra"])
+    if len(cell_of_tet) != n_tets:
+        raise ValueError("%d finite cells in `infinite` but %d tetrahedra" % (len(cell_of_tet), n_tets))
+    vid = match_vertices(vertices, scan_points)
+    hit = vid >= 0
+    sensors = np.asarray(sensor_position, dtype=np.float64).reshape(-1, 3)
+    if len(sensors) != len(vid):
+        raise ValueError("%d sensor positions for %d scan points" % (len(sensors), len(vid)))
+
+    v = torch.from_numpy(vertices).to(dev)
+    tets = torch.as_tensor(np.asarray(mdata["tetrahedra"])).to(dev, torch.int32)
+    nbr = ops.tet_neighbors(torch.as_tensor(np.asarray(mdata["facets"])).to(dev), torch.as_tensor(np.asarray(mdata["nfacets"])).to(dev), tets)
+    geom = ops.cell_geometry(v, tets)
+    rays = ops.vertex_ray_features(v, tets, torch.from_numpy(vid[hit]).to(dev), torch.from_numpy(sensors[hit]).to(dev))
+
+    def cell_col(t):
+        col = np.zeros((n_cells,) + tuple(t.shape[1:]))
+        col[cell_of_tet] = t.cpu().numpy()
+        return col.reshape(-1)
+
+    cgeom = {k: cell_col(geom[k]) for k in CGEOM_KEYS}
+    files = {"cb": {}, "fb": {}}
+    for prefix, level in (("cb", "tet"), ("fb", "slot")):
+        for g in VF_GROUPS:
+            for s in VF_STATS:
+                key = "%s_vertex_%s_%s" % (prefix, g, s)
+                if g == "last":
+                    files[prefix][key] = np.zeros(n_cells * (4 if level == "slot" else 1))
+                else:
+                    files[prefix][key] = cell_col(rays["%s_%s_%s" % (g, level, s.replace("dist_", ""))])
+    nbr_tets = nbr.cpu().numpy().astype(np.int64)
+    neighbors = np.full((n_cells, 4), -1, dtype=np.int64)
+    neighbors[cell_of_tet] = np.where(nbr_tets >= 0, cell_of_tet[np.maximum(nbr_tets, 0)], -1) if n_tets else nbr_tets
+    stats = dict(rays["stats"], points=int(len(vid)), unmatched_points=int((~hit).sum()), n_flat=geom["n_flat"])
+    if stats["unmatched_points"]:
+        print("build_scene_features: %d of %d scan points match no vertex of the triangulation and cast no ray" % (stats["unmatched_points"], len(vid)))
+    out = {"cgeom": cgeom, "cbvf": files["cb"], "fbvf": files["fb"], "neighbors": neighbors, "stats": stats,
+           "mean_edge": (geom["sum_longest"] + geom["sum_shortest"]) / (2 * n_cells) if n_cells else float("nan")}
+    if out_base is not None:
+        for name in ("cgeom", "cbvf", "fbvf"):
+            np.savez(out_base + "_%s.npz" % name, **out[name])
+    return out

@@ -1075,6 +1075,68 @@ int dgnn_mesh_component_keep(const int32_t* comp, int64_t n_faces, const int64_t
                              int64_t min_faces, int32_t* keep_out, int64_t* n_kept_out, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The scene front end: cell adjacency, cell geometry (`_cgeom`) and the vertex-ray visibility aggregates (`_cbvf`, `_fbvf`) of a
+ * triangulation in `_3dt.npz` layout (vertices fp64 [n_vertices, 3], tetrahedra int32 [n_tets, 4] = the finite cells, facets int32
+ * [n_facets, 3], nfacets int32 [n_facets, 2], -1 = the infinite cell).  DESIGN.md section 25.  Everything is fp64, every operation
+ * rounded on its own (no fused multiply-add); (a, b, c) . (d, e, f) below means (a d + b e) + c f.  Every entry point SYNCHRONISES `stream`
+ * (status read).  DGNN_E_INVALID: an id out of range; DGNN_E_UNSUPPORTED: 4 n_tets, n_vertices or n_rays beyond int32.
+ *
+ * dgnn_tet_neighbors: neighbors_out int32 [n_tets, 4]: slot k = the cell across the facet opposite vertex k of the tet (the facet made of
+ *   its three other vertices), -1 = the infinite cell (also where no facet names the slot).  n_bad_out DEVICE int64 [1] = the (facet,
+ *   cell) pairs whose facet is not made of three vertices of the cell nfacets names; such a pair writes nothing.  scratch: 256 bytes.
+ *
+ * dgnn_cell_geometry: per tet (p0, p1, p2, p3), with u = p1 - p0, v = p2 - p0, w = p3 - p0, a x b the usual cross product (each component
+ *   one product minus one product):
+ *     det      = u . (v x w)
+ *     vol      = |det| / 6
+ *     radius   = sqrt(r . r) / (2 |det|) with r = ((u . u) (v x w) + (v . v) (w x u)) + (w . w) (u x v) per component; +inf when det == 0
+ *                (n_flat_out DEVICE int64 [1] counts those tets)
+ *     longest, shortest = max, min of sqrt(d . d), d = pj - pi over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
+ *   edge_sums_out DEVICE fp64 [2] = the sums of longest_out and of shortest_out in a fixed order: chunks of 256 tets summed serially from
+ *   0.0, then the chunk sums serially from 0.0 (the loader's mean_edge = (the two sums) / (2 * number of cells)).
+ *   scratch   dgnn_cell_geometry_scratch_bytes(n_tets) bytes.
+ *
+ * dgnn_vertex_incidence: rowptr_out int32 [n_vertices + 1], entries_out int32 [4 n_tets]: row v holds the entries 4 t + k with
+ *   tetrahedra[t][k] == v.  The order inside a row is not specified (and may differ between runs); nothing computed from it depends on it.
+ *   scratch   dgnn_vertex_incidence_scratch_bytes(n_vertices) bytes.
+ *
+ * dgnn_vertex_rays: ray r runs from p = vertices[ray_vertex[r]] towards s = sensors[r] (fp64 [n_rays, 3]); rowptr / entries as above.
+ *   used      a ray with s == p is skipped (stats 2); with unique != 0 only the lowest-index ray of every vertex is used, the others are
+ *             skipped (stats 1).
+ *   cell      side 0 (`outside`, towards the sensor), side 1 (`inside`, away from it).  For an incident tet with p at slot k and the other
+ *             vertices q0, q1, q2 in slot order, D = sign det[q0 - p, q1 - p, q2 - p] and S_i = sign det[qa - p, qb - p, s - p] over
+ *             (a, b) = (0,1), (1,2), (2,0), all EXACT on the input coordinates (csrc/exact_orient.h: an fp64 filter, then an exact
+ *             expansion).  The tet qualifies for side 0 when D != 0 and every S_i D >= 0 (the sensor on the tet's side of each of its three
+ *             facets through p, or on the plane), for side 1 when D != 0 and every S_i D <= 0.  Per side the LOWEST qualifying tet index
+ *             is taken; none: the side records nothing (stats 3, 4).
+ *   dist      t = n . (q0 - p) / (n . d), n = (q1 - q0) x (q2 - q0), d = e / sqrt(e . e) (each component divided) with e = s - p, negated
+ *             for side 1.
+ *   per ray   ray_tet_out, ray_slot_out int32 [n_rays, 2] (-1 = none), ray_dist_out fp64 [n_rays, 2] (0 where none).
+ *   per tet   tet_count_out int32 [2, n_tets], tet_stat_out fp64 [2, 3, n_tets] = min, max, sum of dist over the rays that chose the tet
+ *             on that side; slot_count_out int32 [2, n_tets, 4], slot_stat_out fp64 [2, 3, n_tets, 4] the same per (tet, slot k).  min and
+ *             max are 0 where the count is 0.  The sums add from 0.0 in ascending ray index: bit-identical from run to run.
+ *   stats_out DEVICE int64 [6]: rays used, duplicates skipped, s == p skipped, used rays without an outside cell, without an inside cell,
+ *             orientation signs the exact stage decided.
+ *   scratch   dgnn_vertex_rays_scratch_bytes(n_rays, n_tets, n_vertices) bytes.
+ *   DGNN_E_INVALID also: an entry that is not a corner of the ray's vertex, non-finite coordinates; DGNN_E_UNSUPPORTED also: a non-zero
+ *   coordinate magnitude outside [2^-300, 2^300] (the exact predicate's range).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_tet_neighbors_scratch_bytes(void);
+int dgnn_tet_neighbors(const int32_t* tetrahedra, int64_t n_tets, const int32_t* facets, const int32_t* nfacets, int64_t n_facets,
+                       int32_t* neighbors_out, int64_t* n_bad_out, void* scratch, void* stream);
+int64_t dgnn_cell_geometry_scratch_bytes(int64_t n_tets);
+int dgnn_cell_geometry(const double* vertices, int64_t n_vertices, const int32_t* tetrahedra, int64_t n_tets, double* radius_out, double* vol_out,
+                       double* longest_out, double* shortest_out, double* edge_sums_out, int64_t* n_flat_out, void* scratch, void* stream);
+int64_t dgnn_vertex_incidence_scratch_bytes(int64_t n_vertices);
+int dgnn_vertex_incidence(const int32_t* tetrahedra, int64_t n_tets, int64_t n_vertices, int32_t* rowptr_out, int32_t* entries_out, void* scratch,
+                          void* stream);
+int64_t dgnn_vertex_rays_scratch_bytes(int64_t n_rays, int64_t n_tets, int64_t n_vertices);
+int dgnn_vertex_rays(const double* vertices, int64_t n_vertices, const int32_t* tetrahedra, int64_t n_tets, const int32_t* rowptr,
+                     const int32_t* entries, const int32_t* ray_vertex, const double* sensors, int64_t n_rays, int unique, int32_t* ray_tet_out,
+                     int32_t* ray_slot_out, double* ray_dist_out, int32_t* tet_count_out, double* tet_stat_out, int32_t* slot_count_out,
+                     double* slot_stat_out, int64_t* stats_out, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Occupancy of points in an arbitrary triangle mesh (reference utils/libmesh check_mesh_contains) and the generators of the
  * evaluation-sample builder (reference processing/<dataset>/sample_mesh.py).  DESIGN.md section 21.
  *

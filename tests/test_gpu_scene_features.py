@@ -1,0 +1,291 @@
+"""The device scene front end (ops.tet_neighbors / cell_geometry / vertex_incidence / vertex_ray_features and
+processing.scene_features.build_scene_features) against the CPU model tests/scene_features_model.py: neighbours, counts and the chosen
+(tet, slot) exactly, every fp64 column bit for bit (the same operations in the same order, no contraction), reruns bit-identical; on
+Ignatius scene 99 also against the files the reference's binary recorded (tests/golden/ignatius_scene_features*.npz)."""
+import functools
+import inspect
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import mesh_metrics_model as mm
+import scene_features_model as sf
+from helpers import gold
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+CASES = ["one_tet", "one_tet_mirrored", "shared_facet", "edge_ring", "duplicates", "duplicates_all", "lattice", "hub", "random_200", "random_3000",
+         "ignatius"]
+STATS = ("count", "min", "max", "sum")
+
+
+def _scene(v, tets):
+    fac, nfac = sf.facets_from_tets(tets)
+    return dict(vertices=np.asarray(v, np.float64), tetrahedra=np.asarray(tets, np.int32), facets=fac, nfacets=nfac)
+
+
+def _sensors_in_and_out(scene, seed):
+    """one ray per vertex: even vertices look at a point inside the unit cube, odd ones at a point on a sphere around it (outside the hull,
+    so hull vertices leave at once); then a few second rays to vertices that have one"""
+    rng = np.random.default_rng(seed)
+    n = len(scene["vertices"])
+    inside = rng.random((n, 3))
+    d = rng.standard_normal((n, 3))
+    outside = 0.5 + 3.0 * d / np.linalg.norm(d, axis=1, keepdims=True)
+    s = np.where((np.arange(n) % 2 == 0)[:, None], inside, outside)
+    extra = rng.integers(0, n, 17)
+    return np.concatenate([rng.permutation(n), extra]), np.concatenate([s, rng.random((17, 3))])
+
+
+@functools.lru_cache(maxsize=None)
+def _case(which):
+    """-> (scene, ray_vertex, sensors, unique, the model's neighbours, geometry, rays); computed once, read only"""
+    unique = True
+    if which in ("one_tet", "one_tet_mirrored"):
+        v = np.array([[0.0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]])
+        scene = _scene(v, [[0, 1, 2, 3]])
+        rv = np.arange(4)
+        s = np.tile(v.mean(axis=0), (4, 1)) if which == "one_tet" else 2 * v - v.mean(axis=0)
+    elif which in ("shared_facet", "duplicates", "duplicates_all"):
+        v = np.array([[0.0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1], [0, 0, -1]])
+        scene = _scene(v, [[0, 2, 1, 4], [0, 1, 2, 3]])                 # the facet (0, 1, 2) lies in the plane z = 0
+        if which == "shared_facet":
+            rv, s = np.array([0, 1]), np.array([[0.25, 0.25, 0.0], [0.0, 0.5, 0.0]])          # in the facet; along its edge (1, 2)
+        else:
+            rv = np.array([0, 0, 0, 3, 0, 3])
+            s = np.array([[0.25, 0.25, 0.0], [0.2, 0.2, 0.2], [0.0, 0, 0], [0, 0, 1.0], [0.1, 0.2, -0.3], [0.1, 0.1, 0.1]])
+            unique = which == "duplicates"
+    elif which == "edge_ring":
+        ang = 2 * np.pi * np.arange(5) / 5
+        v = np.concatenate([[[0.0, 0, 0], [0, 0, 1]], np.stack([np.cos(ang), np.sin(ang), np.full(5, 0.5)], axis=1)])
+        scene = _scene(v, [[0, 1, 2 + i, 2 + (i + 1) % 5] for i in range(5)])
+        rv, s = np.array([0, 1, 2]), np.array([[0.0, 0, 2], [0, 0, -3], v[4]])      # along the shared edge, both ways; along a rim edge's chord
+    elif which == "lattice":
+        g = np.arange(4.0)
+        scene = mm.scene_from_points(np.stack(np.meshgrid(g, g, g, indexing="ij"), axis=-1).reshape(-1, 3))
+        steps = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, 0, -1], [1, 1, 0], [1, 1, 1], [-1, 1, 0], [2, -1, 0]], dtype=np.float64)
+        rv = np.arange(64)
+        s = scene["vertices"] + steps[rv % 8]                                # along lattice lines and diagonals: in facets and on edges
+    elif which == "hub":
+        rng = np.random.default_rng(5)
+        d = rng.standard_normal((200, 3))
+        scene = mm.scene_from_points(np.concatenate([[[0.0, 0, 0]], d / np.linalg.norm(d, axis=1, keepdims=True)]))
+        rv, s, unique = np.zeros(300, dtype=np.int64), np.array([0.3, -0.5, 0.8]) + 0.08 * rng.standard_normal((300, 3)), False   # a narrow bundle
+    elif which.startswith("random_"):
+        scene = mm.random_scene(int(which[7:]), seed=3)
+        rv, s = _sensors_in_and_out(scene, seed=4)
+    else:
+        fx, g = sf.load_fixture(), gold("ignatius_3dt.npz")
+        scene = dict(vertices=g["vertices"], tetrahedra=g["tetrahedra"], facets=fx["facets"], nfacets=fx["nfacets"])
+        rv, s = sf.match_vertices(g["vertices"], fx["points"]), fx["sensor_position"]
+    nbr, bad = sf.tet_neighbors(scene["facets"], scene["nfacets"], scene["tetrahedra"])
+    assert bad == 0
+    geom = sf.cell_geometry(scene["vertices"], scene["tetrahedra"])
+    rays = sf.vertex_rays(scene["vertices"], scene["tetrahedra"], rv, s, unique=unique)
+    for a in list(scene.values()) + [rv, s, nbr]:
+        a.setflags(write=False)
+    return scene, rv, s, unique, nbr, geom, rays
+
+
+def _t(x):
+    return torch.from_numpy(np.array(x)).to(DEV)          # (a copy: the shared cases are read-only)
+
+
+def _rays(which, dev=DEV):
+    from dgnn_amd import ops
+    scene, rv, s, unique = _case(which)[:4]
+    return ops.vertex_ray_features(_t(scene["vertices"]).to(dev), _t(scene["tetrahedra"]).to(dev), _t(rv).to(dev), _t(s).to(dev), unique=unique)
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.int64)
+
+
+def test_the_hand_made_cases_mean_what_they_say():
+    r = _case("one_tet")[6]
+    assert r["ray_tet"].tolist() == [[0, -1]] * 4 and r["ray_slot"][:, 0].tolist() == [0, 1, 2, 3]
+    r = _case("one_tet_mirrored")[6]
+    assert r["ray_tet"].tolist() == [[-1, 0]] * 4 and r["stats"]["no_outside"] == 4          # the rays leave the hull at once
+    r = _case("shared_facet")[6]
+    assert r["ray_tet"][:, 0].tolist() == [0, 0] and r["stats"]["exact_used"] > 0             # both tets hold the ray: the lower index
+    r = _case("edge_ring")[6]
+    assert r["ray_tet"].tolist() == [[0, -1]] * 3 and r["outside_tet_count"].tolist() == [3, 0, 0, 0, 0]   # all five tets hold the edge's ray
+    r = _case("duplicates")[6]          # the lowest-index ray of vertex 3 is the one with sensor == vertex: its second ray is a duplicate
+    assert r["stats"]["duplicates"] == 3 and r["stats"]["degenerate"] == 2 and r["stats"]["used"] == 1
+    assert _case("duplicates_all")[6]["stats"]["used"] == 4
+    assert _case("lattice")[5]["n_flat"] > 0 and _case("lattice")[6]["stats"]["exact_used"] > 500
+    r = _case("hub")[6]
+    assert r["stats"]["used"] == 300 and min(r["outside_tet_count"].max(), r["inside_tet_count"].max()) >= 40 and (r["ray_tet"] >= 0).all()
+    r = _case("random_3000")[6]
+    assert r["stats"]["no_outside"] > 0 and r["stats"]["duplicates"] == 17 and r["stats"]["no_inside"] > 0
+
+
+@pytest.mark.parametrize("which", CASES)
+def test_neighbors_geometry_and_incidence_equal_the_model(which):
+    from dgnn_amd import ops
+    scene, _, _, _, nbr, geom, _ = _case(which)
+    v, tets = _t(scene["vertices"]), _t(scene["tetrahedra"])
+    got = ops.tet_neighbors(_t(scene["facets"]), _t(scene["nfacets"]), tets)
+    assert got.dtype == torch.int32 and got.is_cuda and np.array_equal(got.cpu().numpy(), nbr)
+    g = ops.cell_geometry(v, tets)
+    for k in ("radius", "vol", "longest_edge", "shortest_edge"):
+        assert g[k].dtype == torch.float64 and g[k].is_cuda and np.array_equal(_bits(g[k].cpu().numpy()), _bits(geom[k])), k
+    assert g["n_flat"] == geom["n_flat"]
+    assert _bits(g["sum_longest"]) == _bits(geom["sum_longest"]) and _bits(g["sum_shortest"]) == _bits(geom["sum_shortest"])
+    rowptr, entries = ops.vertex_incidence(tets, len(scene["vertices"]))
+    want_ptr, want_ent = sf.vertex_incidence(scene["tetrahedra"], len(scene["vertices"]))
+    rowptr, entries = rowptr.cpu().numpy(), entries.cpu().numpy()
+    assert np.array_equal(rowptr, want_ptr)
+    row = np.repeat(np.arange(len(want_ptr) - 1), np.diff(want_ptr))
+    assert np.array_equal(entries[np.lexsort((entries, row))], want_ent)          # the order inside a row is open
+
+
+@pytest.mark.parametrize("which", CASES)
+def test_rays_equal_the_model_bit_for_bit_and_rerun_identically(which):
+    want = _case(which)[6]
+    got, again = _rays(which), _rays(which)
+    assert np.array_equal(got["ray_tet"].cpu().numpy(), want["ray_tet"]) and np.array_equal(got["ray_slot"].cpu().numpy(), want["ray_slot"])
+    assert np.array_equal(_bits(got["ray_dist"].cpu().numpy()), _bits(want["ray_dist"]))
+    for side in sf.SIDES:
+        for level in ("tet", "slot"):
+            k = "%s_%s_count" % (side, level)
+            assert got[k].dtype == torch.int32 and np.array_equal(got[k].cpu().numpy(), want[k]), k
+            for stat in STATS[1:]:
+                k = "%s_%s_%s" % (side, level, stat)
+                assert got[k].dtype == torch.float64 and np.array_equal(_bits(got[k].cpu().numpy()), _bits(want[k])), k
+    assert got["stats"] == {k: want["stats"][k] for k in got["stats"]}
+    for k, a in got.items():
+        assert (a == again[k]) if k == "stats" else torch.equal(a.view(torch.int64) if a.dtype == torch.float64 else a, again[k].view(
+            torch.int64) if a.dtype == torch.float64 else again[k]), k
+
+
+def test_a_prebuilt_incidence_in_any_row_order_gives_the_same_rays():
+    from dgnn_amd import ops
+    scene, rv, s, unique = _case("random_200")[:4]
+    want = _rays("random_200")
+    rowptr, entries = sf.vertex_incidence(scene["tetrahedra"], len(scene["vertices"]))
+    entries = entries.copy()
+    for a, b in zip(rowptr[:-1], rowptr[1:]):
+        entries[a:b] = entries[a:b][::-1]
+    got = ops.vertex_ray_features(_t(scene["vertices"]), _t(scene["tetrahedra"]), _t(rv), _t(s), unique=unique, incidence=(_t(rowptr), _t(entries)))
+    for k in ("ray_tet", "ray_slot", "ray_dist", "outside_tet_sum", "inside_slot_sum"):
+        assert torch.equal(got[k], want[k]), k
+
+
+def test_bad_input_is_refused():
+    from dgnn_amd import ops
+    from dgnn_amd._lib import DgnnError
+    scene, rv, s = _case("shared_facet")[:3]
+    v, tets = _t(scene["vertices"]), _t(scene["tetrahedra"])
+    with pytest.raises(DgnnError):
+        ops.tet_neighbors(_t(np.array([[0, 1, 3]], dtype=np.int32)), _t(np.array([[0, -1]], dtype=np.int32)), tets)       # no face of cell 0
+    with pytest.raises(DgnnError):
+        ops.vertex_ray_features(v, tets, _t(np.array([0, 5])), _t(s))                                                      # no vertex 5
+    with pytest.raises(DgnnError):
+        ops.cell_geometry(v, _t(np.array([[0, 1, 2, 7]], dtype=np.int32)))
+    rowptr, entries = sf.vertex_incidence(scene["tetrahedra"], 5)
+    with pytest.raises(DgnnError):
+        ops.vertex_ray_features(v, tets, _t(rv), _t(s), incidence=(_t(rowptr), _t(entries[::-1].copy())))               # rows of other vertices
+
+
+@pytest.fixture
+def current_device_calls(monkeypatch):
+    """Records every call of torch.cuda.current_device() made from the package: the ops must run where their tensors are, so with one GPU
+    a fallback to the current device is still seen (the pattern of test_iou_gpu_runs_on_the_device_of_its_labels)."""
+    real = torch.cuda.current_device
+    calls = []
+
+    def spy():
+        caller = inspect.stack()[1].filename
+        if os.sep + "dgnn_amd" + os.sep in caller:
+            calls.append(caller)
+        return real()
+    monkeypatch.setattr(torch.cuda, "current_device", spy)
+    return calls
+
+
+def test_tensors_stay_on_the_device_of_the_inputs(current_device_calls):
+    from dgnn_amd import ops
+    dev = torch.device("cuda", torch.cuda.device_count() - 1)          # a second device where there is one
+    scene, rv, s, unique, nbr, geom, want = _case("random_200")
+    v, tets = _t(scene["vertices"]).to(dev), _t(scene["tetrahedra"]).to(dev)
+    got_nbr = ops.tet_neighbors(_t(scene["facets"]).to(dev), _t(scene["nfacets"]).to(dev), tets)
+    g = ops.cell_geometry(v, tets)
+    r = ops.vertex_ray_features(v, tets, _t(rv).to(dev), _t(s).to(dev), unique=unique)
+    assert current_device_calls == []
+    assert got_nbr.device == dev and g["vol"].device == dev and all(a.device == dev for k, a in r.items() if k != "stats")
+    assert np.array_equal(got_nbr.cpu().numpy(), nbr) and np.array_equal(_bits(g["radius"].cpu().numpy()), _bits(geom["radius"]))
+    assert np.array_equal(_bits(r["outside_slot_sum"].cpu().numpy()), _bits(want["outside_slot_sum"]))
+
+
+# ---- the scene files of Ignatius ---------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _ignatius_built(out_base):
+    from dgnn_amd.processing.scene_features import build_scene_features
+    fx, g = sf.load_fixture(), gold("ignatius_3dt.npz")
+    mdata = dict(vertices=g["vertices"], tetrahedra=g["tetrahedra"], facets=fx["facets"], nfacets=fx["nfacets"])
+    return fx, g, build_scene_features(mdata, g["infinite"], fx["points"], fx["sensor_position"], out_base=out_base, device=DEV)
+
+
+def test_ignatius_meets_the_recorded_files_and_the_recorded_adjacency(tmp_path, current_device_calls):
+    fx, g, out = _ignatius_built(str(tmp_path / "99"))
+    assert current_device_calls == []
+    cols = dict(out["cgeom"], **out["cbvf"], **out["fbvf"])
+    rec = sf.recorded_columns(fx)
+    sf.check_against_recorded(cols, rec)
+    assert all(not cols[k].any() for k in cols if "_last_" in k)
+    assert out["stats"]["unmatched_points"] == 0 and out["stats"]["duplicates"] == 7 and out["stats"]["no_outside"] == 159 and out["stats"]["no_inside"] == 49
+    inf = np.asarray(g["infinite"])
+    want = (rec["longest_edge"].sum() + rec["shortest_edge"].sum()) / (2 * len(inf))
+    assert abs(out["mean_edge"] - want) <= 1e-13 * want
+    adj = gold("static_f4_ignatius_full.npz")["adj_dst"].reshape(-1, 4)
+    fin = inf == 0
+    nb = out["neighbors"]
+    assert (nb[~fin] == -1).all()
+    both = fin[:, None] & (nb >= 0)
+    assert np.array_equal(nb[both], adj[both]) and (inf[adj[fin[:, None] & (nb < 0)]] == 1).all() and (inf[adj[both]] == 0).all()
+
+
+def test_written_files_have_the_reference_layout_and_load_like_the_recorded_ones(tmp_path):
+    from dgnn_amd.config import reconbench_pretrained
+    from dgnn_amd.processing.data import dataLoader
+    ours, theirs = tmp_path / "ours" / "gt", tmp_path / "recorded" / "gt"
+    ours.mkdir(parents=True)
+    theirs.mkdir(parents=True)
+    fx, g, _ = _ignatius_built(str(ours / "99"))
+    rec = sf.recorded_columns(fx)
+    layout = {"cgeom": ["radius", "vol", "longest_edge", "shortest_edge"], "cbvf": [str(k) for k in fx["vf_keys_cb"]],
+              "fbvf": [str(k) for k in fx["vf_keys_fb"]]}
+    n = len(g["infinite"])
+    adj = np.stack([np.repeat(np.arange(n), 4), gold("static_f4_ignatius_full.npz")["adj_dst"]], axis=1).astype(np.int32)
+    for folder in (ours, theirs):
+        np.savez(str(folder / "99_labels.npz"), infinite=g["infinite"])
+        np.savez(str(folder / "99_adjacencies.npz"), adjacencies=adj)
+    for name, keys in layout.items():
+        np.savez(str(theirs / ("99_%s.npz" % name)), **{k: rec[k] for k in keys})
+        z = np.load(str(ours / ("99_%s.npz" % name)))
+        assert z.files == keys, name
+        assert all(z[k].dtype == np.float64 and z[k].shape == rec[k].shape for k in keys), name
+
+    def load(folder):
+        clf = reconbench_pretrained(device=DEV)
+        clf["features"]["node_features"] = ["shape", "vertex", "count", "min", "max", "sum"]
+        clf["features"]["edge_features"] = ["vertex", "count", "min", "max", "sum"]
+        clf["inference"]["has_label"] = 0
+        clf["temp"]["cell_order"] = "none"
+        dl = dataLoader(clf, verbosity=0)
+        dl.run(dict(path=str(folder.parent), filename="99", gtfile="gt/99", category="", id="99", scan_conf=None, ioufile=None))
+        return dl
+
+    a, b = load(ours), load(theirs)
+    assert a.node_feature_names == b.node_feature_names and a.edge_feature_names == b.edge_feature_names
+    assert a.features.shape == (n, 13) and a.edge_features.shape == (4 * n, 8)
+    # standardised fp32 columns: one fp32 ulp is 6e-8 |want|; the fp64 inputs differ by 1e-12 relative at most (the bound above)
+    for got, want in ((a.features, b.features), (a.edge_features, b.edge_features)):
+        got, want = got.double().cpu().numpy(), want.double().cpu().numpy()
+        err = np.abs(got - want) / np.maximum(1.0, np.abs(want))
+        print("max error %.3g" % err.max())
+        assert err.max() <= 1e-6
