@@ -127,6 +127,10 @@ SIGNATURES = {
     "dgnn_box_points": (i32, [i64, f64, u64, vp, vp]),
     "dgnn_jitter_points": (i32, [vp, i64, f64, u64, vp, vp]),
     "dgnn_face_normals": (i32, [vp, i64, vp, i64, vp, vp, vp]),
+    "dgnn_tet_sample_points_scratch_bytes": (i64, []),
+    "dgnn_tet_sample_points": (i32, [vp, i64, vp, i64, i64, u64, u64, vp, vp, vp]),
+    "dgnn_cell_labels_scratch_bytes": (i64, [i64, i64, i32]),
+    "dgnn_cell_labels": (i32, [vp, i64, vp, i64, i32, i64, vp, i64, vp, i64, vp, i64, i64, u64, u64, vp, vp, vp, vp]),
     "dgnn_khop_scratch_elems": (i64, [i64, i64]),
     "dgnn_khop_count": (i32, [vp, vp, i64, i32, vp, vp, vp, vp]),
     "dgnn_khop_expand": (i32, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

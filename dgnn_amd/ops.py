@@ -2232,6 +2232,61 @@ def jitter_points(points64, sigma, seed=0):
     return out
 
 
+# ---- ground-truth cell labels: the share of each tet inside a closed mesh (csrc/meshcontains.hip) -----------------------
+@on_device_of
+def tet_sample_points(vertices, tetrahedra, n_samples, seed=0, tet_offset=0):
+    """n_samples points in every tet, uniform by volume, fp64 [T * n_samples, 3] on the GPU (dgnn_tet_sample_points; the draws, the fold
+    onto the tet and the operation order are in include/dgnn_hip.h): row t * n_samples + j is sample j of tet t, the very point
+    cell_labels tests.  tet_offset shifts the counters, so a chunk [a, b) of the tets with tet_offset=a gives rows of the whole call.
+    ValueError for n_samples < 1, DgnnError for a tet id out of range."""
+    dev = _dev_of(vertices, tetrahedra)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    k, t = int(n_samples), tets.size(0)
+    if k < 1:
+        raise ValueError("tet_sample_points: n_samples %d < 1" % k)
+    out = _empty(dev, torch.float64, t * k, 3)
+    scratch = torch.empty(int(lib().dgnn_tet_sample_points_scratch_bytes()), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_tet_sample_points(ptr(v), v.size(0), ptr(tets), t, k, _seed64(seed), _seed64(tet_offset), ptr(out), ptr(scratch), stream_ptr()),
+          "dgnn_tet_sample_points")
+    return out
+
+
+@on_device_of
+def cell_labels(mesh_vertices, mesh_faces, vertices, tetrahedra, n_samples=100, seed=0, tet_offset=0, hash_resolution=512, max_entries=2 ** 30):
+    """The share of every tet (vertices [V, 3], tetrahedra int [T, 4]) inside the closed mesh (mesh_vertices [M, 3], mesh_faces int [F, 3]):
+    n_samples points per tet, each tested as mesh_contains tests it, in one fused kernel that keeps the samples in registers
+    (dgnn_cell_labels; definitions in include/dgnn_hip.h).  -> dict: "count" int32 [T] (the inside samples), "inside_perc" = count /
+    n_samples and "outside_perc" = (n_samples - count) / n_samples, fp64 [T], all on the GPU; "n_samples"; "n_disagree": the samples whose
+    two ray parities differ (counted as outside).  The result does not depend on max_entries; tet_offset as in tet_sample_points.
+    ValueError for n_samples < 1 and for what mesh_contains refuses in a mesh (no faces, no extent, a face id out of range, a non-finite
+    referenced vertex); DgnnError for a tet id out of range."""
+    dev = _dev_of(vertices, tetrahedra, mesh_vertices, mesh_faces)
+    mv = _on(mesh_vertices, dev, torch.float64, 3)
+    mf = _on(mesh_faces, dev, torch.int32, 3)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    k, t, nv, nf, R = int(n_samples), tets.size(0), mv.size(0), mf.size(0), int(hash_resolution)
+    if k < 1:
+        raise ValueError("cell_labels: n_samples %d < 1" % k)
+    if nf == 0:
+        raise ValueError("cell_labels: a mesh without faces")
+    scratch = torch.empty(int(lib().dgnn_cell_labels_scratch_bytes(nv, nf, R)), dtype=torch.uint8, device=dev)
+    shift, n_entries = C.c_int32(0), C.c_int64(0)
+    _check_value(lib().dgnn_mesh_contains_plan(ptr(mv), nv, ptr(mf), nf, R, int(max_entries), C.byref(shift), C.byref(n_entries), ptr(scratch),
+                                               stream_ptr()), "dgnn_mesh_contains_plan")
+    cap = max(int(n_entries.value), 1)
+    entries = torch.empty(cap, dtype=torch.int32, device=dev)
+    count = _empty(dev, torch.int32, t)
+    dis = torch.zeros(1, dtype=torch.int64, device=dev)
+    # the mesh passed the plan above: what is refused from here on is the tets' ids
+    check(lib().dgnn_cell_labels(ptr(mv), nv, ptr(mf), nf, R, int(max_entries), ptr(entries), cap, ptr(v), v.size(0), ptr(tets), t, k, _seed64(seed),
+                                 _seed64(tet_offset), ptr(count), ptr(dis), ptr(scratch), stream_ptr()), "dgnn_cell_labels")
+    kd = torch.full_like(count, k, dtype=torch.float64)          # a tensor divisor: a true fp64 division (a Python scalar would be multiplied by 1 / k)
+    return {"count": count, "inside_perc": count.double() / kd, "outside_perc": (k - count).double() / kd, "n_samples": k,
+            "n_disagree": int(dis.item())}
+
+
 # ---- ingest: feature scaling (csrc/ingest.hip) ------------------------------------------------------------------------------------
 SCALE_KINDS = {"none": 0, "standard": 1, "minmax": 2, "robust": 3}
 

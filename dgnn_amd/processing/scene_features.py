@@ -2,8 +2,9 @@
 files `<scene>_cgeom.npz`, `<scene>_cbvf.npz`, `<scene>_fbvf.npz`.
 
 The reference gets these files from an external binary; their definitions here are the ones that reproduce its recorded output for
-Ignatius scene 99 (counts and edge lengths exactly, the other columns to the last bits).  The facet-ray files (`_cbff`, `_fbff`), `_fgeom`
-and `_labels` are not built.
+Ignatius scene 99 (counts and edge lengths exactly, the other columns to the last bits).  The facet-ray files (`_cbff`, `_fbff`) and `_fgeom`
+are not built.  The training target `<scene>_labels.npz` comes from build_cell_labels and a closed ground-truth mesh; the
+binary's own sample count and generator are not known, so its labels are a definition of this package's, not a reproduction.
 
 Rows: the cells of a scene are its finite tets in `tetrahedra` order with the infinite cells interleaved where `infinite` is 1; finite
 cell number r is tet r.  Infinite cells hold 0 in every column.  Edge row 4 c + k belongs to the facet of cell c opposite its vertex k (the
@@ -89,4 +90,43 @@ def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base
     if out_base is not None:
         for name in ("cgeom", "cbvf", "fbvf"):
             np.savez(out_base + "_%s.npz" % name, **out[name])
+    return out
+
+
+def build_cell_labels(mdata, infinite, gt_vertices, gt_faces, n_samples=100, seed=0, out_base=None, device=None):
+    """The training target of a scene: the share of every cell inside the closed ground-truth mesh (gt_vertices [M, 3], gt_faces [F, 3]),
+    from n_samples points per tet (ops.cell_labels on `device`, default: the current GPU).  mdata and infinite as in build_scene_features.
+    Returns a dict: "inside_perc", "outside_perc" fp64 [n_cells] (finite cells: their tets' fractions in tet order; infinite cells: 0 and
+    1), "infinite" int32 [n_cells] as given, and "stats": n_samples, n_disagree, the cells with fraction 0 ("n_outside"), 1 ("n_inside")
+    and in between ("n_partial", infinite cells not counted) and "watertight" (ops.mesh_topology).  A mesh that is not watertight is
+    labelled all the same, after a warning.  With out_base the file out_base + "_labels.npz" is written with the keys inside_perc,
+    outside_perc, infinite in this order, as the reference's and this package's dataLoader read it."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    inf = np.asarray(infinite).reshape(-1)
+    finite = inf.astype(bool) == 0
+    n_cells, n_tets = len(inf), len(mdata["tetrahedra"])
+    if int(finite.sum()) != n_tets:
+        raise ValueError("%d finite cells in `infinite` but %d tetrahedra" % (int(finite.sum()), n_tets))
+    v = torch.from_numpy(np.asarray(mdata["vertices"], dtype=np.float64)).to(dev)
+    tets = torch.as_tensor(np.asarray(mdata["tetrahedra"])).to(dev, torch.int32)
+    gv = torch.from_numpy(np.asarray(gt_vertices, dtype=np.float64)).to(dev)
+    gf = torch.as_tensor(np.asarray(gt_faces)).to(dev, torch.int32)
+    lab = ops.cell_labels(gv, gf, v, tets, n_samples=n_samples, seed=seed)
+    try:
+        watertight = ops.mesh_topology(gf, gv.size(0))["watertight"]
+    except ops.DgnnError:          # a face with a repeated vertex
+        watertight = 0
+    if not watertight:
+        print("Warning: the ground-truth mesh is not watertight; its cell labels follow the ray parities all the same.")
+    if lab["n_disagree"]:
+        print("Warning: contains1 != contains2 for %d of %d samples (counted as outside)." % (lab["n_disagree"], n_tets * lab["n_samples"]))
+    inside, outside = np.zeros(n_cells), np.ones(n_cells)
+    inside[finite], outside[finite] = lab["inside_perc"].cpu().numpy(), lab["outside_perc"].cpu().numpy()
+    count = lab["count"].cpu().numpy()
+    stats = dict(n_samples=lab["n_samples"], n_disagree=lab["n_disagree"], n_outside=int((count == 0).sum()), n_inside=int((count == lab["n_samples"]).sum()),
+                 watertight=int(watertight))
+    stats["n_partial"] = n_tets - stats["n_outside"] - stats["n_inside"]
+    out = {"inside_perc": inside, "outside_perc": outside, "infinite": inf.astype(np.int32), "stats": stats}
+    if out_base is not None:
+        np.savez(out_base + "_labels.npz", inside_perc=out["inside_perc"], outside_perc=out["outside_perc"], infinite=out["infinite"])
     return out

@@ -1175,6 +1175,43 @@ int dgnn_face_normals(const double* vertices, int64_t n_vertices, const int32_t*
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Ground-truth cell labels: the share of each tetrahedron that lies inside a closed triangle mesh, by sampling (what the reference gets
+ * from its external binary as <scene>_labels.npz inside_perc / outside_perc).  DESIGN.md section 26.  Every *, + and - below is one fp64
+ * rounding, in the order written (no contraction).
+ *
+ * sample j (0 <= j < k = n_samples) of tet t: the 64-bit counter c = 3 ((tet_offset + t) k + j) + 1, wrapping mod 2^64, and
+ *   s = u01(mm_hash(seed, c)), t = u01(mm_hash(seed, c + 1)), u = u01(mm_hash(seed, c + 2)), u01(h) = (h >> 11) 2^-53 (dgnn_box_points' draw);
+ *   the unit cube folded onto the unit tet:
+ *     if s + t > 1: s = 1 - s, t = 1 - t
+ *     st = s + t
+ *     if t + u > 1:        (s, t, u) <- (s, 1 - u, (1 - s) - t)
+ *     else if st + u > 1:  (s, t, u) <- ((1 - t) - u, t, (st + u) - 1)
+ *   the point, per coordinate, with e_i = p_i - p_0 over the vertices p_0..p_3 of the tet's `tetrahedra` row:
+ *     x = ((s e_1 + t e_2) + u e_3) + p_0
+ * A sample is inside exactly when dgnn_mesh_contains says so for x (the same frame, candidate grid, 2D test, depth and (above odd) &
+ * (below odd)); a sample whose two parities differ counts as outside and is tallied in n_disagree.
+ *
+ * dgnn_tet_sample_points: points_out fp64 [n_tets n_samples, 3], row t k + j = sample j of tet t, for vertices fp64 [n_vertices, 3] and
+ *   tetrahedra int32 [n_tets, 4].  scratch: dgnn_tet_sample_points_scratch_bytes() bytes.  SYNCHRONISES `stream` once (ids).
+ * dgnn_cell_labels: count_out int32 [n_tets] = the inside samples of each tet (inside_perc = (double)count / (double)k, outside_perc =
+ *   (double)(k - count) / (double)k), n_disagree_out DEVICE int64 [1] (NULL: not written).  The mesh arguments (mesh_vertices, faces,
+ *   hash_resolution, max_entries, entries, entry_capacity) are dgnn_mesh_contains' and are planned the same way; scratch:
+ *   dgnn_cell_labels_scratch_bytes(n_mesh_vertices, n_faces, hash_resolution) bytes.  No sample is written to memory and T k carries no int32
+ *   limit (n_samples itself is at most 2^31 - 1); integer counts without atomics: bit-identical from run to run.  SYNCHRONISES `stream`
+ *   four times (the plan's three, the tets' ids).
+ * DGNN_E_INVALID: n_samples < 1, a tetrahedron's vertex id out of range (validated before any kernel indexes with it), and for
+ * dgnn_cell_labels what dgnn_mesh_contains refuses.  n_tets == 0: nothing is written but n_disagree_out = 0.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_tet_sample_points_scratch_bytes(void);
+int dgnn_tet_sample_points(const double* vertices, int64_t n_vertices, const int32_t* tetrahedra, int64_t n_tets, int64_t n_samples, uint64_t seed,
+                           uint64_t tet_offset, double* points_out, void* scratch, void* stream);
+int64_t dgnn_cell_labels_scratch_bytes(int64_t n_mesh_vertices, int64_t n_faces, int32_t hash_resolution);
+int dgnn_cell_labels(const double* mesh_vertices, int64_t n_mesh_vertices, const int32_t* faces, int64_t n_faces, int32_t hash_resolution,
+                     int64_t max_entries, int32_t* entries, int64_t entry_capacity, const double* vertices, int64_t n_vertices,
+                     const int32_t* tetrahedra, int64_t n_tets, int64_t n_samples, uint64_t seed, uint64_t tet_offset, int32_t* count_out,
+                     int64_t* n_disagree_out, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-scene standardisation (reference processing/data.py:444-506 sklearn StandardScaler + :512-519
  * float32 cast): out[i,c] = float((x[i,c] - mean_c) / std_c) for c >= c_first, plain cast for c < c_first;
  * fp64 statistics (population variance, zero scale -> 1).  scratch: dgnn_standardize_scratch_doubles(c) doubles.
