@@ -404,8 +404,10 @@ struct GroupRow {
 __device__ __forceinline__ GroupRow chunk_row(int rp, int nr, int r) {
     const bool rv = r < nr;
     const int rc = rv ? r : nr - 1;
-    const int b = __shfl(rp, rc);
-    return {rv, rc, b, rv ? __shfl(rp, rc + 1) - b : 0};
+    // every lane takes part in both shuffles: a lane that sits out hands 0 to the lane that reads it, and the lane holding rowptr[rc + 1] may belong
+    // to a group without a row (8-lane groups, 9 rows in the chunk: row 8 reads lane 9, whose group has row 9)
+    const int b = __shfl(rp, rc), e = __shfl(rp, rc + 1);
+    return {rv, rc, b, rv ? e - b : 0};
 }
 
 template <int G, typename T, bool ADD>
@@ -901,7 +903,7 @@ __global__ void __launch_bounds__(256) k_agg_bwd_mm(const int32_t* __restrict__ 
                     const bool ok = ej[r] >= 0 && con && rv;
                     const float dm = ok ? (pow2 ? __fmul_rn(gq[r][u], ij[r]) : __fdiv_rn(gq[r][u], cj[r])) : 0.f;
                     if (DX && ok) acc = __fadd_rn(acc, __fmul_rn(dm, d[u][r]));
-                    dph[u][r] = __fmul_rn(dm, xq[u]);
+                    dph[u][r] = ok ? __fmul_rn(dm, xq[u]) : 0.f;      // an empty slot adds nothing to dWe / dbe whatever its row's x holds (0 * NaN is NaN)
                 }
                 o[u] = (ADD && addrow) ? __fadd_rn(acc, aq[u]) : acc;
             }
@@ -1260,9 +1262,9 @@ int agg_bwd_phi_add(AggBwd<T> p, const void* phi, int64_t ldphi, const void* add
 
 // given-phi form (Updated variant) with the two additions of a conv layer's backward folded into the stores: dx_src[row] += add[row] for
 // row < n_add (add may be NULL), dphi_out[e] = dphi_e + dphi_ext[e] (dphi_ext may be NULL).  bf16: storage 1, fp32: 0.
-// library-internal (csrc/train.hip): dgnn_sage_aggregate_bwd_phi_add whose dx store also applies the ReLU mask of the layer below, dx * [x_src > 0]
+// csrc/train.hip's form (exported so that the tests reach it): dgnn_sage_aggregate_bwd_phi_add whose dx store also applies the ReLU mask of the layer below, dx * [x_src > 0]
 // (mask_dx != 0).
-int dgnn_sage_aggregate_bwd_phi_add_masked(const int32_t* t_rowptr, const int32_t* t_dst, const int32_t* t_eid, int64_t n_src, const int32_t* rowptr_dst,
+extern "C" int dgnn_sage_aggregate_bwd_phi_add_masked(const int32_t* t_rowptr, const int32_t* t_dst, const int32_t* t_eid, int64_t n_src, const int32_t* rowptr_dst,
                                            const void* x_src, int64_t ldx, int c_in, const void* phi, int64_t ldphi, const void* da, int64_t ldda,
                                            void* dx_src, int64_t lddx, const void* add, int64_t ldadd, int64_t n_add, void* dphi_out, int64_t lddphi,
                                            const void* dphi_ext, int bf16, int mask_dx, void* stream) {

@@ -271,6 +271,12 @@ int dgnn_sage_aggregate_bwd_phi_add(const int32_t* t_rowptr, const int32_t* t_ds
                                     const void* x_src, int64_t ldx, int c_in, const void* phi, int64_t ldphi, const void* da, int64_t ldda,
                                     void* dx_src, int64_t lddx, const void* add, int64_t ldadd, int64_t n_add, void* dphi_out, int64_t lddphi,
                                     const void* dphi_ext, int bf16, void* stream);
+/* The same with the ReLU mask of the layer below folded into the dx store (mask_dx != 0): dx_src[row] = x_src[row] > 0 ? dx_src[row] : +0,
+ * after the addend (x_src is relu(y_below); needs dx_src).  mask_dx = 0: dgnn_sage_aggregate_bwd_phi_add. */
+int dgnn_sage_aggregate_bwd_phi_add_masked(const int32_t* t_rowptr, const int32_t* t_dst, const int32_t* t_eid, int64_t n_src,
+                                           const int32_t* rowptr_dst, const void* x_src, int64_t ldx, int c_in, const void* phi, int64_t ldphi,
+                                           const void* da, int64_t ldda, void* dx_src, int64_t lddx, const void* add, int64_t ldadd, int64_t n_add,
+                                           void* dphi_out, int64_t lddphi, const void* dphi_ext, int bf16, int mask_dx, void* stream);
 
 /* dgnn_sage_aggregate_bwd in fused mode (f_e = 20, fp32) with `dx_src[row] += add[row]` for row < n_add folded into the store of dx_src:
  * the x_dst = x[:n_dst] branch of a conv layer (:217, lin_i) sends its gradient dz . Wi to the first n_dst rows of dx; the addend is

@@ -14,5 +14,6 @@ for e in "DGNN_TRAIN_COMPOSITE=0" "DGNN_TRAIN_WHOLE_MODEL=0" "DGNN_KHOP_ONE_CALL
          "DGNN_AGG_MFMA=0" "DGNN_FILTER_MFMA=0 DGNN_GEMM_MODE=f32" "DGNN_KL_LOSS_ONE_LAUNCH=0" "DGNN_TRAIN_KEEP_GRADS=0" "DGNN_BN_ZMASK=0" "DGNN_UPDATED_MASK_DX=0" \
          "DGNN_AGG_BWD_NODX=0 DGNN_AGG_MFMA=0" "DGNN_GEMM_MID=0" "DGNN_SMALL_SPLITK=0" "DGNN_SMALL_BY_TILES=0"; do
   echo "== $e"
-  env $e timeout 600 python -m pytest tests/test_gpu_train.py tests/test_gpu_parity.py tests/test_gpu_bf16.py -m gpu -q -x 2>&1 | tail -2 || { echo "== $e failed: stopping"; exit 1; }
+  case "$e" in *DGNN_AGG_*) extra=tests/test_gpu_aggregate_edges.py ;; *) extra= ;; esac      # the aggregate's switches: its edge suite too
+  env $e timeout 600 python -m pytest tests/test_gpu_train.py tests/test_gpu_parity.py tests/test_gpu_bf16.py $extra -m gpu -q -x 2>&1 | tail -2 || { echo "== $e failed: stopping"; exit 1; }
 done
