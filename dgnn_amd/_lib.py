@@ -132,6 +132,9 @@ SIGNATURES = {
     "dgnn_tet_sample_points": (i32, [vp, i64, vp, i64, i64, u64, u64, vp, vp, vp]),
     "dgnn_cell_labels_scratch_bytes": (i64, [i64, i64, i32]),
     "dgnn_cell_labels": (i32, [vp, i64, vp, i64, i32, i64, vp, i64, vp, i64, vp, i64, i64, u64, u64, vp, vp, vp, vp]),
+    "dgnn_ray_first_hit_scratch_bytes": (i64, [i64, i32]),
+    "dgnn_ray_first_hit_plan": (i32, [vp, i64, vp, i64, i32, vp, vp, vp, vp]),
+    "dgnn_ray_first_hit": (i32, [vp, i64, vp, i64, i32, vp, vp, i64, f64, vp, vp, vp, vp, vp, i64, vp, vp]),
     "dgnn_khop_scratch_elems": (i64, [i64, i64]),
     "dgnn_khop_count": (i32, [vp, vp, i64, i32, vp, vp, vp, vp]),
     "dgnn_khop_expand": (i32, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -2287,6 +2287,49 @@ def cell_labels(mesh_vertices, mesh_faces, vertices, tetrahedra, n_samples=100, 
             "n_disagree": int(dis.item())}
 
 
+# ---- first-hit ray casting on a triangle mesh (csrc/raycast.hip) ---------------------------------------------------------
+RAY_HIT_STATS = ("hits", "skipped", "degenerate", "exact_used")
+
+
+def default_grid_resolution(n_faces):
+    """The grid resolution ray_first_hit takes when none is given: sqrt(n_faces) / 2 cells along the longest axis, within [1, 256] (the sweep
+    behind it is profiles/scan_mesh.md).  The answer does not depend on it."""
+    return max(1, min(256, int(round(0.5 * float(n_faces) ** 0.5))))
+
+
+@on_device_of
+def ray_first_hit(vertices, faces, origins, aims, t_min=0.0, grid_resolution=None, return_stats=False):
+    """The first face of the mesh (vertices [V, 3], faces int [F, 3]) that each ray from origins[r] through aims[r] (fp16 / fp32 / fp64 [n, 3],
+    promoted to fp64) crosses beyond t_min, the aim being at t = 1 (dgnn_ray_first_hit; the exact crossing rule, the parameter and the tie
+    rule are in include/dgnn_hip.h).  -> (face int32 [n], -1 = none; t fp64 [n], 0 where none; point fp64 [n, 3] = origin + t (aim - origin),
+    zeros where none), all on the GPU; with return_stats also a dict of RAY_HIT_STATS -> int.  grid_resolution (None: default_grid_resolution
+    of the face count) sizes the candidate grid; the answer does not depend on it.  ValueError for a mesh without faces, a face id out of
+    range, a non-finite referenced vertex, origin or aim and a negative t_min; DgnnError for a coordinate magnitude outside [2^-300, 2^300]
+    and a grid_resolution outside [1, 1024]."""
+    dev = _dev_of(origins, aims, vertices, faces)
+    v = _on(vertices, dev, torch.float64, 3)
+    f = _on(faces, dev, torch.int32, 3)
+    o, g = _points64(origins, dev), _points64(aims, dev)
+    if o.size(0) != g.size(0):
+        raise ValueError("ray_first_hit: %d origins for %d aims" % (o.size(0), g.size(0)))
+    nv, nf, n = v.size(0), f.size(0), o.size(0)
+    if nf == 0:
+        raise ValueError("ray_first_hit: a mesh without faces")
+    R = default_grid_resolution(nf) if grid_resolution is None else int(grid_resolution)
+    scratch = torch.empty(int(lib().dgnn_ray_first_hit_scratch_bytes(nf, R)), dtype=torch.uint8, device=dev)
+    n_entries = C.c_int64(0)
+    _check_value(lib().dgnn_ray_first_hit_plan(ptr(v), nv, ptr(f), nf, R, C.byref(n_entries), None, ptr(scratch), stream_ptr()), "dgnn_ray_first_hit_plan")
+    cap = max(int(n_entries.value), 1)
+    entries = torch.empty(cap, dtype=torch.int32, device=dev)
+    face, t, point = _empty(dev, torch.int32, n), _empty(dev, torch.float64, n), _empty(dev, torch.float64, n, 3)
+    stats = torch.zeros(len(RAY_HIT_STATS), dtype=torch.int64, device=dev)
+    _check_value(lib().dgnn_ray_first_hit(ptr(v), nv, ptr(f), nf, R, ptr(o), ptr(g), n, float(t_min), ptr(face), ptr(t), ptr(point), ptr(stats), ptr(entries),
+                                          cap, ptr(scratch), stream_ptr()), "dgnn_ray_first_hit")
+    if return_stats:
+        return face, t, point, dict(zip(RAY_HIT_STATS, (int(x) for x in stats.cpu())))
+    return face, t, point
+
+
 # ---- ingest: feature scaling (csrc/ingest.hip) ------------------------------------------------------------------------------------
 SCALE_KINDS = {"none": 0, "standard": 1, "minmax": 2, "robust": 3}
 

@@ -1218,6 +1218,47 @@ int dgnn_cell_labels(const double* mesh_vertices, int64_t n_mesh_vertices, const
                      int64_t* n_disagree_out, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * First hit of rays on a triangle mesh: the primitive of the virtual scanner (dgnn_amd/processing/scan_mesh.py; what the reference gets
+ * from its external `scan` binary, processing/modelnet/scan.py, processing/shapenet/scan.py).  DESIGN.md section 27.  The binary's rule is
+ * not known: this is this library's definition, not a reproduction.  Every *, +, - and / below is one fp64 rounding, in the order written (no
+ * contraction); (a, b, c) . (d, e, f) means (a d + b e) + c f and a x b has one product minus one product per component.
+ *
+ * dgnn_ray_first_hit: for vertices fp64 [n_vertices, 3], faces int32 [n_faces, 3], origins and aims fp64 [n_rays, 3], t_min >= 0: ray r is
+ *   o + t d with o = origins[r], g = aims[r], d = g - o.  It is unbounded: the aim is at t = 1.
+ *   crossing  for face (a, b, c): s1 = sign det[g - o, a - o, b - o], s2 = sign det[g - o, b - o, c - o], s3 = sign det[g - o, c - o, a - o],
+ *             each EXACT on the input coordinates (csrc/exact_orient.h orient_sign(o, g, x, y): an fp64 filter, then an exact expansion).
+ *             The line crosses the face when the three are all >= 0 or all <= 0 and not all 0: a line in the face's plane crosses nothing, a
+ *             line through a shared edge or vertex crosses every incident face, and no rounding opens a gap between two faces that share
+ *             an edge.  A face without area or with a repeated id is never crossed.
+ *   t         n = (b - a) x (c - a), t = (n . (a - o)) / (n . d).  A crossed face with n . d == 0 or a non-finite t is dropped and counted
+ *             (stats 2); one with t <= t_min is dropped silently.
+ *   result    the smallest t over the faces left, ties in t to the lowest face id: hit_face_out int32 [n_rays] (-1 = none), hit_t_out fp64
+ *             [n_rays] (0 where none), hit_point_out fp64 [n_rays, 3] = o + t d per coordinate, one product and one sum (zeros where none;
+ *             NULL: not written).  A ray with o == g is skipped: face -1, counted (stats 1).
+ *   stats_out DEVICE int64 [4]: rays with a hit; rays skipped; crossings dropped as degenerate, every (ray, face) pair once, over all
+ *             faces; the signs of the HIT faces (three per hit) that the exact stage decided.
+ *   grid      candidates come from a uniform grid over the box of the referenced vertices: grid_resolution R in [1, 1024] cells along the
+ *             longest axis, ceil(extent / (longest / R)) on the others (1 without extent); a face is entered in every cell its bounding box
+ *             touches.  The whole line is walked through the box, every bound widened by 2^-46 of the largest coordinate magnitude of the box
+ *             and the ray, and no hit is final before the walk ends: the set of tested faces contains every crossed face, and the
+ *             result, a minimum under a total order, depends neither on R nor on the order of the entries.  `entries` int32
+ *             [entry_capacity] holds the (face, cell) entries: dgnn_ray_first_hit_plan returns their number (n_entries_out, and the cells
+ *             per axis in cells_out [3] when not NULL: HOST values).
+ *   scratch   dgnn_ray_first_hit_scratch_bytes(n_faces, grid_resolution) bytes for either call.
+ * DGNN_E_INVALID: no faces, a face id out of range, a non-finite coordinate of a referenced vertex, an origin or an aim (an unreferenced
+ * vertex is not read), t_min < 0, entry_capacity too small; DGNN_E_UNSUPPORTED: a non-zero coordinate magnitude outside [2^-300, 2^300]
+ * (the exact predicate's range), R outside [1, 1024], 2^31 or more entries.  Ids and coordinates are validated before any kernel uses
+ * them.  Both calls SYNCHRONISE `stream` three times (ids, box and coordinates, entry total).  No floating-point atomics: bit-identical
+ * from run to run.  One lane per ray; n_rays has no int32 limit.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_ray_first_hit_scratch_bytes(int64_t n_faces, int32_t grid_resolution);
+int dgnn_ray_first_hit_plan(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t grid_resolution,
+                            int64_t* n_entries_out, int32_t* cells_out, void* scratch, void* stream);
+int dgnn_ray_first_hit(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t grid_resolution,
+                       const double* origins, const double* aims, int64_t n_rays, double t_min, int32_t* hit_face_out, double* hit_t_out,
+                       double* hit_point_out, int64_t* stats_out, int32_t* entries, int64_t entry_capacity, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-scene standardisation (reference processing/data.py:444-506 sklearn StandardScaler + :512-519
  * float32 cast): out[i,c] = float((x[i,c] - mean_c) / std_c) for c >= c_first, plain cast for c < c_first;
  * fp64 statistics (population variance, zero scale -> 1).  scratch: dgnn_standardize_scratch_doubles(c) doubles.
