@@ -13,6 +13,10 @@
 //   8 CONSUMERS  16 output channels each, their [Wj | Wi] rows resident as fp16 (hi, lo) fragments (64 VGPRs): D[channel][cell] on v_mfma_f32_16x16x32_f16
 //                with the weights as the A operand, 48 products per tile; epilogue per lane = one cell x 4 consecutive channels: inverse scales,
 //                bias / BatchNorm / ReLU, one 16-byte non-temporal store;
+//   The ring's swizzle and its addresses (profiles/r09_ws_loop.md): piece q of a row sits at piece q ^ (row & 15).  A consumer's 32 reads per tile come from
+//   FOUR bases (the key meets only the bits of s & 3 and tq of a piece index 4 s + tq) plus immediate offsets.  Rows at a padded stride (8 CIN + 16 bytes,
+//   natural piece order) were measured instead: a ds_read_b128 is served in four NON-contiguous groups of 16 lanes ({0-3, 12-15, 20-27}, ...), lanes of
+//   two tq share a group, and SQ_LDS_BANK_CONFLICT went from 0 to 4 cycles on every read -- the swizzle stays.
 //   The ring slots are handed over by LDS counters, no barrier in the loop: `ready[slot]` +1 per producer that has parked its rows of a tile, `done[slot]` +1
 //   per consumer that has read them; every wavefront runs at its own pace, a producer only waits when the slot it is about to write (two tiles back) has
 //   not been drained.  EVERY adder waits for the slot first, the producer groups past the end of the graph included -- a count that lands early can stand
@@ -120,15 +124,18 @@ __device__ __forceinline__ uint32_t bits(float f) { return __builtin_bit_cast(ui
 // knobs (a launch argument, though every launch passes WS_KNOBS: with the value folded into the kernel the compiler schedules the loop differently and the
 // layers ran 4-5 % slower): bit 0 = non-temporal row stores, bits 4-5 = who runs the decoder's stage B (see b_on_consumers)
 constexpr int WS_KNOBS = 1 | (0 << 4);
-template <int CIN, int RING, bool DEC, bool IO16 = false>
+template <int CIN, int RING, bool DEC, bool IO16 = false, bool LDC = false>
 __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src, const int32_t* __restrict__ eid,
-                                                        int64_t n_dst, const float* __restrict__ x, const float* __restrict__ xdst, int64_t ldx,
+                                                        int64_t n_dst, const float* __restrict__ x, const float* __restrict__ xdst, int64_t ldx_arg,
                                                         const float* __restrict__ ea, int64_t lde, const float* __restrict__ We, const float* __restrict__ be,
                                                         const float* __restrict__ Wj, const float* __restrict__ bj, const float* __restrict__ Wi,
                                                         const float* __restrict__ scale, const float* __restrict__ shift, int relu, float* __restrict__ out,
                                                         int64_t ldo, int64_t ntiles, int knobs, WsDec dec) {
     static_assert(CIN == 128 || (CIN == 64 && !DEC), "input widths of the shipped model's 128-wide layers");
     static_assert(!IO16 || !DEC, "the decoder-carrying launch of the bf16-storage chain stays with fused_bf16.hip");
+    // LDC: the input rows are dense (ldx == CIN, the previous fused layer's output: layers 1-3 of the shipped chain) -- a row's offset is a shift, not the
+    // quarter-rate 64-bit multiply by a run-time stride (15 per tile and producer).  Any other stride runs the LDC = false instantiation.
+    const int64_t ldx = LDC ? (int64_t)CIN : ldx_arg;
     // IO16: x / xdst / out are uint16_t rows (ldx / ldo in elements of that type)
     const uint16_t* const x16 = reinterpret_cast<const uint16_t*>(x);
     const uint16_t* const xdst16 = reinterpret_cast<const uint16_t*>(xdst);
@@ -371,12 +378,22 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
             if (it >= 1 && it <= my_n) {
                 const int sl = (int)((it - 1) % RING);
                 wait_for(ready + sl, (uint32_t)(WS_NP * ((it - 1) / RING + 1)));
-                const char* tb = ring + sl * G::SLOT;
                 f32x4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-                // (the swizzle key passes through an empty asm every tile: left alone, the compiler keeps all 32 loop-invariant read addresses in registers
-                // -- 19 spilled in the decoder-carrying instantiation -- instead of two integer instructions per read)
-                int key = jcol;
+                // Ring-read addresses: FOUR bases per tile, everything else in the reads' immediate offsets.  The swizzle (piece ^ jcol for the rows jcol and
+                // 16 + jcol this lane reads) touches the low four bits of a piece index only, and of 4 s + tq only s & 3 and tq live there: piece =
+                // ((4 (s & 3) + tq) ^ jcol) + 16 (s >> 2) = (4 (s & 3) ^ key) + 16 (s >> 2) with key = jcol ^ tq; the lo quarters (+ 2 PP pieces) and the second
+                // row block (+ 16 rows) are constants on top.  base[m] = row + (((4 m) ^ key) << 4) serves the eight reads of k-steps m, m + 4: nine integer
+                // instructions per tile instead of two per read (41), the same addresses.
+                // (the key passes through an empty asm every tile: left alone, the compiler keeps all 32 loop-invariant read addresses in registers -- 19
+                // spilled in the decoder-carrying instantiation; the bases pass through one so that the reads stay base + immediate)
+                int key = jcol ^ tq;
                 asm volatile("" : "+v"(key));
+                uint32_t rbase[4];
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    rbase[m] = (uint32_t)(sl * G::SLOT + jcol * G::ROWB) + (uint32_t)(((4 * m) ^ key) << 4);
+                    asm volatile("" : "+v"(rbase[m]));
+                }
                 // ring reads one whole k-step ahead of the products (two register sets).  The scheduling barrier pins that order: left alone, the compiler
                 // sinks every read to just in front of its first use and waits for it on the spot -- sixteen exposed LDS round trips per tile.  (Two steps
                 // ahead = three sets: over the 128-register budget, spills inside the loop, twice the time.)
@@ -384,9 +401,9 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
                 auto ld_step = [&](int s, int set) {
 #pragma unroll
                     for (int b = 0; b < 2; ++b) {
-                        const char* rp = tb + (16 * b + jcol) * G::ROWB;
-                        xh[set][b] = H8(*reinterpret_cast<const uint4*>(rp + (((4 * s + tq) ^ key) << 4)));
-                        xl[set][b] = H8(*reinterpret_cast<const uint4*>(rp + (((2 * PP + 4 * s + tq) ^ key) << 4)));
+                        const char* rp = ring + rbase[s & 3] + (16 * b * G::ROWB + ((s >> 2) << 8));
+                        xh[set][b] = H8(*reinterpret_cast<const uint4*>(rp));
+                        xl[set][b] = H8(*reinterpret_cast<const uint4*>(rp + 2 * PP * 16));
                     }
                 };
                 ld_step(0, 0);
@@ -489,41 +506,60 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
     const int p = w;
     const int P0 = NCH * jcol;                     // the lane's NCH channels (contiguous ownership)
     const int Q0 = 4 * jcol;                       // LINE_OWN: its two quads start at Q0 and 64 + Q0
-    auto load_rp = [&](int64_t it, int& vb) {
-        if (it < my_n) {
+    // Loop bookkeeping in 32 bits (the scalar unit compares no 64-bit values for order: `it < my_n` and the clamp of n_dst - i0 went through the vector
+    // unit, three times per tile): a workgroup's tile count is far below 2^31, and the only group that can be short (nv < 4) is this producer's in the
+    // graph's LAST tile, which only this workgroup's last iteration can be.
+    const int n_my = (int)my_n;
+    const int it_short = (n_my > 0 && tile_of(n_my - 1) == ntiles - 1) ? n_my - 1 : -1;
+    const int nv_short = (int)max((int64_t)0, min((int64_t)4, n_dst - ((ntiles - 1) * WS_TILE + 4 * p)));
+    auto nv_of = [&](int it) { return it == it_short ? nv_short : 4; };
+    auto load_rp = [&](int it, int& vb) {
+        if (it < n_my) {
             const int64_t i0 = tile_of(it) * WS_TILE + 4 * p;
-            const int nv = (int)max((int64_t)0, min((int64_t)4, n_dst - i0));
+            const int nv = nv_of(it);
             vb = nv > 0 ? rowptr[i0 + (lane < nv ? lane : nv)] : 0;
         }
     };
-    auto load_idx = [&](int64_t it, int vb, bool& reg, int& vsrc, int& veid) {
+    // A regular group's indices in the lane layout that uses them: the four source ids of the lane's own cell (one 16-byte load; a group's first edge need
+    // not sit on a 16-byte boundary behind ragged cells, hence the 4-byte-aligned type) and the edge id of lane jcol -- no lane exchange at the head of
+    // the gather chain (these were the src / eid of edge `lane`, handed round by nine ds_bpermute_b32 per tile)
+    // (not in the decoder-carrying instantiation: the three more loop-carried registers spill there -- it keeps vs[0] / veid = src / eid of edge `lane`)
+    typedef int32_t i32x4a_t __attribute__((ext_vector_type(4), aligned(4)));
+    constexpr bool IDX_LANE = !DEC;
+    auto load_idx = [&](int it, int vb, bool& reg, int (&vs)[4], int& veid) {
         reg = false;
-        if (it < my_n) {
-            const int64_t i0 = tile_of(it) * WS_TILE + 4 * p;
-            const int nv = (int)max((int64_t)0, min((int64_t)4, n_dst - i0));
+        if (it < n_my) {
+            const int nv = nv_of(it);
             if (nv > 0) {
                 const int b0 = __builtin_amdgcn_readfirstlane(vb);
                 reg = __all(vb == b0 + 4 * (lane < nv ? lane : nv)) != 0;
                 if (reg) {
-                    const int k_me = b0 + (lane < 4 * nv ? lane : 4 * nv - 1);
-                    vsrc = src[k_me];
-                    veid = eid ? eid[k_me] : k_me;
+                    if constexpr (IDX_LANE) {
+                        const i32x4a_t s4 = *reinterpret_cast<const i32x4a_t*>(src + b0 + 4 * (tq < nv ? tq : nv - 1));
+                        vs[0] = s4[0], vs[1] = s4[1], vs[2] = s4[2], vs[3] = s4[3];
+                        const int k_e = b0 + (jcol < 4 * nv ? jcol : 4 * nv - 1);
+                        veid = eid ? eid[k_e] : k_e;
+                    } else {
+                        const int k_me = b0 + (lane < 4 * nv ? lane : 4 * nv - 1);
+                        vs[0] = src[k_me];
+                        veid = eid ? eid[k_me] : k_me;
+                    }
                 }
             }
         }
     };
-    int vb1 = 0, vb2 = 0, vsrc1 = 0, veid1 = 0;
+    int vb1 = 0, vb2 = 0, vs1[4] = {0, 0, 0, 0}, veid1 = 0;
     bool reg1 = false;
     load_rp(0, vb1);
     load_rp(1, vb2);
-    load_idx(0, vb1, reg1, vsrc1, veid1);
+    load_idx(0, vb1, reg1, vs1, veid1);
 
     // DEC: on the tiles the rule gives to the producers (b_on_consumers) this wavefront also runs stage B of tile it - 3 (hidden block p & 3 of row block
     // p >> 2) -- BETWEEN issuing its gathers for tile `it` and using them: the job fills the gather latency, and its data (the consumers' stage A2 of tile
     // it - 3, behind their product of tile it - 2) is complete about when the slot the producer is going to write is handed back anyway.  Three more
     // iterations drain the last three tiles.
-    for (int64_t it = 0; it < my_n + (DEC ? 3 : 0); ++it) {
-        int nv = 0, sl = 0, tl = 0, vsrc = 0, veid = 0;
+    for (int it = 0; it < n_my + (DEC ? 3 : 0); ++it) {
+        int nv = 0, sl = 0, tl = 0, vs[4] = {0, 0, 0, 0}, veid = 0;
         bool regular = false;
         f32x4_t xo[NV], q0, q1, rr[4][NV];              // the gathered rows (DEC: in flight across stage B); read only on the path that loaded them
         uint32_t xo16[NCH / 2], rr16[4][NCH / 2];       // IO16: the same rows as packed pairs of 16-bit values, decoded where they are used
@@ -545,13 +581,21 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
             }
         };
         auto neighbour_rows = [&]() {
-            const float* er = ea + (int64_t)__shfl(veid, jcol) * lde;
+            auto src_of = [&](int r) {
+                if constexpr (IDX_LANE) return vs[r];
+                else return __shfl(vs[0], tl * 4 + r);
+            };
+            auto eid_of = [&]() {
+                if constexpr (IDX_LANE) return veid;
+                else return __shfl(veid, jcol);
+            };
+            const float* er = ea + (int64_t)eid_of() * lde;
             q0 = *reinterpret_cast<const f32x4_t*>(er + 8 * (tq < 2 ? tq : 2));
             q1 = *reinterpret_cast<const f32x4_t*>(er + 8 * (tq < 1 ? tq : 1) + 4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if constexpr (IO16) {
-                    const uint16_t* rp = x16 + (int64_t)__shfl(vsrc, tl * 4 + r) * ldx + P0;
+                    const uint16_t* rp = x16 + (int64_t)src_of(r) * ldx + P0;
                     if constexpr (NCH == 8) {
                         const uint4 u = *reinterpret_cast<const uint4*>(rp);
                         rr16[r][0] = u.x, rr16[r][1] = u.y, rr16[r][2] = u.z, rr16[r][3] = u.w;
@@ -560,21 +604,22 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
                         rr16[r][0] = u.x, rr16[r][1] = u.y;
                     }
                 } else {
-                    const float* rp = x + (int64_t)__shfl(vsrc, tl * 4 + r) * ldx + (LINE_OWN ? Q0 : P0);
+                    const float* rp = x + (int64_t)src_of(r) * ldx + (LINE_OWN ? Q0 : P0);
 #pragma unroll
                     for (int v = 0; v < NV; ++v) rr[r][v] = *reinterpret_cast<const f32x4_t*>(rp + (LINE_OWN ? 64 : 4) * v);
                 }
             }
         };
-        if (it < my_n) {
+        if (it < n_my) {
             const int64_t i0 = tile_of(it) * WS_TILE + 4 * p;
-            sl = (int)(it % RING);
-            nv = (int)max((int64_t)0, min((int64_t)4, n_dst - i0));
+            sl = it % RING;
+            nv = nv_of(it);
             regular = reg1;
-            vsrc = vsrc1;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vs[r] = vs1[r];
             veid = veid1;
             vb1 = vb2;
-            load_idx(it + 1, vb1, reg1, vsrc1, veid1);
+            load_idx(it + 1, vb1, reg1, vs1, veid1);
             load_rp(it + 2, vb2);
             tl = tq < nv ? tq : nv - 1;      // a short group at the end of the graph: clamped (duplicated) cells
             cell = i0 + tl;
@@ -582,13 +627,13 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
         if constexpr (DEC) {
             // (the gathers leave ahead of stage B only in this instantiation: in the plain one the loads and their use stay in ONE basic block -- split, the
             // plain launch lost 9 %: 0.412 -> 0.450 ms)
-            if (it < my_n && nv > 0) {
+            if (it < n_my && nv > 0) {
                 own_row();
                 if (regular) neighbour_rows();
             }
             if (it >= 3 && !b_on_consumers((uint32_t)(it - 3))) stage_b((uint32_t)(it - 3), p & 3, p >> 2);
         }
-        if (it < my_n) {
+        if (it < n_my) {
             if (nv > 0) {
                 if constexpr (!DEC) own_row();
                 float aout[NCH], xv[NCH];
@@ -759,17 +804,25 @@ int dgnn_sage_layer_fused_ws_try(const LayerCall& c, const DecoderTail& t) {
     int grid = (int)(ntiles < DGNN_NUM_CU ? ntiles : DGNN_NUM_CU);
     if (grid < 1) grid = 1;
     const WsDec d{t.W0, t.b0, t.scale1, t.shift1, t.W3, t.b3, t.logits};
-#define DGNN_WS_GO(C_, D_)                                                                                                                                  \
+    // dense input rows (the previous fused layer's output) take the instantiation with the stride folded in; any other stride the run-time-stride one
+    const bool ldc = c.ldx == c.c_in;
+#define DGNN_WS_GO(C_, D_, L_)                                                                                                                              \
     do {                                                                                                                                                    \
         static bool attr_[DGNN_MAX_DEVICES] = {};                                                                                                           \
         const size_t sm_ = D_ ? WsL<C_, 2>::SMEM_DEC : WsL<C_, 2>::SMEM;                                                                                    \
-        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<C_, 2, D_>), sm_, attr_);                                                     \
-        hipLaunchKernelGGL((k_sage_fused_ws<C_, 2, D_>), dim3(grid), dim3(1024), sm_, c.stream, c.rowptr, c.src, c.eid, c.n_dst, c.x_src, c.x_dst, c.ldx,    \
-                           c.edge_attr, c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, c.out, c.ldo, ntiles, WS_KNOBS, d);                  \
+        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<C_, 2, D_, false, L_>), sm_, attr_);                                          \
+        hipLaunchKernelGGL((k_sage_fused_ws<C_, 2, D_, false, L_>), dim3(grid), dim3(1024), sm_, c.stream, c.rowptr, c.src, c.eid, c.n_dst, c.x_src,        \
+                           c.x_dst, c.ldx, c.edge_attr, c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, c.out, c.ldo, ntiles, WS_KNOBS, d);  \
     } while (0)
-    if (c.c_in == 64) DGNN_WS_GO(64, false);
-    else if (dec) DGNN_WS_GO(128, true);
-    else DGNN_WS_GO(128, false);
+#define DGNN_WS_GO2(C_, D_)                \
+    do {                                   \
+        if (ldc) DGNN_WS_GO(C_, D_, true); \
+        else DGNN_WS_GO(C_, D_, false);    \
+    } while (0)
+    if (c.c_in == 64) DGNN_WS_GO2(64, false);
+    else if (dec) DGNN_WS_GO2(128, true);
+    else DGNN_WS_GO2(128, false);
+#undef DGNN_WS_GO2
 #undef DGNN_WS_GO
     return dgnn_check_launch(dec ? "sage_layer_fused_decoder_fwd(wave-specialised)" : "sage_layer_fused_fwd(wave-specialised)");
 }
@@ -791,18 +844,22 @@ int dgnn_sage_layer_fused_ws16_try(const LayerCall16& c) {
     const float* xs = static_cast<const float*>(c.x_src);
     const float* xd = static_cast<const float*>(c.x_dst);
     float* o = reinterpret_cast<float*>(c.out);
+    const bool ldc = c.ldx == c.c_in;      // (as in dgnn_sage_layer_fused_ws_try)
+#define DGNN_WS_GO16(C_, R_, L_)                                                                                                                            \
+    do {                                                                                                                                                    \
+        static bool attr_[DGNN_MAX_DEVICES] = {};                                                                                                           \
+        const size_t sm_ = WsL<C_, R_>::SMEM;                                                                                                               \
+        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<C_, R_, false, true, L_>), sm_, attr_);                                       \
+        hipLaunchKernelGGL((k_sage_fused_ws<C_, R_, false, true, L_>), dim3(grid), dim3(1024), sm_, c.stream, c.rowptr, c.src, c.eid, c.n_dst, xs, xd,      \
+                           c.ldx, c.edge_attr, c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, o, c.ldo, ntiles, WS_KNOBS, d);               \
+    } while (0)
     if (c.c_in == 64) {
-        static bool attr_[DGNN_MAX_DEVICES] = {};
-        const size_t sm_ = WsL<64, 4>::SMEM;
-        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<64, 4, false, true>), sm_, attr_);
-        hipLaunchKernelGGL((k_sage_fused_ws<64, 4, false, true>), dim3(grid), dim3(1024), sm_, c.stream, c.rowptr, c.src, c.eid, c.n_dst, xs, xd, c.ldx, c.edge_attr,
-                           c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, o, c.ldo, ntiles, WS_KNOBS, d);
+        if (ldc) DGNN_WS_GO16(64, 4, true);
+        else DGNN_WS_GO16(64, 4, false);
     } else {
-        static bool attr_[DGNN_MAX_DEVICES] = {};
-        const size_t sm_ = WsL<128, 2>::SMEM;
-        dgnn_allow_dynamic_lds(reinterpret_cast<const void*>(&k_sage_fused_ws<128, 2, false, true>), sm_, attr_);
-        hipLaunchKernelGGL((k_sage_fused_ws<128, 2, false, true>), dim3(grid), dim3(1024), sm_, c.stream, c.rowptr, c.src, c.eid, c.n_dst, xs, xd, c.ldx, c.edge_attr,
-                           c.lde, c.We, c.be, c.Wj, c.bj, c.Wi, c.scale, c.shift, c.relu, o, c.ldo, ntiles, WS_KNOBS, d);
+        if (ldc) DGNN_WS_GO16(128, 2, true);
+        else DGNN_WS_GO16(128, 2, false);
     }
+#undef DGNN_WS_GO16
     return dgnn_check_launch("sage_layer_fused_fwd_bf16(wave-specialised)");
 }
