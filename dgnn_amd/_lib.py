@@ -135,6 +135,11 @@ SIGNATURES = {
     "dgnn_ray_first_hit_scratch_bytes": (i64, [i64, i32]),
     "dgnn_ray_first_hit_plan": (i32, [vp, i64, vp, i64, i32, vp, vp, vp, vp]),
     "dgnn_ray_first_hit": (i32, [vp, i64, vp, i64, i32, vp, vp, i64, f64, vp, vp, vp, vp, vp, i64, vp, vp]),
+    "dgnn_insphere_sign": (i32, [vp, i64, vp, vp, vp]),
+    "dgnn_delaunay_default_capacity": (i64, [i64]),
+    "dgnn_delaunay_scratch_bytes": (i64, [i64, i64]),
+    "dgnn_delaunay": (i32, [vp, i64, i64, vp, vp, vp, vp, vp]),
+    "dgnn_delaunay_violations": (i32, [vp, i64, vp, vp, i64, vp, vp]),
     "dgnn_khop_scratch_elems": (i64, [i64, i64]),
     "dgnn_khop_count": (i32, [vp, vp, i64, i32, vp, vp, vp, vp]),
     "dgnn_khop_expand": (i32, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

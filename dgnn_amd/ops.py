@@ -2372,3 +2372,177 @@ def scale_features(x64, c_first: int, kind: str, feature_range=(0, 1), sum_cols=
                                         s0, s1, int(div_col or 0), d0, d1, float(div_scalar if div_scalar is not None else 1.0), k0, k1,
                                         ptr(out), c, ptr(stats), ptr(scratch), stream_ptr()), "dgnn_scale_features_f64")
     return (out, stats) if return_stats else out
+
+
+# ---- exact in-sphere predicate, 3D Delaunay triangulation, its certificate (csrc/exact_insphere.h, csrc/delaunay.hip) ----
+DELAUNAY_STATS = ("rounds", "points_per_round_min", "points_per_round_max", "max_cavity", "exact_insphere", "exact_orient", "cells_allocated",
+                  "need", "dup_a", "dup_b", "slow_paths")
+VIOLATIONS = ("flat", "negative", "nonlocal_facets", "concave_hull_edges", "bad_links")
+_E_CAPACITY, _E_DUPLICATE = -5, -6
+_EVEN_PERMS = ((0, 1, 2, 3), (0, 2, 3, 1), (0, 3, 1, 2), (1, 0, 3, 2), (1, 2, 0, 3), (1, 3, 2, 0), (2, 0, 1, 3), (2, 1, 3, 0), (2, 3, 0, 1),
+               (3, 0, 2, 1), (3, 1, 0, 2), (3, 2, 1, 0))
+# the facet opposite slot s of a positive tet, ordered so that the tet's own vertex s -- and so every point -- lies on its negative side
+_OUTWARD_FACET = ((1, 2, 3), (0, 3, 2), (0, 1, 3), (0, 2, 1))
+
+
+@on_device_of
+def insphere_sign(points5):
+    """(signs int8 [n] on the GPU, exact-stage calls int) of dgnn_insphere_sign for points5 fp64 [n, 5, 3] = (a, b, c, d, e) per case: +1 when e
+    lies strictly inside the sphere through a..d, 0 on it, -1 outside; 0 for flat a..d.  Exact for coordinates that are 0 or of a magnitude
+    in [2^-150, 2^150]; DgnnError outside that range (NaN and infinities included)."""
+    dev = _dev_of(points5)
+    p = torch.as_tensor(points5).to(dev, torch.float64).contiguous()
+    if p.dim() != 3 or tuple(p.shape[1:]) != (5, 3):
+        raise ValueError("expected [n, 5, 3], got %s" % (tuple(p.shape),))
+    n = p.size(0)
+    out = _empty(dev, torch.int8, n)
+    counts = torch.zeros(3, dtype=torch.int64, device=dev)
+    check(lib().dgnn_insphere_sign(ptr(p), n, ptr(out), ptr(counts), stream_ptr()), "dgnn_insphere_sign")
+    return out, int(counts[0].item())
+
+
+def delaunay_priority(n, seed=0, device=None):
+    """The default insertion order of `delaunay`: the rank of point i is its place in the ascending order of mm_hash(seed, i) (the counter hash
+    of include/dgnn_hip.h, 64 bits, unsigned; ties by index) -> (order int64 [n]: order[r] = the point of rank r) on `device`."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    m34, m37, m33 = (1 << 34) - 1, (1 << 37) - 1, (1 << 33) - 1
+
+    def s64(x):   # a 64-bit constant as the int64 with the same bits
+        x &= (1 << 64) - 1
+        return x - (1 << 64) if x >> 63 else x
+
+    z = torch.arange(n, dtype=torch.int64, device=dev) * s64(0x9E3779B97F4A7C15) + s64(int(seed))   # int64 arithmetic wraps: the uint64 bits
+    z = (z ^ ((z >> 30) & m34)) * s64(0xBF58476D1CE4E5B9)
+    z = (z ^ ((z >> 27) & m37)) * s64(0x94D049BB133111EB)
+    z = z ^ ((z >> 31) & m33)
+    return torch.sort(z ^ s64(1 << 63), stable=True)[1]   # the sign bit flipped: signed order = unsigned order
+
+
+@on_device_of
+def delaunay(points, priority=None, seed=0, cell_capacity=None):
+    """The Delaunay triangulation of distinct fp64 points [n, 3] (dgnn_delaunay; contract in include/dgnn_hip.h) -> dict on the GPU:
+      "tetrahedra" int32 [T, 4]: the finite cells, each with its smallest vertex id first and, among the row's even permutations, the
+          lexicographically smallest; det[v1 - v0, v2 - v0, v3 - v0] > 0 exactly; rows sorted lexicographically;
+      "neighbors" int32 [T + H, 4]: cells T..T+H-1 are the infinite cells, one per hull facet, ordered by (finite cell, slot).  Slot k of a
+          finite cell: the cell across the facet opposite vertex k.  Slot 0 of an infinite cell: its finite cell; slots 1..3: the infinite
+          cells across the hull edges opposite the three vertices of its row in "hull_facets";
+      "hull_facets" int32 [H, 3]: every input point lies on or behind each (orient <= 0);
+      "stats": rounds, points_per_round_min / _max, max_cavity, exact_insphere, exact_orient (exact-stage calls), capacity_retries,
+          slow_paths, cells_allocated, cell_capacity, workspace_bytes.
+    priority: an int permutation [n], the point of the lowest value goes first where points contend; None: the order of delaunay_priority(n,
+    seed).  In general position the result does not depend on either.  cell_capacity: cells of storage (default about 8 n + 64; doubled
+    and retried when too small).  ValueError: n < 4, non-finite coordinates, a priority that is no permutation.  DgnnError: coordinates outside
+    the predicate's range, a duplicate point (the pair is named), all points coplanar."""
+    dev = _dev_of(points)
+    p = _on(points, dev, torch.float64, 3)
+    n = p.size(0)
+    if n < 4:
+        raise ValueError("delaunay: %d points, at least 4 are needed" % n)
+    if not bool(torch.isfinite(p).all()):
+        raise ValueError("delaunay: a coordinate is not finite")
+    if priority is None:
+        order = delaunay_priority(n, seed, dev)
+    else:
+        pr = torch.as_tensor(priority)
+        if pr.dtype.is_floating_point or pr.dtype == torch.bool or pr.dim() != 1 or pr.numel() != n:
+            raise ValueError("delaunay: priority must be an int permutation [%d]" % n)
+        pr = pr.to(dev, torch.int64)
+        srt, order = torch.sort(pr, stable=True)
+        if not bool((srt == torch.arange(n, device=dev)).all()):
+            raise ValueError("delaunay: priority is not a permutation of 0..%d (ties are refused)" % (n - 1))
+    pts = p[order].contiguous()
+    cap = int(cell_capacity) if cell_capacity is not None else int(lib().dgnn_delaunay_default_capacity(n))
+    cap, retries = max(cap, 5), 0
+    while True:
+        cells, nbrs = _empty(dev, torch.int32, cap, 4), _empty(dev, torch.int32, cap, 4)
+        nbytes = int(lib().dgnn_delaunay_scratch_bytes(n, cap))
+        if nbytes <= 0:
+            raise DgnnError("delaunay: %d points with %d cells exceed the int32 indexing" % (n, cap))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        st = (C.c_int64 * 16)()
+        code = lib().dgnn_delaunay(ptr(pts), n, cap, ptr(cells), ptr(nbrs), st, ptr(scratch), stream_ptr())
+        if code == _E_CAPACITY:
+            cap, retries = max(2 * cap, int(st[DELAUNAY_STATS.index("need")])), retries + 1
+            continue
+        if code == _E_DUPLICATE:
+            a, b = int(order[int(st[DELAUNAY_STATS.index("dup_a")])]), int(order[int(st[DELAUNAY_STATS.index("dup_b")])])
+            raise DgnnError("delaunay: points %d and %d are equal" % (min(a, b), max(a, b)))
+        _check_value(code, "dgnn_delaunay")
+        break
+    raw = dict(zip(DELAUNAY_STATS, (int(x) for x in st)))
+    nc = raw["cells_allocated"]
+    tv, tn = cells[:nc].long(), nbrs[:nc].long()
+    alive = tv[:, 0] >= 0
+    ghost = alive & (tv == n).any(dim=1)
+    fin_ids = torch.nonzero(alive & ~ghost).reshape(-1)
+    vmap = torch.cat([order, torch.full((1,), -1, dtype=torch.int64, device=dev)])
+    v = vmap[tv[fin_ids]]                                                  # original ids of the finite cells' vertices
+    perms = torch.tensor(_EVEN_PERMS, dtype=torch.int64, device=dev)
+    k1 = v[:, perms[:, 0]] * (n + 1) + v[:, perms[:, 1]]                   # the first two vertices fix an even permutation
+    sel = perms[torch.argmin(k1, dim=1)]
+    tets, nb_raw = torch.gather(v, 1, sel), torch.gather(tn[fin_ids], 1, sel)
+    srt = torch.sort(tets[:, 2] * (n + 1) + tets[:, 3], stable=True)[1]
+    srt = srt[torch.sort((tets[:, 0] * (n + 1) + tets[:, 1])[srt], stable=True)[1]]
+    tets, nb_raw, fin_ids = tets[srt], nb_raw[srt], fin_ids[srt]
+    T = tets.size(0)
+    hpos = torch.nonzero(ghost[nb_raw].reshape(-1)).reshape(-1)           # (finite cell, slot) of the hull facets, ascending
+    H = hpos.numel()
+    inf_raw = nb_raw.reshape(-1)[hpos]
+    newidx = torch.full((nc,), -1, dtype=torch.int64, device=dev)
+    newidx[fin_ids] = torch.arange(T, device=dev)
+    newidx[inf_raw] = T + torch.arange(H, device=dev)
+    hi, hs = hpos // 4, hpos % 4
+    facet_slots = torch.tensor(_OUTWARD_FACET, dtype=torch.int64, device=dev)[hs]
+    hull = torch.gather(tets[hi], 1, facet_slots)
+    ov = vmap[tv[inf_raw]]                                                 # the infinite cells' vertices, -1 = the ghost
+    inf_nb = torch.empty((H, 4), dtype=torch.int64, device=dev)
+    inf_nb[:, 0] = hi
+    for j in range(3):
+        pos = (ov == hull[:, j:j + 1]).int().argmax(dim=1, keepdim=True)
+        inf_nb[:, j + 1] = newidx[torch.gather(tn[inf_raw], 1, pos).reshape(-1)]
+    neighbors = torch.cat([newidx[nb_raw], inf_nb]).to(torch.int32)
+    if T == 0 or int(neighbors.min()) < 0:
+        raise DgnnError("delaunay: the cells do not close up (%d finite, %d infinite)" % (T, H))
+    stats = {k: raw[k] for k in ("rounds", "points_per_round_min", "points_per_round_max", "max_cavity", "exact_insphere", "exact_orient",
+                                 "slow_paths", "cells_allocated")}
+    stats.update(capacity_retries=retries, cell_capacity=cap, workspace_bytes=nbytes + 2 * cells.numel() * 4)
+    return {"tetrahedra": tets.to(torch.int32), "neighbors": neighbors, "hull_facets": hull.to(torch.int32), "stats": stats}
+
+
+def facet_neighbors(tetrahedra):
+    """(neighbors int64 [T, 4] with -1 where no cell lies across, facets shared by more than two cells) of any cell list, by matching the
+    sorted vertex triples of the facets (torch sort on the GPU).  Slot k is the facet opposite vertex k."""
+    t = tetrahedra.long()
+    T = t.size(0)
+    dev = t.device
+    opp = torch.tensor(((1, 2, 3), (0, 2, 3), (0, 1, 3), (0, 1, 2)), dtype=torch.int64, device=dev)
+    f = torch.sort(t[:, opp], dim=2)[0].reshape(-1, 3)
+    _, inv, counts = torch.unique(f, dim=0, return_inverse=True, return_counts=True)
+    nbr = torch.full((4 * T,), -1, dtype=torch.int64, device=dev)
+    order = torch.sort(inv, stable=True)[1]
+    si = inv[order]
+    pair = (si[1:] == si[:-1]) & (counts[si[1:]] == 2)
+    a, b = order[:-1][pair], order[1:][pair]
+    nbr[a], nbr[b] = b // 4, a // 4
+    return nbr.reshape(T, 4), int((counts > 2).sum())
+
+
+@on_device_of
+def delaunay_violations(vertices, tetrahedra):
+    """A certificate for any `_3dt`-style cell list (dgnn_delaunay_violations on the neighbours of facet_neighbors), all exact -> dict of
+    counts: "flat" and "negative" cells, "overfull_facets" (more than two cells), "nonlocal_facets" (interior facets whose opposite vertex
+    lies strictly inside the cell's sphere), "concave_hull_edges" ((hull facet, edge) pairs where the next hull facet's apex lies strictly
+    beyond the facet), "bad_links".  All zero for a Delaunay triangulation of its vertices' hull."""
+    dev = _dev_of(vertices, tetrahedra)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    T = tets.size(0)
+    if T and (int(tets.min()) < 0 or int(tets.max()) >= v.size(0)):
+        raise DgnnError("delaunay_violations: a vertex id out of range")
+    nbr, overfull = facet_neighbors(tets) if T else (torch.zeros((0, 4), dtype=torch.int64, device=dev), 0)
+    nbr = nbr.to(torch.int32).contiguous()
+    counts = torch.zeros(len(VIOLATIONS) + 1, dtype=torch.int64, device=dev)
+    check(lib().dgnn_delaunay_violations(ptr(v), v.size(0), ptr(tets), ptr(nbr), T, ptr(counts), stream_ptr()), "dgnn_delaunay_violations")
+    out = dict(zip(VIOLATIONS, (int(x) for x in counts.cpu()[:len(VIOLATIONS)])))
+    out["overfull_facets"] = overfull
+    return out

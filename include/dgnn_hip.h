@@ -1424,6 +1424,58 @@ int dgnn_relu_bwd(const float* y, const float* g, int64_t n, float* out, void* s
 int dgnn_scatter_rows_f32(const float* in, int64_t ld_in, const int64_t* idx, int64_t n, int cols, float* out,
                           int64_t ld_out, void* stream);
 
+/* ---- exact in-sphere predicate, 3D Delaunay triangulation and its certificate (csrc/exact_insphere.h, csrc/delaunay.hip) ----
+ *
+ * dgnn_insphere_sign: points5 fp64 [n, 5, 3] (a, b, c, d, e per case) -> sign_out int8 [n]: +1 when e lies strictly inside the sphere through
+ *   a, b, c, d, 0 on it, -1 outside, for any non-flat a..d; 0 for flat (coplanar) a..d.  With L the determinant of the rows
+ *   [x y z x^2+y^2+z^2 1] of a..e the result is -sign(L) * sign(det[b - a, c - a, d - a]), both signs exact.
+ *   filter  every +, - and * below is one fp64 operation (no contraction).  p' = p - e for p = a..d (12 differences);
+ *           ab = a'x b'y - b'x a'y, and bc, cd, da, ac, bd likewise; abc = a'z bc - b'z ac + c'z ab, bcd = b'z cd - c'z bd + d'z bc,
+ *           cda = c'z da + d'z ac + a'z cd, dab = d'z ab + a'z bd + b'z da; lift(p) = p'x p'x + p'y p'y + p'z p'z;
+ *           L~ = (lift(d) abc - lift(c) dab) + (lift(b) cda - lift(a) bcd).  The permanent is the same expression with every product taken by
+ *           magnitude and every difference replaced by a sum.  sign(L~) is returned when |L~| > (16 + 224 eps) eps permanent + 2^-600,
+ *           eps = 2^-53; the derivation of both terms is in csrc/exact_insphere.h.
+ *   exact   otherwise L is summed exactly on the raw coordinates: 360 products of five coordinates in a fixed-point accumulator of 58 64-bit
+ *           limbs.  The orientation has its own filter and exact stage (csrc/exact_orient.h).
+ *   range   every coordinate 0 or of a magnitude in [2^-150, 2^150]; anything else (NaN, infinities, subnormals) returns DGNN_E_UNSUPPORTED
+ *           and is never answered approximately.
+ *   exact_out int64 [3] on the device: exact-stage calls of L, exact-stage calls of the orientation, an error word.  Synchronises the stream.
+ *
+ * dgnn_delaunay: points fp64 [n, 3], distinct, GIVEN IN PRIORITY ORDER (row r is the point of priority rank r; the lowest rank is inserted
+ *   first among points that contend).  Builds the Delaunay triangulation with a ghost vertex (id n): cells_out / neighbors_out int32
+ *   [cell_capacity, 4] hold stats_out[DGNN_DELAUNAY_CELLS] rows on return; a row whose first vertex is -1 is a dead cell; a row with the
+ *   ghost is an infinite cell (its other three vertices are a hull facet; with p in the ghost's slot the row is positively oriented exactly
+ *   for p strictly beyond that facet); every other row is a finite cell with det[v1 - v0, v2 - v0, v3 - v0] > 0 exactly.  neighbors_out[c][k]
+ *   is the cell across the facet opposite vertex k.  The set of finite cells is a function of the points and their order alone (in general
+ *   position of the points alone); row numbers are a function of those too -- nothing depends on the schedule, reruns are bit-identical.
+ *   A cell conflicts with p when p is strictly inside its sphere (finite), or strictly beyond its facet, or in the facet's plane and in
+ *   conflict with the finite cell behind it (infinite).  No input point is strictly inside any finite cell's sphere on return.
+ *   stats_out: int64 [DGNN_DELAUNAY_N_STATS] on the HOST.  scratch: dgnn_delaunay_scratch_bytes(n, cell_capacity) bytes; nothing is
+ *   allocated inside.  Returns DGNN_E_INVALID for n < 4 or a non-finite coordinate, DGNN_E_UNSUPPORTED for a coordinate outside the
+ *   predicate's range or a device loop that reached its cap (cell count), DGNN_E_DUPLICATE for two equal points (their ranks in
+ *   stats_out[DGNN_DELAUNAY_DUP_A / _B]), DGNN_E_DEGENERATE when all points are coplanar, DGNN_E_CAPACITY when cell_capacity is too small
+ *   (stats_out[DGNN_DELAUNAY_NEED] cells were needed at that moment; call again with more).  At most n rounds; synchronises the stream
+ *   several times per round.
+ *
+ * dgnn_delaunay_violations: any cell list (vertices fp64 [n_vertices, 3], tetrahedra int32 [n_tets, 4]) with its neighbour table (int32
+ *   [n_tets, 4], -1 = no cell across) -> counts_out int64 [DGNN_VIOLATION_N + 1] on the device (the last word is an error word): flat cells,
+ *   negatively oriented cells, interior facets whose opposite vertex lies strictly inside the cell's sphere (counted once per facet),
+ *   (hull facet, edge) pairs at which the hull is locally concave, and links that do not share a facet.  All exact.  Synchronises. */
+#define DGNN_E_CAPACITY -5   /* caller-provided storage too small; the need is reported */
+#define DGNN_E_DUPLICATE -6  /* two equal input points */
+#define DGNN_E_DEGENERATE -7 /* all input points coplanar */
+enum { DGNN_DELAUNAY_ROUNDS = 0, DGNN_DELAUNAY_WIN_MIN, DGNN_DELAUNAY_WIN_MAX, DGNN_DELAUNAY_MAX_CAVITY, DGNN_DELAUNAY_EXACT_INSPHERE,
+       DGNN_DELAUNAY_EXACT_ORIENT, DGNN_DELAUNAY_CELLS, DGNN_DELAUNAY_NEED, DGNN_DELAUNAY_DUP_A, DGNN_DELAUNAY_DUP_B, DGNN_DELAUNAY_SLOW_PATHS,
+       DGNN_DELAUNAY_N_STATS = 16 };
+enum { DGNN_VIOLATION_FLAT = 0, DGNN_VIOLATION_NEGATIVE, DGNN_VIOLATION_NONLOCAL, DGNN_VIOLATION_CONCAVE, DGNN_VIOLATION_BAD_LINK, DGNN_VIOLATION_N };
+int dgnn_insphere_sign(const double* points5, int64_t n, int8_t* sign_out, int64_t* exact_out, void* stream);
+int64_t dgnn_delaunay_default_capacity(int64_t n);
+int64_t dgnn_delaunay_scratch_bytes(int64_t n, int64_t cell_capacity);
+int dgnn_delaunay(const double* points, int64_t n, int64_t cell_capacity, int32_t* cells_out, int32_t* neighbors_out, int64_t* stats_out,
+                  void* scratch, void* stream);
+int dgnn_delaunay_violations(const double* vertices, int64_t n_vertices, const int32_t* tetrahedra, const int32_t* neighbors, int64_t n_tets,
+                             int64_t* counts_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
