@@ -13,11 +13,14 @@
 
 #include "common.h"
 #include "mesh_common.h"
+#include "vec3.h"
 #include "fixed_sum.h"
 
 namespace {
 
-constexpr int CT_THREADS = 256;
+using dgnn_exact::V3;
+using dgnn_exact::load_v3;
+
 constexpr int32_t CT_BAD_ID = 1, CT_MALFORMED = 2, CT_BAD_MEAN = 4, CT_W_RANGE = 8;
 
 struct CtState {
@@ -25,19 +28,13 @@ struct CtState {
     unsigned long long rows, neutral, zeros;
 };
 
-struct D3 { double x, y, z; };
-__device__ __forceinline__ D3 ld3(const double* v, int32_t i) { return D3{v[3 * (int64_t)i], v[3 * (int64_t)i + 1], v[3 * (int64_t)i + 2]}; }
-__device__ __forceinline__ D3 sub(const D3& a, const D3& b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ D3 cross(const D3& a, const D3& b) { return D3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double dot(const D3& a, const D3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-
 // per-thread counters of a kernel, added up per wave (every lane arrives: the callers' loops are block-uniform) and sent with one atomic each
 struct CtCounts { int32_t rows, neutral, zeros, max_w; };
 __device__ __forceinline__ void ct_flush(CtCounts c, CtState* st) {
+    c.rows = wave_sum(c.rows);
+    c.neutral = wave_sum(c.neutral);
+    c.zeros = wave_sum(c.zeros);
     for (int o = 32; o > 0; o >>= 1) {
-        c.rows += __shfl_xor(c.rows, o);
-        c.neutral += __shfl_xor(c.neutral, o);
-        c.zeros += __shfl_xor(c.zeros, o);
         const int32_t m = __shfl_xor(c.max_w, o);
         c.max_w = m > c.max_w ? m : c.max_w;
     }
@@ -62,7 +59,7 @@ __device__ __forceinline__ int32_t quantise(double bw, double q, CtCounts& c, Ct
 // circumradius, positive on the cell's own side); 0 and *neutral = 1 for a degenerate side.  false: the facet is not a face of the cell / an id
 // out of range.
 __device__ __forceinline__ bool side_cosine(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ tets, int32_t cell, int32_t ia,
-                                            int32_t ib, int32_t ic, const D3& a, const D3& n, double nn, double* cosine, int* neutral, CtState* st) {
+                                            int32_t ib, int32_t ic, const V3& a, const V3& n, double nn, double* cosine, int* neutral, CtState* st) {
     int32_t t[4], opp = -1;
     int in = 0;
 #pragma unroll
@@ -75,14 +72,14 @@ __device__ __forceinline__ bool side_cosine(const double* __restrict__ v, int64_
     const bool has = (t[0] == ia || t[1] == ia || t[2] == ia || t[3] == ia) && (t[0] == ib || t[1] == ib || t[2] == ib || t[3] == ib) &&
                      (t[0] == ic || t[1] == ic || t[2] == ic || t[3] == ic);
     if (in != 3 || !has) { atomicOr(&st->err, CT_MALFORMED); return false; }
-    const D3 p0 = ld3(v, t[0]);
-    const D3 u = sub(ld3(v, t[1]), p0), vv = sub(ld3(v, t[2]), p0), w = sub(ld3(v, t[3]), p0);
-    const D3 vw = cross(vv, w), wu = cross(w, u), uv = cross(u, vv);
+    const V3 p0 = load_v3(v, t[0]);
+    const V3 u = sub(load_v3(v, t[1]), p0), vv = sub(load_v3(v, t[2]), p0), w = sub(load_v3(v, t[3]), p0);
+    const V3 vw = cross(vv, w), wu = cross(w, u), uv = cross(u, vv);
     const double det = dot(u, vw), u2 = dot(u, u), v2 = dot(vv, vv), w2 = dot(w, w), d2 = 2.0 * det;
-    const D3 c{((u2 * vw.x + v2 * wu.x) + w2 * uv.x) / d2, ((u2 * vw.y + v2 * wu.y) + w2 * uv.y) / d2, ((u2 * vw.z + v2 * wu.z) + w2 * uv.z) / d2};
+    const V3 c{((u2 * vw.x + v2 * wu.x) + w2 * uv.x) / d2, ((u2 * vw.y + v2 * wu.y) + w2 * uv.y) / d2, ((u2 * vw.z + v2 * wu.z) + w2 * uv.z) / d2};
     const double R = sqrt(dot(c, c));
-    const double sd = dot(n, sub(ld3(v, opp), a));
-    const D3 g{(p0.x + c.x) - a.x, (p0.y + c.y) - a.y, (p0.z + c.z) - a.z};
+    const double sd = dot(n, sub(load_v3(v, opp), a));
+    const V3 g{(p0.x + c.x) - a.x, (p0.y + c.y) - a.y, (p0.z + c.z) - a.z};
     const double hn = dot(n, g);
     const double h = (sd > 0 ? hn : -hn) / nn;
     const double r = h / R;
@@ -97,7 +94,7 @@ __device__ __forceinline__ bool side_cosine(const double* __restrict__ v, int64_
 
 // KIND 1: val[f] = A_f (quantised later); KIND 2: q, w at once.  Every facet that is not a graph row gets 0 everywhere.
 template <int KIND>
-__global__ void __launch_bounds__(CT_THREADS) k_facet_terms(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ tets, int64_t nc,
+__global__ void __launch_bounds__(MESH_THREADS) k_facet_terms(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ tets, int64_t nc,
                                                             const int32_t* __restrict__ facets, const int32_t* __restrict__ nfacets, int64_t nf,
                                                             double bw, double* __restrict__ val, double* __restrict__ q_out,
                                                             int32_t* __restrict__ w_out, CtState* st) {
@@ -116,8 +113,8 @@ __global__ void __launch_bounds__(CT_THREADS) k_facet_terms(const double* __rest
         }
         if (ok && c0 >= 0 && c1 >= 0) {
             ++cnt.rows;
-            const D3 a = ld3(v, ia);
-            const D3 n = cross(sub(ld3(v, ib), a), sub(ld3(v, ic), a));
+            const V3 a = load_v3(v, ia);
+            const V3 n = cross(sub(load_v3(v, ib), a), sub(load_v3(v, ic), a));
             const double nn = sqrt(dot(n, n));
             if (KIND == 1) {
                 q = 0.5 * nn;
@@ -143,7 +140,7 @@ __global__ void __launch_bounds__(CT_THREADS) k_facet_terms(const double* __rest
 }
 
 // mean = total / rows (one division, the same in every thread); a mean that is 0 or not finite is an error and leaves zeros
-__global__ void __launch_bounds__(CT_THREADS) k_area_quantise(const double* __restrict__ area, const int32_t* __restrict__ nfacets, int64_t nf,
+__global__ void __launch_bounds__(MESH_THREADS) k_area_quantise(const double* __restrict__ area, const int32_t* __restrict__ nfacets, int64_t nf,
                                                               const double* __restrict__ total, double bw, double* __restrict__ q_out,
                                                               int32_t* __restrict__ w_out, CtState* st) {
     CtCounts cnt{0, 0, 0, 0};
@@ -207,7 +204,7 @@ extern "C" int dgnn_facet_cut_terms(const double* vertices, int64_t n_vertices, 
     DGNN_REQUIRE(n_cells < INT32_MAX / 4 && n_vertices < INT32_MAX && n_facets < INT32_MAX, DGNN_E_UNSUPPORTED,
                  "facet_cut_terms: sizes exceed the int32 indexing");
     const CtLayout L = ct_layout(scratch, n_facets);
-    const dim3 block(CT_THREADS), grid(dgnn_grid_cap(dgnn_cdiv(n_facets > 0 ? n_facets : 1, CT_THREADS)));
+    const dim3 block(MESH_THREADS), grid = mesh_launch_grid(n_facets);
     (void)hipMemsetAsync(L.st, 0, sizeof(CtState), stream);
     if (n_facets > 0) {
         if (kind == 1) {

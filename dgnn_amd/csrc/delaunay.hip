@@ -29,8 +29,8 @@ int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t*
 namespace {
 
 using dgnn_exact::V3;
+using dgnn_exact::load_v3;
 
-constexpr int DL_THREADS = 256;
 constexpr int DL_LIST = 128;           // the fast path's per-lane cavity list
 constexpr int32_t DL_INF = 0x7fffffff;
 enum { DL_LOOP = 1, DL_DUP = 2, DL_RANGE = 4, DL_NONFINITE = 8, DL_INTERNAL = 16 };
@@ -44,9 +44,6 @@ struct DlHead {
 
 struct Ctr { int in, orient; };
 
-inline dim3 dl_grid(int64_t n) { return dim3(dgnn_grid_cap(dgnn_cdiv(n > 0 ? n : 1, DL_THREADS))); }
-
-__device__ __forceinline__ V3 ldp(const double* __restrict__ p, int i) { return V3{p[3 * (int64_t)i], p[3 * (int64_t)i + 1], p[3 * (int64_t)i + 2]}; }
 __device__ __forceinline__ void flush(DlHead* h, const Ctr& c) {
     if (c.in) atomicAdd(&h->ex_insphere, (unsigned long long)c.in);
     if (c.orient) atomicAdd(&h->ex_orient, (unsigned long long)c.orient);
@@ -57,7 +54,7 @@ __device__ __forceinline__ int slot_of(const int32_t* v, int32_t x) { return v[0
 __device__ __forceinline__ int orient_with(const double* __restrict__ P, const int32_t* v, int k, const V3& q, Ctr& ctr) {
     V3 w[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = j == k ? q : ldp(P, v[j]);
+    for (int j = 0; j < 4; ++j) w[j] = j == k ? q : load_v3(P, v[j]);
     int ex = 0;
     const int s = dgnn_exact::orient_sign(w[0], w[1], w[2], w[3], &ex);
     ctr.orient += ex;
@@ -66,7 +63,7 @@ __device__ __forceinline__ int orient_with(const double* __restrict__ P, const i
 
 __device__ __forceinline__ bool in_sphere(const double* __restrict__ P, const int32_t* v, const V3& q, Ctr& ctr) {
     int ex = 0;
-    const int s = dgnn_exact::insphere_pos(ldp(P, v[0]), ldp(P, v[1]), ldp(P, v[2]), ldp(P, v[3]), q, &ex);
+    const int s = dgnn_exact::insphere_pos(load_v3(P, v[0]), load_v3(P, v[1]), load_v3(P, v[2]), load_v3(P, v[3]), q, &ex);
     ctr.in += ex;
     return s > 0;
 }
@@ -104,14 +101,14 @@ __device__ __forceinline__ int orient2(double ax, double ay, double bx, double b
 
 __global__ void k_find_i2(const double* __restrict__ P, int n, DlHead* h) {   // the lowest point not collinear with points 0 and 1
     Ctr ctr{0, 0};
-    const V3 a = ldp(P, 0), b = ldp(P, 1);
+    const V3 a = load_v3(P, 0), b = load_v3(P, 1);
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.x == b.x && a.y == b.y && a.z == b.z) {
         atomicOr(&h->err, DL_DUP);
         atomicMin(&h->dup, 1ull << 32);
     }
     for (int i = 2 + blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         if (i >= h->i2) continue;   // (a stale read only costs the test)
-        const V3 c = ldp(P, i);
+        const V3 c = load_v3(P, i);
         if (orient2(a.x, a.y, b.x, b.y, c.x, c.y, ctr) || orient2(a.y, a.z, b.y, b.z, c.y, c.z, ctr) || orient2(a.z, a.x, b.z, b.x, c.z, c.x, ctr))
             atomicMin(&h->i2, i);
     }
@@ -121,11 +118,11 @@ __global__ void k_find_i2(const double* __restrict__ P, int n, DlHead* h) {   //
 __global__ void k_find_i3(const double* __restrict__ P, int n, DlHead* h) {   // the lowest point not coplanar with points 0, 1 and i2
     Ctr ctr{0, 0};
     const int i2 = h->i2;
-    const V3 a = ldp(P, 0), b = ldp(P, 1), c = ldp(P, i2);
+    const V3 a = load_v3(P, 0), b = load_v3(P, 1), c = load_v3(P, i2);
     for (int i = 2 + blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         if (i == i2) continue;
         int ex = 0;
-        if (dgnn_exact::orient_sign(a, b, c, ldp(P, i), &ex)) atomicMin(&h->i3, i);
+        if (dgnn_exact::orient_sign(a, b, c, load_v3(P, i), &ex)) atomicMin(&h->i3, i);
         ctr.orient += ex;
     }
     flush(h, ctr);
@@ -134,7 +131,7 @@ __global__ void k_find_i3(const double* __restrict__ P, int n, DlHead* h) {   //
 __global__ void k_init(const double* __restrict__ P, int32_t G, int32_t* tv, int32_t* tn, int32_t* state, DlHead* h) {
     if (blockIdx.x || threadIdx.x) return;
     int32_t v[4] = {0, 1, h->i2, h->i3};
-    if (dgnn_exact::orient_sign(ldp(P, v[0]), ldp(P, v[1]), ldp(P, v[2]), ldp(P, v[3])) < 0) {
+    if (dgnn_exact::orient_sign(load_v3(P, v[0]), load_v3(P, v[1]), load_v3(P, v[2]), load_v3(P, v[3])) < 0) {
         const int32_t t = v[2];
         v[2] = v[3];
         v[3] = t;
@@ -183,7 +180,7 @@ __device__ __forceinline__ bool listed(const int32_t* list, int n, int32_t c) {
     return false;
 }
 
-__global__ void __launch_bounds__(DL_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_grow(const double* __restrict__ P, int n, const int32_t* tv, const int32_t* tn, int32_t* state, const int32_t* __restrict__ pcell,
        const int32_t* __restrict__ cand, int32_t* owner, int32_t* cavq, DlHead* h) {
     Ctr ctr{0, 0};
@@ -192,13 +189,13 @@ k_grow(const double* __restrict__ P, int n, const int32_t* tv, const int32_t* tn
         if (state[q] != ST_FREE) continue;
         const int32_t c0 = pcell[q];
         if (cand[c0] != q) continue;
-        const V3 pq = ldp(P, q);
+        const V3 pq = load_v3(P, q);
         if (!conflict(P, tv, tn, G, c0, pq, ctr)) {   // an empty cavity: q is a vertex of the cell that holds it
             int32_t dv = -1;
             for (int j = 0; j < 4; ++j) {
                 const int32_t v = tv[4 * (int64_t)c0 + j];
                 if (v == G) continue;
-                const V3 pv = ldp(P, v);
+                const V3 pv = load_v3(P, v);
                 if (pv.x == pq.x && pv.y == pq.y && pv.z == pq.z) dv = v;
             }
             atomicOr(&h->err, dv >= 0 ? DL_DUP : DL_INTERNAL);
@@ -238,12 +235,12 @@ __global__ void k_big_seed(const int32_t* __restrict__ pcell, int32_t* mark, DlH
     if (blockIdx.x == 0 && threadIdx.x == 0) mark[pcell[h->bigmin]] = 1;
 }
 
-__global__ void __launch_bounds__(DL_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_big_sweep(const double* __restrict__ P, int n, int32_t ncell, const int32_t* tv, const int32_t* tn, const int32_t* __restrict__ cand, int32_t* mark,
             DlHead* h) {
     Ctr ctr{0, 0};
     const int32_t q = h->bigmin, G = n;
-    const V3 pq = ldp(P, q);
+    const V3 pq = load_v3(P, q);
     for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < ncell; c += gridDim.x * blockDim.x) {
         if (mark[c] != 1) continue;
         for (int k = 0; k < 4; ++k) {
@@ -291,7 +288,7 @@ __global__ void k_big_commit(int32_t ncell, const int32_t* __restrict__ mark, in
         }
 }
 
-__global__ void __launch_bounds__(DL_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_verify(int n, const int32_t* tn, int32_t* state, const int32_t* __restrict__ pcell, const int32_t* __restrict__ owner,
          const int32_t* __restrict__ cavq, int32_t* cav, DlHead* h) {
     for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x) {
@@ -434,7 +431,7 @@ __global__ void k_commit(int32_t ncell, int32_t N, int32_t D, const int32_t* __r
 }
 
 // exact visibility walk to a cell that conflicts with q: the finite cell that holds it (closed), or the infinite cell it lies strictly beyond
-__global__ void __launch_bounds__(DL_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_relocate(const double* __restrict__ P, int n, int32_t ncell, int first_round, const int32_t* __restrict__ tv, const int32_t* __restrict__ tn,
            int32_t* state, int32_t* pcell, const int32_t* __restrict__ cav, const int32_t* __restrict__ firstnew, DlHead* h) {
     Ctr ctr{0, 0};
@@ -448,7 +445,7 @@ k_relocate(const double* __restrict__ P, int n, int32_t ncell, int first_round, 
             if (w < 0) continue;
             cur = firstnew[w];
         }
-        const V3 pq = ldp(P, q);
+        const V3 pq = load_v3(P, q);
         bool done = false;
         for (int64_t step = 0; step <= 4 * (int64_t)ncell + 16 && !done; ++step) {
             int32_t v[4];
@@ -497,7 +494,7 @@ __global__ void k_insphere(const double* __restrict__ pts, int64_t n, int8_t* __
 enum { VI_FLAT = 0, VI_NEGATIVE, VI_NONLOCAL, VI_CONCAVE, VI_BAD_LINK, VI_N };
 
 // one thread per (cell, slot) of any cell list with its neighbour table (-1 = no cell across)
-__global__ void __launch_bounds__(DL_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_violations(const double* __restrict__ P, int64_t nv, const int32_t* __restrict__ tets, const int32_t* __restrict__ nbr, int64_t nt,
              unsigned long long* counts, int32_t* err) {
     unsigned long long loc[VI_N] = {0, 0, 0, 0, 0};
@@ -513,7 +510,7 @@ k_violations(const double* __restrict__ P, int64_t nv, const int32_t* __restrict
         const int32_t nb = nbr[i];
         ok &= nb >= -1 && nb < nt;
         if (!ok) { atomicOr(err, DL_INTERNAL); continue; }
-        const V3 a = ldp(P, v[0]), b = ldp(P, v[1]), cc = ldp(P, v[2]), d = ldp(P, v[3]);
+        const V3 a = load_v3(P, v[0]), b = load_v3(P, v[1]), cc = load_v3(P, v[2]), d = load_v3(P, v[3]);
         const int o = dgnn_exact::orient_sign(a, b, cc, d);
         if (k == 0) {
             loc[VI_FLAT] += o == 0;
@@ -529,7 +526,7 @@ k_violations(const double* __restrict__ P, int64_t nv, const int32_t* __restrict
                 if (!on) opp = opp < 0 ? w : -2;
             }
             if (opp < 0 || opp >= nv) { ++loc[VI_BAD_LINK]; continue; }
-            if (dgnn_exact::insphere_sign(a, b, cc, d, ldp(P, opp)) > 0) ++loc[VI_NONLOCAL];
+            if (dgnn_exact::insphere_sign(a, b, cc, d, load_v3(P, opp)) > 0) ++loc[VI_NONLOCAL];
             continue;
         }
         if (o == 0) continue;
@@ -556,7 +553,7 @@ k_violations(const double* __restrict__ P, int64_t nv, const int32_t* __restrict
             }
             if (apex < 0 || apex >= nv) { ++loc[VI_BAD_LINK]; continue; }
             V3 w4[4] = {a, b, cc, d};
-            w4[k] = ldp(P, apex);
+            w4[k] = load_v3(P, apex);
             if (dgnn_exact::orient_sign(w4[0], w4[1], w4[2], w4[3]) * o < 0) ++loc[VI_CONCAVE];   // the other facet's apex lies strictly beyond this facet
         }
     }
@@ -606,7 +603,7 @@ extern "C" int64_t dgnn_delaunay_scratch_bytes(int64_t n, int64_t cell_capacity)
     return dl_sizes_ok(n, cell_capacity) ? dl_layout(nullptr, n, cell_capacity).bytes : 0;
 }
 
-#define DL_LAUNCH(kernel, count, ...) hipLaunchKernelGGL(kernel, dl_grid(count), dim3(DL_THREADS), 0, stream, __VA_ARGS__)
+#define DL_LAUNCH(kernel, count, ...) hipLaunchKernelGGL(kernel, mesh_launch_grid(count), dim3(MESH_THREADS), 0, stream, __VA_ARGS__)
 
 extern "C" int dgnn_delaunay(const double* points, int64_t n, int64_t cell_capacity, int32_t* cells_out, int32_t* neighbors_out, int64_t* stats_out,
                              void* scratch, void* stream_) {

@@ -14,9 +14,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-namespace dgnn_exact {
+#include "vec3.h"
 
-struct V3 { double x, y, z; };
+namespace dgnn_exact {
 
 __device__ __forceinline__ bool orient_coord_ok(double x) {
     const double m = fabs(x);

@@ -28,7 +28,6 @@ namespace {
 
 // error bits of the status word (checked once after the costs and graph are built)
 constexpr int32_t GC_BAD_EDGE = 1, GC_NONFINITE = 2, GC_COST_RANGE = 4, GC_CAP_OVERFLOW = 8, GC_NEG_WEIGHT = 16;
-constexpr int GC_THREADS = 256;
 constexpr int GC_BFS_GRID = 1024;      // blocks of a BFS level launch (grid-stride over the frontier)
 constexpr int GC_BFS_BATCH = 8;        // BFS levels queued between two reads of the frontier size
 constexpr int64_t GC_MAX_STEPS = 1 << 19;
@@ -270,20 +269,7 @@ __global__ void k_bfs_level(const int32_t* __restrict__ rowptr, const int32_t* _
 }
 
 // ---- result ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void gc_block_add(unsigned long long* dst, long long v) {
-    __shared__ long long part[GC_THREADS / DGNN_WAVE];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (lane_id() == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long s = 0;
-        for (int k = 0; k < GC_THREADS / DGNN_WAVE; ++k) s += part[k];
-        if (s) atomicAdd(dst, (unsigned long long)s);   // integer sums: the total does not depend on the order
-    }
-    __syncthreads();
-}
-
-__global__ void __launch_bounds__(GC_THREADS) k_labels_energy(const int32_t* __restrict__ h, const int32_t* __restrict__ d0,
+__global__ void __launch_bounds__(MESH_THREADS) k_labels_energy(const int32_t* __restrict__ h, const int32_t* __restrict__ d0,
                                                               const int32_t* __restrict__ d1, const int32_t* __restrict__ rt, int64_t n,
                                                               int32_t* __restrict__ labels, GcState* st) {
     long long ed = 0, fl = 0, mn = 0;
@@ -294,13 +280,13 @@ __global__ void __launch_bounds__(GC_THREADS) k_labels_energy(const int32_t* __r
         fl += (a > b ? a - b : 0) - rt[i];
         mn += a < b ? a : b;
     }
-    gc_block_add(&st->sums[0], ed);
-    gc_block_add(&st->sums[2], fl);
-    gc_block_add(&st->sums[3], mn);
+    block_add_atomic(&st->sums[0], ed);
+    block_add_atomic(&st->sums[2], fl);
+    block_add_atomic(&st->sums[3], mn);
 }
 
 template <bool PER_ROW>
-__global__ void __launch_bounds__(GC_THREADS) k_pair_energy(const int32_t* __restrict__ edges, int64_t rows, const int32_t* __restrict__ labels,
+__global__ void __launch_bounds__(MESH_THREADS) k_pair_energy(const int32_t* __restrict__ edges, int64_t rows, const int32_t* __restrict__ labels,
                                                             const int32_t* __restrict__ rw, int32_t w, GcState* st) {
     long long cut = 0;
     for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
@@ -308,7 +294,7 @@ __global__ void __launch_bounds__(GC_THREADS) k_pair_energy(const int32_t* __res
         if constexpr (PER_ROW) cut += differ ? (long long)rw[r] : 0;
         else cut += differ;
     }
-    gc_block_add(&st->sums[1], PER_ROW ? cut : cut * (long long)w);
+    block_add_atomic(&st->sums[1], PER_ROW ? cut : cut * (long long)w);
 }
 
 __global__ void k_outputs(const GcState* st, int64_t* energy_out, int64_t* flow_out, int32_t* stats_out, int32_t steps, int32_t relabels) {
@@ -360,23 +346,22 @@ int gc_solve(const char* what, const float* logits, int64_t ld, int64_t n, const
                  (long long)n, (long long)n_rows);
     const GcLayout L = gc_layout(scratch, n, n_rows);
     const int64_t arcs = 2 * n_rows;
-    const dim3 block(GC_THREADS);
-    auto grid = [](int64_t items) { return dim3(dgnn_grid_cap(dgnn_cdiv(items > 0 ? items : 1, GC_THREADS))); };
+    const dim3 block(MESH_THREADS);
     GcState hs{};
 
     // costs; graph: degrees counted into `cursor`, scanned into rowptr, cursor = rowptr again as the fill's claim pointers
     (void)hipMemsetAsync(L.st, 0, sizeof(GcState), stream);
     (void)hipMemsetAsync(L.cursor, 0, sizeof(int32_t) * (n + 1), stream);
     (void)hipMemsetAsync(L.touched, 0, sizeof(int32_t) * (n > 0 ? n : 1), stream);
-    hipLaunchKernelGGL(k_costs, grid(n), block, 0, stream, logits, ld, n, unary_weight, L.d0, L.d1, L.e, L.rt, L.st);
-    hipLaunchKernelGGL(k_count<PER_ROW>, grid(n_rows), block, 0, stream, edges, n_rows, n, row_weights, L.cursor, L.st);
+    hipLaunchKernelGGL(k_costs, mesh_launch_grid(n), block, 0, stream, logits, ld, n, unary_weight, L.d0, L.d1, L.e, L.rt, L.st);
+    hipLaunchKernelGGL(k_count<PER_ROW>, mesh_launch_grid(n_rows), block, 0, stream, edges, n_rows, n, row_weights, L.cursor, L.st);
     int rc = dgnn_exclusive_scan_i32(L.cursor, n, L.rowptr, L.sums, stream);
     if (rc) return rc;
     (void)hipMemcpyAsync(L.cursor, L.rowptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToDevice, stream);
-    hipLaunchKernelGGL(k_fill, grid(n_rows), block, 0, stream, edges, n_rows, n, L.cursor, L.nbr, L.aid);
-    hipLaunchKernelGGL(k_sort_segments, grid(n), block, 0, stream, L.rowptr, n, L.nbr, L.aid, L.pos);
-    hipLaunchKernelGGL(k_rev<PER_ROW>, grid(arcs), block, 0, stream, L.rowptr, n, L.aid, L.pos, row_weights, w, L.rev, L.res, L.push);
-    hipLaunchKernelGGL(k_check_caps<PER_ROW>, grid(n), block, 0, stream, L.rowptr, L.aid, L.e, L.rt, n, row_weights, w, L.st);
+    hipLaunchKernelGGL(k_fill, mesh_launch_grid(n_rows), block, 0, stream, edges, n_rows, n, L.cursor, L.nbr, L.aid);
+    hipLaunchKernelGGL(k_sort_segments, mesh_launch_grid(n), block, 0, stream, L.rowptr, n, L.nbr, L.aid, L.pos);
+    hipLaunchKernelGGL(k_rev<PER_ROW>, mesh_launch_grid(arcs), block, 0, stream, L.rowptr, n, L.aid, L.pos, row_weights, w, L.rev, L.res, L.push);
+    hipLaunchKernelGGL(k_check_caps<PER_ROW>, mesh_launch_grid(n), block, 0, stream, L.rowptr, L.aid, L.e, L.rt, n, row_weights, w, L.st);
     if ((rc = dgnn_check_launch(at("build")))) return rc;
     if ((rc = mm_read(&hs, L.st, sizeof(GcState), stream, what))) return rc;
     if (hs.err) {
@@ -395,7 +380,7 @@ int gc_solve(const char* what, const float* logits, int64_t ld, int64_t n, const
             return DGNN_E_UNSUPPORTED;
         }
         (void)hipMemsetAsync(&L.st->excess_hit, 0, sizeof(int32_t) * 4, stream);   // excess_hit, cnt[0..2]
-        hipLaunchKernelGGL(k_bfs_init, grid(n), block, 0, stream, L.e, L.rt, n, L.h, L.hnew, L.fr0, L.st);
+        hipLaunchKernelGGL(k_bfs_init, mesh_launch_grid(n), block, 0, stream, L.e, L.rt, n, L.h, L.hnew, L.fr0, L.st);
         int level = 0;
         for (;;) {   // at most n + 1 non-empty levels
             for (int b = 0; b < GC_BFS_BATCH; ++b, ++level)
@@ -413,16 +398,16 @@ int gc_solve(const char* what, const float* logits, int64_t ld, int64_t n, const
             return DGNN_E_UNSUPPORTED;
         }
         for (int64_t s = 0; s < k; ++s) {
-            hipLaunchKernelGGL(k_push, grid(n), block, 0, stream, L.rowptr, L.nbr, L.h, n, L.e, L.rt, L.res, L.push, L.hnew, L.touched);
-            hipLaunchKernelGGL(k_gather, grid(n), block, 0, stream, L.rowptr, L.rev, n, L.e, L.res, L.push, L.h, L.hnew, L.touched);
+            hipLaunchKernelGGL(k_push, mesh_launch_grid(n), block, 0, stream, L.rowptr, L.nbr, L.h, n, L.e, L.rt, L.res, L.push, L.hnew, L.touched);
+            hipLaunchKernelGGL(k_gather, mesh_launch_grid(n), block, 0, stream, L.rowptr, L.rev, n, L.e, L.res, L.push, L.h, L.hnew, L.touched);
         }
         steps += k;
         if ((rc = dgnn_check_launch(at("push-relabel")))) return rc;
     }
 
     // labels = reached by the last BFS; energy, flow and the identity between them
-    hipLaunchKernelGGL(k_labels_energy, grid(n), block, 0, stream, L.h, L.d0, L.d1, L.rt, n, labels_out, L.st);
-    hipLaunchKernelGGL(k_pair_energy<PER_ROW>, grid(n_rows), block, 0, stream, edges, n_rows, labels_out, row_weights, w, L.st);
+    hipLaunchKernelGGL(k_labels_energy, mesh_launch_grid(n), block, 0, stream, L.h, L.d0, L.d1, L.rt, n, labels_out, L.st);
+    hipLaunchKernelGGL(k_pair_energy<PER_ROW>, mesh_launch_grid(n_rows), block, 0, stream, edges, n_rows, labels_out, row_weights, w, L.st);
     hipLaunchKernelGGL(k_outputs, dim3(1), dim3(64), 0, stream, L.st, energy_out, flow_out, stats_out, (int32_t)steps, relabels);
     if ((rc = dgnn_check_launch(at("energy")))) return rc;
     if ((rc = mm_read(&hs, L.st, sizeof(GcState), stream, what))) return rc;

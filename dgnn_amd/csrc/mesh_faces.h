@@ -10,7 +10,6 @@ int dgnn_radix_sort_u64_i32(uint64_t* const keys[2], int32_t* const vals[2], int
 
 namespace {
 
-constexpr int MT_THREADS = 256;
 // status bits
 constexpr int32_t MT_BAD_ID = 1, MT_NONFINITE = 2, MT_NOT_FACE = 4, MT_NOT_INTERFACE = 8, MT_RANGE = 16, MT_DEGENERATE = 32;
 
@@ -18,8 +17,6 @@ struct MtState {
     int32_t err, exact_used, pad[2];
     unsigned long long undetermined;
 };
-
-dim3 mt_grid(int64_t items) { return dim3(dgnn_grid_cap(dgnn_cdiv(items > 0 ? items : 1, MT_THREADS))); }
 
 __global__ void k_check_faces(const int32_t* __restrict__ faces, int64_t n, int64_t nv, MtState* st) {
     for (int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; f < n; f += (int64_t)gridDim.x * blockDim.x) {
@@ -76,11 +73,7 @@ __global__ void k_link_union(const uint64_t* __restrict__ keys, const int32_t* _
 
 int mt_read_status(MtState* hs, const MtState* st, hipStream_t stream, const char* what) {
     int rc = dgnn_check_launch(what);
-    if (rc) return rc;
-    if (hipMemcpyAsync(hs, st, sizeof(MtState), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
-        dgnn_set_error("%s: %s", what, hipGetErrorString(hipGetLastError()));
-        return DGNN_E_LAUNCH;
-    }
+    if (rc || (rc = mm_read(hs, st, sizeof(MtState), stream, what))) return rc;
     if (!hs->err) return DGNN_OK;
     const int32_t e = hs->err;
     dgnn_set_error("%s: %s%s%s%s%s%s", what, e & MT_BAD_ID ? "an id out of range; " : "", e & MT_NONFINITE ? "non-finite coordinates; " : "",

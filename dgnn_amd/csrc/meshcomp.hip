@@ -128,17 +128,17 @@ __global__ void k_comp_sums(const int32_t* __restrict__ seg_begin, const int32_t
 
 // ---- keep --------------------------------------------------------------------------------------------------------------------
 // one block: the component with the most faces, ties to the smaller id -> *best (-1 without components)
-__global__ void __launch_bounds__(MT_THREADS) k_largest(const int64_t* __restrict__ count, int64_t k, int32_t* __restrict__ best) {
-    __shared__ long long s_cnt[MT_THREADS];
-    __shared__ int32_t s_id[MT_THREADS];
+__global__ void __launch_bounds__(MESH_THREADS) k_largest(const int64_t* __restrict__ count, int64_t k, int32_t* __restrict__ best) {
+    __shared__ long long s_cnt[MESH_THREADS];
+    __shared__ int32_t s_id[MESH_THREADS];
     long long bc = -1;
     int32_t bi = -1;
-    for (int64_t c = threadIdx.x; c < k; c += MT_THREADS)   // ascending ids per thread: `>` keeps the smaller id on a tie
+    for (int64_t c = threadIdx.x; c < k; c += MESH_THREADS)   // ascending ids per thread: `>` keeps the smaller id on a tie
         if (count[c] > bc) { bc = count[c]; bi = (int32_t)c; }
     s_cnt[threadIdx.x] = bc;
     s_id[threadIdx.x] = bi;
     __syncthreads();
-    for (int o = MT_THREADS / 2; o > 0; o >>= 1) {
+    for (int o = MESH_THREADS / 2; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) {
             const long long oc = s_cnt[threadIdx.x + o];
             const int32_t oi = s_id[threadIdx.x + o];
@@ -163,8 +163,7 @@ __global__ void k_keep(const int32_t* __restrict__ comp, int64_t n, const int64_
         keep[f] = kp;
         kept += kp;
     }
-    for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);   // every lane is here: the loop has ended for all of them
-    if (lane_id() == 0 && kept) atomicAdd(n_kept, kept);
+    wave_add_atomic(kept, n_kept);   // every lane is here: the loop has ended for all of them
 }
 
 // ---- scratch layouts ---------------------------------------------------------------------------------------------------------
@@ -225,23 +224,23 @@ extern "C" int dgnn_mesh_components(const int32_t* faces, int64_t n_faces, int64
     DGNN_REQUIRE(n_faces >= 0 && n_vertices >= 0 && scratch && n_components_out && (n_faces == 0 || (faces && comp_out)), DGNN_E_INVALID,
                  "mesh_components: bad args");
     const CompLayout L = comp_layout(scratch, n_faces);
-    const dim3 block(MT_THREADS);
+    const dim3 block(MESH_THREADS);
     (void)hipMemsetAsync(L.st, 0, sizeof(MtState), stream);
     (void)hipMemsetAsync(n_components_out, 0, sizeof(int32_t), stream);
-    if (n_faces > 0) hipLaunchKernelGGL(k_check_faces, mt_grid(n_faces), block, 0, stream, faces, n_faces, n_vertices, L.st);
+    if (n_faces > 0) hipLaunchKernelGGL(k_check_faces, mesh_launch_grid(n_faces), block, 0, stream, faces, n_faces, n_vertices, L.st);
     MtState hs{};
     int rc = mt_read_status(&hs, L.st, stream, "mesh_components");
     if (rc || n_faces == 0) return rc;
     const int vb = key_bits(n_vertices);
     const int64_t n3 = 3 * n_faces;
     int cur = 0;
-    hipLaunchKernelGGL(k_edge_keys, mt_grid(n3), block, 0, stream, faces, n3, vb, 1, L.S.keys[0], L.S.vals[0]);
-    hipLaunchKernelGGL(k_iota, mt_grid(n_faces), block, 0, stream, L.parent, n_faces);
+    hipLaunchKernelGGL(k_edge_keys, mesh_launch_grid(n3), block, 0, stream, faces, n3, vb, 1, L.S.keys[0], L.S.vals[0]);
+    hipLaunchKernelGGL(k_iota, mesh_launch_grid(n_faces), block, 0, stream, L.parent, n_faces);
     if ((rc = dgnn_radix_sort_u64_i32(L.S.keys, L.S.vals, n3, 2 * vb, L.S.hist, L.S.scanned, L.S.sums, stream, &cur))) return rc;
-    hipLaunchKernelGGL(k_link_union, mt_grid(n3), block, 0, stream, L.S.keys[cur], L.S.vals[cur], n3, L.parent);
-    hipLaunchKernelGGL(k_face_roots, mt_grid(n_faces), block, 0, stream, L.parent, n_faces, L.root, L.is_root);
+    hipLaunchKernelGGL(k_link_union, mesh_launch_grid(n3), block, 0, stream, L.S.keys[cur], L.S.vals[cur], n3, L.parent);
+    hipLaunchKernelGGL(k_face_roots, mesh_launch_grid(n_faces), block, 0, stream, L.parent, n_faces, L.root, L.is_root);
     if ((rc = dgnn_exclusive_scan_i32(L.is_root, n_faces, L.rank, L.scan_sums, stream))) return rc;
-    hipLaunchKernelGGL(k_number, mt_grid(n_faces), block, 0, stream, L.root, L.rank, n_faces, comp_out);
+    hipLaunchKernelGGL(k_number, mesh_launch_grid(n_faces), block, 0, stream, L.root, L.rank, n_faces, comp_out);
     (void)hipMemcpyAsync(n_components_out, L.rank + n_faces, sizeof(int32_t), hipMemcpyDeviceToDevice, stream);
     return dgnn_check_launch("mesh_components");
 }
@@ -266,21 +265,21 @@ extern "C" int dgnn_mesh_component_measures(const double* vertices, int64_t n_ve
                  (long long)n_faces);
     if (k == 0) return DGNN_OK;
     const MeasLayout L = meas_layout(scratch, n_faces, k);
-    const dim3 block(MT_THREADS);
+    const dim3 block(MESH_THREADS);
     (void)hipMemsetAsync(L.st, 0, sizeof(MtState), stream);
-    hipLaunchKernelGGL(k_check_measures, mt_grid(n_faces), block, 0, stream, faces, comp, n_faces, n_vertices, k, L.st);
+    hipLaunchKernelGGL(k_check_measures, mesh_launch_grid(n_faces), block, 0, stream, faces, comp, n_faces, n_vertices, k, L.st);
     MtState hs{};
     int rc = mt_read_status(&hs, L.st, stream, "mesh_component_measures");
     if (rc) return rc;
     int cur = 0;
-    hipLaunchKernelGGL(k_comp_keys, mt_grid(n_faces), block, 0, stream, comp, n_faces, L.S.keys[0], L.S.vals[0]);
+    hipLaunchKernelGGL(k_comp_keys, mesh_launch_grid(n_faces), block, 0, stream, comp, n_faces, L.S.keys[0], L.S.vals[0]);
     if ((rc = dgnn_radix_sort_u64_i32(L.S.keys, L.S.vals, n_faces, key_bits(k), L.S.hist, L.S.scanned, L.S.sums, stream, &cur))) return rc;
     (void)hipMemsetAsync(L.seg_begin, 0, sizeof(int32_t) * k, stream);   // a component id without faces: an empty segment
     (void)hipMemsetAsync(L.seg_end, 0, sizeof(int32_t) * k, stream);
-    hipLaunchKernelGGL(k_terms, mt_grid(n_faces), block, 0, stream, vertices, faces, L.S.keys[cur], L.S.vals[cur], n_faces, L.seg_begin, L.seg_end,
+    hipLaunchKernelGGL(k_terms, mesh_launch_grid(n_faces), block, 0, stream, vertices, faces, L.S.keys[cur], L.S.vals[cur], n_faces, L.seg_begin, L.seg_end,
                        L.t_area, L.t_vol);
-    hipLaunchKernelGGL(k_run_partials, mt_grid(dgnn_cdiv(n_faces, MC_CHUNK)), block, 0, stream, L.S.keys[cur], n_faces, L.t_area, L.t_vol);
-    hipLaunchKernelGGL(k_comp_sums, mt_grid(k), block, 0, stream, L.seg_begin, L.seg_end, k, L.t_area, L.t_vol, n_faces_out, area_out, volume_out);
+    hipLaunchKernelGGL(k_run_partials, mesh_launch_grid(dgnn_cdiv(n_faces, MC_CHUNK)), block, 0, stream, L.S.keys[cur], n_faces, L.t_area, L.t_vol);
+    hipLaunchKernelGGL(k_comp_sums, mesh_launch_grid(k), block, 0, stream, L.seg_begin, L.seg_end, k, L.t_area, L.t_vol, n_faces_out, area_out, volume_out);
     return dgnn_check_launch("mesh_component_measures");
 }
 
@@ -300,8 +299,8 @@ extern "C" int dgnn_mesh_component_keep(const int32_t* comp, int64_t n_faces, co
     (void)hipMemsetAsync(st, 0, sizeof(MtState), stream);
     (void)hipMemsetAsync(n_kept_out, 0, sizeof(int64_t), stream);
     if (n_faces > 0) {
-        if (rule == MC_RULE_LARGEST) hipLaunchKernelGGL(k_largest, dim3(1), dim3(MT_THREADS), 0, stream, component_faces, n_components, best);
-        hipLaunchKernelGGL(k_keep, mt_grid(n_faces), dim3(MT_THREADS), 0, stream, comp, n_faces, component_faces, n_components, rule, min_faces, best,
+        if (rule == MC_RULE_LARGEST) hipLaunchKernelGGL(k_largest, dim3(1), dim3(MESH_THREADS), 0, stream, component_faces, n_components, best);
+        hipLaunchKernelGGL(k_keep, mesh_launch_grid(n_faces), dim3(MESH_THREADS), 0, stream, comp, n_faces, component_faces, n_components, rule, min_faces, best,
                            keep_out, (unsigned long long*)n_kept_out, st);
     }
     MtState hs{};

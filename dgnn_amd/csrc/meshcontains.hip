@@ -7,8 +7,7 @@
 //              xy bounding box touches (cells clamped to [0, R - 1] before the shift), a point reads the list of its own cell.  A point
 //              that passes the strict barycentric test of a triangle lies inside that triangle's box, so any shift offers a superset of
 //              the triangles that count and the answer is the all-pairs answer; shift = the smallest with at most max_entries entries.
-//              Built by count / scan / fill with ONE WORK ITEM PER (triangle, cell) ENTRY, so a triangle over the whole grid costs what
-//              its entries cost, spread over the machine.
+//              Built by the entry-grid builder of mesh_grid.h: one work item per (triangle, cell) entry.
 //   query      one lane per point (DESIGN §21 says why), every loop bounded by a list length; per candidate the reference's 2D test and
 //              depth, operand for operand; the two parities are integer counts, so the order inside a cell does not matter.
 //   generators box points, Gaussian jitter (Box-Muller) and face normals, all fp64, randomness from mm_hash (mesh_common.h).
@@ -18,13 +17,10 @@
 #include <math.h>
 
 #include "common.h"
-#include "mesh_common.h"
-
-int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* sums_scratch, hipStream_t stream);  // plan.hip
+#include "mesh_grid.h"
 
 namespace {
 
-constexpr int MC_THREADS = 256;
 constexpr int MC_MAX_R = 4096;     // hash_resolution; (MC_MAX_R - 1) >> (MC_SHIFTS - 1) == 0: the coarsest grid is one cell
 constexpr int MC_SHIFTS = 13;
 constexpr int32_t MC_BAD_ID = 1, MC_NONFINITE = 2, MC_BAD_TET = 4;
@@ -41,29 +37,10 @@ struct Frame {          // by value to the kernels
     int32_t R, shift, G;   // G cells per axis at `shift`
 };
 
-dim3 mc_grid(int64_t items) { return dim3(dgnn_grid_cap(dgnn_cdiv(items > 0 ? items : 1, MC_THREADS))); }
-
-// ---- validation and bounding box ----------------------------------------------------------------------------------------------
-__global__ void k_mc_check_faces(const int32_t* __restrict__ faces, int64_t n3, int64_t nv, McState* st) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x)
-        if (faces[i] < 0 || faces[i] >= nv) atomicOr(&st->err, MC_BAD_ID);
-}
-
-// faces are validated: min / max over the vertices they reference (integer keys: order-free)
-__global__ void k_mc_bbox(const double* __restrict__ v, const int32_t* __restrict__ faces, int64_t n3, McState* st) {
-    unsigned long long lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0, 0, 0};
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t id = faces[i];
-        for (int a = 0; a < 3; ++a) {
-            const double x = v[3 * id + a];
-            if (!isfinite(x)) { atomicOr(&st->err, MC_NONFINITE); continue; }
-            const unsigned long long k = f64_key(x);
-            lo[a] = k < lo[a] ? k : lo[a];
-            hi[a] = k > hi[a] ? k : hi[a];
-        }
-    }
-    for (int a = 0; a < 3; ++a) wave_minmax_atomic(lo[a], hi[a], &st->lo[a], &st->hi[a]);
-}
+// the bounding box (k_bbox_referenced) leaves out a coordinate that is not finite
+struct McRefuse {
+    __device__ int32_t operator()(double x) const { return isfinite(x) ? 0 : MC_NONFINITE; }
+};
 
 // rv = scale * v + translate (a multiply, then an add: the library is built without contraction)
 __global__ void k_mc_rescale(const double* __restrict__ v, int64_t nv, Frame f, double* __restrict__ rv) {
@@ -78,7 +55,7 @@ __global__ void k_mc_rescale(const double* __restrict__ v, int64_t nv, Frame f, 
 __device__ __forceinline__ int32_t mc_cell(double x, int32_t R) { return !(x > 0) ? 0 : (x >= (double)(R - 1) ? R - 1 : (int32_t)x); }
 
 // tbox[t] = (x0, y0, x1, y1): the cells at full resolution of the triangle's xy bounding box; entries at every shift -> totals
-__global__ void __launch_bounds__(MC_THREADS) k_mc_tri_box(const double* __restrict__ rv, const int32_t* __restrict__ faces, int64_t nf, int32_t R,
+__global__ void __launch_bounds__(MESH_THREADS) k_mc_tri_box(const double* __restrict__ rv, const int32_t* __restrict__ faces, int64_t nf, int32_t R,
                                                            int4* __restrict__ tbox, McState* st) {
     long long tot[MC_SHIFTS];
 #pragma unroll
@@ -93,47 +70,26 @@ __global__ void __launch_bounds__(MC_THREADS) k_mc_tri_box(const double* __restr
         for (int s = 0; s < MC_SHIFTS; ++s) tot[s] += (long long)((x1 >> s) - (x0 >> s) + 1) * ((y1 >> s) - (y0 >> s) + 1);
     }
 #pragma unroll
-    for (int s = 0; s < MC_SHIFTS; ++s) {
-        long long x = tot[s];
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-        if (lane_id() == 0 && x) atomicAdd(&st->totals[s], (unsigned long long)x);   // integer sums: order-free
-    }
+    for (int s = 0; s < MC_SHIFTS; ++s) wave_add_atomic(tot[s], &st->totals[s]);
 }
 
-// ---- the grid: count / scan / fill, one work item per (triangle, cell) entry ------------------------------------------------------
-__global__ void k_mc_tri_count(const int4* __restrict__ tbox, int64_t nf, int32_t shift, int32_t* __restrict__ tcnt) {
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nf; t += (int64_t)gridDim.x * blockDim.x) {
+// ---- the grid (mesh_grid.h): the cells of a triangle's box at `shift`, row-major ------------------------------------------------------
+struct McCells {
+    const int4* tbox;
+    int32_t shift, G;
+    __device__ int32_t count(int64_t t) const {
         const int4 b = tbox[t];
-        tcnt[t] = ((b.z >> shift) - (b.x >> shift) + 1) * ((b.w >> shift) - (b.y >> shift) + 1);
+        return ((b.z >> shift) - (b.x >> shift) + 1) * ((b.w >> shift) - (b.y >> shift) + 1);
     }
-}
+    __device__ int32_t cell(int64_t t, int32_t k) const {
+        const int4 b = tbox[t];
+        const int32_t y0 = b.y >> shift, ny = (b.w >> shift) - y0 + 1;
+        return G * ((b.x >> shift) + k / ny) + y0 + k % ny;
+    }
+};
 
-// entry e belongs to the triangle t with toff[t] <= e < toff[t + 1] (toff ascending, toff[nf] = n_entries: the search ends inside
-// [0, nf)); its cell is the (e - toff[t])-th of the triangle's box, row-major
-__device__ __forceinline__ int32_t mc_entry(const int32_t* __restrict__ toff, const int4* __restrict__ tbox, int64_t nf, int32_t shift, int32_t G,
-                                            int32_t e, int32_t* cell) {
-    int64_t lo = 0, hi = nf - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (toff[mid] <= e) lo = mid;
-        else hi = mid - 1;
-    }
-    const int4 b = tbox[lo];
-    const int32_t y0 = b.y >> shift, ny = (b.w >> shift) - y0 + 1, k = e - toff[lo];
-    *cell = G * ((b.x >> shift) + k / ny) + y0 + k % ny;
-    return (int32_t)lo;
-}
-
-// fill == 0: ccnt[cell] += 1; fill != 0: entries[cursor[cell]++] = t (the order inside a cell is whatever the atomics give: the query
-// only counts)
-__global__ void k_mc_entries(const int32_t* __restrict__ toff, const int4* __restrict__ tbox, int64_t nf, int32_t shift, int32_t G, int64_t n_entries,
-                             int fill, int32_t* __restrict__ ccnt, int32_t* __restrict__ entries) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n_entries; e += (int64_t)gridDim.x * blockDim.x) {
-        int32_t cell;
-        const int32_t t = mc_entry(toff, tbox, nf, shift, G, (int32_t)e, &cell);
-        const int32_t slot = atomicAdd(ccnt + cell, 1);
-        if (fill) entries[slot] = t;
-    }
+__global__ void k_mc_tri_count(McCells cells, int64_t nf, int32_t* __restrict__ tcnt) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nf; t += (int64_t)gridDim.x * blockDim.x) tcnt[t] = cells.count(t);
 }
 
 // ---- the query -----------------------------------------------------------------------------------------------------------------
@@ -184,13 +140,7 @@ __device__ __forceinline__ uint32_t mc_point_parities(const double* __restrict__
     return (above & 1) | ((below & 1) << 1);
 }
 
-// adds the wave's sum of `dis` to st->n_disagree: an integer sum, so order-free
-__device__ __forceinline__ void mc_add_disagree(long long dis, McState* st) {
-    for (int o = 32; o > 0; o >>= 1) dis += __shfl_xor(dis, o);
-    if (lane_id() == 0 && dis) atomicAdd(&st->n_disagree, (unsigned long long)dis);
-}
-
-__global__ void __launch_bounds__(MC_THREADS) k_mc_query(const double* __restrict__ rv, const int32_t* __restrict__ faces,
+__global__ void __launch_bounds__(MESH_THREADS) k_mc_query(const double* __restrict__ rv, const int32_t* __restrict__ faces,
                                                          const int32_t* __restrict__ rowptr, const int32_t* __restrict__ entries, Frame f,
                                                          const double* __restrict__ pts, int64_t np, uint8_t* __restrict__ out, McState* st) {
     long long dis = 0;
@@ -200,7 +150,7 @@ __global__ void __launch_bounds__(MC_THREADS) k_mc_query(const double* __restric
         out[i] = (uint8_t)(c1 & c2);
         dis += c1 != c2;
     }
-    mc_add_disagree(dis, st);
+    wave_add_atomic(dis, &st->n_disagree);
 }
 
 __global__ void k_mc_disagree_out(const McState* st, int64_t* out) {
@@ -241,11 +191,6 @@ __global__ void k_face_normals(const double* __restrict__ v, int64_t nv, const i
 }
 
 // ---- cell labels: the share of each tet inside the mesh, by sampling -----------------------------------------------------
-__global__ void k_cl_check_tets(const int32_t* __restrict__ tets, int64_t n4, int64_t nv, McState* st) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
-        if (tets[i] < 0 || tets[i] >= nv) atomicOr(&st->err, MC_BAD_TET);
-}
-
 // sample j of tet t (ids validated): three draws from the counters c, c + 1, c + 2 with c = 3 ((tet_offset + t) k + j) + 1 (mod 2^64),
 // folded from the unit cube onto the unit tet, then x = ((s e1 + t e2) + u e3) + p0 per coordinate; one rounding per operation
 __device__ __forceinline__ void cl_sample(const double (&p)[4][3], uint64_t seed, uint64_t c, double* x) {
@@ -277,7 +222,7 @@ __device__ __forceinline__ void cl_load_tet(const double* __restrict__ v, const 
 }
 
 // the sampler alone: one lane per sample, points_out row t k + j
-__global__ void __launch_bounds__(MC_THREADS) k_tet_sample(const double* __restrict__ v, const int32_t* __restrict__ tets, int64_t nt, int64_t k,
+__global__ void __launch_bounds__(MESH_THREADS) k_tet_sample(const double* __restrict__ v, const int32_t* __restrict__ tets, int64_t nt, int64_t k,
                                                            uint64_t seed, uint64_t tet_offset, double* __restrict__ out) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nt * k; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t t = i / k, j = i - t * k;
@@ -294,16 +239,16 @@ __global__ void __launch_bounds__(MC_THREADS) k_tet_sample(const double* __restr
 // and stored by the tet's first lane.  Integer counts without atomics: the same bits on every run.  Every loop has a wave-uniform trip
 // count, so all 64 lanes reach each ballot.
 template <int LG>
-__global__ void __launch_bounds__(MC_THREADS) k_cl_count(const double* __restrict__ rv, const int32_t* __restrict__ faces,
+__global__ void __launch_bounds__(MESH_THREADS) k_cl_count(const double* __restrict__ rv, const int32_t* __restrict__ faces,
                                                          const int32_t* __restrict__ rowptr, const int32_t* __restrict__ entries, Frame f,
                                                          const double* __restrict__ v, const int32_t* __restrict__ tets, int64_t nt, int64_t k,
                                                          uint64_t seed, uint64_t tet_offset, int32_t* __restrict__ count, McState* st) {
     constexpr int G = 1 << LG, PER = 64 >> LG;
     constexpr uint64_t MASK = LG == 6 ? ~0ull : (1ull << (G & 63)) - 1;
     const int lane = lane_id(), sub = lane >> LG, j0 = lane & (G - 1);
-    const int64_t n_groups = (nt + PER - 1) / PER, n_waves = (int64_t)gridDim.x * (MC_THREADS / 64);
+    const int64_t n_groups = (nt + PER - 1) / PER, n_waves = (int64_t)gridDim.x * (MESH_THREADS / 64);
     long long dis = 0;
-    for (int64_t grp = (int64_t)blockIdx.x * (MC_THREADS / 64) + wave_id_uniform(); grp < n_groups; grp += n_waves) {
+    for (int64_t grp = (int64_t)blockIdx.x * (MESH_THREADS / 64) + wave_id_uniform(); grp < n_groups; grp += n_waves) {
         const int64_t t = grp * PER + sub;
         const bool live = t < nt;
         double p[4][3];
@@ -324,23 +269,18 @@ __global__ void __launch_bounds__(MC_THREADS) k_cl_count(const double* __restric
         }
         if (live && j0 == 0) count[t] = cnt;
     }
-    mc_add_disagree(dis, st);
+    wave_add_atomic(dis, &st->n_disagree);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-struct McLayout { McState* st; double* rv; int4* tbox; int32_t *tcnt, *toff, *ccnt, *rowptr, *sums; int64_t bytes; };
+struct McLayout { McState* st; double* rv; int4* tbox; GridBufs g; int64_t bytes; };
 McLayout mc_layout(void* base, int64_t nv, int64_t nf, int64_t R) {
     Take t{(char*)base, 256};
     McLayout L{};
     L.st = (McState*)base;
-    const int64_t cells = R * R, m = nf > cells ? nf : cells;
     L.rv = t.take<double>(3 * nv);
     L.tbox = t.take<int4>(nf);
-    L.tcnt = t.take<int32_t>(nf + 1);
-    L.toff = t.take<int32_t>(nf + 1);
-    L.ccnt = t.take<int32_t>(cells + 1);
-    L.rowptr = t.take<int32_t>(cells + 1);
-    L.sums = t.take<int32_t>(dgnn_cdiv(m + 1, 2048) + 2);
+    L.g = take_grid(t, nf, R * R);
     L.bytes = t.off;
     return L;
 }
@@ -363,28 +303,30 @@ int mc_plan(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf
     DGNN_REQUIRE(R <= MC_MAX_R, DGNN_E_UNSUPPORTED, "%s: hash_resolution %d above %d", what, R, MC_MAX_R);
     DGNN_REQUIRE(max_entries >= 1, DGNN_E_INVALID, "%s: max_entries < 1", what);
     DGNN_REQUIRE(nf < INT32_MAX / 4 && nv < INT32_MAX, DGNN_E_UNSUPPORTED, "%s: sizes exceed the int32 indexing", what);
-    const dim3 block(MC_THREADS);
+    const dim3 block(MESH_THREADS);
     McState hs{};
     hs.lo[0] = hs.lo[1] = hs.lo[2] = ~0ull;
     (void)hipMemcpyAsync(L.st, &hs, sizeof(McState), hipMemcpyHostToDevice, stream);
-    hipLaunchKernelGGL(k_mc_check_faces, mc_grid(3 * nf), block, 0, stream, faces, 3 * nf, nv, L.st);
+    hipLaunchKernelGGL(k_check_ids, mesh_launch_grid(3 * nf), block, 0, stream, faces, 3 * nf, nv, &L.st->err, MC_BAD_ID);
     int rc = dgnn_check_launch(what);
     if (rc || (rc = mm_read(&hs, L.st, sizeof(McState), stream, what)) || (rc = mc_status(hs, what))) return rc;   // ids are read below: checked first
-    hipLaunchKernelGGL(k_mc_bbox, mc_grid(3 * nf), block, 0, stream, vertices, faces, 3 * nf, L.st);
+    hipLaunchKernelGGL(k_bbox_referenced<McRefuse>, mesh_launch_grid(3 * nf), block, 0, stream, vertices, faces, 3 * nf, McRefuse{}, &L.st->err, L.st->lo,
+                       L.st->hi);
     if ((rc = dgnn_check_launch(what)) || (rc = mm_read(&hs, L.st, sizeof(McState), stream, what)) || (rc = mc_status(hs, what))) return rc;
     Frame f{};
     f.R = R;
+    double lo[3], hi[3];
+    bbox_unkey(hs.lo, hs.hi, lo, hi);
     for (int a = 0; a < 3; ++a) {
-        const double lo = f64_unkey(hs.lo[a]), hi = f64_unkey(hs.hi[a]);
-        const double ext = hi - lo;
+        const double ext = hi[a] - lo[a];
         DGNN_REQUIRE(ext > 0, DGNN_E_INVALID, "%s: the mesh has no extent on axis %d", what, a);
         f.scale[a] = (double)(R - 1) / ext;
-        const double m = f.scale[a] * lo;
+        const double m = f.scale[a] * lo[a];
         f.translate[a] = 0.5 - m;
         DGNN_REQUIRE(isfinite(f.scale[a]) && isfinite(f.translate[a]), DGNN_E_INVALID, "%s: the extent %g of axis %d does not rescale", what, ext, a);
     }
-    hipLaunchKernelGGL(k_mc_rescale, mc_grid(3 * nv), block, 0, stream, vertices, nv, f, L.rv);
-    hipLaunchKernelGGL(k_mc_tri_box, mc_grid(nf), block, 0, stream, L.rv, faces, nf, R, L.tbox, L.st);
+    hipLaunchKernelGGL(k_mc_rescale, mesh_launch_grid(3 * nv), block, 0, stream, vertices, nv, f, L.rv);
+    hipLaunchKernelGGL(k_mc_tri_box, mesh_launch_grid(nf), block, 0, stream, L.rv, faces, nf, R, L.tbox, L.st);
     if ((rc = dgnn_check_launch(what)) || (rc = mm_read(&hs, L.st, sizeof(McState), stream, what))) return rc;
     int s = 0;
     while (s < MC_SHIFTS && hs.totals[s] > (unsigned long long)max_entries) ++s;
@@ -397,25 +339,18 @@ int mc_plan(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf
     return DGNN_OK;
 }
 
-// the candidate grid of the planned frame: count / scan / fill into L.rowptr and `entries` (ne of them)
+// the candidate grid of the planned frame into L.g.rowptr and `entries` (ne of them): the counts at the chosen shift (only the plan's
+// totals over all shifts told which), then the shared builder
 int mc_build_grid(const McLayout& L, const Frame& f, int64_t n_faces, int64_t ne, int32_t* entries, hipStream_t stream) {
-    const dim3 block(MC_THREADS);
-    const int64_t cells = (int64_t)f.G * f.G;
-    int rc;
-    hipLaunchKernelGGL(k_mc_tri_count, mc_grid(n_faces), block, 0, stream, L.tbox, n_faces, f.shift, L.tcnt);
-    if ((rc = dgnn_exclusive_scan_i32(L.tcnt, n_faces, L.toff, L.sums, stream))) return rc;
-    (void)hipMemsetAsync(L.ccnt, 0, sizeof(int32_t) * (cells + 1), stream);
-    hipLaunchKernelGGL(k_mc_entries, mc_grid(ne), block, 0, stream, L.toff, L.tbox, n_faces, f.shift, f.G, ne, 0, L.ccnt, (int32_t*)nullptr);
-    if ((rc = dgnn_exclusive_scan_i32(L.ccnt, cells, L.rowptr, L.sums, stream))) return rc;
-    (void)hipMemcpyAsync(L.ccnt, L.rowptr, sizeof(int32_t) * (cells + 1), hipMemcpyDeviceToDevice, stream);   // the fill's cursors
-    hipLaunchKernelGGL(k_mc_entries, mc_grid(ne), block, 0, stream, L.toff, L.tbox, n_faces, f.shift, f.G, ne, 1, L.ccnt, entries);
-    return DGNN_OK;
+    const McCells cells{L.tbox, f.shift, f.G};
+    hipLaunchKernelGGL(k_mc_tri_count, mesh_launch_grid(n_faces), dim3(MESH_THREADS), 0, stream, cells, n_faces, L.g.tcnt);
+    return build_entry_grid(L.g, cells, n_faces, (int64_t)f.G * f.G, ne, entries, stream);
 }
 
 // ids of the tets in [0, nv), checked on the device before any kernel reads through them.  `st` is zero in err on entry.  Synchronises once.
 int cl_check_tets(const int32_t* tets, int64_t nt, int64_t nv, McState* st, hipStream_t stream, const char* what) {
     McState hs{};
-    hipLaunchKernelGGL(k_cl_check_tets, mc_grid(4 * nt), dim3(MC_THREADS), 0, stream, tets, 4 * nt, nv, st);
+    hipLaunchKernelGGL(k_check_ids, mesh_launch_grid(4 * nt), dim3(MESH_THREADS), 0, stream, tets, 4 * nt, nv, &st->err, MC_BAD_TET);
     int rc = dgnn_check_launch(what);
     if (rc || (rc = mm_read(&hs, st, sizeof(McState), stream, what))) return rc;
     return mc_status(hs, what);
@@ -425,7 +360,7 @@ template <int LG>
 void cl_launch(const McLayout& L, const Frame& f, const int32_t* faces, const int32_t* entries, const double* v, const int32_t* tets, int64_t nt, int64_t k,
                uint64_t seed, uint64_t tet_offset, int32_t* count, hipStream_t stream) {
     const int64_t waves = dgnn_cdiv(nt, 64 >> LG);
-    hipLaunchKernelGGL(k_cl_count<LG>, dim3(dgnn_grid_cap(dgnn_cdiv(waves, MC_THREADS / 64))), dim3(MC_THREADS), 0, stream, L.rv, faces, L.rowptr, entries, f, v,
+    hipLaunchKernelGGL(k_cl_count<LG>, dim3(dgnn_grid_cap(dgnn_cdiv(waves, MESH_THREADS / 64))), dim3(MESH_THREADS), 0, stream, L.rv, faces, L.g.rowptr, entries, f, v,
                        tets, nt, k, seed, tet_offset, count, L.st);
 }
 
@@ -466,21 +401,21 @@ extern "C" int dgnn_mesh_contains(const double* vertices, int64_t n_vertices, co
     if (n_disagree_out) (void)hipMemsetAsync(n_disagree_out, 0, sizeof(int64_t), stream);
     if (n_points == 0) return dgnn_check_launch("mesh_contains");
     if ((rc = mc_build_grid(L, f, n_faces, ne, entries, stream))) return rc;
-    hipLaunchKernelGGL(k_mc_query, mc_grid(n_points), dim3(MC_THREADS), 0, stream, L.rv, faces, L.rowptr, entries, f, points, n_points, contains_out, L.st);
+    hipLaunchKernelGGL(k_mc_query, mesh_launch_grid(n_points), dim3(MESH_THREADS), 0, stream, L.rv, faces, L.g.rowptr, entries, f, points, n_points, contains_out, L.st);
     if (n_disagree_out) hipLaunchKernelGGL(k_mc_disagree_out, dim3(1), dim3(64), 0, stream, L.st, n_disagree_out);
     return dgnn_check_launch("mesh_contains");
 }
 
 extern "C" int dgnn_box_points(int64_t n_points, double boxsize, uint64_t seed, double* points_out, void* stream_) {
     DGNN_REQUIRE(n_points >= 0 && (n_points == 0 || points_out), DGNN_E_INVALID, "box_points: bad args");
-    if (n_points > 0) hipLaunchKernelGGL(k_box_points, mc_grid(3 * n_points), dim3(MC_THREADS), 0, (hipStream_t)stream_, 3 * n_points, boxsize, seed, points_out);
+    if (n_points > 0) hipLaunchKernelGGL(k_box_points, mesh_launch_grid(3 * n_points), dim3(MESH_THREADS), 0, (hipStream_t)stream_, 3 * n_points, boxsize, seed, points_out);
     return dgnn_check_launch("box_points");
 }
 
 extern "C" int dgnn_jitter_points(const double* points, int64_t n_points, double sigma, uint64_t seed, double* points_out, void* stream_) {
     DGNN_REQUIRE(n_points >= 0 && (n_points == 0 || (points && points_out)), DGNN_E_INVALID, "jitter_points: bad args");
     if (n_points > 0)
-        hipLaunchKernelGGL(k_jitter_points, mc_grid(3 * n_points), dim3(MC_THREADS), 0, (hipStream_t)stream_, points, 3 * n_points, sigma, seed, points_out);
+        hipLaunchKernelGGL(k_jitter_points, mesh_launch_grid(3 * n_points), dim3(MESH_THREADS), 0, (hipStream_t)stream_, points, 3 * n_points, sigma, seed, points_out);
     return dgnn_check_launch("jitter_points");
 }
 
@@ -492,7 +427,7 @@ extern "C" int dgnn_face_normals(const double* vertices, int64_t n_vertices, con
     McState* st = (McState*)scratch;
     McState hs{};
     (void)hipMemsetAsync(st, 0, sizeof(McState), stream);
-    if (n_faces > 0) hipLaunchKernelGGL(k_face_normals, mc_grid(n_faces), dim3(MC_THREADS), 0, stream, vertices, n_vertices, faces, n_faces, normals_out, st);
+    if (n_faces > 0) hipLaunchKernelGGL(k_face_normals, mesh_launch_grid(n_faces), dim3(MESH_THREADS), 0, stream, vertices, n_vertices, faces, n_faces, normals_out, st);
     int rc = dgnn_check_launch("face_normals");
     if (rc || (rc = mm_read(&hs, st, sizeof(McState), stream, "face_normals"))) return rc;
     return mc_status(hs, "face_normals");
@@ -547,7 +482,7 @@ extern "C" int dgnn_tet_sample_points(const double* vertices, int64_t n_vertices
     (void)hipMemsetAsync(st, 0, sizeof(McState), stream);
     int rc = cl_check_tets(tetrahedra, n_tets, n_vertices, st, stream, "tet_sample_points");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_tet_sample, mc_grid(n_tets * n_samples), dim3(MC_THREADS), 0, stream, vertices, tetrahedra, n_tets, n_samples, seed, tet_offset,
+    hipLaunchKernelGGL(k_tet_sample, mesh_launch_grid(n_tets * n_samples), dim3(MESH_THREADS), 0, stream, vertices, tetrahedra, n_tets, n_samples, seed, tet_offset,
                        points_out);
     return dgnn_check_launch("tet_sample_points");
 }

@@ -19,13 +19,16 @@
 
 #include "common.h"
 #include "mesh_common.h"
+#include "vec3.h"
 #include "fixed_sum.h"
 
 int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* sums_scratch, hipStream_t stream);  // plan.hip
 
 namespace {
 
-constexpr int MM_THREADS = 256;
+using dgnn_exact::V3;
+using dgnn_exact::load_v3;
+
 constexpr int32_t MM_MAX_STEPS = 1 << 16;            // walk steps per query
 constexpr int32_t MM_NBR_UNSET = (int32_t)0x80808080;
 constexpr int MM_MAX_DIM = 1024;                      // grid bins per axis
@@ -48,19 +51,6 @@ inline float f32_unkey(unsigned int k) {
     float f;
     memcpy(&f, &u, 4);
     return f;
-}
-
-__device__ __forceinline__ void mm_block_add(unsigned long long* dst, long long v) {
-    __shared__ long long part[MM_THREADS / DGNN_WAVE];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (lane_id() == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long s = 0;
-        for (int k = 0; k < MM_THREADS / DGNN_WAVE; ++k) s += part[k];
-        if (s) atomicAdd(dst, (unsigned long long)s);   // integer sums: order-free
-    }
-    __syncthreads();
 }
 
 // ---- uniform grid geometry (host picks it, kernels read it by value) ----------------------------------------------------------
@@ -112,11 +102,8 @@ __device__ __forceinline__ int32_t bin_axis(double t, int32_t d) {
 }
 
 // ---- fp64 orientation --------------------------------------------------------------------------------------------------------
-struct D3 { double x, y, z; };
-__device__ __forceinline__ D3 ld3(const double* v, int32_t i) { return D3{v[3 * (int64_t)i], v[3 * (int64_t)i + 1], v[3 * (int64_t)i + 2]}; }
-
 // det[b - a, c - a, p - a], evaluated left to right (the numpy model, tests/mesh_metrics_model.py, repeats it operation for operation)
-__device__ __forceinline__ double orient(const D3& a, const D3& b, const D3& c, const D3& p) {
+__device__ __forceinline__ double orient(const V3& a, const V3& b, const V3& c, const V3& p) {
     const double ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z;
     const double vx = c.x - a.x, vy = c.y - a.y, vz = c.z - a.z;
     const double wx = p.x - a.x, wy = p.y - a.y, wz = p.z - a.z;
@@ -147,11 +134,6 @@ __global__ void k_check_vertices(const double* __restrict__ v, int64_t nv, MmSta
         }
     }
     for (int a = 0; a < 3; ++a) wave_minmax_atomic(lo[a], hi[a], &st->lo64[a], &st->hi64[a]);
-}
-
-__global__ void k_check_tets(const int32_t* __restrict__ tets, int64_t nc, int64_t nv, MmState* st) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < 4 * nc; i += (int64_t)gridDim.x * blockDim.x)
-        if (tets[i] < 0 || tets[i] >= nv) atomicOr(&st->err, MM_BAD_ID);
 }
 
 // facet f = vertices (x, y, z) between cells nfacets[f] = (a, b), -1 = the infinite cell: nbr[4 c + k] = the other cell, k = the vertex
@@ -198,7 +180,7 @@ __global__ void k_start_min(const double* __restrict__ v, const int32_t* __restr
     for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
         double m[3] = {0, 0, 0};
         for (int k = 0; k < 4; ++k) {
-            const D3 p = ld3(v, tets[4 * c + k]);
+            const V3 p = load_v3(v, tets[4 * c + k]);
             m[0] += p.x; m[1] += p.y; m[2] += p.z;
         }
         int32_t b[3];
@@ -242,7 +224,7 @@ __global__ void k_locate(const double* __restrict__ v, const int32_t* __restrict
                          MmState* st) {
     int32_t my_max = 0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < np; i += (int64_t)gridDim.x * blockDim.x) {
-        const D3 q{(double)pts[3 * i], (double)pts[3 * i + 1], (double)pts[3 * i + 2]};
+        const V3 q{(double)pts[3 * i], (double)pts[3 * i + 1], (double)pts[3 * i + 2]};
         if (!isfinite(q.x) || !isfinite(q.y) || !isfinite(q.z)) {
             atomicOr(&st->err, MM_NONFINITE);
             cell_out[i] = -1;
@@ -265,8 +247,8 @@ __global__ void k_locate(const double* __restrict__ v, const int32_t* __restrict
             for (int k = 0; k < 4; ++k) {
                 int32_t a = id[(k + 1) & 3], b = id[(k + 2) & 3], e = id[(k + 3) & 3];
                 sort3(a, b, e);
-                const D3 pa = ld3(v, a), pb = ld3(v, b), pe = ld3(v, e);
-                const double o = orient(pa, pb, pe, q), s = orient(pa, pb, pe, ld3(v, id[k]));
+                const V3 pa = load_v3(v, a), pb = load_v3(v, b), pe = load_v3(v, e);
+                const double o = orient(pa, pb, pe, q), s = orient(pa, pb, pe, load_v3(v, id[k]));
                 // q on the side of vertex k (or on the face): >= 0; a flat cell (s == 0) holds only points on its plane
                 const bool neg = s > 0 ? o < 0 : (s < 0 ? o > 0 : o != 0);
                 if (neg) { next = k; break; }
@@ -281,7 +263,7 @@ __global__ void k_locate(const double* __restrict__ v, const int32_t* __restrict
     if (lane_id() == 0 && my_max) atomicMax(&st->max_steps, my_max);
 }
 
-__global__ void __launch_bounds__(MM_THREADS) k_iou_counts(const int32_t* __restrict__ cells, int64_t np, const int32_t* __restrict__ labels,
+__global__ void __launch_bounds__(MESH_THREADS) k_iou_counts(const int32_t* __restrict__ cells, int64_t np, const int32_t* __restrict__ labels,
                                                            int64_t nc, const uint8_t* __restrict__ occ_gt, int32_t* __restrict__ occ_out,
                                                            MmState* st) {
     long long inter = 0, uni = 0;
@@ -292,8 +274,8 @@ __global__ void __launch_bounds__(MM_THREADS) k_iou_counts(const int32_t* __rest
         inter += a & b;
         uni += a | b;
     }
-    mm_block_add(&st->counts[0], inter);
-    mm_block_add(&st->counts[1], uni);
+    block_add_atomic(&st->counts[0], inter);
+    block_add_atomic(&st->counts[1], uni);
 }
 
 __global__ void k_counts_out(const MmState* st, int64_t* counts_out) {
@@ -319,7 +301,7 @@ __global__ void k_face_area(const double* __restrict__ v, int64_t nv, const int3
             if (ia < 0 || ia >= nv || ib < 0 || ib >= nv || ic < 0 || ic >= nv) {
                 atomicOr(&st->err, MM_BAD_ID);
             } else {
-                const D3 a = ld3(v, ia), b = ld3(v, ib), c = ld3(v, ic);
+                const V3 a = load_v3(v, ia), b = load_v3(v, ib), c = load_v3(v, ic);
                 const double ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z, wx = c.x - a.x, wy = c.y - a.y, wz = c.z - a.z;
                 const double cx = uy * wz - uz * wy, cy = uz * wx - ux * wz, cz = ux * wy - uy * wx;
                 ar = 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
@@ -346,7 +328,7 @@ __global__ void k_sample(const double* __restrict__ v, const int32_t* __restrict
         }
         if (u + w > 1.0) { u = 1.0 - u; w = 1.0 - w; }
         const int64_t f = face_ids ? face_ids[lo] : lo;
-        const D3 a = ld3(v, facets[3 * f]), b = ld3(v, facets[3 * f + 1]), e = ld3(v, facets[3 * f + 2]);
+        const V3 a = load_v3(v, facets[3 * f]), b = load_v3(v, facets[3 * f + 1]), e = load_v3(v, facets[3 * f + 2]);
         pts[3 * i] = (float)((u * (b.x - a.x) + w * (e.x - a.x)) + a.x);
         pts[3 * i + 1] = (float)((u * (b.y - a.y) + w * (e.y - a.y)) + a.y);
         pts[3 * i + 2] = (float)((u * (b.z - a.z) + w * (e.z - a.z)) + a.z);
@@ -501,8 +483,6 @@ int mm_status(const MmState& hs, const char* what) {
     return hs.err == MM_CAP ? DGNN_E_UNSUPPORTED : DGNN_E_INVALID;
 }
 
-dim3 mm_grid(int64_t items) { return dim3(dgnn_grid_cap(dgnn_cdiv(items > 0 ? items : 1, MM_THREADS))); }
-
 }  // namespace
 
 // ================================================================================================================================
@@ -521,18 +501,18 @@ extern "C" int dgnn_locate_points(const double* vertices, int64_t n_vertices, co
     DGNN_REQUIRE(n_cells < INT32_MAX / 4 && n_vertices < INT32_MAX && n_points < INT32_MAX, DGNN_E_UNSUPPORTED,
                  "locate_points: sizes exceed the int32 indexing");
     const LocLayout L = loc_layout(scratch, n_cells);
-    const dim3 block(MM_THREADS);
+    const dim3 block(MESH_THREADS);
     MmState hs{};
     hs.lo64[0] = hs.lo64[1] = hs.lo64[2] = ~0ull;
     (void)hipMemcpyAsync(L.st, &hs, sizeof(MmState), hipMemcpyHostToDevice, stream);
     (void)hipMemsetAsync(L.nbr, 0x80, sizeof(int32_t) * 4 * (n_cells > 0 ? n_cells : 1), stream);
-    hipLaunchKernelGGL(k_check_vertices, mm_grid(n_vertices), block, 0, stream, vertices, n_vertices, L.st);
-    hipLaunchKernelGGL(k_check_tets, mm_grid(4 * n_cells), block, 0, stream, tets, n_cells, n_vertices, L.st);
+    hipLaunchKernelGGL(k_check_vertices, mesh_launch_grid(n_vertices), block, 0, stream, vertices, n_vertices, L.st);
+    hipLaunchKernelGGL(k_check_ids, mesh_launch_grid(4 * n_cells), block, 0, stream, tets, 4 * n_cells, n_vertices, &L.st->err, MM_BAD_ID);
     int rc = dgnn_check_launch("locate_points (check)");
     if (rc || (rc = mm_read(&hs, L.st, sizeof(MmState), stream, "locate_points"))) return rc;   // tets are read by id below: checked first
     if ((rc = mm_status(hs, "locate_points"))) return rc;
-    hipLaunchKernelGGL(k_nbr_fill, mm_grid(n_facets), block, 0, stream, tets, n_cells, facets, nfacets, n_facets, n_vertices, L.nbr, L.st);
-    hipLaunchKernelGGL(k_nbr_check, mm_grid(4 * n_cells), block, 0, stream, L.nbr, n_cells, L.st);
+    hipLaunchKernelGGL(k_nbr_fill, mesh_launch_grid(n_facets), block, 0, stream, tets, n_cells, facets, nfacets, n_facets, n_vertices, L.nbr, L.st);
+    hipLaunchKernelGGL(k_nbr_check, mesh_launch_grid(4 * n_cells), block, 0, stream, L.nbr, n_cells, L.st);
     if ((rc = dgnn_check_launch("locate_points (neighbours)")) || (rc = mm_read(&hs, L.st, sizeof(MmState), stream, "locate_points"))) return rc;
     if ((rc = mm_status(hs, "locate_points"))) return rc;
     if (n_points == 0) {
@@ -545,15 +525,15 @@ extern "C" int dgnn_locate_points(const double* vertices, int64_t n_vertices, co
         return dgnn_check_launch("locate_points");
     }
     double lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) { lo[a] = f64_unkey(hs.lo64[a]); hi[a] = f64_unkey(hs.hi64[a]); }
+    bbox_unkey(hs.lo64, hs.hi64, lo, hi);
     const Grid g = grid_for(lo, hi, start_bins(n_cells));
     const int64_t nb = (int64_t)g.d[0] * g.d[1] * g.d[2];
-    hipLaunchKernelGGL(k_fill_i32, mm_grid(nb), block, 0, stream, L.start, nb, (int32_t)INT32_MAX);
-    hipLaunchKernelGGL(k_start_min, mm_grid(n_cells), block, 0, stream, vertices, tets, n_cells, g, L.start);
-    hipLaunchKernelGGL(k_start_axis, mm_grid(nb / g.d[0]), block, 0, stream, L.start, g, 0, L.start2);
-    hipLaunchKernelGGL(k_start_axis, mm_grid(nb / g.d[1]), block, 0, stream, L.start2, g, 1, L.start);
-    hipLaunchKernelGGL(k_start_axis, mm_grid(nb / g.d[2]), block, 0, stream, L.start, g, 2, L.start2);
-    hipLaunchKernelGGL(k_locate, mm_grid(n_points), block, 0, stream, vertices, tets, L.nbr, L.start2, g, points, n_points, cell_out, L.st);
+    hipLaunchKernelGGL(k_fill_i32, mesh_launch_grid(nb), block, 0, stream, L.start, nb, (int32_t)INT32_MAX);
+    hipLaunchKernelGGL(k_start_min, mesh_launch_grid(n_cells), block, 0, stream, vertices, tets, n_cells, g, L.start);
+    hipLaunchKernelGGL(k_start_axis, mesh_launch_grid(nb / g.d[0]), block, 0, stream, L.start, g, 0, L.start2);
+    hipLaunchKernelGGL(k_start_axis, mesh_launch_grid(nb / g.d[1]), block, 0, stream, L.start2, g, 1, L.start);
+    hipLaunchKernelGGL(k_start_axis, mesh_launch_grid(nb / g.d[2]), block, 0, stream, L.start, g, 2, L.start2);
+    hipLaunchKernelGGL(k_locate, mesh_launch_grid(n_points), block, 0, stream, vertices, tets, L.nbr, L.start2, g, points, n_points, cell_out, L.st);
     if ((rc = dgnn_check_launch("locate_points (walk)")) || (rc = mm_read(&hs, L.st, sizeof(MmState), stream, "locate_points"))) return rc;
     if (steps_out) (void)hipMemcpyAsync(steps_out, &L.st->max_steps, sizeof(int32_t), hipMemcpyDeviceToDevice, stream);
     if ((rc = mm_status(hs, "locate_points"))) return rc;
@@ -568,7 +548,7 @@ extern "C" int dgnn_mesh_iou_counts(const int32_t* cells, int64_t n_points, cons
     MmState* st = (MmState*)scratch;
     (void)hipMemsetAsync(st, 0, sizeof(MmState), stream);
     if (n_points > 0)
-        hipLaunchKernelGGL(k_iou_counts, mm_grid(n_points), dim3(MM_THREADS), 0, stream, cells, n_points, labels, n_cells, occ_gt, occ_out, st);
+        hipLaunchKernelGGL(k_iou_counts, mesh_launch_grid(n_points), dim3(MESH_THREADS), 0, stream, cells, n_points, labels, n_cells, occ_gt, occ_out, st);
     hipLaunchKernelGGL(k_counts_out, dim3(1), dim3(64), 0, stream, st, counts_out);
     return dgnn_check_launch("mesh_iou_counts");
 }
@@ -588,14 +568,14 @@ extern "C" int dgnn_sample_faces(const double* vertices, int64_t n_vertices, con
     DGNN_REQUIRE(n_faces < INT32_MAX && n_facets < INT32_MAX && n_vertices < INT32_MAX, DGNN_E_UNSUPPORTED, "sample_faces: sizes exceed the int32 indexing");
     const SampLayout L = samp_layout(scratch, n_faces);
     double* cum = cumarea_out ? cumarea_out : L.area;
-    const dim3 block(MM_THREADS);
+    const dim3 block(MESH_THREADS);
     MmState hs{};
     (void)hipMemsetAsync(L.st, 0, sizeof(MmState), stream);
     (void)hipMemsetAsync(L.total, 0, sizeof(double), stream);
     if (n_faces > 0) {
-        hipLaunchKernelGGL(k_face_area, mm_grid(n_faces), block, 0, stream, vertices, n_vertices, facets, n_facets, face_ids, n_faces, cum, L.st);
+        hipLaunchKernelGGL(k_face_area, mesh_launch_grid(n_faces), block, 0, stream, vertices, n_vertices, facets, n_facets, face_ids, n_faces, cum, L.st);
         fixed_sum(cum, n_faces, 1, L.part, L.total, stream);
-        hipLaunchKernelGGL(k_chunk_add, mm_grid(n_faces), block, 0, stream, cum, n_faces, L.part);
+        hipLaunchKernelGGL(k_chunk_add, mesh_launch_grid(n_faces), block, 0, stream, cum, n_faces, L.part);
     }
     double total = 0;
     int rc = dgnn_check_launch("sample_faces (areas)");
@@ -604,7 +584,7 @@ extern "C" int dgnn_sample_faces(const double* vertices, int64_t n_vertices, con
     if ((rc = mm_status(hs, "sample_faces"))) return rc;
     if (n_samples == 0) return DGNN_OK;
     DGNN_REQUIRE(total > 0 && isfinite(total), DGNN_E_INVALID, "sample_faces: %lld samples asked of faces with total area %g", (long long)n_samples, total);
-    hipLaunchKernelGGL(k_sample, mm_grid(n_samples), block, 0, stream, vertices, facets, face_ids, n_faces, cum, n_samples, seed, points_out, face_out);
+    hipLaunchKernelGGL(k_sample, mesh_launch_grid(n_samples), block, 0, stream, vertices, facets, face_ids, n_faces, cum, n_samples, seed, points_out, face_out);
     return dgnn_check_launch("sample_faces");
 }
 
@@ -620,11 +600,11 @@ extern "C" int dgnn_nearest_neighbor(const float* ref, int64_t n_ref, const floa
                  "nearest_neighbor: bad args (%lld reference points)", (long long)n_ref);
     DGNN_REQUIRE(n_ref < INT32_MAX / 2 && n_query < INT32_MAX, DGNN_E_UNSUPPORTED, "nearest_neighbor: sizes exceed the int32 indexing");
     const NnLayout L = nn_layout(scratch, n_ref, n_query);
-    const dim3 block(MM_THREADS);
+    const dim3 block(MESH_THREADS);
     MmState hs{};
     hs.lo_bits[0] = hs.lo_bits[1] = hs.lo_bits[2] = ~0u;
     (void)hipMemcpyAsync(L.st, &hs, sizeof(MmState), hipMemcpyHostToDevice, stream);
-    hipLaunchKernelGGL(k_bbox_f32, mm_grid(n_ref), block, 0, stream, ref, n_ref, L.st);
+    hipLaunchKernelGGL(k_bbox_f32, mesh_launch_grid(n_ref), block, 0, stream, ref, n_ref, L.st);
     int rc = dgnn_check_launch("nearest_neighbor (bbox)");
     if (rc || (rc = mm_read(&hs, L.st, sizeof(MmState), stream, "nearest_neighbor"))) return rc;
     if ((rc = mm_status(hs, "nearest_neighbor"))) return rc;
@@ -636,11 +616,11 @@ extern "C" int dgnn_nearest_neighbor(const float* ref, int64_t n_ref, const floa
     g.h = (float)g64.h;
     const int64_t nb = (int64_t)g.d[0] * g.d[1] * g.d[2];
     (void)hipMemsetAsync(L.cnt, 0, sizeof(int32_t) * (nb + 1), stream);
-    hipLaunchKernelGGL(k_nn_count, mm_grid(n_ref), block, 0, stream, ref, n_ref, g, L.cnt);
+    hipLaunchKernelGGL(k_nn_count, mesh_launch_grid(n_ref), block, 0, stream, ref, n_ref, g, L.cnt);
     if ((rc = dgnn_exclusive_scan_i32(L.cnt, nb, L.rowptr, L.sums, stream))) return rc;
     (void)hipMemcpyAsync(L.cnt, L.rowptr, sizeof(int32_t) * (nb + 1), hipMemcpyDeviceToDevice, stream);
-    hipLaunchKernelGGL(k_nn_fill, mm_grid(n_ref), block, 0, stream, ref, n_ref, g, L.cnt, L.cells);
-    if (n_query > 0) hipLaunchKernelGGL(k_nn_query, mm_grid(n_query), block, 0, stream, L.rowptr, L.cells, g, query, n_query, dist_out, idx_out, L.st);
+    hipLaunchKernelGGL(k_nn_fill, mesh_launch_grid(n_ref), block, 0, stream, ref, n_ref, g, L.cnt, L.cells);
+    if (n_query > 0) hipLaunchKernelGGL(k_nn_query, mesh_launch_grid(n_query), block, 0, stream, L.rowptr, L.cells, g, query, n_query, dist_out, idx_out, L.st);
     if (sum_out) {
         (void)hipMemsetAsync(sum_out, 0, sizeof(double), stream);
         if (n_query > 0) fixed_sum(dist_out, n_query, 0, L.part, sum_out, stream);

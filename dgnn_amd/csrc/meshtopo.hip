@@ -15,8 +15,7 @@
 namespace {
 
 using dgnn_exact::V3;
-
-__device__ __forceinline__ V3 ldv(const double* v, int32_t i) { return V3{v[3 * (int64_t)i], v[3 * (int64_t)i + 1], v[3 * (int64_t)i + 2]}; }
+using dgnn_exact::load_v3;
 
 __device__ __forceinline__ int32_t coord_bits(const V3& p) {
     int32_t e = 0;
@@ -37,11 +36,6 @@ __device__ __forceinline__ int32_t opposite_vertex(const int32_t* __restrict__ t
         else { miss = t; ++n_miss; }
     }
     return (hits == 3 && n_miss == 1) ? miss : -1;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // ---- orientation -------------------------------------------------------------------------------------------------------------
@@ -68,12 +62,12 @@ __global__ void k_orient(const double* __restrict__ vert, int64_t nv, const int3
                 else if ((d_in = opposite_vertex(tets, ci, x, y, z)) < 0 || (co >= 0 && (d_out = opposite_vertex(tets, co, x, y, z)) < 0)) err = MT_NOT_FACE;
                 else if (d_in >= nv || d_out >= nv) err = MT_BAD_ID;
                 else if (orient) {
-                    const V3 a = ldv(vert, x), b = ldv(vert, y), c = ldv(vert, z), din = ldv(vert, d_in);
+                    const V3 a = load_v3(vert, x), b = load_v3(vert, y), c = load_v3(vert, z), din = load_v3(vert, d_in);
                     err = coord_bits(a) | coord_bits(b) | coord_bits(c) | coord_bits(din);
-                    if (co >= 0) err |= coord_bits(ldv(vert, d_out));
+                    if (co >= 0) err |= coord_bits(load_v3(vert, d_out));
                     if (!err) {
                         int s = dgnn_exact::orient_sign(a, b, c, din, &used);
-                        if (s == 0 && co >= 0) s = -dgnn_exact::orient_sign(a, b, c, ldv(vert, d_out), &used);
+                        if (s == 0 && co >= 0) s = -dgnn_exact::orient_sign(a, b, c, load_v3(vert, d_out), &used);
                         if (s > 0) { const int32_t t = y; y = z; z = t; }
                         und = s == 0;
                     }
@@ -87,8 +81,7 @@ __global__ void k_orient(const double* __restrict__ vert, int64_t nv, const int3
         out[3 * i + 1] = y;
         out[3 * i + 2] = z;
     }
-    n_und = wave_sum_u64(n_und);   // every lane is here: the loop has ended for all of them
-    if (lane_id() == 0 && n_und) atomicAdd(&st->undetermined, n_und);
+    wave_add_atomic(n_und, &st->undetermined);   // every lane is here: the loop has ended for all of them
 }
 
 // ---- vertex compaction ---------------------------------------------------------------------------------------------------------
@@ -122,10 +115,10 @@ __global__ void k_edge_runs(const uint64_t* __restrict__ keys, const int32_t* __
         nonmanifold += len >= 3;
         mismatch += bal != 0;
     }
-    edges = wave_sum_u64(edges);
-    boundary = wave_sum_u64(boundary);
-    nonmanifold = wave_sum_u64(nonmanifold);
-    mismatch = wave_sum_u64(mismatch);
+    edges = wave_sum(edges);
+    boundary = wave_sum(boundary);
+    nonmanifold = wave_sum(nonmanifold);
+    mismatch = wave_sum(mismatch);
     if (lane_id() == 0) {
         if (edges) atomicAdd((unsigned long long*)&counts[0], edges);
         if (boundary) atomicAdd((unsigned long long*)&counts[1], boundary);
@@ -157,7 +150,7 @@ __global__ void k_fan_roots(const int32_t* __restrict__ faces, const int32_t* __
 __global__ void k_fan_count(const int32_t* __restrict__ roots, int64_t nv, long long* __restrict__ counts) {
     unsigned long long bad = 0;
     for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < nv; v += (int64_t)gridDim.x * blockDim.x) bad += roots[v] >= 2;
-    bad = wave_sum_u64(bad);
+    bad = wave_sum(bad);
     if (lane_id() == 0 && bad) atomicAdd((unsigned long long*)&counts[3], bad);
 }
 
@@ -212,7 +205,7 @@ extern "C" int dgnn_orient_interface(const double* vertices, int64_t n_vertices,
     MtState* st = (MtState*)scratch;
     (void)hipMemsetAsync(st, 0, sizeof(MtState), stream);
     if (n_faces > 0)
-        hipLaunchKernelGGL(k_orient, mt_grid(n_faces), dim3(MT_THREADS), 0, stream, vertices, n_vertices, tets, n_cells, facets, nfacets, n_facets,
+        hipLaunchKernelGGL(k_orient, mesh_launch_grid(n_faces), dim3(MESH_THREADS), 0, stream, vertices, n_vertices, tets, n_cells, facets, nfacets, n_facets,
                            labels, face_ids, n_faces, orient, faces_out, st);
     if (n_undetermined_out) (void)hipMemcpyAsync(n_undetermined_out, &st->undetermined, sizeof(int64_t), hipMemcpyDeviceToDevice, stream);
     if (exact_used_out) (void)hipMemcpyAsync(exact_used_out, &st->exact_used, sizeof(int32_t), hipMemcpyDeviceToDevice, stream);
@@ -234,14 +227,14 @@ extern "C" int dgnn_compact_vertices(const int32_t* faces, int64_t n_faces, int6
     const CompactLayout L = compact_layout(scratch, n_vertices);
     (void)hipMemsetAsync(L.st, 0, sizeof(MtState), stream);
     (void)hipMemsetAsync(L.flags, 0, sizeof(int32_t) * (n_vertices > 0 ? n_vertices : 1), stream);
-    if (n_faces > 0) hipLaunchKernelGGL(k_mark_vertices, mt_grid(3 * n_faces), dim3(MT_THREADS), 0, stream, faces, 3 * n_faces, n_vertices, L.flags, L.st);
+    if (n_faces > 0) hipLaunchKernelGGL(k_mark_vertices, mesh_launch_grid(3 * n_faces), dim3(MESH_THREADS), 0, stream, faces, 3 * n_faces, n_vertices, L.flags, L.st);
     MtState hs{};
     int rc = mt_read_status(&hs, L.st, stream, "compact_vertices");
     if (rc) return rc;
     if ((rc = dgnn_compact_i32(nullptr, L.flags, 0, n_vertices, kept_out, n_kept_out, L.cscratch, stream))) return rc;
     if (n_faces > 0) {
-        hipLaunchKernelGGL(k_new_ids, mt_grid(n_vertices), dim3(MT_THREADS), 0, stream, kept_out, n_kept_out, L.new_id);
-        hipLaunchKernelGGL(k_renumber, mt_grid(3 * n_faces), dim3(MT_THREADS), 0, stream, faces, 3 * n_faces, L.new_id, faces_out);
+        hipLaunchKernelGGL(k_new_ids, mesh_launch_grid(n_vertices), dim3(MESH_THREADS), 0, stream, kept_out, n_kept_out, L.new_id);
+        hipLaunchKernelGGL(k_renumber, mesh_launch_grid(3 * n_faces), dim3(MESH_THREADS), 0, stream, faces, 3 * n_faces, L.new_id, faces_out);
     }
     return dgnn_check_launch("compact_vertices");
 }
@@ -256,10 +249,10 @@ extern "C" int dgnn_mesh_topology(const int32_t* faces, int64_t n_faces, int64_t
     DGNN_REQUIRE(n_faces >= 0 && n_vertices >= 0 && scratch && counts_out && (n_faces == 0 || faces), DGNN_E_INVALID, "mesh_topology: bad args");
     DGNN_REQUIRE(n_faces < INT32_MAX / 6 && n_vertices < INT32_MAX, DGNN_E_UNSUPPORTED, "mesh_topology: sizes exceed the int32 indexing");
     const TopoLayout L = topo_layout(scratch, n_faces, n_vertices);
-    const dim3 block(MT_THREADS);
+    const dim3 block(MESH_THREADS);
     (void)hipMemsetAsync(L.st, 0, sizeof(MtState), stream);
     (void)hipMemsetAsync(counts_out, 0, 5 * sizeof(int64_t), stream);
-    if (n_faces > 0) hipLaunchKernelGGL(k_check_faces, mt_grid(n_faces), block, 0, stream, faces, n_faces, n_vertices, L.st);
+    if (n_faces > 0) hipLaunchKernelGGL(k_check_faces, mesh_launch_grid(n_faces), block, 0, stream, faces, n_faces, n_vertices, L.st);
     MtState hs{};
     int rc = mt_read_status(&hs, L.st, stream, "mesh_topology");
     if (rc || n_faces == 0) return rc;
@@ -268,15 +261,15 @@ extern "C" int dgnn_mesh_topology(const int32_t* faces, int64_t n_faces, int64_t
     int cur = 0;
     long long* counts = (long long*)counts_out;
     // edges
-    hipLaunchKernelGGL(k_edge_keys, mt_grid(n3), block, 0, stream, faces, n3, vb, 0, L.keys[0], L.vals[0]);
+    hipLaunchKernelGGL(k_edge_keys, mesh_launch_grid(n3), block, 0, stream, faces, n3, vb, 0, L.keys[0], L.vals[0]);
     if ((rc = dgnn_radix_sort_u64_i32(L.keys, L.vals, n3, 2 * vb, L.hist, L.scanned, L.sums, stream, &cur))) return rc;
-    hipLaunchKernelGGL(k_edge_runs, mt_grid(n3), block, 0, stream, L.keys[cur], L.vals[cur], n3, counts);
+    hipLaunchKernelGGL(k_edge_runs, mesh_launch_grid(n3), block, 0, stream, L.keys[cur], L.vals[cur], n3, counts);
     // vertex fans
-    hipLaunchKernelGGL(k_link_keys, mt_grid(n3), block, 0, stream, faces, n3, vb, L.keys[0], L.vals[0], L.parent);
+    hipLaunchKernelGGL(k_link_keys, mesh_launch_grid(n3), block, 0, stream, faces, n3, vb, L.keys[0], L.vals[0], L.parent);
     if ((rc = dgnn_radix_sort_u64_i32(L.keys, L.vals, 2 * n3, 2 * vb, L.hist, L.scanned, L.sums, stream, &cur))) return rc;
-    hipLaunchKernelGGL(k_link_union, mt_grid(2 * n3), block, 0, stream, L.keys[cur], L.vals[cur], 2 * n3, L.parent);
+    hipLaunchKernelGGL(k_link_union, mesh_launch_grid(2 * n3), block, 0, stream, L.keys[cur], L.vals[cur], 2 * n3, L.parent);
     (void)hipMemsetAsync(L.roots, 0, sizeof(int32_t) * (n_vertices > 0 ? n_vertices : 1), stream);
-    hipLaunchKernelGGL(k_fan_roots, mt_grid(n3), block, 0, stream, faces, L.parent, n3, L.roots);
-    hipLaunchKernelGGL(k_fan_count, mt_grid(n_vertices), block, 0, stream, L.roots, n_vertices, counts);
+    hipLaunchKernelGGL(k_fan_roots, mesh_launch_grid(n3), block, 0, stream, faces, L.parent, n3, L.roots);
+    hipLaunchKernelGGL(k_fan_count, mesh_launch_grid(n_vertices), block, 0, stream, L.roots, n_vertices, counts);
     return dgnn_check_launch("mesh_topology");
 }

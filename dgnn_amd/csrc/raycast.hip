@@ -4,9 +4,9 @@
 //   rule       ray r is o + t d, d = g - o.  A face (a, b, c) is crossed when the three exact signs det[g - o, a - o, b - o], det[g - o, b - o,
 //              c - o], det[g - o, c - o, a - o] (exact_orient.h: filter, then expansion) are all >= 0 or all <= 0 and not all 0; its
 //              parameter is t = n . (a - o) / (n . d), n = (b - a) x (c - a); the answer is the smallest t above t_min, ties to the lowest face.
-//   grid       a uniform 3D grid over the box of the referenced vertices, built as scenefeat.hip builds the vertex incidence and
-//              meshcontains.hip its xy grid: count / scan / fill through a cursor, ONE WORK ITEM PER (face, cell) ENTRY.  A face is entered
-//              in every cell its bounding box touches, through the one monotone map rc_cell.
+//   grid       a uniform 3D grid over the box of the referenced vertices, built by the entry-grid builder of mesh_grid.h (which
+//              meshcontains.hip uses for its xy grid): one work item per (face, cell) entry.  A face is entered in every cell its
+//              bounding box touches, through the one monotone map rc_cell.
 //   traversal  one lane per ray.  The computed t of a sliver says nothing about where the sliver is, so no hit is ever final before the
 //              whole line has been walked: the line is clipped to the box and walked slab by slab along its fastest axis (in cells); per
 //              slab the two other coordinates at the slab's two ends give a rectangle of cells.  Every bound is widened by eps_w = 2^-46
@@ -19,15 +19,13 @@
 //   stats      hits and skipped rays; the signs of the HIT faces that the exact stage decided; crossings dropped as degenerate, each face
 //              once: a ray that meets one recounts over all faces (out of line, rare), since the walk may meet a face in several cells.
 #include "exact_orient.h"
-#include "mesh_common.h"
-
-int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* sums_scratch, hipStream_t stream);   // plan.hip
+#include "mesh_grid.h"
 
 namespace {
 
 using dgnn_exact::V3;
+using dgnn_exact::load_v3;
 
-constexpr int RC_THREADS = 256;
 constexpr int RC_MAX_R = 1024;
 constexpr double RC_MARGIN = 0x1p-46;          // of the largest coordinate magnitude M of the box and the ray: 128 u M, u = 2^-53
 constexpr int32_t RC_BAD_ID = 1, RC_NONFINITE = 2, RC_RANGE = 4;
@@ -47,15 +45,11 @@ struct RcGrid {          // by value to the kernels
     double mag;                               // the largest |coordinate| of the box
 };
 
-dim3 rc_launch_grid(int64_t items) { return dim3(dgnn_grid_cap(dgnn_cdiv(items > 0 ? items : 1, RC_THREADS))); }
-
-__device__ __forceinline__ V3 rc_load(const double* __restrict__ v, int64_t i) { return V3{v[3 * i], v[3 * i + 1], v[3 * i + 2]}; }
-__device__ __forceinline__ V3 rc_sub(const V3& a, const V3& b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 rc_cross(const V3& a, const V3& b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double rc_dot(const V3& a, const V3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ double rc_get(const V3& a, int k) { return k == 0 ? a.x : (k == 1 ? a.y : a.z); }
 __device__ __forceinline__ int32_t rc_pick(const int32_t (&p)[3], int k) { return k == 0 ? p[0] : (k == 1 ? p[1] : p[2]); }
-__device__ __forceinline__ int32_t rc_coord_err(double x) { return !isfinite(x) ? RC_NONFINITE : (dgnn_exact::orient_coord_ok(x) ? 0 : RC_RANGE); }
+// the status bits of a coordinate that is not finite or outside the exact predicate's range; the bounding box (k_bbox_referenced) leaves it out
+struct RcCoordErr {
+    __device__ int32_t operator()(double x) const { return !isfinite(x) ? RC_NONFINITE : (dgnn_exact::orient_coord_ok(x) ? 0 : RC_RANGE); }
+};
 
 // the cell of coordinate x on axis a: a chain of monotone steps (difference, product, truncation, clamp), so x <= y gives cell(x) <= cell(y)
 __device__ __forceinline__ int32_t rc_cell(const RcGrid& g, int a, double x) {
@@ -63,96 +57,51 @@ __device__ __forceinline__ int32_t rc_cell(const RcGrid& g, int a, double x) {
     return !(f > 0) ? 0 : (f >= (double)g.n[a] ? g.n[a] - 1 : (int32_t)f);
 }
 
-__device__ __forceinline__ void rc_wave_add(unsigned long long x, unsigned long long* dst) {   // every lane of the wave is here
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    if (lane_id() == 0 && x) atomicAdd(dst, x);
-}
-
-// ---- validation and bounding box ----------------------------------------------------------------------------------------------
-__global__ void k_rc_check_faces(const int32_t* __restrict__ faces, int64_t n3, int64_t nv, RcState* st) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x)
-        if (faces[i] < 0 || faces[i] >= nv) atomicOr(&st->err, RC_BAD_ID);
-}
-
-// faces are validated: finiteness, the exact predicate's range and min / max over the vertices they reference (integer keys: order-free)
-__global__ void k_rc_bbox(const double* __restrict__ v, const int32_t* __restrict__ faces, int64_t n3, RcState* st) {
-    unsigned long long lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0, 0, 0};
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t id = faces[i];
-        for (int a = 0; a < 3; ++a) {
-            const double x = v[3 * id + a];
-            const int32_t e = rc_coord_err(x);
-            if (e) { atomicOr(&st->err, e); continue; }
-            const unsigned long long k = f64_key(x);
-            lo[a] = k < lo[a] ? k : lo[a];
-            hi[a] = k > hi[a] ? k : hi[a];
-        }
-    }
-    for (int a = 0; a < 3; ++a) wave_minmax_atomic(lo[a], hi[a], &st->lo[a], &st->hi[a]);
-}
-
+// ---- validation ------------------------------------------------------------------------------------------------------------------
 __global__ void k_rc_check_rays(const double* __restrict__ origins, const double* __restrict__ aims, int64_t n3, RcState* st) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t e = rc_coord_err(origins[i]) | rc_coord_err(aims[i]);
+        const int32_t e = RcCoordErr{}(origins[i]) | RcCoordErr{}(aims[i]);
         if (e) atomicOr(&st->err, e);
     }
 }
 
-// ---- the grid: count / scan / fill, one work item per (face, cell) entry ---------------------------------------------------------
+// ---- the grid (mesh_grid.h): the cells of a face's box, z fastest -------------------------------------------------------------------
 struct RcBox { int32_t lo[3], hi[3]; };
 
 // tbox[t] = the cells of the face's bounding box; tcnt[t] = their number; the total -> st->n_entries
-__global__ void __launch_bounds__(RC_THREADS) k_rc_tri_box(const double* __restrict__ v, const int32_t* __restrict__ faces, int64_t nf, RcGrid g,
+__global__ void __launch_bounds__(MESH_THREADS) k_rc_tri_box(const double* __restrict__ v, const int32_t* __restrict__ faces, int64_t nf, RcGrid g,
                                                            RcBox* __restrict__ tbox, int32_t* __restrict__ tcnt, RcState* st) {
     unsigned long long tot = 0;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nf; t += (int64_t)gridDim.x * blockDim.x) {
-        const V3 a = rc_load(v, faces[3 * t]), b = rc_load(v, faces[3 * t + 1]), c = rc_load(v, faces[3 * t + 2]);
+        const V3 a = load_v3(v, faces[3 * t]), b = load_v3(v, faces[3 * t + 1]), c = load_v3(v, faces[3 * t + 2]);
         RcBox bx;
         int64_t cnt = 1;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            bx.lo[k] = rc_cell(g, k, fmin(fmin(rc_get(a, k), rc_get(b, k)), rc_get(c, k)));
-            bx.hi[k] = rc_cell(g, k, fmax(fmax(rc_get(a, k), rc_get(b, k)), rc_get(c, k)));
+            bx.lo[k] = rc_cell(g, k, fmin(fmin(get(a, k), get(b, k)), get(c, k)));
+            bx.hi[k] = rc_cell(g, k, fmax(fmax(get(a, k), get(b, k)), get(c, k)));
             cnt *= bx.hi[k] - bx.lo[k] + 1;
         }
         tbox[t] = bx;
         tcnt[t] = (int32_t)cnt;          // <= RC_MAX_R^3 = 2^30
         tot += (unsigned long long)cnt;
     }
-    rc_wave_add(tot, &st->n_entries);          // an integer sum: order-free
+    wave_add_atomic(tot, &st->n_entries);          // an integer sum: order-free
 }
 
-// entry e belongs to the face t with toff[t] <= e < toff[t + 1] (toff ascending, toff[nf] = n_entries: the search ends inside [0, nf));
-// its cell is the (e - toff[t])-th of the face's box, z fastest
-__device__ __forceinline__ int32_t rc_entry(const int32_t* __restrict__ toff, const RcBox* __restrict__ tbox, int64_t nf, const RcGrid& g, int32_t e,
-                                            int64_t* cell) {
-    int64_t lo = 0, hi = nf - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (toff[mid] <= e) lo = mid;
-        else hi = mid - 1;
+// (the order inside a cell is whatever the builder's atomics give: the walk takes a minimum under a total order)
+struct RcCells {
+    const RcBox* tbox;
+    int32_t n1, n2;          // the grid's cells along y and z
+    __device__ int64_t cell(int64_t t, int32_t k) const {
+        const RcBox b = tbox[t];
+        const int32_t nz = b.hi[2] - b.lo[2] + 1, ny = b.hi[1] - b.lo[1] + 1;
+        const int32_t z = b.lo[2] + k % nz;
+        k /= nz;
+        const int32_t y = b.lo[1] + k % ny, x = b.lo[0] + k / ny;
+        return ((int64_t)x * n1 + y) * n2 + z;
     }
-    const RcBox b = tbox[lo];
-    const int32_t nz = b.hi[2] - b.lo[2] + 1, ny = b.hi[1] - b.lo[1] + 1;
-    int32_t k = e - toff[lo];
-    const int32_t z = b.lo[2] + k % nz;
-    k /= nz;
-    const int32_t y = b.lo[1] + k % ny, x = b.lo[0] + k / ny;
-    *cell = ((int64_t)x * g.n[1] + y) * g.n[2] + z;
-    return (int32_t)lo;
-}
-
-// fill == 0: ccnt[cell] += 1; fill != 0: entries[cursor[cell]++] = t (the order inside a cell is whatever the atomics give: the walk takes
-// a minimum under a total order)
-__global__ void k_rc_entries(const int32_t* __restrict__ toff, const RcBox* __restrict__ tbox, int64_t nf, RcGrid g, int64_t n_entries, int fill,
-                             int32_t* __restrict__ ccnt, int32_t* __restrict__ entries) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n_entries; e += (int64_t)gridDim.x * blockDim.x) {
-        int64_t cell;
-        const int32_t t = rc_entry(toff, tbox, nf, g, (int32_t)e, &cell);
-        const int32_t slot = atomicAdd(ccnt + cell, 1);
-        if (fill) entries[slot] = t;
-    }
-}
+};
 
 // ---- the rays --------------------------------------------------------------------------------------------------------------------
 struct RcBest { double t; int32_t face, exact; };
@@ -161,7 +110,7 @@ struct RcBest { double t; int32_t face, exact; };
 // the exact stage decided.
 __device__ __forceinline__ int rc_face(const double* __restrict__ v, const int32_t* __restrict__ faces, int64_t f, const V3& o, const V3& g, const V3& d,
                                        double* t, int* exact) {
-    const V3 a = rc_load(v, faces[3 * f]), b = rc_load(v, faces[3 * f + 1]), c = rc_load(v, faces[3 * f + 2]);
+    const V3 a = load_v3(v, faces[3 * f]), b = load_v3(v, faces[3 * f + 1]), c = load_v3(v, faces[3 * f + 2]);
     int ex[3] = {0, 0, 0};
     const int s1 = dgnn_exact::orient_sign(o, g, a, b, &ex[0]);
     const int s2 = dgnn_exact::orient_sign(o, g, b, c, &ex[1]);
@@ -169,8 +118,8 @@ __device__ __forceinline__ int rc_face(const double* __restrict__ v, const int32
     *exact = ex[0] + ex[1] + ex[2];
     const bool nonneg = s1 >= 0 && s2 >= 0 && s3 >= 0, nonpos = s1 <= 0 && s2 <= 0 && s3 <= 0;
     if (!(nonneg || nonpos) || (nonneg && nonpos)) return 0;
-    const V3 n = rc_cross(rc_sub(b, a), rc_sub(c, a));
-    const double num = rc_dot(n, rc_sub(a, o)), den = rc_dot(n, d);
+    const V3 n = cross(sub(b, a), sub(c, a));
+    const double num = dot(n, sub(a, o)), den = dot(n, d);
     if (den == 0.0) return 2;
     *t = num / den;
     return isfinite(*t) ? 1 : 2;
@@ -187,15 +136,15 @@ __device__ __noinline__ int64_t rc_count_degenerate(const double* __restrict__ v
     return n;
 }
 
-__global__ void __launch_bounds__(RC_THREADS) k_rc_rays(const double* __restrict__ v, const int32_t* __restrict__ faces, int64_t nf,
+__global__ void __launch_bounds__(MESH_THREADS) k_rc_rays(const double* __restrict__ v, const int32_t* __restrict__ faces, int64_t nf,
                                                         const int32_t* __restrict__ rowptr, const int32_t* __restrict__ entries,
                                                         const RcBox* __restrict__ tbox, RcGrid G, const double* __restrict__ origins, const double* __restrict__ aims, int64_t nr, double t_min,
                                                         int32_t* __restrict__ hit_face, double* __restrict__ hit_t, double* __restrict__ hit_point,
                                                         RcState* st) {
     unsigned long long cnt[RC_N_STATS] = {0, 0, 0, 0};
     for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < nr; r += (int64_t)gridDim.x * blockDim.x) {
-        const V3 o = rc_load(origins, r), g = rc_load(aims, r);
-        const V3 d = rc_sub(g, o);
+        const V3 o = load_v3(origins, r), g = load_v3(aims, r);
+        const V3 d = sub(g, o);
         RcBest best{0.0, -1, 0};
         bool degenerate = false;
         if (o.x == g.x && o.y == g.y && o.z == g.z) {
@@ -204,7 +153,7 @@ __global__ void __launch_bounds__(RC_THREADS) k_rc_rays(const double* __restrict
             const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
             double mag = G.mag;
 #pragma unroll
-            for (int a = 0; a < 3; ++a) mag = fmax(mag, fmax(fabs(oo[a]), fabs(rc_get(g, a))));
+            for (int a = 0; a < 3; ++a) mag = fmax(mag, fmax(fabs(oo[a]), fabs(get(g, a))));
             const double eps = RC_MARGIN * mag;
             // the line clipped to the widened box: [t_in, t_out]; the fastest axis in cells
             double t_in = -INFINITY, t_out = INFINITY, speed = -1.0;
@@ -279,22 +228,17 @@ __global__ void __launch_bounds__(RC_THREADS) k_rc_rays(const double* __restrict
         }
     }
 #pragma unroll
-    for (int j = 0; j < RC_N_STATS; ++j) rc_wave_add(cnt[j], &st->stats[j]);
+    for (int j = 0; j < RC_N_STATS; ++j) wave_add_atomic(cnt[j], &st->stats[j]);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-struct RcLayout { RcState* st; RcBox* tbox; int32_t *tcnt, *toff, *ccnt, *rowptr, *sums; int64_t bytes; };
+struct RcLayout { RcState* st; RcBox* tbox; GridBufs g; int64_t bytes; };
 RcLayout rc_layout(void* base, int64_t nf, int64_t R) {
     Take t{(char*)base, 256};
     RcLayout L{};
     L.st = (RcState*)base;
-    const int64_t cells = R * R * R, m = nf > cells ? nf : cells;
     L.tbox = t.take<RcBox>(nf);
-    L.tcnt = t.take<int32_t>(nf + 1);
-    L.toff = t.take<int32_t>(nf + 1);
-    L.ccnt = t.take<int32_t>(cells + 1);
-    L.rowptr = t.take<int32_t>(cells + 1);
-    L.sums = t.take<int32_t>(dgnn_cdiv(m + 1, 2048) + 2);
+    L.g = take_grid(t, nf, R * R * R);
     L.bytes = t.off;
     return L;
 }
@@ -317,21 +261,21 @@ int rc_plan(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf
     DGNN_REQUIRE(nf > 0, DGNN_E_INVALID, "%s: a mesh without faces", what);
     DGNN_REQUIRE(rc_resolution_ok(R), DGNN_E_UNSUPPORTED, "%s: grid_resolution %d outside [1, %d]", what, R, RC_MAX_R);
     DGNN_REQUIRE(nf < INT32_MAX / 4 && nv < INT32_MAX, DGNN_E_UNSUPPORTED, "%s: sizes exceed the int32 indexing", what);
-    const dim3 block(RC_THREADS);
+    const dim3 block(MESH_THREADS);
     RcState hs{};
     hs.lo[0] = hs.lo[1] = hs.lo[2] = ~0ull;
     (void)hipMemcpyAsync(L.st, &hs, sizeof(RcState), hipMemcpyHostToDevice, stream);
-    hipLaunchKernelGGL(k_rc_check_faces, rc_launch_grid(3 * nf), block, 0, stream, faces, 3 * nf, nv, L.st);
+    hipLaunchKernelGGL(k_check_ids, mesh_launch_grid(3 * nf), block, 0, stream, faces, 3 * nf, nv, &L.st->err, RC_BAD_ID);
     int rc = dgnn_check_launch(what);
     if (rc || (rc = mm_read(&hs, L.st, sizeof(RcState), stream, what)) || (rc = rc_status(hs, what))) return rc;   // ids are read below: checked first
-    hipLaunchKernelGGL(k_rc_bbox, rc_launch_grid(3 * nf), block, 0, stream, vertices, faces, 3 * nf, L.st);
-    if (n_rays > 0) hipLaunchKernelGGL(k_rc_check_rays, rc_launch_grid(3 * n_rays), block, 0, stream, origins, aims, 3 * n_rays, L.st);
+    hipLaunchKernelGGL(k_bbox_referenced<RcCoordErr>, mesh_launch_grid(3 * nf), block, 0, stream, vertices, faces, 3 * nf, RcCoordErr{}, &L.st->err, L.st->lo,
+                       L.st->hi);
+    if (n_rays > 0) hipLaunchKernelGGL(k_rc_check_rays, mesh_launch_grid(3 * n_rays), block, 0, stream, origins, aims, 3 * n_rays, L.st);
     if ((rc = dgnn_check_launch(what)) || (rc = mm_read(&hs, L.st, sizeof(RcState), stream, what)) || (rc = rc_status(hs, what))) return rc;
     RcGrid g{};
     double longest = 0.0;
+    bbox_unkey(hs.lo, hs.hi, g.lo, g.hi);
     for (int a = 0; a < 3; ++a) {
-        g.lo[a] = f64_unkey(hs.lo[a]);
-        g.hi[a] = f64_unkey(hs.hi[a]);
         longest = fmax(longest, g.hi[a] - g.lo[a]);
         g.mag = fmax(g.mag, fmax(fabs(g.lo[a]), fabs(g.hi[a])));
     }
@@ -344,7 +288,7 @@ int rc_plan(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf
         g.inv[a] = ext > 0 ? cells / ext : 0.0;
         if (!isfinite(g.inv[a])) { g.n[a] = 1; g.h[a] = ext; g.inv[a] = 0.0; }          // an extent below 2^-1022 or so: one cell
     }
-    hipLaunchKernelGGL(k_rc_tri_box, rc_launch_grid(nf), block, 0, stream, vertices, faces, nf, g, L.tbox, L.tcnt, L.st);
+    hipLaunchKernelGGL(k_rc_tri_box, mesh_launch_grid(nf), block, 0, stream, vertices, faces, nf, g, L.tbox, L.g.tcnt, L.st);
     if ((rc = dgnn_check_launch(what)) || (rc = mm_read(&hs, L.st, sizeof(RcState), stream, what))) return rc;
     DGNN_REQUIRE(hs.n_entries < (unsigned long long)INT32_MAX, DGNN_E_UNSUPPORTED, "%s: %llu grid entries exceed the int32 indexing (lower grid_resolution)", what,
                  hs.n_entries);
@@ -390,16 +334,9 @@ extern "C" int dgnn_ray_first_hit(const double* vertices, int64_t n_vertices, co
     DGNN_REQUIRE(entries && ne <= entry_capacity, DGNN_E_INVALID, "ray_first_hit: %lld grid entries, room for %lld (dgnn_ray_first_hit_plan gives the number)",
                  (long long)ne, (long long)entry_capacity);
     if (n_rays > 0) {
-        const dim3 block(RC_THREADS);
-        const int64_t cells = (int64_t)g.n[0] * g.n[1] * g.n[2];
-        if ((rc = dgnn_exclusive_scan_i32(L.tcnt, n_faces, L.toff, L.sums, stream))) return rc;
-        (void)hipMemsetAsync(L.ccnt, 0, sizeof(int32_t) * (cells + 1), stream);
-        hipLaunchKernelGGL(k_rc_entries, rc_launch_grid(ne), block, 0, stream, L.toff, L.tbox, n_faces, g, ne, 0, L.ccnt, (int32_t*)nullptr);
-        if ((rc = dgnn_exclusive_scan_i32(L.ccnt, cells, L.rowptr, L.sums, stream))) return rc;
-        (void)hipMemcpyAsync(L.ccnt, L.rowptr, sizeof(int32_t) * (cells + 1), hipMemcpyDeviceToDevice, stream);   // the fill's cursors
-        hipLaunchKernelGGL(k_rc_entries, rc_launch_grid(ne), block, 0, stream, L.toff, L.tbox, n_faces, g, ne, 1, L.ccnt, entries);
-        hipLaunchKernelGGL(k_rc_rays, rc_launch_grid(n_rays), block, 0, stream, vertices, faces, n_faces, L.rowptr, entries, L.tbox, g, origins, aims, n_rays, t_min,
-                           hit_face_out, hit_t_out, hit_point_out, L.st);
+        if ((rc = build_entry_grid(L.g, RcCells{L.tbox, g.n[1], g.n[2]}, n_faces, (int64_t)g.n[0] * g.n[1] * g.n[2], ne, entries, stream))) return rc;
+        hipLaunchKernelGGL(k_rc_rays, mesh_launch_grid(n_rays), dim3(MESH_THREADS), 0, stream, vertices, faces, n_faces, L.g.rowptr, entries, L.tbox, g, origins,
+                           aims, n_rays, t_min, hit_face_out, hit_t_out, hit_point_out, L.st);
     }
     (void)hipMemcpyAsync(stats_out, L.st->stats, sizeof(int64_t) * RC_N_STATS, hipMemcpyDeviceToDevice, stream);
     return dgnn_check_launch("ray_first_hit");

@@ -18,27 +18,14 @@
 namespace {
 
 using dgnn_exact::V3;
+using dgnn_exact::load_v3;
 
 constexpr int SF_SIDES = 2;          // 0 = outside (towards the sensor), 1 = inside (away from it)
 constexpr int64_t SF_MAX_RAYS = 0x7f7f7f7f;   // first[] is preset bytewise to this value, which has to lie above every ray index
 enum { SF_USED = 0, SF_DUPLICATE, SF_DEGENERATE, SF_NO_OUTSIDE, SF_NO_INSIDE, SF_EXACT, SF_N_STATS };
 
-__device__ __forceinline__ V3 load_v3(const double* __restrict__ v, int64_t i) { return V3{v[3 * i], v[3 * i + 1], v[3 * i + 2]}; }
-__device__ __forceinline__ V3 sub(const V3& a, const V3& b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 cross(const V3& a, const V3& b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double dot(const V3& a, const V3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ bool coords_ok(const V3& a) {
     return dgnn_exact::orient_coord_ok(a.x) && dgnn_exact::orient_coord_ok(a.y) && dgnn_exact::orient_coord_ok(a.z);
-}
-
-__device__ __forceinline__ void wave_add(unsigned long long x, unsigned long long* dst) {   // every lane of the wave is here
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    if (lane_id() == 0 && x) atomicAdd(dst, x);
-}
-
-__global__ void k_check_tets(const int32_t* __restrict__ tets, int64_t n4, int64_t nv, MtState* st) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
-        if (tets[i] < 0 || tets[i] >= nv) atomicOr(&st->err, MT_BAD_ID);
 }
 
 // ---- neighbours ----------------------------------------------------------------------------------------------------------------
@@ -62,7 +49,7 @@ __global__ void k_neighbors(const int32_t* __restrict__ tets, int64_t nt, const 
         if (hits == 3) nbr[4 * (int64_t)c + slot] = other;
         else ++bad;
     }
-    wave_add(bad, n_bad);
+    wave_add_atomic(bad, n_bad);
 }
 
 // ---- geometry ------------------------------------------------------------------------------------------------------------------
@@ -100,7 +87,7 @@ __global__ void k_cell_geometry(const double* __restrict__ v, int64_t nv, const 
         longest[t] = hi;
         shortest[t] = lo;
     }
-    wave_add(flat, n_flat);
+    wave_add_atomic(flat, n_flat);
 }
 
 // ---- incidence -----------------------------------------------------------------------------------------------------------------
@@ -144,7 +131,7 @@ __device__ __forceinline__ double ray_length(const V3& p, const V3& e, int flip,
     return dot(n, sub(q0, p)) / dot(n, d);
 }
 
-__global__ void __launch_bounds__(MT_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_rays(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ tets, int64_t nt, const int32_t* __restrict__ rowptr,
        const int32_t* __restrict__ entries, const int32_t* __restrict__ ray_vertex, const double* __restrict__ sensors, int64_t nr, int unique,
        const int32_t* __restrict__ first, int32_t* __restrict__ ray_tet, int32_t* __restrict__ ray_slot, double* __restrict__ ray_dist,
@@ -201,7 +188,7 @@ k_rays(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ tet
         }
     }
 #pragma unroll
-    for (int j = 0; j < SF_N_STATS; ++j) wave_add(cnt[j], stats + j);
+    for (int j = 0; j < SF_N_STATS; ++j) wave_add_atomic(cnt[j], stats + j);
 }
 
 // sort keys of one side: the ray's tet, rays without one behind every tet
@@ -319,7 +306,7 @@ extern "C" int dgnn_tet_neighbors(const int32_t* tetrahedra, int64_t n_tets, con
     (void)hipMemsetAsync(head, 0, sizeof(Head), stream);
     if (n_tets > 0) (void)hipMemsetAsync(neighbors_out, 0xff, sizeof(int32_t) * 4 * n_tets, stream);   // -1: the infinite cell
     if (n_facets > 0)
-        hipLaunchKernelGGL(k_neighbors, mt_grid(2 * n_facets), dim3(MT_THREADS), 0, stream, tetrahedra, n_tets, facets, nfacets, 2 * n_facets,
+        hipLaunchKernelGGL(k_neighbors, mesh_launch_grid(2 * n_facets), dim3(MESH_THREADS), 0, stream, tetrahedra, n_tets, facets, nfacets, 2 * n_facets,
                            neighbors_out, head->counters, &head->st);
     (void)hipMemcpyAsync(n_bad_out, head->counters, sizeof(int64_t), hipMemcpyDeviceToDevice, stream);
     MtState hs{};
@@ -344,7 +331,7 @@ extern "C" int dgnn_cell_geometry(const double* vertices, int64_t n_vertices, co
     double* part = (double*)((char*)scratch + 256);
     (void)hipMemsetAsync(head, 0, sizeof(Head), stream);
     if (n_tets > 0)
-        hipLaunchKernelGGL(k_cell_geometry, mt_grid(n_tets), dim3(MT_THREADS), 0, stream, vertices, n_vertices, tetrahedra, n_tets, radius_out, vol_out,
+        hipLaunchKernelGGL(k_cell_geometry, mesh_launch_grid(n_tets), dim3(MESH_THREADS), 0, stream, vertices, n_vertices, tetrahedra, n_tets, radius_out, vol_out,
                            longest_out, shortest_out, head->counters, &head->st);
     fixed_sum(longest_out, n_tets, 0, part, edge_sums_out, stream);          // (the stream orders the two uses of part)
     fixed_sum(shortest_out, n_tets, 0, part, edge_sums_out + 1, stream);
@@ -364,14 +351,14 @@ extern "C" int dgnn_vertex_incidence(const int32_t* tetrahedra, int64_t n_tets, 
     const int64_t n4 = 4 * n_tets;
     (void)hipMemsetAsync(L.head, 0, sizeof(Head), stream);
     if (n_vertices > 0) (void)hipMemsetAsync(L.count, 0, sizeof(int32_t) * n_vertices, stream);
-    if (n4 > 0) hipLaunchKernelGGL(k_incidence_count, mt_grid(n4), dim3(MT_THREADS), 0, stream, tetrahedra, n4, n_vertices, L.count, &L.head->st);
+    if (n4 > 0) hipLaunchKernelGGL(k_incidence_count, mesh_launch_grid(n4), dim3(MESH_THREADS), 0, stream, tetrahedra, n4, n_vertices, L.count, &L.head->st);
     MtState hs{};
     int rc = mt_read_status(&hs, &L.head->st, stream, "vertex_incidence");
     if (rc) return rc;
     if ((rc = dgnn_exclusive_scan_i32(L.count, n_vertices, rowptr_out, L.sums, stream))) return rc;
     if (n4 > 0) {
         (void)hipMemcpyAsync(L.cursor, rowptr_out, sizeof(int32_t) * n_vertices, hipMemcpyDeviceToDevice, stream);
-        hipLaunchKernelGGL(k_incidence_fill, mt_grid(n4), dim3(MT_THREADS), 0, stream, tetrahedra, n4, L.cursor, entries_out);
+        hipLaunchKernelGGL(k_incidence_fill, mesh_launch_grid(n4), dim3(MESH_THREADS), 0, stream, tetrahedra, n4, L.cursor, entries_out);
     }
     return dgnn_check_launch("vertex_incidence");
 }
@@ -392,27 +379,27 @@ extern "C" int dgnn_vertex_rays(const double* vertices, int64_t n_vertices, cons
                      (n_rays == 0 || (ray_vertex && sensors && ray_tet_out && ray_slot_out && ray_dist_out)),
                  DGNN_E_INVALID, "vertex_rays: bad args");
     const RayLayout L = ray_layout(scratch, n_rays, n_tets, n_vertices);
-    const dim3 block(MT_THREADS);
+    const dim3 block(MESH_THREADS);
     (void)hipMemsetAsync(L.head, 0, sizeof(Head), stream);
     if (n_vertices > 0) (void)hipMemsetAsync(L.first, 0x7f, sizeof(int32_t) * n_vertices, stream);   // 0x7f7f7f7f: above every ray index
-    if (n_tets > 0) hipLaunchKernelGGL(k_check_tets, mt_grid(4 * n_tets), block, 0, stream, tetrahedra, 4 * n_tets, n_vertices, &L.head->st);
-    if (n_rays > 0) hipLaunchKernelGGL(k_ray_first, mt_grid(n_rays), block, 0, stream, ray_vertex, n_rays, n_vertices, unique, L.first, &L.head->st);
+    if (n_tets > 0) hipLaunchKernelGGL(k_check_ids, mesh_launch_grid(4 * n_tets), block, 0, stream, tetrahedra, 4 * n_tets, n_vertices, &L.head->st.err, MT_BAD_ID);
+    if (n_rays > 0) hipLaunchKernelGGL(k_ray_first, mesh_launch_grid(n_rays), block, 0, stream, ray_vertex, n_rays, n_vertices, unique, L.first, &L.head->st);
     MtState hs{};
     int rc = mt_read_status(&hs, &L.head->st, stream, "vertex_rays");
     if (rc) return rc;
     if (n_rays > 0)
-        hipLaunchKernelGGL(k_rays, mt_grid(n_rays), block, 0, stream, vertices, n_vertices, tetrahedra, n_tets, rowptr, entries, ray_vertex, sensors, n_rays,
+        hipLaunchKernelGGL(k_rays, mesh_launch_grid(n_rays), block, 0, stream, vertices, n_vertices, tetrahedra, n_tets, rowptr, entries, ray_vertex, sensors, n_rays,
                            unique, L.first, ray_tet_out, ray_slot_out, ray_dist_out, L.head->counters, &L.head->st);
     for (int side = 0; side < SF_SIDES && n_tets > 0; ++side) {
         int cur = 0;
         if (n_rays > 0) {
-            hipLaunchKernelGGL(k_ray_keys, mt_grid(n_rays), block, 0, stream, ray_tet_out, n_rays, side, n_tets, L.keys[0], L.vals[0]);
+            hipLaunchKernelGGL(k_ray_keys, mesh_launch_grid(n_rays), block, 0, stream, ray_tet_out, n_rays, side, n_tets, L.keys[0], L.vals[0]);
             if ((rc = dgnn_radix_sort_u64_i32(L.keys, L.vals, n_rays, key_bits(n_tets + 1), L.hist, L.scanned, L.sums, stream, &cur))) return rc;
         }
         (void)hipMemsetAsync(L.run_begin, 0, sizeof(int32_t) * n_tets, stream);          // a tet without rays: an empty run
         (void)hipMemsetAsync(L.run_end, 0, sizeof(int32_t) * n_tets, stream);
-        if (n_rays > 0) hipLaunchKernelGGL(k_ray_runs, mt_grid(n_rays), block, 0, stream, L.keys[cur], n_rays, n_tets, L.run_begin, L.run_end);
-        hipLaunchKernelGGL(k_ray_fold, mt_grid(n_tets), block, 0, stream, L.vals[cur], L.run_begin, L.run_end, n_tets, side, ray_slot_out, ray_dist_out,
+        if (n_rays > 0) hipLaunchKernelGGL(k_ray_runs, mesh_launch_grid(n_rays), block, 0, stream, L.keys[cur], n_rays, n_tets, L.run_begin, L.run_end);
+        hipLaunchKernelGGL(k_ray_fold, mesh_launch_grid(n_tets), block, 0, stream, L.vals[cur], L.run_begin, L.run_end, n_tets, side, ray_slot_out, ray_dist_out,
                            tet_count_out + side * n_tets, tet_stat_out + side * 3 * n_tets, slot_count_out + side * 4 * n_tets,
                            slot_stat_out + side * 12 * n_tets);
     }

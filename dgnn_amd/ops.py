@@ -1680,7 +1680,7 @@ def binary_graph_cut(logits, edges, unary_weight, binary_weight, return_stats=Fa
     if logits.stride(1) != 1:
         logits = logits.contiguous()
     n, f = logits.size(0), edges.size(0)
-    labels = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    labels = _empty(dev, torch.int32, n)
     out64 = torch.zeros(2, dtype=torch.int64, device=dev)
     stats = torch.zeros(2, dtype=torch.int32, device=dev)
     scratch = torch.empty(int(lib().dgnn_graph_cut_scratch_bytes(n, f)), dtype=torch.uint8, device=dev)
@@ -1721,7 +1721,7 @@ def weighted_graph_cut(logits, edges, unary_weight, row_weights, return_stats=Fa
     if logits.stride(1) != 1:
         logits = logits.contiguous()
     n, f = logits.size(0), edges.size(0)
-    labels = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    labels = _empty(dev, torch.int32, n)
     out64 = torch.zeros(2, dtype=torch.int64, device=dev)
     stats = torch.zeros(2, dtype=torch.int32, device=dev)
     scratch = torch.empty(int(lib().dgnn_graph_cut_weighted_scratch_bytes(n, f)), dtype=torch.uint8, device=dev)
@@ -1762,8 +1762,8 @@ def facet_cut_terms(vertices, tetrahedra, facets, nfacets, kind, binary_weight, 
     if fac.size(0) != nfac.size(0):
         raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
     f = fac.size(0)
-    w = torch.empty(max(f, 1), dtype=torch.int32, device=dev)[:f]
-    q = torch.empty(max(f, 1), dtype=torch.float64, device=dev)[:f] if return_q else None
+    w = _empty(dev, torch.int32, f)
+    q = _empty(dev, torch.float64, f) if return_q else None
     stats = torch.zeros(4, dtype=torch.int64, device=dev)
     scratch = torch.empty(int(lib().dgnn_facet_cut_terms_scratch_bytes(f)), dtype=torch.uint8, device=dev)
     check(lib().dgnn_facet_cut_terms(ptr(v), v.size(0), ptr(tets), tets.size(0), ptr(fac), ptr(nfac), f, CUT_TERM_KINDS[kind], bw, ptr(q), ptr(w),
@@ -1791,6 +1791,13 @@ def _on(x, dev, dtype, cols=None):
     return t
 
 
+def _empty(dev, dtype, *shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return torch.empty(max(n, 1), dtype=dtype, device=dev)[:n].view(*shape)
+
+
 @on_device_of
 def locate_points(vertices, tetrahedra, facets, nfacets, points, return_steps=False):
     """The finite cell of `<scene>_3dt.npz` that contains each point (dgnn_locate_points): vertices fp64 [V, 3], tetrahedra int [N, 4],
@@ -1806,7 +1813,7 @@ def locate_points(vertices, tetrahedra, facets, nfacets, points, return_steps=Fa
     if fac.size(0) != nfac.size(0):
         raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
     n_p, n_c = pts.size(0), tets.size(0)
-    cells = torch.empty(max(n_p, 1), dtype=torch.int32, device=dev)[:n_p]
+    cells = _empty(dev, torch.int32, n_p)
     steps = torch.zeros(1, dtype=torch.int32, device=dev)
     scratch = torch.empty(int(lib().dgnn_locate_scratch_bytes(n_c)), dtype=torch.uint8, device=dev)
     check(lib().dgnn_locate_points(ptr(v), v.size(0), ptr(tets), n_c, ptr(fac), ptr(nfac), fac.size(0), ptr(pts), n_p, ptr(cells), ptr(steps),
@@ -1825,7 +1832,7 @@ def iou_counts(cells, labels, occ_gt):
     if occ.numel() != cells.numel():
         raise ValueError("%d occupancies for %d points" % (occ.numel(), cells.numel()))
     n = cells.numel()
-    out = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    out = _empty(dev, torch.int32, n)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
     scratch = torch.empty(256, dtype=torch.uint8, device=dev)
     check(lib().dgnn_mesh_iou_counts(ptr(cells), n, ptr(labels), labels.numel(), ptr(occ), ptr(out), ptr(counts), ptr(scratch), stream_ptr()),
@@ -1860,9 +1867,9 @@ def sample_interface(vertices, facets, face_ids, n_samples, seed=0, return_cum=F
     ids = None if face_ids is None else _on(face_ids, dev, torch.int32).reshape(-1)
     nfc = fac.size(0) if ids is None else ids.numel()
     n = int(n_samples)
-    pts = torch.empty(max(n, 1), 3, dtype=torch.float32, device=dev)[:n]
-    face = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
-    cum = torch.empty(max(nfc, 1), dtype=torch.float64, device=dev)[:nfc]
+    pts = _empty(dev, torch.float32, n, 3)
+    face = _empty(dev, torch.int32, n)
+    cum = _empty(dev, torch.float64, nfc)
     scratch = torch.empty(int(lib().dgnn_sample_faces_scratch_bytes(nfc)), dtype=torch.uint8, device=dev)
     check(lib().dgnn_sample_faces(ptr(v), v.size(0), ptr(fac), fac.size(0), ptr(ids), nfc, n, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(pts), ptr(face),
                                   ptr(cum) if nfc else None, ptr(scratch), stream_ptr()), "dgnn_sample_faces")
@@ -1879,8 +1886,8 @@ def nearest_neighbor(ref, query):
     nr, nq = r.size(0), q.size(0)
     if nr == 0:
         raise ValueError("nearest_neighbor: the reference set is empty")
-    dist = torch.empty(max(nq, 1), dtype=torch.float32, device=dev)[:nq]
-    idx = torch.empty(max(nq, 1), dtype=torch.int32, device=dev)[:nq]
+    dist = _empty(dev, torch.float32, nq)
+    idx = _empty(dev, torch.int32, nq)
     total = torch.zeros(1, dtype=torch.float64, device=dev)
     scratch = torch.empty(int(lib().dgnn_nearest_scratch_bytes(nr, nq)), dtype=torch.uint8, device=dev)
     check(lib().dgnn_nearest_neighbor(ptr(r), nr, ptr(q), nq, ptr(dist), ptr(idx), ptr(total), ptr(scratch), stream_ptr()), "dgnn_nearest_neighbor")
@@ -1914,7 +1921,7 @@ def orient_interface(vertices, tetrahedra, facets, nfacets, labels, face_ids, or
     if lab.numel() != tets.size(0):
         raise ValueError("%d labels for %d cells" % (lab.numel(), tets.size(0)))
     k = ids.numel()
-    faces = torch.empty(max(k, 1), 3, dtype=torch.int32, device=dev)[:k]
+    faces = _empty(dev, torch.int32, k, 3)
     und = torch.zeros(1, dtype=torch.int64, device=dev)
     used = torch.zeros(1, dtype=torch.int32, device=dev)
     scratch = torch.empty(int(lib().dgnn_orient_interface_scratch_bytes()), dtype=torch.uint8, device=dev)
@@ -1930,7 +1937,7 @@ def compact_vertices(faces, n_vertices):
     dev = _dev_of(faces)
     f = _on(faces, dev, torch.int32, 3)
     nv, k = int(n_vertices), f.size(0)
-    out = torch.empty(max(k, 1), 3, dtype=torch.int32, device=dev)[:k]
+    out = _empty(dev, torch.int32, k, 3)
     kept = torch.empty(max(nv, 1), dtype=torch.int32, device=dev)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
     scratch = torch.empty(int(lib().dgnn_compact_vertices_scratch_bytes(nv)), dtype=torch.uint8, device=dev)
@@ -1966,7 +1973,7 @@ def mesh_components(faces, n_vertices):
     dev = _dev_of(faces)
     f = _on(faces, dev, torch.int32, 3)
     nv, k = int(n_vertices), f.size(0)
-    comp = torch.empty(max(k, 1), dtype=torch.int32, device=dev)[:k]
+    comp = _empty(dev, torch.int32, k)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
     scratch = torch.empty(max(int(lib().dgnn_mesh_components_scratch_bytes(k)), 1), dtype=torch.uint8, device=dev)
     check(lib().dgnn_mesh_components(ptr(f), k, nv, ptr(comp), ptr(cnt), ptr(scratch), stream_ptr()), "dgnn_mesh_components")
@@ -2027,13 +2034,6 @@ def filter_components(faces, comp, counts, largest=False, min_faces=None):
 
 
 # ---- the scene front end: adjacency, cell geometry, vertex-ray visibility (csrc/scenefeat.hip) ---------------------------
-def _empty(dev, dtype, *shape):
-    n = 1
-    for s in shape:
-        n *= s
-    return torch.empty(max(n, 1), dtype=dtype, device=dev)[:n].view(*shape)
-
-
 @on_device_of
 def tet_neighbors(facets, nfacets, tetrahedra):
     """neighbors int32 [T, 4] on the GPU (dgnn_tet_neighbors): slot k = the cell across the facet opposite vertex k of the tet, -1 = the
@@ -2145,6 +2145,20 @@ def _points64(points, dev):
     return _on(t, dev, torch.float64, 3)     # every fp16 / fp32 value is an fp64 value: exact
 
 
+def _planned_entries(dev, what, plan):
+    """The candidate grid's entry list, sized by its planning call: plan(byref(n_entries)) -> status.  -> (entries int32, their number of
+    places, at least one)."""
+    n_entries = C.c_int64(0)
+    _check_value(plan(C.byref(n_entries)), what)
+    cap = max(int(n_entries.value), 1)
+    return torch.empty(cap, dtype=torch.int32, device=dev), cap
+
+
+def _mesh_contains_entries(dev, v, f, R, max_entries, scratch):
+    return _planned_entries(dev, "dgnn_mesh_contains_plan", lambda n: lib().dgnn_mesh_contains_plan(
+        ptr(v), v.size(0), ptr(f), f.size(0), R, int(max_entries), C.byref(C.c_int32(0)), n, ptr(scratch), stream_ptr()))
+
+
 @on_device_of
 def mesh_contains(vertices, faces, points, hash_resolution=512, max_entries=2 ** 30):
     """check_mesh_contains(mesh, points, hash_resolution) of the reference's utils/libmesh on the device (dgnn_mesh_contains; the
@@ -2160,15 +2174,11 @@ def mesh_contains(vertices, faces, points, hash_resolution=512, max_entries=2 **
     nv, nf, n, R = v.size(0), f.size(0), pts.size(0), int(hash_resolution)
     if nf == 0:
         raise ValueError("mesh_contains: a mesh without faces")
-    out = torch.empty(max(n, 1), dtype=torch.bool, device=dev)[:n]
+    out = _empty(dev, torch.bool, n)
     if n == 0:
         return out, 0
     scratch = torch.empty(int(lib().dgnn_mesh_contains_scratch_bytes(nv, nf, R)), dtype=torch.uint8, device=dev)
-    shift, n_entries = C.c_int32(0), C.c_int64(0)
-    _check_value(lib().dgnn_mesh_contains_plan(ptr(v), nv, ptr(f), nf, R, int(max_entries), C.byref(shift), C.byref(n_entries), ptr(scratch),
-                                               stream_ptr()), "dgnn_mesh_contains_plan")
-    cap = max(int(n_entries.value), 1)
-    entries = torch.empty(cap, dtype=torch.int32, device=dev)
+    entries, cap = _mesh_contains_entries(dev, v, f, R, max_entries, scratch)
     dis = torch.zeros(1, dtype=torch.int64, device=dev)
     _check_value(lib().dgnn_mesh_contains(ptr(v), nv, ptr(f), nf, R, int(max_entries), ptr(pts), n, ptr(out), ptr(dis), ptr(entries), cap,
                                           ptr(scratch), stream_ptr()), "dgnn_mesh_contains")
@@ -2199,7 +2209,7 @@ def face_normals(vertices, faces):
     v = _on(vertices, dev, torch.float64, 3)
     f = _on(faces, dev, torch.int32, 3)
     nf = f.size(0)
-    out = torch.empty(max(nf, 1), 3, dtype=torch.float64, device=dev)[:nf]
+    out = _empty(dev, torch.float64, nf, 3)
     scratch = torch.empty(256, dtype=torch.uint8, device=dev)
     _check_value(lib().dgnn_face_normals(ptr(v), v.size(0), ptr(f), nf, ptr(out), ptr(scratch), stream_ptr()), "dgnn_face_normals")
     return out
@@ -2215,7 +2225,7 @@ def box_points(n, boxsize, seed=0, device=None):
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     n = int(n)
     with torch.cuda.device(dev):
-        out = torch.empty(max(n, 1), 3, dtype=torch.float64, device=dev)[:n]
+        out = _empty(dev, torch.float64, n, 3)
         check(lib().dgnn_box_points(n, float(boxsize), _seed64(seed), ptr(out), stream_ptr()), "dgnn_box_points")
     return out
 
@@ -2227,7 +2237,7 @@ def jitter_points(points64, sigma, seed=0):
     dev = _dev_of(points64)
     p = _on(points64, dev, torch.float64, 3)
     n = p.size(0)
-    out = torch.empty(max(n, 1), 3, dtype=torch.float64, device=dev)[:n]
+    out = _empty(dev, torch.float64, n, 3)
     check(lib().dgnn_jitter_points(ptr(p), n, float(sigma), _seed64(seed), ptr(out), stream_ptr()), "dgnn_jitter_points")
     return out
 
@@ -2272,12 +2282,8 @@ def cell_labels(mesh_vertices, mesh_faces, vertices, tetrahedra, n_samples=100, 
     if nf == 0:
         raise ValueError("cell_labels: a mesh without faces")
     scratch = torch.empty(int(lib().dgnn_cell_labels_scratch_bytes(nv, nf, R)), dtype=torch.uint8, device=dev)
-    shift, n_entries = C.c_int32(0), C.c_int64(0)
-    _check_value(lib().dgnn_mesh_contains_plan(ptr(mv), nv, ptr(mf), nf, R, int(max_entries), C.byref(shift), C.byref(n_entries), ptr(scratch),
-                                               stream_ptr()), "dgnn_mesh_contains_plan")
-    cap = max(int(n_entries.value), 1)
-    entries = torch.empty(cap, dtype=torch.int32, device=dev)
-    count = _empty(dev, torch.int32, t)
+    entries, cap = _mesh_contains_entries(dev, mv, mf, R, max_entries, scratch)
+    count =_empty(dev, torch.int32, t)
     dis = torch.zeros(1, dtype=torch.int64, device=dev)
     # the mesh passed the plan above: what is refused from here on is the tets' ids
     check(lib().dgnn_cell_labels(ptr(mv), nv, ptr(mf), nf, R, int(max_entries), ptr(entries), cap, ptr(v), v.size(0), ptr(tets), t, k, _seed64(seed),
@@ -2317,10 +2323,8 @@ def ray_first_hit(vertices, faces, origins, aims, t_min=0.0, grid_resolution=Non
         raise ValueError("ray_first_hit: a mesh without faces")
     R = default_grid_resolution(nf) if grid_resolution is None else int(grid_resolution)
     scratch = torch.empty(int(lib().dgnn_ray_first_hit_scratch_bytes(nf, R)), dtype=torch.uint8, device=dev)
-    n_entries = C.c_int64(0)
-    _check_value(lib().dgnn_ray_first_hit_plan(ptr(v), nv, ptr(f), nf, R, C.byref(n_entries), None, ptr(scratch), stream_ptr()), "dgnn_ray_first_hit_plan")
-    cap = max(int(n_entries.value), 1)
-    entries = torch.empty(cap, dtype=torch.int32, device=dev)
+    entries, cap = _planned_entries(dev, "dgnn_ray_first_hit_plan", lambda n_entries: lib().dgnn_ray_first_hit_plan(
+        ptr(v), nv, ptr(f), nf, R, n_entries, None, ptr(scratch), stream_ptr()))
     face, t, point = _empty(dev, torch.int32, n), _empty(dev, torch.float64, n), _empty(dev, torch.float64, n, 3)
     stats = torch.zeros(len(RAY_HIT_STATS), dtype=torch.int64, device=dev)
     _check_value(lib().dgnn_ray_first_hit(ptr(v), nv, ptr(f), nf, R, ptr(o), ptr(g), n, float(t_min), ptr(face), ptr(t), ptr(point), ptr(stats), ptr(entries),

@@ -109,6 +109,35 @@ def test_forced_coarsening_gives_the_same_answer(name):
     assert np.array_equal(_contains(v, f, _adversarial(name), hash_resolution=64)[0], full[0])
 
 
+@pytest.mark.parametrize("large_first", [True, False])
+def test_one_face_over_every_cell_beside_faces_of_one_cell(large_first):
+    """The entry lookup of the grid builder with very unequal boxes: one face spans the whole xy box, so it has R^2 entries, and 20
+    small faces lie in one cell each, at hash_resolution 2, 3 and 8; the large face is the first of the list or the last.  Once with
+    the default max_entries and once with one entry too few for the full grid, which coarsens it."""
+    import ctypes as C
+    from dgnn_amd._lib import lib, ptr, stream_ptr
+    rng = np.random.default_rng(29)
+    # the frame maps [0, 1] to [0.5, R - 0.5] and cells are int(coord): +- 0.02 about these crosses no boundary at R = 2, 3 or 8
+    slots = np.array([0.14, 0.30, 0.43, 0.57, 0.70, 0.86])
+    small = (slots[rng.integers(0, 6, (20, 1, 3))] + rng.uniform(-0.02, 0.02, (20, 3, 3))).reshape(60, 3)
+    v = np.concatenate([np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.5], [0.0, 1.0, 1.0]]), small])
+    f = np.arange(63, dtype=np.int32).reshape(21, 3)
+    if not large_first:
+        f = np.roll(f, -1, axis=0)
+    pts = mc.adversarial_points(v, f, 300, seed=5)
+    vt, ft = torch.from_numpy(v).to(DEV), torch.from_numpy(f).to(DEV)
+    for R in (2, 3, 8):
+        want, want_dis = mc.contains(v, f, pts, R)
+        scratch = torch.empty(int(lib().dgnn_mesh_contains_scratch_bytes(63, 21, R)), dtype=torch.uint8, device=DEV)
+        for cap, coarsened in ((2 ** 30, False), (R * R + 19, True)):
+            shift, ne = C.c_int32(-1), C.c_int64(-1)
+            assert lib().dgnn_mesh_contains_plan(ptr(vt), 63, ptr(ft), 21, R, cap, C.byref(shift), C.byref(ne), ptr(scratch), stream_ptr()) == 0
+            assert (shift.value > 0) == coarsened and (coarsened or ne.value == R * R + 20)
+            got, n_disagree = _contains(v, f, pts, hash_resolution=R, max_entries=cap)
+            print("R=%d max_entries=%d: shift %d, %d entries, %d mismatches" % (R, cap, shift.value, ne.value, (got != want).sum()))
+            assert np.array_equal(got, want) and n_disagree == want_dis
+
+
 @pytest.mark.parametrize("dtype", [np.float16, np.float32, np.float64])
 @pytest.mark.parametrize("as_tensor", [False, True])
 def test_input_types(dtype, as_tensor):

@@ -132,6 +132,35 @@ def test_a_mesh_of_one_face():
         _same(_cast(mesh, o, g, grid_resolution=R), want)
 
 
+@pytest.mark.parametrize("large_first", [True, False])
+def test_one_face_over_every_cell_beside_faces_of_one_cell(large_first):
+    """The entry lookup of the grid builder with very unequal boxes: one face spans the whole box [0, 1]^3, so it has R^3 entries, and
+    20 small faces lie in one cell each, at 1, 2, 3 and 7 cells per axis; the large face is the first of the list or the last, which puts
+    its run of entries at either end of the offsets the lookup searches."""
+    import ctypes as C
+    from dgnn_amd._lib import lib, ptr, stream_ptr
+    rng = np.random.default_rng(23)
+    slots = np.array([0.07, 0.21, 0.38, 0.62, 0.79, 0.93])          # +- 0.03 crosses no cell boundary k / 2, k / 3 or k / 7
+    small = (slots[rng.integers(0, 6, (20, 1, 3))] + rng.uniform(-0.03, 0.03, (20, 3, 3))).reshape(60, 3)
+    v = np.concatenate([np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 1.0], [0.0, 1.0, 1.0]]), small])
+    f = np.arange(63, dtype=np.int32).reshape(21, 3)
+    if not large_first:
+        f = np.roll(f, -1, axis=0)
+    centroids = v[f].mean(axis=1)
+    o = np.concatenate([np.repeat(centroids, 8, axis=0) + rng.choice([-2.0, 2.0], (168, 3)) * rng.uniform(0.8, 1.2, (168, 3)),
+                        rng.uniform(-1.0, 2.0, (160, 3))])
+    g = np.concatenate([np.repeat(centroids, 8, axis=0) + rng.uniform(-0.005, 0.005, (168, 3)), rng.uniform(0.0, 1.0, (160, 3))])
+    want = rc.first_hit(v, f, o, g)
+    assert {0, 20} <= set(want[0].tolist()) and want[3]["hits"] < len(o)          # the first and the last face are hit, and some rays miss
+    vt, ft = torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda()
+    for R in (1, 2, 3, 7):
+        scratch = torch.empty(int(lib().dgnn_ray_first_hit_scratch_bytes(21, R)), dtype=torch.uint8, device=vt.device)
+        ne = C.c_int64(-1)
+        assert lib().dgnn_ray_first_hit_plan(ptr(vt), 63, ptr(ft), 21, R, C.byref(ne), None, ptr(scratch), stream_ptr()) == 0
+        assert ne.value == R ** 3 + 20
+        _same(_cast((v, f), o, g, grid_resolution=R), want)
+
+
 # ---- exact zeros -------------------------------------------------------------------------------------------------------------------
 def _zero_rays(name):
     """aims at every vertex and every edge midpoint, from three origins each"""
