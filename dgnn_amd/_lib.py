@@ -122,6 +122,9 @@ SIGNATURES = {
     "dgnn_vertex_incidence": (i32, [vp, i64, i64, vp, vp, vp, vp]),
     "dgnn_vertex_rays_scratch_bytes": (i64, [i64, i64, i64]),
     "dgnn_vertex_rays": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dgnn_ray_walk_timing": (i32, [i32, vp]),
+    "dgnn_ray_walk_scratch_bytes": (i64, [i64, i64, i64, i64]),
+    "dgnn_ray_walk": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
     "dgnn_mesh_contains_scratch_bytes": (i64, [i64, i64, i32]),
     "dgnn_mesh_contains_plan": (i32, [vp, i64, vp, i64, i32, i64, vp, vp, vp, vp]),
     "dgnn_mesh_contains": (i32, [vp, i64, vp, i64, i32, i64, vp, i64, vp, vp, vp, i64, vp, vp]),

@@ -11,7 +11,7 @@ int dgnn_radix_sort_u64_i32(uint64_t* const keys[2], int32_t* const vals[2], int
 namespace {
 
 // status bits
-constexpr int32_t MT_BAD_ID = 1, MT_NONFINITE = 2, MT_NOT_FACE = 4, MT_NOT_INTERFACE = 8, MT_RANGE = 16, MT_DEGENERATE = 32;
+constexpr int32_t MT_BAD_ID = 1, MT_NONFINITE = 2, MT_NOT_FACE = 4, MT_NOT_INTERFACE = 8, MT_RANGE = 16, MT_DEGENERATE = 32, MT_PASSES = 64;
 
 struct MtState {
     int32_t err, exact_used, pad[2];
@@ -76,11 +76,12 @@ int mt_read_status(MtState* hs, const MtState* st, hipStream_t stream, const cha
     if (rc || (rc = mm_read(hs, st, sizeof(MtState), stream, what))) return rc;
     if (!hs->err) return DGNN_OK;
     const int32_t e = hs->err;
-    dgnn_set_error("%s: %s%s%s%s%s%s", what, e & MT_BAD_ID ? "an id out of range; " : "", e & MT_NONFINITE ? "non-finite coordinates; " : "",
+    dgnn_set_error("%s: %s%s%s%s%s%s%s", what, e & MT_BAD_ID ? "an id out of range; " : "", e & MT_NONFINITE ? "non-finite coordinates; " : "",
                    e & MT_NOT_FACE ? "a facet that is not a face of the cell nfacets names; " : "",
                    e & MT_NOT_INTERFACE ? "a facet that does not separate an inside cell from an outside one; " : "",
                    e & MT_RANGE ? "a coordinate magnitude outside [2^-300, 2^300] (the exact predicate's range); " : "",
-                   e & MT_DEGENERATE ? "a face with a repeated vertex; " : "");
+                   e & MT_DEGENERATE ? "a face with a repeated vertex; " : "",
+                   e & MT_PASSES ? "the counting and the filling pass disagree (the inputs changed during the call?); " : "");
     return e == MT_RANGE ? DGNN_E_UNSUPPORTED : DGNN_E_INVALID;
 }
 

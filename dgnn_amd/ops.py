@@ -2130,6 +2130,74 @@ def vertex_ray_features(vertices, tetrahedra, ray_vertex, sensors, unique=True, 
     return out
 
 
+# ---- the facet-ray walk: every ray through all the cells it crosses (csrc/raywalk.hip) -------------------------------------
+WALK_STATUS = ("none", "sensor", "hull", "depth", "stuck", "capped")
+WALK_STATS = ("used", "skipped", "perturbed", "exact_used", "degenerate") + WALK_STATUS + ("records", "longest")
+WALK_RECORD_KEYS = ("ray", "side", "step", "cell", "slot", "first", "second")
+WALK_DEFAULT_RECORDS = 1 << 22          # records staged at a time: 48 bytes each plus the sort's histograms
+
+
+@on_device_of
+def ray_walk(vertices, tetrahedra, neighbors, ray_vertex, sensors, unique=True, outside_depth=0, inside_depth=1, max_records=None, incidence=None,
+             return_records=False):
+    """Walks every ray through the triangulation (dgnn_ray_walk; the rule -- the perturbed side test, the start cells, the steps and the
+    ends -- is in include/dgnn_hip.h).  Ray r runs from vertices[ray_vertex[r]] to sensors[r] (fp64 [R, 3]); side `outside` walks towards
+    the sensor, `inside` away from it, through neighbors int [T, 4] (ops.tet_neighbors: -1 = the infinite cell).  The start cell is the
+    vertex family's and is not recorded; outside_depth / inside_depth end a walk after that many recorded cells (0: no limit).
+    max_records bounds the staged record stream (None: WALK_DEFAULT_RECORDS, or T + 1 when that is more -- no walk is longer); no result
+    depends on it.  incidence: the pair of vertex_incidence (built here when None).  -> dict of tensors on the GPU, <side> in RAY_SIDES:
+      "<side>_cell_count" int32 [T], "<side>_cell_{first,second}_{min,max,sum}" fp64 [T]: over the recorded crossings of the cell, the
+      distance from the ray's vertex to where it enters (first) and leaves (second; in the sensor's cell the sensor's distance);
+      "<side>_slot_count" int32 [T, 4], "<side>_slot_{min,max,sum}" fp64 [T, 4]: per facet (c, k) of the cell the ray leaves;
+      "ray_status" int32 [R, 2] (index into WALK_STATUS), "ray_cells" int32 [R, 2]; "stats": dict of WALK_STATS -> int;
+      with return_records "records": dict of WALK_RECORD_KEYS -> tensor, ascending (ray, side, step) (the walk then runs twice).
+    DgnnError for ids out of range, coordinates outside the exact predicate's range and a max_records below the longest walk."""
+    dev = _dev_of(ray_vertex, sensors, vertices, tetrahedra)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    nbr = _on(neighbors, dev, torch.int32, 4)
+    rv = _on(ray_vertex, dev, torch.int32).reshape(-1)
+    s = _on(sensors, dev, torch.float64, 3)
+    if s.size(0) != rv.numel():
+        raise ValueError("%d sensor positions for %d rays" % (s.size(0), rv.numel()))
+    t, r, nv = tets.size(0), rv.numel(), v.size(0)
+    if nbr.size(0) != t:
+        raise ValueError("%d neighbour rows for %d tets" % (nbr.size(0), t))
+    rowptr, entries = vertex_incidence(tets, nv) if incidence is None else (_on(incidence[0], dev, torch.int32), _on(incidence[1], dev, torch.int32))
+    if rowptr.numel() != nv + 1 or entries.numel() != 4 * t:
+        raise ValueError("incidence of %d vertices and %d corners for %d vertices and %d tets" % (rowptr.numel() - 1, entries.numel(), nv, t))
+    m = max(WALK_DEFAULT_RECORDS, t + 1) if max_records is None else int(max_records)
+    nbytes = int(lib().dgnn_ray_walk_scratch_bytes(r, t, nv, m))
+    if nbytes <= 0:
+        raise DgnnError("ray_walk: %d rays, %d tets, max_records %d exceed the int32 indexing" % (r, t, m))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def run(capacity):
+        status, cells = _empty(dev, torch.int32, r, 2), _empty(dev, torch.int32, r, 2)
+        cell_count, cell_stat = _empty(dev, torch.int32, 2, t), _empty(dev, torch.float64, 2, 6, t)
+        slot_count, slot_stat = _empty(dev, torch.int32, 2, t, 4), _empty(dev, torch.float64, 2, 3, t, 4)
+        stats = torch.zeros(len(WALK_STATS), dtype=torch.int64, device=dev)
+        ids, dist = _empty(dev, torch.int32, 5, capacity), _empty(dev, torch.float64, 2, capacity)
+        check(lib().dgnn_ray_walk(ptr(v), nv, ptr(tets), t, ptr(nbr), ptr(rowptr), ptr(entries), ptr(rv), ptr(s), r, int(bool(unique)), int(outside_depth),
+                                  int(inside_depth), m, ptr(status), ptr(cells), ptr(cell_count), ptr(cell_stat), ptr(slot_count), ptr(slot_stat),
+                                  ptr(stats), capacity, ptr(ids), ptr(dist), ptr(scratch), stream_ptr()), "dgnn_ray_walk")
+        out = {"ray_status": status, "ray_cells": cells, "stats": dict(zip(WALK_STATS, (int(x) for x in stats.cpu())))}
+        for i, side in enumerate(RAY_SIDES):
+            out[side + "_cell_count"], out[side + "_slot_count"] = cell_count[i], slot_count[i]
+            for j, stat in enumerate(("min", "max", "sum")):
+                out["%s_cell_first_%s" % (side, stat)], out["%s_cell_second_%s" % (side, stat)] = cell_stat[i, j], cell_stat[i, 3 + j]
+                out["%s_slot_%s" % (side, stat)] = slot_stat[i, j]
+        if capacity:
+            out["records"] = dict(zip(WALK_RECORD_KEYS, list(ids) + list(dist)))
+        return out
+
+    out = run(0)
+    if return_records:          # the stream's length is known only after a walk
+        n = out["stats"]["records"]
+        out = run(n) if n else dict(out, records=dict(zip(WALK_RECORD_KEYS, list(_empty(dev, torch.int32, 5, 0)) + list(_empty(dev, torch.float64, 2, 0)))))
+    return out
+
+
 # ---- occupancy of any triangle mesh and the evaluation-sample generators (csrc/meshcontains.hip; reference utils/libmesh) ----------
 def _check_value(code, what):
     """`check`, with the library's "bad input" status as the ValueError a Python caller expects for bad data"""

@@ -1,10 +1,12 @@
 """Scene preparation on the device: from a triangulation (`<scene>_3dt.npz`) and a scan (points + sensor positions) to the model's input
-files `<scene>_cgeom.npz`, `<scene>_cbvf.npz`, `<scene>_fbvf.npz`.
+files `<scene>_cgeom.npz`, `<scene>_cbvf.npz`, `<scene>_fbvf.npz` and, with facet_rays, `<scene>_cbff.npz`, `<scene>_fbff.npz` (§29).
 
 The reference gets these files from an external binary; their definitions here are the ones that reproduce its recorded output for
-Ignatius scene 99 (counts and edge lengths exactly, the other columns to the last bits).  The facet-ray files (`_cbff`, `_fbff`) and `_fgeom`
-are not built.  The training target `<scene>_labels.npz` comes from build_cell_labels and a closed ground-truth mesh; the
-binary's own sample count and generator are not known, so its labels are a definition of this package's, not a reproduction.
+Ignatius scene 99 (counts and edge lengths exactly, the other columns to the last bits).  The facet-ray files (`_cbff`, `_fbff`) hold the
+aggregates of ops.ray_walk, every ray followed through all the cells it crosses: the binary's own walk cannot be recovered from its files
+(§25), so the rule is this package's definition (§29), not a reproduction.  `_fgeom` is not built.  The training target
+`<scene>_labels.npz` comes from build_cell_labels and a closed ground-truth mesh; the binary's own sample count and generator
+are not known, so its labels are a definition of this package's, not a reproduction.
 
 Rows: the cells of a scene are its finite tets in `tetrahedra` order with the infinite cells interleaved where `infinite` is 1; finite
 cell number r is tet r.  Infinite cells hold 0 in every column.  Edge row 4 c + k belongs to the facet of cell c opposite its vertex k (the
@@ -20,6 +22,7 @@ from .. import ops
 CGEOM_KEYS = ("radius", "vol", "longest_edge", "shortest_edge")
 VF_GROUPS = ("inside", "outside", "last")          # the files' key order; `last` holds 0 everywhere
 VF_STATS = ("count", "dist_min", "dist_max", "dist_sum")
+FF_CELL_GROUPS = tuple("%s_%s" % (g, w) for g in VF_GROUPS for w in ("first", "second"))          # the key order of `_cbff.npz`
 
 
 def match_vertices(vertices, points):
@@ -36,7 +39,7 @@ def match_vertices(vertices, points):
     return np.where(kv[order][pos] == kp, order[pos], -1).astype(np.int64)
 
 
-def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base=None, device=None):
+def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base=None, device=None, facet_rays=False, outside_depth=0, inside_depth=1):
     """mdata: the arrays of `<scene>_3dt.npz` (vertices, tetrahedra, facets, nfacets); infinite [n_cells]: 1 = infinite cell (the
     `infinite` of `_labels.npz`); scan_points, sensor_position [P, 3]: every point that equals a vertex casts that vertex's ray towards its
     sensor, points that share a vertex cast one ray (the lowest-index point's).  Runs ops.tet_neighbors / cell_geometry / vertex_ray_features on
@@ -44,7 +47,11 @@ def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base
       "cgeom", "cbvf", "fbvf": key -> fp64 ndarray, with the reference files' keys in their order ([n_cells] / [4 n_cells] rows);
       "neighbors": int64 ndarray [n_cells, 4], the cell across each facet of the finite cells (-1: an infinite cell; infinite rows: -1);
       "mean_edge": the loader's mean_edge, "stats": the ray stats plus "points", "unmatched_points", "n_flat".
-    With out_base the three files are written as out_base + "_cgeom.npz" etc., readable by the reference's and this package's dataLoader."""
+    With facet_rays also ops.ray_walk(outside_depth, inside_depth) over the same rays, and in the result
+      "cbff": cb_facet_{inside,outside,last}_{first,second}_{count,dist_min,dist_max,dist_sum} [n_cells]: per cell the distances at which the
+      rays that cross it (after their start cell) enter and leave; "fbff": fb_facet_{inside,outside,last}_... [4 n_cells]: per facet of the
+      cell a ray leaves; the `last` groups hold 0, as the vertex family's do; "walk_stats": the stats of ops.ray_walk.
+    With out_base the files are written as out_base + "_cgeom.npz" etc., readable by the reference's and this package's dataLoader."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     inf = np.asarray(infinite).astype(bool).reshape(-1)
     cell_of_tet = np.nonzero(~inf)[0]
@@ -62,7 +69,9 @@ def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base
     tets = torch.as_tensor(np.asarray(mdata["tetrahedra"])).to(dev, torch.int32)
     nbr = ops.tet_neighbors(torch.as_tensor(np.asarray(mdata["facets"])).to(dev), torch.as_tensor(np.asarray(mdata["nfacets"])).to(dev), tets)
     geom = ops.cell_geometry(v, tets)
-    rays = ops.vertex_ray_features(v, tets, torch.from_numpy(vid[hit]).to(dev), torch.from_numpy(sensors[hit]).to(dev))
+    ray_vertex, ray_sensor = torch.from_numpy(vid[hit]).to(dev), torch.from_numpy(sensors[hit]).to(dev)
+    incidence = ops.vertex_incidence(tets, v.size(0))
+    rays = ops.vertex_ray_features(v, tets, ray_vertex, ray_sensor, incidence=incidence)
 
     def cell_col(t):
         col = np.zeros((n_cells,) + tuple(t.shape[1:]))
@@ -87,8 +96,21 @@ def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base
         print("build_scene_features: %d of %d scan points match no vertex of the triangulation and cast no ray" % (stats["unmatched_points"], len(vid)))
     out = {"cgeom": cgeom, "cbvf": files["cb"], "fbvf": files["fb"], "neighbors": neighbors, "stats": stats,
            "mean_edge": (geom["sum_longest"] + geom["sum_shortest"]) / (2 * n_cells) if n_cells else float("nan")}
+    names = ["cgeom", "cbvf", "fbvf"]
+    if facet_rays:
+        walk = ops.ray_walk(v, tets, nbr, ray_vertex, ray_sensor, outside_depth=outside_depth, inside_depth=inside_depth, incidence=incidence)
+        out["cbff"], out["fbff"], out["walk_stats"] = {}, {}, walk["stats"]
+        for g in FF_CELL_GROUPS:
+            for s in VF_STATS:
+                side, which = g.split("_")
+                col = np.zeros(n_cells) if side == "last" else cell_col(walk["%s_cell_%s" % (side, "count" if s == "count" else which + s[4:])])
+                out["cbff"]["cb_facet_%s_%s" % (g, s)] = col
+        for g in VF_GROUPS:
+            for s in VF_STATS:
+                out["fbff"]["fb_facet_%s_%s" % (g, s)] = np.zeros(4 * n_cells) if g == "last" else cell_col(walk["%s_slot_%s" % (g, s.replace("dist_", ""))])
+        names += ["cbff", "fbff"]
     if out_base is not None:
-        for name in ("cgeom", "cbvf", "fbvf"):
+        for name in names:
             np.savez(out_base + "_%s.npz" % name, **out[name])
     return out
 

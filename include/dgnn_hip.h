@@ -1143,6 +1143,69 @@ int dgnn_vertex_rays(const double* vertices, int64_t n_vertices, const int32_t* 
                      double* slot_stat_out, int64_t* stats_out, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The facet-ray walk (`_cbff`, `_fbff`): every ray of dgnn_vertex_rays followed through ALL the cells it crosses.  DESIGN.md section 29.
+ * The rule is this package's own definition (the reference binary's walk is not known).  vertices, tetrahedra, rowptr / entries, ray_vertex,
+ * sensors and unique as for dgnn_vertex_rays; neighbors int32 [n_tets, 4] as dgnn_tet_neighbors writes it (-1 = the infinite cell).  fp64,
+ * every operation rounded on its own; orient(a, b, c, x) = sign det[b - a, c - a, x - a], EXACT (csrc/exact_orient.h).  SYNCHRONISES `stream`.
+ *
+ *   ray       from p = vertices[ray_vertex[r]] to s = sensors[r].  Skipped: s == p, and with unique != 0 every ray but the lowest-index one
+ *             of its vertex.  Lane (r, side): side 0 (`outside`) walks from p towards s, side 1 (`inside`) from p away from s.
+ *   sigma     the side of the ray's line against an edge (u, v): sigma(u, v) = sign det[s' - p, u - p, v - p] with the symbolically perturbed
+ *             sensor s' = s + (eps, eps^2, eps^3), i.e. the first non-zero of
+ *               orient(p, s, u, v), orient(p, px, u, v), orient(p, py, u, v), orient(p, pz, u, v)
+ *             where pa is p with its coordinate a replaced by up(a) = 0 for a < 0, 1 for a == 0, 2 a for a > 0 (a representable point
+ *             straight above p on that axis, so the sign is that of det[e_a, u - p, v - p]).  Later terms are evaluated only when the earlier
+ *             ones are 0.  sigma is 0 only when p, u, v are collinear, it is antisymmetric, and it depends on coordinates alone.
+ *   crossed   a facet (a, b, c) is crossed with sign +1 when sigma(a,b), sigma(b,c), sigma(c,a) are all >= 0 and not all 0, with sign -1
+ *             when all <= 0 and not all 0.
+ *   start     over the tets incident to p (p at slot k, the others q0, q1, q2 in slot order): D = orient(p, q0, q1, q2), then sigma(q0,q1),
+ *             sigma(q1,q2), sigma(q2,q0).  A tet with D != 0 whose facet is crossed with sign D starts side 0, with sign -D side 1; per
+ *             side the lowest such tet index.  None: status `none`.  The exit facet is f = (q0, q1, q2) with its three signs, exit slot k.
+ *   loop      in cell c with exit slot k, exit facet f = (f0, f1, f2) and sg = (sigma(f0,f1), sigma(f1,f2), sigma(f2,f0)):
+ *             1. side 0 only: when orient(f0, f1, f2, s) differs from the crossing sign of sg, s is not strictly beyond the facet: the walk
+ *                ends (`sensor`); a cell other than the start cell is recorded with slot -1 and second = sqrt(e . e), e = s - p.
+ *             2. dist = n . (q0 - p) / (n . d), n = (q1 - q0) x (q2 - q0) with q0, q1, q2 the vertices of c other than slot k in slot order,
+ *                d = e / sqrt(e . e) per component, negated for side 1 (dgnn_vertex_rays' dist).  n . d == 0 or a non-finite dist: dist =
+ *                the previous crossing's dist (0 before the first), counted in stats.
+ *             3. a cell other than the start cell is recorded with slot k and second = dist; when the side's depth is non-zero and that many
+ *                cells are recorded, the walk ends (`depth`).
+ *             4. m = neighbors[c][k]; m == -1 ends the walk (`hull`); more than n_tets steps end it (`capped`).
+ *             5. in m, w = its one vertex not in f (none or several: DGNN_E_INVALID).  a_i = sigma(w, f_i), i = 0, 1, 2.  The facet opposite
+ *                f_i is (w, f_i+1, f_i+2) with the signs (a_i+1, sg_i+1, -a_i+2) (indices mod 3).  Not exactly one of the three crossed: the
+ *                walk ends (`stuck`, m is not recorded).  Otherwise c = m, first = dist, k = the slot of f_i in m, f and sg = that facet and
+ *                its signs; back to 1.
+ *   records   one per recorded cell, in ascending (ray, side, step): cell, slot (-1 in the sensor's cell), first (the distance from p to the
+ *             entry crossing = the dist of the cell before), second.  record_ids_out int32 [5, records_capacity] = ray, side, step, cell,
+ *             slot and record_dist_out fp64 [2, records_capacity] = first, second (records_capacity == 0: not written; else it must hold
+ *             every record).
+ *   per cell  cell_count_out int32 [2, n_tets]; cell_stat_out fp64 [2, 6, n_tets] = min, max, sum of first, then of second, over the records
+ *             of the cell on that side; slot_count_out int32 [2, n_tets, 4], slot_stat_out fp64 [2, 3, n_tets, 4] = the same of second over
+ *             the records with that cell and slot >= 0 (edge row 4 c + k of the cell the ray LEAVES, as in `_fbvf`).  min and max are 0 where
+ *             the count is 0; the sums add from 0.0 in ascending (ray, step).  No floating-point atomics: bit-identical from run to run and
+ *             for every max_records.
+ *   per lane  ray_status_out int32 [n_rays, 2]: 0 none, 1 sensor, 2 hull, 3 depth, 4 stuck, 5 capped; ray_cells_out int32 [n_rays, 2] = the
+ *             recorded cells.
+ *   stats_out DEVICE int64 [13]: rays used, skipped, perturbed (used rays with an axis term evaluated anywhere), orientation signs the exact
+ *             stage decided, degenerate distances, the lanes per status (6, `none` includes the skipped rays' lanes), records, the longest
+ *             lane's records.
+ *   workspace the records are staged in ascending chunks of lanes that hold at most max_records records; DGNN_E_UNSUPPORTED when one lane has
+ *             more (a lane never has more than n_tets + 1).  scratch: dgnn_ray_walk_scratch_bytes(n_rays, n_tets, n_vertices, max_records).
+ *   DGNN_E_INVALID: an id out of range, an entry that is not a corner of the ray's vertex, non-finite coordinates, tetrahedra / neighbors not
+ *   16-byte aligned; DGNN_E_UNSUPPORTED: n_rays >= 2^30, 8 n_tets or 2 max_records beyond int32, a non-zero coordinate magnitude of ANY
+ *   vertex or sensor outside [2^-300, 2^300].
+ * ---------------------------------------------------------------------------------------------- */
+/* Stage times for benchmarks: stage_ms_out (HOST fp64 [4], may be NULL) receives the milliseconds spent since the last call of this function
+ * in 0 the checks, the start cells and the counting walk, 1 the filling walk, 2 the sort, 3 the fold; then the sums are cleared and timing
+ * is switched on or off (off at load).  While on, dgnn_ray_walk synchronises the stream at every stage boundary.  Not thread-safe. */
+int dgnn_ray_walk_timing(int on, double* stage_ms_out);
+int64_t dgnn_ray_walk_scratch_bytes(int64_t n_rays, int64_t n_tets, int64_t n_vertices, int64_t max_records);
+int dgnn_ray_walk(const double* vertices, int64_t n_vertices, const int32_t* tetrahedra, int64_t n_tets, const int32_t* neighbors,
+                  const int32_t* rowptr, const int32_t* entries, const int32_t* ray_vertex, const double* sensors, int64_t n_rays, int unique,
+                  int64_t outside_depth, int64_t inside_depth, int64_t max_records, int32_t* ray_status_out, int32_t* ray_cells_out,
+                  int32_t* cell_count_out, double* cell_stat_out, int32_t* slot_count_out, double* slot_stat_out, int64_t* stats_out,
+                  int64_t records_capacity, int32_t* record_ids_out, double* record_dist_out, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Occupancy of points in an arbitrary triangle mesh (reference utils/libmesh check_mesh_contains) and the generators of the
  * evaluation-sample builder (reference processing/<dataset>/sample_mesh.py).  DESIGN.md section 21.
  *
