@@ -138,6 +138,12 @@ SIGNATURES = {
     "dgnn_ray_first_hit_scratch_bytes": (i64, [i64, i32]),
     "dgnn_ray_first_hit_plan": (i32, [vp, i64, vp, i64, i32, vp, vp, vp, vp]),
     "dgnn_ray_first_hit": (i32, [vp, i64, vp, i64, i32, vp, vp, i64, f64, vp, vp, vp, vp, vp, i64, vp, vp]),
+    "dgnn_point_mesh_distance_scratch_bytes": (i64, [i64, i32]),
+    "dgnn_point_mesh_distance_plan": (i32, [vp, i64, vp, i64, i32, vp, vp, vp]),
+    "dgnn_point_mesh_distance": (i32, [vp, i64, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]),
+    "dgnn_distance_fold_scratch_bytes": (i64, [i64]),
+    "dgnn_distance_fold": (i32, [vp, vp, i64, vp, i32, vp, vp, vp, vp]),
+    "dgnn_row_dot3": (i32, [vp, i64, vp, vp, i64, vp, i64, vp, vp, vp]),
     "dgnn_insphere_sign": (i32, [vp, i64, vp, vp, vp]),
     "dgnn_delaunay_default_capacity": (i64, [i64]),
     "dgnn_delaunay_scratch_bytes": (i64, [i64, i64]),

@@ -39,11 +39,9 @@ struct RcState {
 };
 static_assert(sizeof(RcState) <= 256, "RcState must fit the first scratch slot");
 
-struct RcGrid {          // by value to the kernels
-    double lo[3], hi[3], inv[3], h[3];        // cells per unit length (0 on an axis without extent) and the cell's edge
-    int32_t n[3];
-    double mag;                               // the largest |coordinate| of the box
-};
+using RcGrid = CellGrid;          // the frame, the cell map, the faces' boxes and the cell policy are mesh_grid.h's
+using RcBox = CellBox;
+using RcCells = BoxCells;
 
 __device__ __forceinline__ int32_t rc_pick(const int32_t (&p)[3], int k) { return k == 0 ? p[0] : (k == 1 ? p[1] : p[2]); }
 // the status bits of a coordinate that is not finite or outside the exact predicate's range; the bounding box (k_bbox_referenced) leaves it out
@@ -51,11 +49,7 @@ struct RcCoordErr {
     __device__ int32_t operator()(double x) const { return !isfinite(x) ? RC_NONFINITE : (dgnn_exact::orient_coord_ok(x) ? 0 : RC_RANGE); }
 };
 
-// the cell of coordinate x on axis a: a chain of monotone steps (difference, product, truncation, clamp), so x <= y gives cell(x) <= cell(y)
-__device__ __forceinline__ int32_t rc_cell(const RcGrid& g, int a, double x) {
-    const double f = (x - g.lo[a]) * g.inv[a];
-    return !(f > 0) ? 0 : (f >= (double)g.n[a] ? g.n[a] - 1 : (int32_t)f);
-}
+__device__ __forceinline__ int32_t rc_cell(const RcGrid& g, int a, double x) { return grid_cell(g, a, x); }
 
 // ---- validation ------------------------------------------------------------------------------------------------------------------
 __global__ void k_rc_check_rays(const double* __restrict__ origins, const double* __restrict__ aims, int64_t n3, RcState* st) {
@@ -64,44 +58,6 @@ __global__ void k_rc_check_rays(const double* __restrict__ origins, const double
         if (e) atomicOr(&st->err, e);
     }
 }
-
-// ---- the grid (mesh_grid.h): the cells of a face's box, z fastest -------------------------------------------------------------------
-struct RcBox { int32_t lo[3], hi[3]; };
-
-// tbox[t] = the cells of the face's bounding box; tcnt[t] = their number; the total -> st->n_entries
-__global__ void __launch_bounds__(MESH_THREADS) k_rc_tri_box(const double* __restrict__ v, const int32_t* __restrict__ faces, int64_t nf, RcGrid g,
-                                                           RcBox* __restrict__ tbox, int32_t* __restrict__ tcnt, RcState* st) {
-    unsigned long long tot = 0;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nf; t += (int64_t)gridDim.x * blockDim.x) {
-        const V3 a = load_v3(v, faces[3 * t]), b = load_v3(v, faces[3 * t + 1]), c = load_v3(v, faces[3 * t + 2]);
-        RcBox bx;
-        int64_t cnt = 1;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            bx.lo[k] = rc_cell(g, k, fmin(fmin(get(a, k), get(b, k)), get(c, k)));
-            bx.hi[k] = rc_cell(g, k, fmax(fmax(get(a, k), get(b, k)), get(c, k)));
-            cnt *= bx.hi[k] - bx.lo[k] + 1;
-        }
-        tbox[t] = bx;
-        tcnt[t] = (int32_t)cnt;          // <= RC_MAX_R^3 = 2^30
-        tot += (unsigned long long)cnt;
-    }
-    wave_add_atomic(tot, &st->n_entries);          // an integer sum: order-free
-}
-
-// (the order inside a cell is whatever the builder's atomics give: the walk takes a minimum under a total order)
-struct RcCells {
-    const RcBox* tbox;
-    int32_t n1, n2;          // the grid's cells along y and z
-    __device__ int64_t cell(int64_t t, int32_t k) const {
-        const RcBox b = tbox[t];
-        const int32_t nz = b.hi[2] - b.lo[2] + 1, ny = b.hi[1] - b.lo[1] + 1;
-        const int32_t z = b.lo[2] + k % nz;
-        k /= nz;
-        const int32_t y = b.lo[1] + k % ny, x = b.lo[0] + k / ny;
-        return ((int64_t)x * n1 + y) * n2 + z;
-    }
-};
 
 // ---- the rays --------------------------------------------------------------------------------------------------------------------
 struct RcBest { double t; int32_t face, exact; };
@@ -272,23 +228,10 @@ int rc_plan(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf
                        L.st->hi);
     if (n_rays > 0) hipLaunchKernelGGL(k_rc_check_rays, mesh_launch_grid(3 * n_rays), block, 0, stream, origins, aims, 3 * n_rays, L.st);
     if ((rc = dgnn_check_launch(what)) || (rc = mm_read(&hs, L.st, sizeof(RcState), stream, what)) || (rc = rc_status(hs, what))) return rc;
-    RcGrid g{};
-    double longest = 0.0;
-    bbox_unkey(hs.lo, hs.hi, g.lo, g.hi);
-    for (int a = 0; a < 3; ++a) {
-        longest = fmax(longest, g.hi[a] - g.lo[a]);
-        g.mag = fmax(g.mag, fmax(fabs(g.lo[a]), fabs(g.hi[a])));
-    }
-    for (int a = 0; a < 3; ++a) {          // about cubic cells: R along the longest axis, one where there is no extent
-        const double ext = g.hi[a] - g.lo[a];
-        double cells = longest > 0 ? ceil(ext / (longest / R)) : 1.0;
-        cells = cells < 1 ? 1 : (cells > R ? R : cells);
-        g.n[a] = (int32_t)cells;
-        g.h[a] = ext / cells;
-        g.inv[a] = ext > 0 ? cells / ext : 0.0;
-        if (!isfinite(g.inv[a])) { g.n[a] = 1; g.h[a] = ext; g.inv[a] = 0.0; }          // an extent below 2^-1022 or so: one cell
-    }
-    hipLaunchKernelGGL(k_rc_tri_box, mesh_launch_grid(nf), block, 0, stream, vertices, faces, nf, g, L.tbox, L.g.tcnt, L.st);
+    double lo[3], hi[3];
+    bbox_unkey(hs.lo, hs.hi, lo, hi);
+    const RcGrid g = cell_grid_frame(lo, hi, R);
+    hipLaunchKernelGGL(k_cell_boxes, mesh_launch_grid(nf), block, 0, stream, vertices, faces, nf, g, L.tbox, L.g.tcnt, &L.st->n_entries);
     if ((rc = dgnn_check_launch(what)) || (rc = mm_read(&hs, L.st, sizeof(RcState), stream, what))) return rc;
     DGNN_REQUIRE(hs.n_entries < (unsigned long long)INT32_MAX, DGNN_E_UNSUPPORTED, "%s: %llu grid entries exceed the int32 indexing (lower grid_resolution)", what,
                  hs.n_entries);

@@ -2402,6 +2402,145 @@ def ray_first_hit(vertices, faces, origins, aims, t_min=0.0, grid_resolution=Non
     return face, t, point
 
 
+# ---- point-to-mesh distance and the surface metrics built on it (csrc/meshdist.hip) ---------------------------------------
+MESH_DISTANCE_STATS = ("entries", "max_shells", "shells", "faces_evaluated")
+
+
+def _point_mesh_d2(vertices, faces, points, grid_resolution, what):
+    dev = _dev_of(points, vertices, faces)
+    v = _on(vertices, dev, torch.float64, 3)
+    f = _on(faces, dev, torch.int32, 3)
+    pts = _points64(points, dev)
+    nv, nf, n = v.size(0), f.size(0), pts.size(0)
+    if nf == 0:
+        raise ValueError("%s: a mesh without faces" % what)
+    R = default_grid_resolution(nf) if grid_resolution is None else int(grid_resolution)
+    scratch = torch.empty(int(lib().dgnn_point_mesh_distance_scratch_bytes(nf, R)), dtype=torch.uint8, device=dev)
+    entries, cap = None, 0
+    if R != 0:          # (a resolution the library refuses is refused by the planning call)
+        entries, cap = _planned_entries(dev, "dgnn_point_mesh_distance_plan", lambda n_entries: lib().dgnn_point_mesh_distance_plan(
+            ptr(v), nv, ptr(f), nf, R, n_entries, ptr(scratch), stream_ptr()))
+    d2, dist, face = _empty(dev, torch.float64, n), _empty(dev, torch.float64, n), _empty(dev, torch.int32, n)
+    closest, region = _empty(dev, torch.float64, n, 3), _empty(dev, torch.uint8, n)
+    stats = torch.zeros(len(MESH_DISTANCE_STATS), dtype=torch.int64, device=dev)
+    _check_value(lib().dgnn_point_mesh_distance(ptr(v), nv, ptr(f), nf, R, ptr(pts), n, ptr(d2), ptr(dist), ptr(face), ptr(closest), ptr(region), ptr(stats),
+                                                ptr(entries), cap, ptr(scratch), stream_ptr()), "dgnn_point_mesh_distance")
+    return d2, dist, face, closest, region, stats
+
+
+@on_device_of
+def point_mesh_distance(vertices, faces, points, grid_resolution=None, return_stats=False, return_d2=False):
+    """The distance from each point (fp16 / fp32 / fp64 [n, 3], promoted to fp64) to the mesh (vertices [V, 3], faces int [F, 3]), with where
+    it is attained (dgnn_point_mesh_distance; the rule, operation by operation, and the tie rule are in include/dgnn_hip.h).
+    -> (dist fp64 [n] = sqrt(d2), correctly rounded, face int32 [n], closest fp64 [n, 3], region uint8 [n]: 0 the face's interior, 1..3 on its edge (v0 v1), (v1 v2),
+    (v2 v0), 4..6 at its vertex 0, 1, 2), all on the GPU; with return_d2 the squared distance d2 itself in place of dist; with return_stats also a
+    dict of MESH_DISTANCE_STATS -> int.  grid_resolution sizes the candidate grid (None: default_grid_resolution of the face count; 0: no grid,
+    every face is tested for every point: the faster call when the queries lie far from the surface, profiles/mesh_distance.md); the answer does
+    not depend on it.  ValueError for a mesh without faces, a face id out of range, a
+    non-finite referenced vertex or point; DgnnError for a grid_resolution outside [0, 1024]."""
+    d2, dist, face, closest, region, stats = _point_mesh_d2(vertices, faces, points, grid_resolution, "point_mesh_distance")
+    out = (d2 if return_d2 else dist, face, closest, region)
+    return out + (dict(zip(MESH_DISTANCE_STATS, (int(x) for x in stats.cpu()))),) if return_stats else out
+
+
+@on_device_of
+def distance_fold(dist, cosine=None, thresholds=()):
+    """What the surface metrics need of a list of distances (dgnn_distance_fold): -> (sum of dist, sum of |cosine| (0.0 without), max of dist
+    (0.0 for none), [#{dist <= t} for t in thresholds]), the sums in fp64 in a fixed order, so that reruns give the same bits.  dist and cosine
+    [n] are cast to fp64."""
+    dev = _dev_of(dist, cosine)
+    d = _on(dist, dev, torch.float64).reshape(-1)
+    c = None if cosine is None else _on(cosine, dev, torch.float64).reshape(-1)
+    if c is not None and c.numel() != d.numel():
+        raise ValueError("distance_fold: %d cosines for %d distances" % (c.numel(), d.numel()))
+    n, nt = d.numel(), len(thresholds)
+    thr = torch.tensor([float(t) for t in thresholds], dtype=torch.float64).to(dev) if nt else None
+    sums = torch.zeros(3, dtype=torch.float64, device=dev)
+    counts = torch.zeros(max(nt, 1), dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(lib().dgnn_distance_fold_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_distance_fold(ptr(d), ptr(c), n, ptr(thr), nt, ptr(sums), ptr(counts), ptr(scratch), stream_ptr()), "dgnn_distance_fold")
+    s = sums.cpu()
+    return float(s[0]), float(s[1]), float(s[2]), [int(x) for x in counts.cpu()[:nt]]
+
+
+@on_device_of
+def row_dot3(a, ia, b, ib):
+    """a[ia[i]] . b[ib[i]] as (x0 y0 + x1 y1) + x2 y2 in fp64 (dgnn_row_dot3): the cosine between two lists of unit normals picked by index.
+    ValueError for an index out of range."""
+    dev = _dev_of(a, b, ia, ib)
+    x, y = _on(a, dev, torch.float64, 3), _on(b, dev, torch.float64, 3)
+    i, j = _on(ia, dev, torch.int32).reshape(-1), _on(ib, dev, torch.int32).reshape(-1)
+    if i.numel() != j.numel():
+        raise ValueError("row_dot3: %d and %d indices" % (i.numel(), j.numel()))
+    out = _empty(dev, torch.float64, i.numel())
+    scratch = torch.empty(256, dtype=torch.uint8, device=dev)
+    _check_value(lib().dgnn_row_dot3(ptr(x), x.size(0), ptr(i), ptr(y), y.size(0), ptr(j), i.numel(), ptr(out), ptr(scratch), stream_ptr()), "dgnn_row_dot3")
+    return out
+
+
+def metric_key(name, threshold):
+    """the key of a thresholded surface metric: "fscore@0.01" """
+    return "%s@%g" % (name, threshold)
+
+
+def surface_metric_values(fold_ab, n_a, fold_ba, n_b, thresholds, with_normals=True):
+    """The surface metrics from the two folds (distance_fold's results: A -> B over n_a samples of A, B -> A over n_b samples of B): accuracy =
+    mean A -> B, completeness = mean B -> A, chamfer_mesh = their mean, hausdorff = the larger maximum, precision@t / recall@t = the share of
+    A- / B-samples within t, fscore@t = 2PR / (P + R) (0 when P + R == 0), normal_consistency = the mean of the two mean |cosine|."""
+    sa, ca, ma, ka = fold_ab
+    sb, cb, mb, kb = fold_ba
+    out = {"accuracy": sa / n_a, "completeness": sb / n_b}
+    out["chamfer_mesh"] = 0.5 * (out["accuracy"] + out["completeness"])
+    out["hausdorff"] = max(ma, mb)
+    for t, x, y in zip(thresholds, ka, kb):
+        p, r = x / n_a, y / n_b
+        out[metric_key("precision", t)], out[metric_key("recall", t)] = p, r
+        out[metric_key("fscore", t)] = 2 * p * r / (p + r) if p + r > 0 else 0.0
+    if with_normals:
+        out["normal_consistency"] = 0.5 * (ca / n_a + cb / n_b)
+    return out
+
+
+def empty_surface_metrics(thresholds, with_normals=True):
+    """what the surface metrics are when a side has nothing to measure: inf distances, zero scores"""
+    inf = float("inf")
+    return surface_metric_values((inf, 0.0, inf, [0] * len(thresholds)), 1, (inf, 0.0, inf, [0] * len(thresholds)), 1, thresholds, with_normals)
+
+
+def surface_metrics(a_vertices, a_faces, b_vertices, b_faces, n_samples, thresholds, seed=0, return_samples=False):
+    """Mesh A against mesh B the way the reconstruction benchmarks score: n_samples points drawn on each by area (sample_interface: fp32, seed
+    `seed` for A and seed + 1 for B), each sent to the OTHER MESH by point_mesh_distance (no sampling noise on the far side), the cosine between
+    the sample's face normal and its closest face's normal (face_normals, row_dot3; a face without area has the zero normal and adds 0), and
+    distance_fold.  -> dict of the keys of surface_metric_values.  A side without faces, or whose faces all have the zero normal (no area to
+    sample), gives inf distances and zero scores with a warning; any other failure raises.  With return_samples also the dict of what was measured ("a_points", "a_face", "ab_dist", "ab_face", "ab_cosine" and
+    the same for b)."""
+    thresholds = [float(t) for t in thresholds]
+    dev = _dev_of(a_vertices, a_faces, b_vertices, b_faces)
+    va, vb = _on(a_vertices, dev, torch.float64, 3), _on(b_vertices, dev, torch.float64, 3)
+    fa, fb = _on(a_faces, dev, torch.int32, 3), _on(b_faces, dev, torch.int32, 3)
+    n = int(n_samples)
+    if n < 1:
+        raise ValueError("surface_metrics: n_samples %d < 1" % n)
+    if fa.size(0) == 0 or fb.size(0) == 0:
+        print("WARNING: a mesh has no faces; surface distances set to inf and scores to 0")
+        out = empty_surface_metrics(thresholds)
+        return (out, {}) if return_samples else out
+    na, nb = face_normals(va, fa), face_normals(vb, fb)
+    if not (bool(na.any()) and bool(nb.any())):          # every normal zero: no face has area, nothing to sample
+        print("WARNING: a mesh has no area to sample; surface distances set to inf and scores to 0")
+        out = empty_surface_metrics(thresholds)
+        return (out, {}) if return_samples else out
+    pa, ia = sample_interface(va, fa, None, n, seed=seed)
+    pb, ib = sample_interface(vb, fb, None, n, seed=seed + 1)
+    dab, fab, _, _ = point_mesh_distance(vb, fb, pa)
+    dba, fba, _, _ = point_mesh_distance(va, fa, pb)
+    cab, cba = row_dot3(na, ia, nb, fab), row_dot3(nb, ib, na, fba)
+    out = surface_metric_values(distance_fold(dab, cab, thresholds), n, distance_fold(dba, cba, thresholds), n, thresholds)
+    if return_samples:
+        return out, dict(a_points=pa, a_face=ia, ab_dist=dab, ab_face=fab, ab_cosine=cab, b_points=pb, b_face=ib, ba_dist=dba, ba_face=fba, ba_cosine=cba)
+    return out
+
+
 # ---- ingest: feature scaling (csrc/ingest.hip) ------------------------------------------------------------------------------------
 SCALE_KINDS = {"none": 0, "standard": 1, "minmax": 2, "robust": 3}
 

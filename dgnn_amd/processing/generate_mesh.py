@@ -214,6 +214,60 @@ def chamfer_gpu(data, mdata, interfaces, clf):
     return chamfer_distance(torch.from_numpy(gt_points).to(recon_points.device), recon_points)
 
 
+SURFACE_METRIC_NAMES = ("accuracy", "completeness", "fscore", "normal_consistency", "hausdorff")
+
+
+def _fscore_thresholds(clf):
+    from .evaluate_mesh import DEFAULT_FSCORE_THRESHOLDS
+
+    value = getattr(getattr(clf, "evaluation", None), "fscore_thresholds", None)
+    return [float(t) for t in value] if value is not None else list(DEFAULT_FSCORE_THRESHOLDS)
+
+
+def surface_metrics_gpu(data, vertices, faces, clf, names):
+    """The metrics `names` (within SURFACE_METRIC_NAMES) of the mesh (vertices [V, 3], faces int32 [F, 3] on the device) against
+    eval/<id or category>/pointcloud.npz (`points`, `normals`): evaluate_mesh.pointcloud_metrics with seed clf.evaluation.seed and the
+    thresholds clf.evaluation.fscore_thresholds (default 0.01, 0.02).  -> dict: the names as keys; for "fscore" the value at the FIRST
+    threshold, and "fscore@t", "precision@t", "recall@t" for every threshold t.  Raises on failure."""
+    from ..ops import metric_key
+    from .evaluate_mesh import pointcloud_metrics
+
+    subfolder = data['id'] if data['id'] else data['category']
+    cloud = np.load(os.path.join(data.path, "eval", subfolder, "pointcloud.npz"))
+    thresholds = _fscore_thresholds(clf)
+    seed = getattr(getattr(clf, "evaluation", None), "seed", None) or 0
+    v = torch.as_tensor(np.asarray(vertices, dtype=np.float64)).to(faces.device)
+    m = pointcloud_metrics(v, faces, cloud["points"], cloud["normals"] if "normals" in cloud else None, thresholds, seed=seed,
+                           name=getattr(data, "filename", ""))
+    out = dict()
+    for name in names:
+        if name == "fscore":
+            if thresholds:
+                out["fscore"] = m[metric_key("fscore", thresholds[0])]
+            out.update({k: x for k, x in m.items() if "@" in k})
+        else:
+            out[name] = m[name]          # (normal_consistency without `normals` in the file: a KeyError, i.e. the caller's warning)
+    return out
+
+
+def _gpu_surface_metrics(data, clf, vertices, faces, metrics, eval_dict):
+    """the surface metrics among `metrics` into eval_dict; a failure warns in the reference's style and writes inf (distances) or 0.0 (scores)"""
+    names = [m for m in SURFACE_METRIC_NAMES if m in metrics]
+    if not names:
+        return
+    try:
+        eval_dict.update(surface_metrics_gpu(data, vertices, faces, clf, names))
+    except Exception:  # noqa: BLE001  (the reference: bare except, :157-159)
+        print("WARNING: Could not calculate surface metrics for mesh ", data['filename'])
+        from ..ops import metric_key
+
+        for name in names:
+            eval_dict[name] = float("inf") if name in ("accuracy", "completeness", "hausdorff") else 0.0
+        if "fscore" in names:          # the same keys as on success
+            for t in _fscore_thresholds(clf):
+                eval_dict.update({metric_key(k, t): 0.0 for k in ("fscore", "precision", "recall")})
+
+
 def _components_rule(value):
     """clf.mesh.components -> None (no filter), "largest" or an int n >= 1 (components with at least n faces)"""
     if value is None:
@@ -315,6 +369,11 @@ def generate(data, prediction, clf):
         ``evaluation.solver: gpu`` iou is then check_mesh_contains of the filtered mesh (iou_mesh_gpu: the walk in the labelled
         tetrahedralization would score the unfiltered labels) and chamfer samples the kept facets only.  Any other value of the
         key raises ValueError; a failing device step warns and returns the unfiltered mesh.
+    * with ``clf.evaluation.solver == "gpu"`` the names ``accuracy``, ``completeness``, ``hausdorff``, ``normal_consistency`` and ``fscore``
+      in ``clf.temp.metrics`` are computed against ``pointcloud.npz`` (surface_metrics_gpu): on the exported, component-filtered
+      faces with ``mesh.solver: gpu``, else on the interface facets; ``fscore`` writes the value at the first threshold of
+      ``clf.evaluation.fscore_thresholds`` (default 0.01, 0.02) and ``fscore@t``, ``precision@t``, ``recall@t`` for every threshold.  A
+      failure warns and writes inf (distances) or 0.0 (scores, the thresholded keys included); without the gpu solver the names are ignored, as unknown names are.
     """
     dev = prediction.device if prediction.is_cuda else torch.device(getattr(clf.temp, "device", "cuda:0"))
     pred_dev = prediction.to(dev, torch.float32)
@@ -402,6 +461,9 @@ def _generate_gpu_metrics(data, clf, mdata, labels, interfaces, faces, trimesh):
         else:
             print("WARNING: trimesh is not installed; mesh metrics {} are not computed for {}".format(["watertight"], getattr(data, "filename", "")))
     _gpu_iou_chamfer(data, clf, mdata, labels, interfaces, metrics, eval_dict)
+    if any(m in metrics for m in SURFACE_METRIC_NAMES):          # on the interface facets, in the tetrahedralization's own vertices
+        facets = torch.from_numpy(np.ascontiguousarray(mdata["facets"], dtype=np.int32)).to(interfaces.device)[interfaces.long()]
+        _gpu_surface_metrics(data, clf, mdata["vertices"], facets, metrics, eval_dict)
     return mesh, eval_dict
 
 
@@ -472,6 +534,7 @@ def _generate_gpu_mesh(data, clf, mdata, labels, interfaces, trimesh):
             _gpu_iou_chamfer(data, clf, mdata, labels, interfaces, metrics, eval_dict)
         else:
             _gpu_iou_chamfer_filtered(data, clf, mdata, mesh, interfaces[mesh.keep_mask], metrics, eval_dict)
+        _gpu_surface_metrics(data, clf, mesh.vertices, mesh.faces_dev, metrics, eval_dict)          # on the exported (filtered) faces
         return mesh, eval_dict
     wanted = [m for m in ("iou", "chamfer") if m in metrics]
     if trimesh is None:

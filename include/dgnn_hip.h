@@ -1322,6 +1322,67 @@ int dgnn_ray_first_hit(const double* vertices, int64_t n_vertices, const int32_t
                        double* hit_point_out, int64_t* stats_out, int32_t* entries, int64_t entry_capacity, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Distance from points to a triangle mesh, with the closest face: the primitive of the surface metrics (ops.surface_metrics: accuracy,
+ * completeness, Hausdorff distance, F-score, normal consistency).  DESIGN.md section 30.  Every *, +, - and / below is one fp64 rounding, in
+ * the order written (no contraction); x . y means (x0 y0 + x1 y1) + x2 y2 and x X y has one product minus one product per component.
+ *
+ * dgnn_point_mesh_distance: for vertices fp64 [n_vertices, 3], faces int32 [n_faces, 3], points fp64 [n_points, 3]: for every point p the
+ *   lexicographic minimum over ALL faces f of (d2_f, f), with the closest point and the region of that face:
+ *   segment   (u, v), taken with u the endpoint of the LOWER VERTEX ID (so two faces that share an edge or a vertex compute the same bits
+ *             for it, and the tie goes to the lower face, not to the winding that happened to round lower): e = v - u, w = p - u,
+ *             ee = e . e, we = w . e; we <= 0 or ee == 0: c = u; else we >= ee: c = v; else t = we / ee, c = u + t e per coordinate (one
+ *             product, one sum).  d2 = (p - c) . (p - c).
+ *   face      (v0, v1, v2): the segments (v0, v1), (v1, v2), (v2, v0) in this order, a later one replacing an earlier one only when its
+ *             d2 is smaller.  Then the plane candidate: n = (v1 - v0) X (v2 - v0), nn = n . n; when nn > 0 and ((vj - vi) X (p - vi)) . n > 0
+ *             for (i, j) = (0, 1), (1, 2), (2, 0): s = ((p - v0) . n) / nn, q = p - s n per coordinate (one product, one difference), c[k] =
+ *             min(max(q[k], min_i vi[k]), max_i vi[k]) on the three axes k (the foot of the perpendicular, clamped to the face's bounding
+ *             box: exactly onto the plane of an axis-aligned face), d2 = (p - c) . (p - c), and it replaces the segments' result when
+ *             smaller (on equality the segment stays).  d2 is thus always the squared distance, as rounded, to the closest point that is
+ *             reported, and that point lies in the face's bounding box (up to the rounding of u + t e) even where a sliver's computed
+ *             normal is far from the true one: what the search's stopping bound rests on.  A face without area (collinear or repeated vertices) is its segments, a face of one repeated vertex that
+ *             point; short of overflow nothing non-finite comes from finite input.
+ *   region    of the winning candidate: 0 the face's interior (the plane candidate), 1..3 on the edge (v0 v1), (v1 v2), (v2 v0), 4..6 at
+ *             vertex 0, 1, 2 (a segment clamped to an endpoint reports that endpoint's position in the face).
+ *   outputs   d2_out fp64 [n], dist_out fp64 [n] = sqrt(d2), correctly rounded (NULL: not written), face_out int32 [n], closest_out fp64
+ *             [n, 3], region_out uint8 [n].
+ *   grid      grid_resolution R = 0: no grid, every lane tests every face.  R in [1, 1024]: a uniform grid over the box of the referenced
+ *             vertices, R cells along the longest axis, ceil(extent / (longest / R)) on the others (1 without extent); a face is entered
+ *             in every cell its bounding box touches.  One lane per point reads the cells in Chebyshev shells about the point's (clamped)
+ *             cell and stops when its best d2 is below the squared distance, shrunk by 2^-46 of the largest coordinate magnitude of the box
+ *             and the point, to every cell not yet read (csrc/meshdist.hip has the derivation): the result does not depend on R.
+ *             `entries` int32 [entry_capacity] holds the (face, cell) entries: dgnn_point_mesh_distance_plan returns their number (0 for
+ *             R = 0, where entries may be NULL).
+ *   stats_out DEVICE int64 [4]: the grid's entries; the most shells one point read; the shells read in total; the (point, face)
+ *             evaluations (R = 0: n_points * n_faces).  A point deep inside an empty region, at about the same distance from much of the
+ *             mesh, reads nearly the whole grid (O(R^3) cells): for such queries R = 0 is the faster call.
+ *   scratch   dgnn_point_mesh_distance_scratch_bytes(n_faces, grid_resolution) bytes for either call.
+ * DGNN_E_INVALID: no faces, a face id out of range, a non-finite coordinate of a referenced vertex or of a point (an unreferenced vertex
+ * is not read), entry_capacity too small; DGNN_E_UNSUPPORTED: R outside [0, 1024], 2^31 or more entries.  No exact predicate is involved:
+ * there is no coordinate-range refusal.  Ids and coordinates are validated before any kernel uses them.  Both calls SYNCHRONISE `stream`
+ * twice (ids, box and coordinates), three times with a grid (the entry total).  No floating-point atomics: bit-identical from run to run.
+ * n_points == 0 is fine (the mesh is still validated).
+ *
+ * dgnn_distance_fold: for dist fp64 [n], cosine fp64 [n] or NULL, thresholds fp64 [n_thresholds] (all DEVICE): sums_out DEVICE fp64 [3] =
+ *   the sum of dist, the sum of |cosine| (0 for NULL), the maximum of dist (0 for n == 0), the sums in fixed_sum.h's order (serial sums over
+ *   chunks of 256 elements, then the chunk totals serially); counts_out DEVICE int64 [n_thresholds] = #{i: dist[i] <= thresholds[t]}
+ *   (integer sums: order-free).  scratch: dgnn_distance_fold_scratch_bytes(n) bytes.  Bit-identical from run to run.
+ *
+ * dgnn_row_dot3: out[i] = a[ia[i]] . b[ib[i]] for a fp64 [n_a, 3], b fp64 [n_b, 3], ia, ib int32 [n] (the cosine between a sample's face
+ *   normal and its closest face's normal).  DGNN_E_INVALID for an index out of range (validated first: SYNCHRONISES once).  scratch: 256 bytes.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_point_mesh_distance_scratch_bytes(int64_t n_faces, int32_t grid_resolution);
+int dgnn_point_mesh_distance_plan(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t grid_resolution,
+                                  int64_t* n_entries_out, void* scratch, void* stream);
+int dgnn_point_mesh_distance(const double* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t grid_resolution,
+                             const double* points, int64_t n_points, double* d2_out, double* dist_out, int32_t* face_out, double* closest_out,
+                             uint8_t* region_out, int64_t* stats_out, int32_t* entries, int64_t entry_capacity, void* scratch, void* stream);
+int64_t dgnn_distance_fold_scratch_bytes(int64_t n);
+int dgnn_distance_fold(const double* dist, const double* cosine, int64_t n, const double* thresholds, int32_t n_thresholds, double* sums_out,
+                       int64_t* counts_out, void* scratch, void* stream);
+int dgnn_row_dot3(const double* a, int64_t n_a, const int32_t* ia, const double* b, int64_t n_b, const int32_t* ib, int64_t n, double* out,
+                  void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-scene standardisation (reference processing/data.py:444-506 sklearn StandardScaler + :512-519
  * float32 cast): out[i,c] = float((x[i,c] - mean_c) / std_c) for c >= c_first, plain cast for c < c_first;
  * fp64 statistics (population variance, zero scale -> 1).  scratch: dgnn_standardize_scratch_doubles(c) doubles.
