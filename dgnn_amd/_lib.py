@@ -149,6 +149,10 @@ SIGNATURES = {
     "dgnn_delaunay_scratch_bytes": (i64, [i64, i64]),
     "dgnn_delaunay": (i32, [vp, i64, i64, vp, vp, vp, vp, vp]),
     "dgnn_delaunay_violations": (i32, [vp, i64, vp, vp, i64, vp, vp]),
+    "dgnn_vertex_components_scratch_bytes": (i64, [i64, i64]),
+    "dgnn_vertex_components": (i32, [vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
+    "dgnn_manifold_repair_scratch_bytes": (i64, [i64, i64]),
+    "dgnn_manifold_repair": (i32, [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp]),
     "dgnn_khop_scratch_elems": (i64, [i64, i64]),
     "dgnn_khop_count": (i32, [vp, vp, i64, i32, vp, vp, vp, vp]),
     "dgnn_khop_expand": (i32, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -2757,3 +2757,65 @@ def delaunay_violations(vertices, tetrahedra):
     out = dict(zip(VIOLATIONS, (int(x) for x in counts.cpu()[:len(VIOLATIONS)])))
     out["overfull_facets"] = overfull
     return out
+
+
+# ---- singular vertices and their repair by relabelling cells (csrc/manifold.hip) ------------------------------------------
+MANIFOLD_STATS = ("rounds", "moves", "flipped_cells", "to_inside", "to_outside", "flipped_cost", "singular_before", "singular_after")
+
+
+def _labelled_cells(tetrahedra, neighbors, labels, what):
+    dev = _dev_of(labels, tetrahedra, neighbors)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    nbr = _on(neighbors, dev, torch.int32, 4)
+    lab = _on(labels, dev, torch.int32).reshape(-1)
+    if nbr.size(0) != tets.size(0) or lab.numel() != tets.size(0):
+        raise ValueError("%s: %d cells, %d neighbour rows, %d labels" % (what, tets.size(0), nbr.size(0), lab.numel()))
+    return dev, tets, nbr, lab
+
+
+@on_device_of
+def vertex_components(tetrahedra, neighbors, labels, n_vertices):
+    """(n_inside int32 [V], n_outside int32 [V], n_singular) of dgnn_vertex_components: per vertex the connected components a(v) of the
+    inside cells (label 0) and b(v) of the outside cells (label 1, the infinite cell among them) of its star, two cells joined when they
+    share a facet through the vertex and carry the same label; a vertex is singular when a > 1 or b > 1, and the interface of the labels is
+    a closed manifold surface exactly when none is.  tetrahedra int [T, 4], neighbors int [T, 4] slot-wise with -1 = the
+    infinite cell (tet_neighbors; of `delaunay`: the first T rows with ids >= T set to -1).  DgnnError for malformed input."""
+    dev, tets, nbr, lab = _labelled_cells(tetrahedra, neighbors, labels, "vertex_components")
+    t, nv = tets.size(0), int(n_vertices)
+    n_in, n_out = torch.zeros(max(nv, 1), dtype=torch.int32, device=dev)[:nv], torch.zeros(max(nv, 1), dtype=torch.int32, device=dev)[:nv]
+    nbytes = int(lib().dgnn_vertex_components_scratch_bytes(t, nv))
+    if nbytes <= 0:
+        raise DgnnError("vertex_components: %d cells with %d vertices exceed the int32 indexing" % (t, nv))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    n_singular = C.c_int64(0)
+    check(lib().dgnn_vertex_components(ptr(tets), ptr(nbr), ptr(lab), t, nv, ptr(n_in), ptr(n_out), C.byref(n_singular), ptr(scratch), stream_ptr()),
+          "dgnn_vertex_components")
+    return n_in, n_out, int(n_singular.value)
+
+
+@on_device_of
+def manifold_repair(tetrahedra, neighbors, labels, n_vertices, cost=None, max_rounds=None, return_flipped=False):
+    """Relabels cells until no vertex is singular or no move is left (dgnn_manifold_repair; the rule is in include/dgnn_hip.h):
+    per round every singular vertex offers its cheapest component -- by (sum of `cost`, smallest cell id) -- that holds neither the infinite
+    cell nor an already flipped cell, the vertices that own their whole star win, and the winners' components change side.  A cell flips at
+    most once.  cost: int [T], each >= 0 (None: all ones, the fewest cells flip).  max_rounds only stops early: the result after r rounds.
+    -> (labels int32 [T] on the GPU (a new tensor), stats dict of MANIFOLD_STATS; singular_after = the stuck vertices of a call that ran to
+    its end) (+ flipped int32 [T] with return_flipped).  DgnnError for malformed input."""
+    dev, tets, nbr, lab = _labelled_cells(tetrahedra, neighbors, labels, "manifold_repair")
+    t, nv = tets.size(0), int(n_vertices)
+    out = lab.clone()
+    cst = None
+    if cost is not None:
+        cst = _on(cost, dev, torch.int32).reshape(-1)
+        if cst.numel() != t:
+            raise ValueError("manifold_repair: %d costs for %d cells" % (cst.numel(), t))
+    flipped = torch.zeros(max(t, 1), dtype=torch.int32, device=dev)[:t] if return_flipped else None
+    nbytes = int(lib().dgnn_manifold_repair_scratch_bytes(t, nv))
+    if nbytes <= 0:
+        raise DgnnError("manifold_repair: %d cells with %d vertices exceed the int32 indexing" % (t, nv))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    st = (C.c_int64 * len(MANIFOLD_STATS))()
+    check(lib().dgnn_manifold_repair(ptr(tets), ptr(nbr), ptr(out), ptr(cst), t, nv, -1 if max_rounds is None else max(int(max_rounds), 0),
+                                     ptr(flipped), st, ptr(scratch), stream_ptr()), "dgnn_manifold_repair")
+    stats = dict(zip(MANIFOLD_STATS, (int(x) for x in st)))
+    return (out, stats, flipped) if return_flipped else (out, stats)

@@ -6,7 +6,8 @@ of facets whose two cells carry different labels (:101-105) -- two Python loops 
 three small kernels here.  The optional integer alpha-expansion graph cut (:15-58, third-party ``gco``) runs exactly on
 the device with ``graph_cut.solver: gpu`` (``graph_cut_gpu``), and the iou / chamfer metrics with ``evaluation.solver: gpu``
 (``iou_gpu`` / ``chamfer_gpu``), and the mesh object with its watertight and components metrics and the small-component filter with
-``mesh.solver: gpu`` (``mesh_gpu`` / ``watertight_gpu`` / ``mesh_components_gpu``); without that key the ``trimesh`` mesh object stays a CPU-side third-party step.  ``labels`` can be replaced by the graph-cut labels before ``interface_from_labels``.
+``mesh.solver: gpu`` (``mesh_gpu`` / ``watertight_gpu`` / ``mesh_components_gpu``), where ``mesh.manifold: repair`` also relabels cells until the
+surface is manifold (``manifold_repair_gpu``); without that key the ``trimesh`` mesh object stays a CPU-side third-party step.  ``labels`` can be replaced by the graph-cut labels before ``interface_from_labels``.
 """
 from __future__ import annotations
 
@@ -328,6 +329,52 @@ def watertight_gpu(mesh, name=""):
     return mesh_topology(faces, len(mesh.vertices))["watertight"]
 
 
+MANIFOLD_COST_CAP = 1 << 20
+
+
+def _manifold_mode(clf):
+    """clf.mesh.manifold -> None (the labels stay as they are) or "repair"; the repair needs ``mesh.solver: gpu``"""
+    mode = getattr(getattr(clf, "mesh", None), "manifold", None)
+    if mode is None:
+        return None
+    if mode != "repair":
+        raise ValueError("mesh.manifold: %r (expected null or \"repair\")" % (mode,))
+    if getattr(clf.mesh, "solver", None) != "gpu":
+        raise ValueError("mesh.manifold: \"repair\" needs mesh.solver: gpu (the repair runs on the device only)")
+    return mode
+
+
+def _manifold_cost(clf, prediction_finite):
+    """clf.mesh.manifold_cost -> None ("count", the default: every cell costs 1, the fewest cells flip) or, for "margin", int32 [Nf] on the
+    device: min(round(|logit 0 - logit 1| * mesh.manifold_cost_scale), 2^20) (scale default 1000) -- the cells the network is least sure of
+    flip first.  `prediction_finite`: the logits fp32 [Nf, 2] of the finite cells."""
+    kind = getattr(clf.mesh, "manifold_cost", None)
+    if kind is None or kind == "count":
+        return None
+    if kind != "margin":
+        raise ValueError("mesh.manifold_cost: %r (expected null, \"count\" or \"margin\")" % (kind,))
+    scale = getattr(clf.mesh, "manifold_cost_scale", None)
+    scale = 1000.0 if scale is None else float(scale)
+    if not scale >= 0.0:
+        raise ValueError("mesh.manifold_cost_scale: %r (expected a number >= 0)" % (scale,))
+    margin = (prediction_finite[:, 0].double() - prediction_finite[:, 1].double()).abs() * scale
+    return torch.nan_to_num(margin, nan=0.0).round().clamp(max=MANIFOLD_COST_CAP).to(torch.int32)
+
+
+def manifold_repair_gpu(mdata, labels, cost=None):
+    """The labels of the finite cells of the tetrahedralization `mdata` (`_3dt.npz`) relabelled until the interface is a closed manifold
+    surface or no move is left (ops.manifold_repair on the adjacency of ops.tet_neighbors).  labels: int [Nf] (0 = inside),
+    cost: int [Nf] >= 0 or None (all ones).  Runs on the device of `labels`.  -> (labels int32 [Nf] on the device, the op's stats:
+    singular_after = the vertices still singular, `stuck`)."""
+    from ..ops import manifold_repair, tet_neighbors
+
+    dev = labels.device if isinstance(labels, torch.Tensor) and labels.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    tets = torch.from_numpy(np.ascontiguousarray(mdata["tetrahedra"], dtype=np.int32)).to(dev)
+    nbr = tet_neighbors(torch.from_numpy(np.ascontiguousarray(mdata["facets"], dtype=np.int32)).to(dev),
+                        torch.from_numpy(np.ascontiguousarray(mdata["nfacets"], dtype=np.int32)).to(dev), tets)
+    return manifold_repair(tets, nbr, torch.as_tensor(labels).to(dev), len(mdata["vertices"]), cost=cost)
+
+
 def mesh_components_gpu(mesh):
     """The number of connected components of an InterfaceMesh (faces connected through shared edges; ops.mesh_components):
     what the reference reports from trimesh's body_count.  A mesh without faces has 0."""
@@ -369,6 +416,13 @@ def generate(data, prediction, clf):
         ``evaluation.solver: gpu`` iou is then check_mesh_contains of the filtered mesh (iou_mesh_gpu: the walk in the labelled
         tetrahedralization would score the unfiltered labels) and chamfer samples the kept facets only.  Any other value of the
         key raises ValueError; a failing device step warns and returns the unfiltered mesh.
+      - ``clf.mesh.manifold``: absent / None = the labels stay as they are; ``"repair"`` = the finite cells' labels (from the arg-max or
+        from either graph cut) are relabelled before the interface is extracted until no vertex of the surface is singular or no move is
+        left (manifold_repair_gpu), and everything after -- orientation, components, metrics, export -- sees the repaired
+        labels.  ``clf.mesh.manifold_cost``: ``"count"`` (default; every cell costs 1, the fewest cells flip) or ``"margin"`` (a cell
+        costs min(round(|logit 0 - logit 1| * ``mesh.manifold_cost_scale``), 2^20), scale default 1000: the least certain cells flip
+        first).  ``eval_dict["manifold_flipped"]`` = the cells that changed side, ``eval_dict["manifold_stuck"]`` = the vertices still
+        singular (warned about once when > 0).  ``"repair"`` without ``mesh.solver: gpu``, and any other value, raises ValueError.
     * with ``clf.evaluation.solver == "gpu"`` the names ``accuracy``, ``completeness``, ``hausdorff``, ``normal_consistency`` and ``fscore``
       in ``clf.temp.metrics`` are computed against ``pointcloud.npz`` (surface_metrics_gpu): on the exported, component-filtered
       faces with ``mesh.solver: gpu``, else on the interface facets; ``fscore`` writes the value at the first threshold of
@@ -405,6 +459,10 @@ def generate(data, prediction, clf):
                 labels_dev = torch.as_tensor(np.asarray(lab), dtype=torch.int32, device=dev)
         except Exception:  # noqa: BLE001  (the reference: bare except, :88-91)
             print("WARNING: Graph cut for {} didn't work. Using raw predictions for mesh generation.".format(data.filename))
+    manifold = None
+    if _manifold_mode(clf):          # a configuration mistake raises here
+        cost = _manifold_cost(clf, pred_dev.detach()[(infinite == 0).to(dev)])
+        labels_dev, manifold = manifold_repair_gpu(mdata, labels_dev, cost=cost)
     interfaces_dev = interface_from_labels(labels_dev, torch.from_numpy(nfacets))
     interfaces = interfaces_dev.cpu().numpy()
     faces = mdata["facets"][interfaces]
@@ -414,7 +472,12 @@ def generate(data, prediction, clf):
     except ImportError:
         trimesh = None
     if getattr(getattr(clf, "mesh", None), "solver", None) == "gpu":
-        return _generate_gpu_mesh(data, clf, mdata, labels_dev, interfaces_dev, trimesh)
+        mesh, eval_dict = _generate_gpu_mesh(data, clf, mdata, labels_dev, interfaces_dev, trimesh)
+        if manifold is not None:
+            eval_dict["manifold_flipped"], eval_dict["manifold_stuck"] = manifold["flipped_cells"], manifold["singular_after"]
+            if manifold["singular_after"]:
+                print("WARNING: {} vertices of mesh {} stay non-manifold after the repair".format(manifold["singular_after"], getattr(data, "filename", "")))
+        return mesh, eval_dict
     if getattr(getattr(clf, "evaluation", None), "solver", None) == "gpu":
         return _generate_gpu_metrics(data, clf, mdata, labels_dev, interfaces_dev, faces, trimesh)
     if trimesh is None:

@@ -1600,6 +1600,53 @@ int dgnn_delaunay(const double* points, int64_t n, int64_t cell_capacity, int32_
 int dgnn_delaunay_violations(const double* vertices, int64_t n_vertices, const int32_t* tetrahedra, const int32_t* neighbors, int64_t n_tets,
                              int64_t* counts_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Singular vertices of a labelled tetrahedralization and their repair by relabelling cells.  DESIGN.md section 31.  Integers only; nothing
+ * depends on the schedule: reruns are bit-identical.  tetrahedra int32 [n_tets, 4] (the finite cells), neighbors int32 [n_tets, 4] as
+ * dgnn_tet_neighbors writes it (slot k = the cell across the facet opposite vertex k, -1 = the infinite cell), labels int32 [n_tets]
+ * (0 inside, 1 outside; the infinite cell is outside).  tetrahedra and neighbors are read a row (16 bytes) at a time and must be 16-byte
+ * aligned.  Both entry points SYNCHRONISE `stream` (status reads).
+ *
+ *   star graph of vertex v
+ *     nodes   every cell c with tetrahedra[c][k] == v for some k (its corner 4 c + k), and one node INF when for some such corner a slot
+ *             j != k has neighbors[c][j] == -1 (a hull facet through v).
+ *     edges   corner (c, k) -- the corner of n = neighbors[c][j] that holds v, for every j != k with n >= 0 and labels[n] == labels[c];
+ *             corner (c, k) -- INF for every j != k with neighbors[c][j] == -1 when labels[c] == 1.
+ *     a(v)    the connected components whose cells are labelled 0; b(v) those labelled 1, the component of INF among them (it counts also
+ *             when no cell was joined to it).  v is SINGULAR when a(v) > 1 or b(v) > 1.
+ *
+ * dgnn_vertex_components: n_inside_out, n_outside_out int32 [n_vertices] = a(v), b(v) (0, 0 for a vertex of no cell); *n_singular_out (HOST
+ *   int64) = the number of singular vertices.
+ *
+ * dgnn_manifold_repair: labels is read and rewritten in place.  cost int32 [n_tets], each >= 0 (NULL: every cell costs 1).  flipped[c] = 0.
+ *   A round, on the labels and marks as the round finds them:
+ *     1  the components of every vertex as above.
+ *     2  a component of a singular vertex v is a CANDIDATE when its side has at least two components at v, it does not hold INF and none of
+ *        its cells has flipped[c] == 1.  Its key is (the sum of cost over its cells, int64; its smallest cell id).  The MOVE of v is the
+ *        candidate with the lexicographically smallest key; a singular vertex without a candidate has no move.
+ *     3  claim[c] = the smallest v, among the vertices with a move, that has c in its star.  A vertex with a move WINS when claim[c] == v for
+ *        every cell c of its star.
+ *     4  every cell c of the move of every winner: labels[c] = 1 - labels[c], flipped[c] = 1.
+ *   Rounds repeat until a round has no move (at most n_tets rounds apply one, a cell flipping at most once), or max_rounds rounds have been
+ *   applied (max_rounds < 0: no limit): the labels after r rounds are those of r rounds of the unlimited call.  One host read per round.
+ *   stats_out: int64 [DGNN_MANIFOLD_N_STATS] on the HOST: rounds that applied a move, moves applied, cells flipped, of those 1 -> 0 and
+ *   0 -> 1, the sum of cost over the flipped cells, singular vertices before the first round and on the returned labels (the STUCK vertices
+ *   when no limit ended the call).  flipped_out int32 [n_tets] or NULL: the marks.
+ *
+ *   scratch   dgnn_vertex_components_scratch_bytes / dgnn_manifold_repair_scratch_bytes (n_tets, n_vertices) bytes (0: sizes beyond int32).
+ *   DGNN_E_INVALID: a vertex or neighbour id out of range, a cell with a repeated vertex, a neighbour that does not hold the three shared
+ *   vertices or does not name the cell back in the slot of its fourth, a label outside {0, 1}, a negative cost.  DGNN_E_UNSUPPORTED:
+ *   4 n_tets + n_vertices beyond int32.
+ * ---------------------------------------------------------------------------------------------- */
+enum { DGNN_MANIFOLD_ROUNDS = 0, DGNN_MANIFOLD_MOVES, DGNN_MANIFOLD_FLIPPED_CELLS, DGNN_MANIFOLD_TO_INSIDE, DGNN_MANIFOLD_TO_OUTSIDE,
+       DGNN_MANIFOLD_FLIPPED_COST, DGNN_MANIFOLD_SINGULAR_BEFORE, DGNN_MANIFOLD_SINGULAR_AFTER, DGNN_MANIFOLD_N_STATS };
+int64_t dgnn_vertex_components_scratch_bytes(int64_t n_tets, int64_t n_vertices);
+int dgnn_vertex_components(const int32_t* tetrahedra, const int32_t* neighbors, const int32_t* labels, int64_t n_tets, int64_t n_vertices,
+                           int32_t* n_inside_out, int32_t* n_outside_out, int64_t* n_singular_out, void* scratch, void* stream);
+int64_t dgnn_manifold_repair_scratch_bytes(int64_t n_tets, int64_t n_vertices);
+int dgnn_manifold_repair(const int32_t* tetrahedra, const int32_t* neighbors, int32_t* labels, const int32_t* cost, int64_t n_tets,
+                         int64_t n_vertices, int64_t max_rounds, int32_t* flipped_out, int64_t* stats_out, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
