@@ -95,6 +95,10 @@ SIGNATURES = {
     "dgnn_graph_cut_weighted": (i32, [vp, i64, i64, vp, i64, f32, vp, vp, vp, vp, vp, vp, vp]),
     "dgnn_facet_cut_terms_scratch_bytes": (i64, [i64]),
     "dgnn_facet_cut_terms": (i32, [vp, i64, vp, i64, vp, vp, i64, i32, f64, vp, vp, vp, vp, vp]),
+    "dgnn_cell_circumspheres_scratch_bytes": (i64, []),
+    "dgnn_cell_circumspheres": (i32, [vp, i64, vp, i64, vp, vp, vp, vp]),
+    "dgnn_facet_geometry_scratch_bytes": (i64, [i64]),
+    "dgnn_facet_geometry": (i32, [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]),
     "dgnn_locate_scratch_bytes": (i64, [i64]),
     "dgnn_locate_points": (i32, [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp]),
     "dgnn_mesh_iou_counts": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp]),

@@ -4,7 +4,8 @@
 //
 //   k_facet_terms   one thread per facet: the nfacets row decides whether the facet is a graph row (both cells finite); a row gathers its
 //                   three vertices (area) or its three vertices and the four vertices of each of its two cells (beta: the circumsphere is
-//                   recomputed per side, no per-cell pass).  beta quantises at once; area stores A_f (0 for the other facets).
+//                   recomputed per side, no per-cell pass; the arithmetic is facet_geom.h's, which facetgeom.hip runs in two passes: DESIGN
+//                   §23 compares them).  beta quantises at once; area stores A_f (0 for the other facets).
 //   fixed_sum       the sum of the A_f in a fixed order (fixed_sum.h)
 //   k_area_quantise q_f = A_f / mean, w_f = rint(binary_weight q_f)
 // All fp64, the operation order of the header, no contraction (the build's -ffp-contract=off); the counters are integer atomics: reruns are
@@ -13,11 +14,12 @@
 
 #include "common.h"
 #include "mesh_common.h"
-#include "vec3.h"
+#include "facet_geom.h"
 #include "fixed_sum.h"
 
 namespace {
 
+using dgnn_exact::FacetPlane;
 using dgnn_exact::V3;
 using dgnn_exact::load_v3;
 
@@ -55,46 +57,29 @@ __device__ __forceinline__ int32_t quantise(double bw, double q, CtCounts& c, Ct
     return w;
 }
 
-// cos phi of the facet (a, b, c) seen from the cell `cell` (header: the circumcentre's signed distance to the facet's plane over the
-// circumradius, positive on the cell's own side); 0 and *neutral = 1 for a degenerate side.  false: the facet is not a face of the cell / an id
-// out of range.
+// cos phi of the facet `p` = (ia, ib, ic) seen from the cell `cell`, its circumsphere recomputed here (facet_geom.h: sphere_cosine; 0 and
+// *neutral += 1 for a degenerate side).  false: the facet is not a face of the cell / an id out of range.
 __device__ __forceinline__ bool side_cosine(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ tets, int32_t cell, int32_t ia,
-                                            int32_t ib, int32_t ic, const V3& a, const V3& n, double nn, double* cosine, int* neutral, CtState* st) {
-    int32_t t[4], opp = -1;
-    int in = 0;
+                                            int32_t ib, int32_t ic, const FacetPlane& p, double* cosine, int* neutral, CtState* st) {
+    int32_t t[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         t[k] = tets[4 * (int64_t)cell + k];
         if (t[k] < 0 || t[k] >= nv) { atomicOr(&st->err, CT_BAD_ID); return false; }
-        if (t[k] == ia || t[k] == ib || t[k] == ic) ++in;
-        else opp = t[k];
     }
-    const bool has = (t[0] == ia || t[1] == ia || t[2] == ia || t[3] == ia) && (t[0] == ib || t[1] == ib || t[2] == ib || t[3] == ib) &&
-                     (t[0] == ic || t[1] == ic || t[2] == ic || t[3] == ic);
-    if (in != 3 || !has) { atomicOr(&st->err, CT_MALFORMED); return false; }
-    const V3 p0 = load_v3(v, t[0]);
-    const V3 u = sub(load_v3(v, t[1]), p0), vv = sub(load_v3(v, t[2]), p0), w = sub(load_v3(v, t[3]), p0);
-    const V3 vw = cross(vv, w), wu = cross(w, u), uv = cross(u, vv);
-    const double det = dot(u, vw), u2 = dot(u, u), v2 = dot(vv, vv), w2 = dot(w, w), d2 = 2.0 * det;
-    const V3 c{((u2 * vw.x + v2 * wu.x) + w2 * uv.x) / d2, ((u2 * vw.y + v2 * wu.y) + w2 * uv.y) / d2, ((u2 * vw.z + v2 * wu.z) + w2 * uv.z) / d2};
-    const double R = sqrt(dot(c, c));
-    const double sd = dot(n, sub(load_v3(v, opp), a));
-    const V3 g{(p0.x + c.x) - a.x, (p0.y + c.y) - a.y, (p0.z + c.z) - a.z};
-    const double hn = dot(n, g);
-    const double h = (sd > 0 ? hn : -hn) / nn;
-    const double r = h / R;
-    if (det == 0 || nn == 0 || sd == 0 || !isfinite(R) || !isfinite(h) || !isfinite(r)) {
-        *cosine = 0;
-        *neutral += 1;
-        return true;
-    }
-    *cosine = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
+    const int slot = dgnn_exact::facet_opposite_slot(t, ia, ib, ic);
+    if (slot < 0) { atomicOr(&st->err, CT_MALFORMED); return false; }
+    const dgnn_exact::Sphere s = dgnn_exact::cell_sphere(load_v3(v, t[0]), load_v3(v, t[1]), load_v3(v, t[2]), load_v3(v, t[3]));
+    const int32_t opp = slot == 0 ? t[0] : (slot == 1 ? t[1] : (slot == 2 ? t[2] : t[3]));
+    *cosine = dgnn_exact::sphere_cosine(s.o, s.R, p, load_v3(v, opp), neutral);
     return true;
 }
 
-// KIND 1: val[f] = A_f (quantised later); KIND 2: q, w at once.  Every facet that is not a graph row gets 0 everywhere.
+// KIND 1: val[f] = A_f (quantised later); KIND 2: q, w at once.  Every facet that is not a graph row gets 0 everywhere.  (waves_per_eu, a
+// minimum, is on both instantiations: the beta form stays at 4 waves per SIMD, 128 VGPRs without scratch -- left alone the scheduler takes 130
+// and loses a wave; the area form has 34 VGPRs and 8 waves with or without it.)
 template <int KIND>
-__global__ void __launch_bounds__(MESH_THREADS) k_facet_terms(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ tets, int64_t nc,
+__global__ void __launch_bounds__(MESH_THREADS) __attribute__((amdgpu_waves_per_eu(4))) k_facet_terms(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ tets, int64_t nc,
                                                             const int32_t* __restrict__ facets, const int32_t* __restrict__ nfacets, int64_t nf,
                                                             double bw, double* __restrict__ val, double* __restrict__ q_out,
                                                             int32_t* __restrict__ w_out, CtState* st) {
@@ -113,16 +98,13 @@ __global__ void __launch_bounds__(MESH_THREADS) k_facet_terms(const double* __re
         }
         if (ok && c0 >= 0 && c1 >= 0) {
             ++cnt.rows;
-            const V3 a = load_v3(v, ia);
-            const V3 n = cross(sub(load_v3(v, ib), a), sub(load_v3(v, ic), a));
-            const double nn = sqrt(dot(n, n));
+            const FacetPlane p = dgnn_exact::facet_plane(load_v3(v, ia), load_v3(v, ib), load_v3(v, ic));
             if (KIND == 1) {
-                q = 0.5 * nn;
+                q = 0.5 * p.nn;
             } else {
                 double cos0 = 0, cos1 = 0;
                 int neutral = 0;
-                if (side_cosine(v, nv, tets, c0, ia, ib, ic, a, n, nn, &cos0, &neutral, st) &&
-                    side_cosine(v, nv, tets, c1, ia, ib, ic, a, n, nn, &cos1, &neutral, st)) {
+                if (side_cosine(v, nv, tets, c0, ia, ib, ic, p, &cos0, &neutral, st) && side_cosine(v, nv, tets, c1, ia, ib, ic, p, &cos1, &neutral, st)) {
                     cnt.neutral += neutral;
                     q = 1.0 - (cos0 < cos1 ? cos0 : cos1);
                     w = quantise(bw, q, cnt, st);

@@ -2076,6 +2076,63 @@ def cell_geometry(vertices, tetrahedra):
             "sum_longest": float(s[0]), "sum_shortest": float(s[1])}
 
 
+FGEOM_KEYS = ("area", "cos_own", "cos_neighbor", "beta")          # the keys of `_fgeom.npz`, in the file's order
+
+
+@on_device_of
+def cell_circumspheres(vertices, tetrahedra):
+    """The circumsphere of every finite cell (dgnn_cell_circumspheres; §23's expressions): dict of "centre" fp64 [T, 3] and
+    "radius" fp64 [T] on the GPU, "n_flat" int: the cells with det == 0, whose radius is inf or NaN, and "records": the [T, 4] array
+    (o.x, o.y, o.z, R) that the two are views of and that facet_geometry reads in place.  DgnnError for a vertex id out of range."""
+    dev = _dev_of(vertices, tetrahedra)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    t = tets.size(0)
+    rec = _empty(dev, torch.float64, t, 4)
+    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(lib().dgnn_cell_circumspheres_scratch_bytes()), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_cell_circumspheres(ptr(v), v.size(0), ptr(tets), t, ptr(rec), ptr(stats), ptr(scratch), stream_ptr()), "dgnn_cell_circumspheres")
+    return {"centre": rec[:, :3], "radius": rec[:, 3], "n_flat": int(stats[3].item()), "records": rec}
+
+
+@on_device_of
+def facet_geometry(vertices, tetrahedra, facets, nfacets, spheres=None):
+    """The `_fgeom` columns of the finite cells from the arrays of `<scene>_3dt.npz` (dgnn_facet_geometry; the definition is in
+    include/dgnn_hip.h and DESIGN §32): row 4 t + k belongs to the facet of tet t opposite its vertex k and holds the facet's "area", the
+    circumsphere cosine of §23 on the tet's side ("cos_own") and on the other side ("cos_neighbor"; 1.0 when that is the infinite cell) and
+    "beta" = 1 - min of the two.  vertices fp64 [V, 3], tetrahedra int [T, 4], facets int [F, 3], nfacets int [F, 2].  spheres: the dict of
+    cell_circumspheres for these cells (computed here when None).
+    -> dict of the four FGEOM_KEYS tensors, fp64 [4 T] on the GPU (0 in a row that no facet names), and "stats": {"rows" (rows written),
+    "hull_rows" (those whose neighbour is the infinite cell), "neutral_sides", "n_flat"}.  DgnnError for an id out of range and for a facet
+    that is not a face of a cell its nfacets row names."""
+    dev = _dev_of(vertices, tetrahedra, facets, nfacets)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    fac = _on(facets, dev, torch.int32, 3)
+    nfac = _on(nfacets, dev, torch.int32, 2)
+    if fac.size(0) != nfac.size(0):
+        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
+    t = tets.size(0)
+    rec = None
+    if spheres is not None:
+        if not isinstance(spheres, dict) or "records" not in spheres or "n_flat" not in spheres:
+            raise ValueError("facet_geometry: spheres must be the dict cell_circumspheres returned (its \"records\" and \"n_flat\")")
+        rec = _on(spheres["records"], dev, torch.float64, 4)
+        if rec.size(0) != t:
+            raise ValueError("spheres of %d cells for %d tetrahedra" % (rec.size(0), t))
+        if rec.data_ptr() % 32:          # a view into a larger tensor: the kernel loads whole 32-byte records
+            rec = rec.clone()
+    out = _empty(dev, torch.float64, 4, 4 * t)
+    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(lib().dgnn_facet_geometry_scratch_bytes(t)), dtype=torch.uint8, device=dev)
+    check(lib().dgnn_facet_geometry(ptr(v), v.size(0), ptr(tets), t, ptr(fac), ptr(nfac), fac.size(0), ptr(rec), ptr(out), ptr(stats), ptr(scratch),
+                                    stream_ptr()), "dgnn_facet_geometry")
+    s = [int(x) for x in stats.cpu()]
+    res = {k: out[i] for i, k in enumerate(FGEOM_KEYS)}
+    res["stats"] = {"rows": s[0], "hull_rows": s[1], "neutral_sides": s[2], "n_flat": int(spheres["n_flat"]) if spheres is not None else s[3]}
+    return res
+
+
 @on_device_of
 def vertex_incidence(tetrahedra, n_vertices):
     """(rowptr int32 [V + 1], entries int32 [4 T]) on the GPU (dgnn_vertex_incidence): row v holds 4 t + k for every corner

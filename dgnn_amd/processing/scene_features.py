@@ -1,10 +1,13 @@
 """Scene preparation on the device: from a triangulation (`<scene>_3dt.npz`) and a scan (points + sensor positions) to the model's input
-files `<scene>_cgeom.npz`, `<scene>_cbvf.npz`, `<scene>_fbvf.npz` and, with facet_rays, `<scene>_cbff.npz`, `<scene>_fbff.npz` (§29).
+files `<scene>_cgeom.npz`, `<scene>_cbvf.npz`, `<scene>_fbvf.npz`, with facet_rays `<scene>_cbff.npz`, `<scene>_fbff.npz` (§29) and,
+with facet_geometry, `<scene>_fgeom.npz` (§32).
 
 The reference gets these files from an external binary; their definitions here are the ones that reproduce its recorded output for
 Ignatius scene 99 (counts and edge lengths exactly, the other columns to the last bits).  The facet-ray files (`_cbff`, `_fbff`) hold the
 aggregates of ops.ray_walk, every ray followed through all the cells it crosses: the binary's own walk cannot be recovered from its files
-(§25), so the rule is this package's definition (§29), not a reproduction.  `_fgeom` is not built.  The training target
+(§25), so the rule is this package's definition (§29), not a reproduction.  `_fgeom` (the edge feature `shape`) is missing from the
+reference's data and its four column names are unknown: ops.facet_geometry defines them here (§32: facet area, the two circumsphere cosines
+of §23, the beta-skeleton term).  The training target
 `<scene>_labels.npz` comes from build_cell_labels and a closed ground-truth mesh; the binary's own sample count and generator
 are not known, so its labels are a definition of this package's, not a reproduction.
 
@@ -20,6 +23,7 @@ import torch
 from .. import ops
 
 CGEOM_KEYS = ("radius", "vol", "longest_edge", "shortest_edge")
+FGEOM_KEYS = ops.FGEOM_KEYS          # the key order of `_fgeom.npz`
 VF_GROUPS = ("inside", "outside", "last")          # the files' key order; `last` holds 0 everywhere
 VF_STATS = ("count", "dist_min", "dist_max", "dist_sum")
 FF_CELL_GROUPS = tuple("%s_%s" % (g, w) for g in VF_GROUPS for w in ("first", "second"))          # the key order of `_cbff.npz`
@@ -39,7 +43,8 @@ def match_vertices(vertices, points):
     return np.where(kv[order][pos] == kp, order[pos], -1).astype(np.int64)
 
 
-def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base=None, device=None, facet_rays=False, outside_depth=0, inside_depth=1):
+def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base=None, device=None, facet_rays=False, outside_depth=0, inside_depth=1,
+                         facet_geometry=False):
     """mdata: the arrays of `<scene>_3dt.npz` (vertices, tetrahedra, facets, nfacets); infinite [n_cells]: 1 = infinite cell (the
     `infinite` of `_labels.npz`); scan_points, sensor_position [P, 3]: every point that equals a vertex casts that vertex's ray towards its
     sensor, points that share a vertex cast one ray (the lowest-index point's).  Runs ops.tet_neighbors / cell_geometry / vertex_ray_features on
@@ -51,6 +56,10 @@ def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base
       "cbff": cb_facet_{inside,outside,last}_{first,second}_{count,dist_min,dist_max,dist_sum} [n_cells]: per cell the distances at which the
       rays that cross it (after their start cell) enter and leave; "fbff": fb_facet_{inside,outside,last}_... [4 n_cells]: per facet of the
       cell a ray leaves; the `last` groups hold 0, as the vertex family's do; "walk_stats": the stats of ops.ray_walk.
+    With facet_geometry also ops.facet_geometry, and in the result
+      "fgeom": FGEOM_KEYS -> fp64 ndarray [4 n_cells] (area, cos_own, cos_neighbor, beta per facet of the cell; DESIGN §32);
+      "fgeom_stats": the stats of ops.facet_geometry.  ValueError when they count other than 4 rows per tetrahedron: the `_3dt` does not
+      list every facet of every finite cell once.
     With out_base the files are written as out_base + "_cgeom.npz" etc., readable by the reference's and this package's dataLoader."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     inf = np.asarray(infinite).astype(bool).reshape(-1)
@@ -67,7 +76,8 @@ def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base
 
     v = torch.from_numpy(vertices).to(dev)
     tets = torch.as_tensor(np.asarray(mdata["tetrahedra"])).to(dev, torch.int32)
-    nbr = ops.tet_neighbors(torch.as_tensor(np.asarray(mdata["facets"])).to(dev), torch.as_tensor(np.asarray(mdata["nfacets"])).to(dev), tets)
+    fac, nfac = torch.as_tensor(np.asarray(mdata["facets"])).to(dev), torch.as_tensor(np.asarray(mdata["nfacets"])).to(dev)
+    nbr = ops.tet_neighbors(fac, nfac, tets)
     geom = ops.cell_geometry(v, tets)
     ray_vertex, ray_sensor = torch.from_numpy(vid[hit]).to(dev), torch.from_numpy(sensors[hit]).to(dev)
     incidence = ops.vertex_incidence(tets, v.size(0))
@@ -109,6 +119,13 @@ def build_scene_features(mdata, infinite, scan_points, sensor_position, out_base
             for s in VF_STATS:
                 out["fbff"]["fb_facet_%s_%s" % (g, s)] = np.zeros(4 * n_cells) if g == "last" else cell_col(walk["%s_slot_%s" % (g, s.replace("dist_", ""))])
         names += ["cbff", "fbff"]
+    if facet_geometry:
+        fg = ops.facet_geometry(v, tets, fac, nfac)
+        if fg["stats"]["rows"] != 4 * n_tets:
+            raise ValueError("the facets of the triangulation name %d (cell, slot) rows, its %d tetrahedra have %d: `facets` / `nfacets` do not list every "
+                             "facet of every finite cell once" % (fg["stats"]["rows"], n_tets, 4 * n_tets))
+        out["fgeom"], out["fgeom_stats"] = {k: cell_col(fg[k].reshape(n_tets, 4)) for k in FGEOM_KEYS}, fg["stats"]
+        names.append("fgeom")
     if out_base is not None:
         for name in names:
             np.savez(out_base + "_%s.npz" % name, **out[name])

@@ -1,5 +1,5 @@
 """From a scan to a scene folder: the triangulator between scan_mesh and build_scene_features / build_cell_labels; make_scene
-chains all of them, with facet_rays through the facet-ray walk as well.
+chains all of them, with facet_rays through the facet-ray walk and with facet_geometry through ops.facet_geometry (§32) as well.
 
 The reference gets `<scene>_3dt.npz` and `<scene>_adjacencies.npz` from an external binary; here they come from ops.delaunay -- the exact
 Delaunay triangulation of the scan's distinct points with one infinite cell per hull facet.
@@ -64,13 +64,14 @@ def triangulate_scan(points, out_base=None, priority=None, seed=0, device=None):
     return out
 
 
-def make_scene(gt_vertices, gt_faces, out_base, n_samples=100, label_seed=0, priority=None, device=None, facet_rays=False, **scan_args):
+def make_scene(gt_vertices, gt_faces, out_base, n_samples=100, label_seed=0, priority=None, device=None, facet_rays=False, facet_geometry=False, **scan_args):
     """A closed ground-truth mesh -> every file dataLoader.run opens for node_features within {shape, vertex, count, min, max, sum} and
     edge_features within {vertex, count, min, max, sum}: scan_mesh(**scan_args) -> triangulate_scan -> build_scene_features ->
     build_cell_labels, written as out_base + "_3dt.npz", "_adjacencies.npz", "_cgeom.npz", "_cbvf.npz", "_fbvf.npz", "_labels.npz".
     With facet_rays also "_cbff.npz" and "_fbff.npz" (every ray walked through all its cells): the scene then supports the wider
-    sets, node_features within {shape, vertex, facet, ...} and edge_features within {vertex, facet, ...} (all but the edge feature `shape`,
-    whose `_fgeom` is not built).  Returns the four stages' results: dict of "scan", "triangulation", "features", "labels"."""
+    sets, node_features within {shape, vertex, facet, ...} and edge_features within {vertex, facet, ...}.  With facet_geometry also
+    "_fgeom.npz" (DESIGN §32), the edge feature `shape`; with both flags the folder holds all nine files and loads under the reference's
+    shipped lists, edge_features [shape, vertex, facet, count, min, max, sum].  Returns the four stages' results: dict of "scan", "triangulation", "features", "labels"."""
     from .scan_mesh import scan_mesh
     from .scene_features import build_cell_labels, build_scene_features
 
@@ -80,6 +81,6 @@ def make_scene(gt_vertices, gt_faces, out_base, n_samples=100, label_seed=0, pri
     scan = scan_mesh(gt_vertices, gt_faces, device=device, **scan_args)
     tri = triangulate_scan(scan["points"], out_base=out_base, priority=priority, seed=scan_args.get("seed", 0), device=device)
     feat = build_scene_features(tri["mdata"], tri["infinite"], scan["points"], scan["sensor_position"], out_base=out_base, device=device,
-                                facet_rays=facet_rays)
+                                facet_rays=facet_rays, facet_geometry=facet_geometry)
     lab = build_cell_labels(tri["mdata"], tri["infinite"], gt_vertices, gt_faces, n_samples=n_samples, seed=label_seed, out_base=out_base, device=device)
     return dict(scan=scan, triangulation=tri, features=feat, labels=lab)

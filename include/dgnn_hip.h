@@ -938,6 +938,42 @@ int dgnn_facet_cut_terms(const double* vertices, int64_t n_vertices, const int32
                          const int32_t* nfacets, int64_t n_facets, int kind, double binary_weight, double* q_out, int32_t* w_out,
                          int64_t* stats_out, void* scratch, void* stream);
 
+/* The facet geometry columns of `<scene>_fgeom.npz` (a definition of this package's own: the reference's file is
+ * missing and its column names are unknown).  Inputs in the layout above; the arithmetic, operation for operation, is the one stated for
+ * dgnn_facet_cut_terms (csrc/facet_geom.h holds it once for both), in two passes: every cell's circumsphere once, then every facet.
+ *
+ * dgnn_cell_circumspheres: centre_radius_out DEVICE fp64 [n_cells, 4], 32-byte aligned: (o.x, o.y, o.z, R) per cell with c as above,
+ *   o = p0 + c per component and R = sqrt(c . c).  A flat cell (det == 0) divides by zero: its R is inf or NaN, its o not finite; no flag
+ *   is kept, the conditions of a NEUTRAL side catch it.  stats_out DEVICE int64 [4] (NULL: not written): [3] = the cells with det == 0,
+ *   [0..2] = 0.  scratch: dgnn_cell_circumspheres_scratch_bytes() bytes.
+ *
+ * dgnn_facet_geometry: out DEVICE fp64 [4, 4 n_cells], zero-filled by the call, the four columns area, cos_own, cos_neighbor, beta of the
+ *   rows 4 t + k = the facet of cell t opposite its vertex k (the row order of `_adjacencies.npz`).  Per facet f = (a, b, c) as stored:
+ *     n = (b - a) X (c - a);  nn = sqrt(n . n);  area = 0.5 * nn;
+ *     per side s with T = nfacets[f, s]:  T >= 0: cos_s = cos phi_T from T's stored (o, R): sd = n . (d - a); hn = n . (o - a);
+ *       h = (sd > 0 ? hn : -hn) / nn; r = h / R; cos_s = min(max(r, -1), 1); NEUTRAL (cos_s = 0, counted) when nn == 0, sd == 0 or one of R, h,
+ *       r is not finite -- dgnn_facet_cut_terms' rule: det == 0 makes R not finite;  T < 0 (the infinite cell): cos_s = 1.0, not counted:
+ *       the circumsphere of an infinite cell is the half-space beyond the hull facet, its centre infinitely far on its own side, h / R -> 1;
+ *     beta = 1.0 - (cos_0 < cos_1 ? cos_0 : cos_1);
+ *     every side with a cell T writes the row 4 T + k, k = the slot of T's one vertex that is not on the facet:
+ *       (area, cos_own = cos_s, cos_neighbor = cos_(1-s), beta).  A facet with both nfacets entries < 0 writes nothing.
+ *   area and beta are bit-equal on the two directed rows of a facet, cos_own and cos_neighbor swap; all four are finite on every input,
+ *   the cosines in [-1, 1], beta in [0, 2]; at a facet between two finite cells beta is dgnn_facet_cut_terms' q (kind 2) bit for bit.
+ *   spheres   DEVICE fp64 [n_cells, 4] as dgnn_cell_circumspheres wrote it (32-byte aligned), or NULL: computed into the scratch here.
+ *   stats_out DEVICE int64 [4] (NULL: not written): rows written, rows whose neighbour is the infinite cell, neutral sides, flat cells
+ *             (0 when `spheres` was given).  A `_3dt` that lists every facet of every finite cell once gives rows == 4 n_cells.
+ *   scratch   dgnn_facet_geometry_scratch_bytes(n_cells) bytes.
+ * DGNN_E_INVALID: a vertex id of a facet or of a cell outside [0, n_vertices), a cell id >= n_cells, a facet that is not a face of a cell
+ * its nfacets row names.  DGNN_E_UNSUPPORTED: 4 n_cells, n_vertices or 3 n_facets beyond int32.  Both calls SYNCHRONISE `stream` once, at
+ * their end.  Every row has one writer, the counters are integer atomics: reruns are bit-identical. */
+int64_t dgnn_cell_circumspheres_scratch_bytes(void);
+int dgnn_cell_circumspheres(const double* vertices, int64_t n_vertices, const int32_t* tets, int64_t n_cells, double* centre_radius_out,
+                            int64_t* stats_out, void* scratch, void* stream);
+int64_t dgnn_facet_geometry_scratch_bytes(int64_t n_cells);
+int dgnn_facet_geometry(const double* vertices, int64_t n_vertices, const int32_t* tets, int64_t n_cells, const int32_t* facets,
+                        const int32_t* nfacets, int64_t n_facets, const double* spheres, double* out, int64_t* stats_out, void* scratch,
+                        void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Mesh metrics of the interface surface (reference processing/generate_mesh.py:126-163, processing/evaluate_mesh.py compute_iou /
  * compute_chamfer).  DESIGN.md section 14.
