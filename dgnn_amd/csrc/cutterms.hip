@@ -15,6 +15,7 @@
 #include "common.h"
 #include "mesh_common.h"
 #include "facet_geom.h"
+#include "tet_common.h"
 #include "fixed_sum.h"
 
 namespace {
@@ -67,11 +68,10 @@ __device__ __forceinline__ bool side_cosine(const double* __restrict__ v, int64_
         t[k] = tets[4 * (int64_t)cell + k];
         if (t[k] < 0 || t[k] >= nv) { atomicOr(&st->err, CT_BAD_ID); return false; }
     }
-    const int slot = dgnn_exact::facet_opposite_slot(t, ia, ib, ic);
+    const int slot = facet_opposite_slot(t, ia, ib, ic);
     if (slot < 0) { atomicOr(&st->err, CT_MALFORMED); return false; }
     const dgnn_exact::Sphere s = dgnn_exact::cell_sphere(load_v3(v, t[0]), load_v3(v, t[1]), load_v3(v, t[2]), load_v3(v, t[3]));
-    const int32_t opp = slot == 0 ? t[0] : (slot == 1 ? t[1] : (slot == 2 ? t[2] : t[3]));
-    *cosine = dgnn_exact::sphere_cosine(s.o, s.R, p, load_v3(v, opp), neutral);
+    *cosine = dgnn_exact::sphere_cosine(s.o, s.R, p, load_v3(v, row_at(t, slot)), neutral);
     return true;
 }
 

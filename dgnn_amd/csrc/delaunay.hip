@@ -86,8 +86,8 @@ __device__ bool conflict(const double* __restrict__ P, const int32_t* tv, const 
 __global__ void k_check_points(const double* __restrict__ P, int64_t n3, DlHead* h) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x) {
         const double x = P[i];
-        if (!(fabs(x) <= 1.7976931348623157e308)) atomicOr(&h->err, DL_NONFINITE);
-        else if (!dgnn_exact::insphere_coord_ok(x)) atomicOr(&h->err, DL_RANGE);
+        if (!dgnn_exact::coord_finite(x)) atomicOr(&h->err, DL_NONFINITE);
+        else if (!dgnn_exact::insphere_coord_ok(x)) atomicOr(&h->err, DL_RANGE);          // (its range is narrower than coord_class's)
     }
 }
 

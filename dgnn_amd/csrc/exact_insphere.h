@@ -31,10 +31,7 @@
 
 namespace dgnn_exact {
 
-__device__ __forceinline__ bool insphere_coord_ok(double x) {
-    const double m = fabs(x);
-    return m == 0.0 || (m >= 0x1p-150 && m <= 0x1p150);
-}
+__device__ __forceinline__ bool insphere_coord_ok(double x) { return coord_in_range(x, 0x1p150); }
 
 constexpr int IS_LIMBS = 58;        // 64-bit limbs of the accumulator, 32 bits of weight each
 constexpr int IS_BASE = -1010;      // exponent of limb 0's lowest bit

@@ -18,9 +18,19 @@
 
 namespace dgnn_exact {
 
-__device__ __forceinline__ bool orient_coord_ok(double x) {
+// 0 or a magnitude in [1 / lim, lim], lim a power of two (NaN and the infinities fail it)
+__device__ __forceinline__ bool coord_in_range(double x, double lim) {
     const double m = fabs(x);
-    return m == 0.0 || (m >= 0x1p-300 && m <= 0x1p300);
+    return m == 0.0 || (m >= 1.0 / lim && m <= lim);
+}
+__device__ __forceinline__ bool orient_coord_ok(double x) { return coord_in_range(x, 0x1p300); }
+__device__ __forceinline__ bool orient_coords_ok(const V3& a) { return orient_coord_ok(a.x) && orient_coord_ok(a.y) && orient_coord_ok(a.z); }
+
+// one coordinate for the orientation predicate: fine, not finite, or finite and out of range; the callers map it onto their status bits
+enum CoordClass { COORD_FINE = 0, COORD_NONFINITE, COORD_RANGE };
+__device__ __forceinline__ bool coord_finite(double x) { return fabs(x) <= 1.79769313486231570815e308; }
+__device__ __forceinline__ CoordClass coord_class(double x) {
+    return !coord_finite(x) ? COORD_NONFINITE : (orient_coord_ok(x) ? COORD_FINE : COORD_RANGE);
 }
 
 __device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {

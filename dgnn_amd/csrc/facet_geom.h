@@ -27,19 +27,6 @@ __device__ __forceinline__ FacetPlane facet_plane(const V3& a, const V3& b, cons
     return FacetPlane{a, n, sqrt(dot(n, n))};
 }
 
-// the slot of the one vertex of the cell t[0..3] that is not on the facet (ia, ib, ic); -1: the facet is not a face of the cell
-__device__ __forceinline__ int facet_opposite_slot(const int32_t t[4], int32_t ia, int32_t ib, int32_t ic) {
-    int in = 0, slot = -1;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (t[k] == ia || t[k] == ib || t[k] == ic) ++in;
-        else slot = k;
-    }
-    const bool has = (t[0] == ia || t[1] == ia || t[2] == ia || t[3] == ia) && (t[0] == ib || t[1] == ib || t[2] == ib || t[3] == ib) &&
-                     (t[0] == ic || t[1] == ic || t[2] == ic || t[3] == ic);
-    return in == 3 && has ? slot : -1;
-}
-
 // cos phi of the facet seen from the cell with the circumsphere (o, R) and the opposite vertex d: the circumcentre's signed distance to the
 // facet's plane over the circumradius, positive on the cell's own side.  0 and *neutral += 1 for a degenerate side: nn == 0, sd == 0 or one
 // of R, h, r not finite (a flat cell, det == 0, is among these: its R is not finite).

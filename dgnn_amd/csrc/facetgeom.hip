@@ -11,6 +11,7 @@
 #include "common.h"
 #include "mesh_common.h"
 #include "facet_geom.h"
+#include "tet_common.h"
 
 namespace {
 
@@ -34,7 +35,7 @@ __global__ void __launch_bounds__(MESH_THREADS) k_cell_spheres(const double* __r
         const int64_t t = t0 + threadIdx.x;
         if (t >= nt) continue;
         const int32_t i0 = tets[4 * t], i1 = tets[4 * t + 1], i2 = tets[4 * t + 2], i3 = tets[4 * t + 3];
-        if (i0 < 0 || i0 >= nv || i1 < 0 || i1 >= nv || i2 < 0 || i2 >= nv || i3 < 0 || i3 >= nv) {
+        if (!tet_ids_ok(i0, i1, i2, i3, nv)) {
             atomicOr(&st->err, FG_BAD_ID);
             out[t] = SphereRec{0.0, 0.0, 0.0, 0.0};
             continue;
@@ -73,20 +74,19 @@ __global__ void __launch_bounds__(MESH_THREADS) k_facet_geometry(const double* _
             int32_t t[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) t[k] = tets[4 * (int64_t)cell[s] + k];
-            if (t[0] < 0 || t[0] >= nv || t[1] < 0 || t[1] >= nv || t[2] < 0 || t[2] >= nv || t[3] < 0 || t[3] >= nv) {
+            if (!tet_ids_ok(t, nv)) {
                 atomicOr(&st->err, FG_BAD_ID);
                 ok = false;
                 continue;
             }
-            slot[s] = dgnn_exact::facet_opposite_slot(t, ia, ib, ic);
+            slot[s] = facet_opposite_slot(t, ia, ib, ic);
             if (slot[s] < 0) {
                 atomicOr(&st->err, FG_MALFORMED);
                 ok = false;
                 continue;
             }
-            const int32_t opp = slot[s] == 0 ? t[0] : (slot[s] == 1 ? t[1] : (slot[s] == 2 ? t[2] : t[3]));
             const SphereRec r = spheres[cell[s]];
-            cosine[s] = dgnn_exact::sphere_cosine(V3{r.ox, r.oy, r.oz}, r.R, p, load_v3(v, opp), &side_neutral);
+            cosine[s] = dgnn_exact::sphere_cosine(V3{r.ox, r.oy, r.oz}, r.R, p, load_v3(v, row_at(t, slot[s])), &side_neutral);
         }
         if (!ok) continue;
         neutral += side_neutral;

@@ -18,6 +18,7 @@
 //              writer per cell.
 // The host loop reads one small record per round and ends when a round had no move.
 #include "mesh_faces.h"
+#include "tet_common.h"
 
 namespace {
 
@@ -60,17 +61,10 @@ __global__ void k_mr_check(const int32_t* __restrict__ tets, const int32_t* __re
                     if (k != j) hull[v[k]] = 1;   // every writer stores the same value
                 continue;
             }
-            int hits = 0, back = -1;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const int32_t w = tets[4 * (int64_t)n[j] + s];
-                bool shared = false;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) shared |= k != j && w == v[k];
-                hits += shared;
-                if (!shared) back = s;
-            }
-            if (n[j] == (int32_t)c || hits != 3 || back < 0 || nbr[4 * (int64_t)n[j] + back] != (int32_t)c) err |= MR_NEIGHBOR;
+            int32_t f0, f1, f2;   // the facet shared with n[j]: the cell's vertices other than slot j
+            row_others(v, j, f0, f1, f2);
+            const int back = facet_opposite_slot(tets + 4 * (int64_t)n[j], f0, f1, f2);
+            if (n[j] == (int32_t)c || back < 0 || nbr[4 * (int64_t)n[j] + back] != (int32_t)c) err |= MR_NEIGHBOR;
         }
         if (err) atomicOr(&st->err, err);
     }

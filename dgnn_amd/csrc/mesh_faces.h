@@ -1,5 +1,6 @@
-// Pieces shared by the kernels that read a triangle list (meshtopo.hip, meshcomp.hip): the status word and its synchronising read, the
-// face check, the sorted undirected-edge keys and the lock-free union-find.
+// Pieces shared by the kernels that read a triangle list (meshtopo.hip, meshcomp.hip) and by the scene kernels that report through the same
+// status word: the status word and its synchronising read, the face check, the sorted undirected-edge keys, the lock-free union-find and the
+// radix-sort workspace.
 #pragma once
 #include "mesh_common.h"
 
@@ -83,6 +84,23 @@ int mt_read_status(MtState* hs, const MtState* st, hipStream_t stream, const cha
                    e & MT_DEGENERATE ? "a face with a repeated vertex; " : "",
                    e & MT_PASSES ? "the counting and the filling pass disagree (the inputs changed during the call?); " : "");
     return e == MT_RANGE ? DGNN_E_UNSUPPORTED : DGNN_E_INVALID;
+}
+
+// the workspace of dgnn_radix_sort_u64_i32 for m elements: the two key and value buffers it ping-pongs between, its histogram and scan
+struct SortBufs { uint64_t* keys[2]; int32_t *vals[2], *hist, *scanned, *sums; };
+void take_sort(Take& t, int64_t m, SortBufs& S) {
+    const int64_t h = dgnn_radix_sort_hist_elems(m);
+    S.keys[0] = t.take<uint64_t>(m);
+    S.keys[1] = t.take<uint64_t>(m);
+    S.vals[0] = t.take<int32_t>(m);
+    S.vals[1] = t.take<int32_t>(m);
+    S.hist = t.take<int32_t>(h);
+    S.scanned = t.take<int32_t>(h);
+    S.sums = t.take<int32_t>(dgnn_cdiv(h, 2048) + 4);
+}
+// sorts S.keys[0] / S.vals[0]; the result is in S.keys[*cur] / S.vals[*cur]
+int sort_pairs(const SortBufs& S, int64_t n, int bits, hipStream_t stream, int* cur) {
+    return dgnn_radix_sort_u64_i32(S.keys, S.vals, n, bits, S.hist, S.scanned, S.sums, stream, cur);
 }
 
 int key_bits(int64_t nv) {

@@ -167,18 +167,6 @@ __global__ void k_keep(const int32_t* __restrict__ comp, int64_t n, const int64_
 }
 
 // ---- scratch layouts ---------------------------------------------------------------------------------------------------------
-struct SortBufs { uint64_t* keys[2]; int32_t *vals[2], *hist, *scanned, *sums; };
-void take_sort(Take& t, int64_t m, SortBufs& S) {
-    const int64_t h = dgnn_radix_sort_hist_elems(m);
-    S.keys[0] = t.take<uint64_t>(m);
-    S.keys[1] = t.take<uint64_t>(m);
-    S.vals[0] = t.take<int32_t>(m);
-    S.vals[1] = t.take<int32_t>(m);
-    S.hist = t.take<int32_t>(h);
-    S.scanned = t.take<int32_t>(h);
-    S.sums = t.take<int32_t>(dgnn_cdiv(h, 2048) + 4);
-}
-
 struct CompLayout { MtState* st; SortBufs S; int32_t *parent, *root, *is_root, *rank, *scan_sums; int64_t bytes; };
 CompLayout comp_layout(void* base, int64_t nf) {
     Take t{(char*)base, 256};
@@ -236,7 +224,7 @@ extern "C" int dgnn_mesh_components(const int32_t* faces, int64_t n_faces, int64
     int cur = 0;
     hipLaunchKernelGGL(k_edge_keys, mesh_launch_grid(n3), block, 0, stream, faces, n3, vb, 1, L.S.keys[0], L.S.vals[0]);
     hipLaunchKernelGGL(k_iota, mesh_launch_grid(n_faces), block, 0, stream, L.parent, n_faces);
-    if ((rc = dgnn_radix_sort_u64_i32(L.S.keys, L.S.vals, n3, 2 * vb, L.S.hist, L.S.scanned, L.S.sums, stream, &cur))) return rc;
+    if ((rc = sort_pairs(L.S, n3, 2 * vb, stream, &cur))) return rc;
     hipLaunchKernelGGL(k_link_union, mesh_launch_grid(n3), block, 0, stream, L.S.keys[cur], L.S.vals[cur], n3, L.parent);
     hipLaunchKernelGGL(k_face_roots, mesh_launch_grid(n_faces), block, 0, stream, L.parent, n_faces, L.root, L.is_root);
     if ((rc = dgnn_exclusive_scan_i32(L.is_root, n_faces, L.rank, L.scan_sums, stream))) return rc;
@@ -273,7 +261,7 @@ extern "C" int dgnn_mesh_component_measures(const double* vertices, int64_t n_ve
     if (rc) return rc;
     int cur = 0;
     hipLaunchKernelGGL(k_comp_keys, mesh_launch_grid(n_faces), block, 0, stream, comp, n_faces, L.S.keys[0], L.S.vals[0]);
-    if ((rc = dgnn_radix_sort_u64_i32(L.S.keys, L.S.vals, n_faces, key_bits(k), L.S.hist, L.S.scanned, L.S.sums, stream, &cur))) return rc;
+    if ((rc = sort_pairs(L.S, n_faces, key_bits(k), stream, &cur))) return rc;
     (void)hipMemsetAsync(L.seg_begin, 0, sizeof(int32_t) * k, stream);   // a component id without faces: an empty segment
     (void)hipMemsetAsync(L.seg_end, 0, sizeof(int32_t) * k, stream);
     hipLaunchKernelGGL(k_terms, mesh_launch_grid(n_faces), block, 0, stream, vertices, faces, L.S.keys[cur], L.S.vals[cur], n_faces, L.seg_begin, L.seg_end,

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "mesh_common.h"
 #include "vec3.h"
+#include "tet_common.h"
 #include "fixed_sum.h"
 
 int dgnn_exclusive_scan_i32(const int32_t* in, int64_t n, int32_t* out, int32_t* sums_scratch, hipStream_t stream);  // plan.hip
@@ -151,13 +152,8 @@ __global__ void k_nbr_fill(const int32_t* __restrict__ tets, int64_t nc, const i
         for (int s = 0; s < 2; ++s) {
             const int32_t c = c2[s];
             if (c < 0) continue;
-            int32_t miss = -1, hits = 0;
-            for (int k = 0; k < 4; ++k) {
-                const int32_t t = tets[4 * (int64_t)c + k];
-                if (t == x || t == y || t == z) ++hits;
-                else miss = k;
-            }
-            if (hits != 3 || miss < 0) { atomicOr(&st->err, MM_MALFORMED); continue; }
+            const int miss = facet_opposite_slot(tets + 4 * (int64_t)c, x, y, z);
+            if (miss < 0) { atomicOr(&st->err, MM_MALFORMED); continue; }
             nbr[4 * (int64_t)c + miss] = c2[1 - s];
         }
     }

@@ -9,33 +9,32 @@
 //              (vertex, link vertex) keys of every face corner: corners that share a key are joined in a union-find (hooking the larger
 //              root under the smaller by compare-and-swap), and a vertex is non-manifold when its corners keep two or more roots.
 //              Integer sums only: the counts do not depend on the schedule.
-#include "mesh_faces.h"
 #include "exact_orient.h"
+#include "mesh_faces.h"
+#include "tet_common.h"
 
 namespace {
 
 using dgnn_exact::V3;
 using dgnn_exact::load_v3;
 
+// the status bits of a point whose coordinates the exact predicate cannot take
 __device__ __forceinline__ int32_t coord_bits(const V3& p) {
     int32_t e = 0;
     const double c[3] = {p.x, p.y, p.z};
     for (int k = 0; k < 3; ++k) {
-        if (!isfinite(c[k])) e |= MT_NONFINITE;
-        else if (!dgnn_exact::orient_coord_ok(c[k])) e |= MT_RANGE;
+        const dgnn_exact::CoordClass cls = dgnn_exact::coord_class(c[k]);
+        if (cls == dgnn_exact::COORD_NONFINITE) e |= MT_NONFINITE;
+        else if (cls == dgnn_exact::COORD_RANGE) e |= MT_RANGE;
     }
     return e;
 }
 
-// the vertex of cell c that is not x, y or z; -1 when (x, y, z) is not a face of c
+// the vertex of cell c that is not x, y or z; -1 when (x, y, z) is not a face of c (tet_common.h: the facet / slot rule)
 __device__ __forceinline__ int32_t opposite_vertex(const int32_t* __restrict__ tets, int32_t c, int32_t x, int32_t y, int32_t z) {
-    int32_t miss = -1, hits = 0, n_miss = 0;
-    for (int k = 0; k < 4; ++k) {
-        const int32_t t = tets[4 * (int64_t)c + k];
-        if (t == x || t == y || t == z) ++hits;
-        else { miss = t; ++n_miss; }
-    }
-    return (hits == 3 && n_miss == 1) ? miss : -1;
+    const int32_t* const row = tets + 4 * (int64_t)c;
+    const int slot = facet_opposite_slot(row, x, y, z);
+    return slot < 0 ? -1 : row[slot];
 }
 
 // ---- orientation -------------------------------------------------------------------------------------------------------------
@@ -167,20 +166,12 @@ CompactLayout compact_layout(void* base, int64_t nv) {
     return L;
 }
 
-struct TopoLayout { MtState* st; uint64_t* keys[2]; int32_t *vals[2], *hist, *scanned, *sums, *parent, *roots; int64_t bytes; };
+struct TopoLayout { MtState* st; SortBufs S; int32_t *parent, *roots; int64_t bytes; };
 TopoLayout topo_layout(void* base, int64_t nfc, int64_t nv) {
     Take t{(char*)base, 256};
     TopoLayout L{};
-    const int64_t m = 6 * nfc;   // link keys; the 3 nfc edge keys use the front
-    const int64_t h = dgnn_radix_sort_hist_elems(m);
     L.st = (MtState*)base;
-    L.keys[0] = t.take<uint64_t>(m);
-    L.keys[1] = t.take<uint64_t>(m);
-    L.vals[0] = t.take<int32_t>(m);
-    L.vals[1] = t.take<int32_t>(m);
-    L.hist = t.take<int32_t>(h);
-    L.scanned = t.take<int32_t>(h);
-    L.sums = t.take<int32_t>(dgnn_cdiv(h, 2048) + 4);
+    take_sort(t, 6 * nfc, L.S);   // link keys; the 3 nfc edge keys use the front
     L.parent = t.take<int32_t>(3 * nfc);
     L.roots = t.take<int32_t>(nv);
     L.bytes = t.off;
@@ -261,13 +252,13 @@ extern "C" int dgnn_mesh_topology(const int32_t* faces, int64_t n_faces, int64_t
     int cur = 0;
     long long* counts = (long long*)counts_out;
     // edges
-    hipLaunchKernelGGL(k_edge_keys, mesh_launch_grid(n3), block, 0, stream, faces, n3, vb, 0, L.keys[0], L.vals[0]);
-    if ((rc = dgnn_radix_sort_u64_i32(L.keys, L.vals, n3, 2 * vb, L.hist, L.scanned, L.sums, stream, &cur))) return rc;
-    hipLaunchKernelGGL(k_edge_runs, mesh_launch_grid(n3), block, 0, stream, L.keys[cur], L.vals[cur], n3, counts);
+    hipLaunchKernelGGL(k_edge_keys, mesh_launch_grid(n3), block, 0, stream, faces, n3, vb, 0, L.S.keys[0], L.S.vals[0]);
+    if ((rc = sort_pairs(L.S, n3, 2 * vb, stream, &cur))) return rc;
+    hipLaunchKernelGGL(k_edge_runs, mesh_launch_grid(n3), block, 0, stream, L.S.keys[cur], L.S.vals[cur], n3, counts);
     // vertex fans
-    hipLaunchKernelGGL(k_link_keys, mesh_launch_grid(n3), block, 0, stream, faces, n3, vb, L.keys[0], L.vals[0], L.parent);
-    if ((rc = dgnn_radix_sort_u64_i32(L.keys, L.vals, 2 * n3, 2 * vb, L.hist, L.scanned, L.sums, stream, &cur))) return rc;
-    hipLaunchKernelGGL(k_link_union, mesh_launch_grid(2 * n3), block, 0, stream, L.keys[cur], L.vals[cur], 2 * n3, L.parent);
+    hipLaunchKernelGGL(k_link_keys, mesh_launch_grid(n3), block, 0, stream, faces, n3, vb, L.S.keys[0], L.S.vals[0], L.parent);
+    if ((rc = sort_pairs(L.S, 2 * n3, 2 * vb, stream, &cur))) return rc;
+    hipLaunchKernelGGL(k_link_union, mesh_launch_grid(2 * n3), block, 0, stream, L.S.keys[cur], L.S.vals[cur], 2 * n3, L.parent);
     (void)hipMemsetAsync(L.roots, 0, sizeof(int32_t) * (n_vertices > 0 ? n_vertices : 1), stream);
     hipLaunchKernelGGL(k_fan_roots, mesh_launch_grid(n3), block, 0, stream, faces, L.parent, n3, L.roots);
     hipLaunchKernelGGL(k_fan_count, mesh_launch_grid(n_vertices), block, 0, stream, L.roots, n_vertices, counts);

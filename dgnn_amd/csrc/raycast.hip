@@ -46,7 +46,10 @@ using RcCells = BoxCells;
 __device__ __forceinline__ int32_t rc_pick(const int32_t (&p)[3], int k) { return k == 0 ? p[0] : (k == 1 ? p[1] : p[2]); }
 // the status bits of a coordinate that is not finite or outside the exact predicate's range; the bounding box (k_bbox_referenced) leaves it out
 struct RcCoordErr {
-    __device__ int32_t operator()(double x) const { return !isfinite(x) ? RC_NONFINITE : (dgnn_exact::orient_coord_ok(x) ? 0 : RC_RANGE); }
+    __device__ int32_t operator()(double x) const {
+        const dgnn_exact::CoordClass k = dgnn_exact::coord_class(x);
+        return k == dgnn_exact::COORD_FINE ? 0 : (k == dgnn_exact::COORD_NONFINITE ? RC_NONFINITE : RC_RANGE);
+    }
 };
 
 __device__ __forceinline__ int32_t rc_cell(const RcGrid& g, int a, double x) { return grid_cell(g, a, x); }

@@ -2,8 +2,8 @@
 // aggregates of what it meets (`_cbff`, `_fbff`).  DESIGN §29; the rule is in include/dgnn_hip.h, operation by operation.  Every sign is exact
 // (exact_orient.h), every distance plain fp64 with each operation rounding on its own (-ffp-contract=off).
 //
-//   start    one thread per ray scans the tets incident to its vertex, as k_rays of scenefeat.hip does, with the perturbed side test sigma;
-//            per side the lowest qualifying tet (a minimum over a set: the row order of the incidence does not matter), its slot and the three
+//   start    one thread per ray scans the tets incident to its vertex through the prologue of tet_rays.h, which k_rays of scenefeat.hip
+//            runs too, here with the perturbed side test sigma; per side the lowest qualifying tet (a minimum over a set: the row order of the incidence does not matter), its slot and the three
 //            edge signs of its exit facet.
 //   walk     one lane per (ray, side).  A step is a chain of two dependent gathers: the tet row and the neighbour row of the new cell are
 //            read together (both addresses follow from the cell id, 16 bytes each), then the one apex vertex.  Three new signs decide the exit;
@@ -19,18 +19,15 @@
 // Every device loop is capped (the scan by the incidence row, the walk by n_tets steps); trouble goes to the status word.
 #include <chrono>
 
-#include "exact_orient.h"
-#include "mesh_faces.h"
+#include "tet_rays.h"
 
 namespace {
-
-using dgnn_exact::V3;
-using dgnn_exact::load_v3;
 
 enum { RW_NONE = 0, RW_SENSOR, RW_HULL, RW_DEPTH, RW_STUCK, RW_CAPPED, RW_N_STATUS };
 enum { RW_USED = 0, RW_SKIPPED, RW_PERTURBED, RW_EXACT, RW_DEGENERATE, RW_STATUS0, RW_RECORDS = RW_STATUS0 + RW_N_STATUS, RW_LONGEST, RW_N_STATS };
 static_assert(RW_N_STATS == 13, "the layout of stats_out in include/dgnn_hip.h");
-constexpr int64_t RW_MAX_RAYS = (int64_t)1 << 30;          // 2 n_rays lanes in int32; first[] is preset to 0x7f7f7f7f, above every ray index
+constexpr int64_t RW_MAX_RAYS = (int64_t)1 << 30;          // 2 n_rays lanes in int32
+static_assert(RW_MAX_RAYS <= RAY_FIRST_NONE, "the preset of first[] has to lie above every ray index");
 
 struct RwHead { MtState st; unsigned long long counters[RW_N_STATS]; };
 static_assert(sizeof(RwHead) <= 256, "RwHead must fit the first scratch slot");
@@ -71,15 +68,6 @@ __device__ __forceinline__ int crossing(int x, int y, int z) {
 
 __device__ __forceinline__ int32_t pack_start(int k, int s0, int s1, int s2) { return k | ((s0 + 1) << 2) | ((s1 + 1) << 4) | ((s2 + 1) << 6); }
 
-__device__ __forceinline__ int4 load_row(const int32_t* __restrict__ rows, int64_t c) { return *reinterpret_cast<const int4*>(rows + 4 * c); }
-__device__ __forceinline__ int32_t row_at(const int4& r, int k) { return k == 0 ? r.x : (k == 1 ? r.y : (k == 2 ? r.z : r.w)); }
-// the ids of the other three vertices around slot k, in slot order
-__device__ __forceinline__ void row_others(const int4& r, int k, int32_t& a, int32_t& b, int32_t& c) {
-    a = k <= 0 ? r.y : r.x;
-    b = k <= 1 ? r.z : r.y;
-    c = k <= 2 ? r.w : r.z;
-}
-
 // ---- checks ------------------------------------------------------------------------------------------------------------------------
 __global__ void k_walk_check_neighbors(const int32_t* __restrict__ nbr, int64_t n4, int64_t nt, int32_t* err) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
@@ -88,17 +76,8 @@ __global__ void k_walk_check_neighbors(const int32_t* __restrict__ nbr, int64_t 
 
 __global__ void k_walk_check_coords(const double* __restrict__ x, int64_t n3, int32_t* err) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x) {
-        const double a = x[i];
-        if (!(fabs(a) <= 1.79769313486231570815e308)) atomicOr(err, MT_NONFINITE);
-        else if (!dgnn_exact::orient_coord_ok(a)) atomicOr(err, MT_RANGE);
-    }
-}
-
-__global__ void k_walk_ray_first(const int32_t* __restrict__ ray_vertex, int64_t nr, int64_t nv, int unique, int32_t* first, int32_t* err) {
-    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < nr; r += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t a = ray_vertex[r];
-        if (a < 0 || a >= nv) atomicOr(err, MT_BAD_ID);
-        else if (unique) atomicMin(first + a, (int32_t)r);
+        const dgnn_exact::CoordClass k = dgnn_exact::coord_class(x[i]);
+        if (k != dgnn_exact::COORD_FINE) atomicOr(err, k == dgnn_exact::COORD_NONFINITE ? MT_NONFINITE : MT_RANGE);
     }
 }
 
@@ -118,14 +97,12 @@ k_walk_start(const double* __restrict__ v, const int32_t* __restrict__ tets, int
         if ((s.x == p.x && s.y == p.y && s.z == p.z) || (unique && first[vid] != (int32_t)r)) ++n_skipped;
         else {
             ++n_used;
-            const int64_t b = rowptr[vid], e = rowptr[vid + 1];
-            if (b < 0 || e < b || e > 4 * nt) atomicOr(&st->err, MT_BAD_ID);
-            else
+            int64_t b, e;
+            if (corner_row(rowptr, vid, nt, b, e, st))
                 for (int64_t i = b; i < e; ++i) {
-                    const int32_t ent = entries[i];
-                    if (ent < 0 || ent >= 4 * nt || tets[ent] != vid) { atomicOr(&st->err, MT_BAD_ID); continue; }   // not a corner of this vertex
-                    const int32_t t = ent >> 2;
-                    const int k = ent & 3;
+                    int32_t t;
+                    int k;
+                    if (!corner_of(tets, nt, entries[i], vid, t, k, st)) continue;
                     int32_t i0, i1, i2;
                     row_others(load_row(tets, t), k, i0, i1, i2);
                     const V3 q0 = load_v3(v, i0), q1 = load_v3(v, i1), q2 = load_v3(v, i2);
@@ -189,10 +166,8 @@ k_walk(WalkIn in, WalkRec rec, int32_t* __restrict__ ray_cells, int32_t* __restr
             const int32_t info = in.start_info[lane];
             int k = info & 3, sg0 = ((info >> 2) & 3) - 1, sg1 = ((info >> 4) & 3) - 1, sg2 = ((info >> 6) & 3) - 1;
             const V3 p = load_v3(in.v, in.ray_vertex[r]), s = load_v3(in.sensors, r);
-            const V3 e = sub(s, p);
-            const double len = sqrt(dot(e, e));
-            V3 d{e.x / len, e.y / len, e.z / len};
-            if (side) d = V3{-d.x, -d.y, -d.z};
+            double len;
+            const V3 d = unit_ray(sub(s, p), side, len);
             const int32_t depth = in.depth[side];
             const int32_t expect = FILL ? ray_cells[lane] : 0;
             const int64_t base = FILL ? rec.offs[lane - in.lane0] : 0;
@@ -230,10 +205,9 @@ k_walk(WalkIn in, WalkRec rec, int32_t* __restrict__ ray_cells, int32_t* __restr
                     int32_t i0, i1, i2;
                     row_others(row, k, i0, i1, i2);
                     const V3 q0 = pick(i0, f0, f1, P0, P1, P2), q1 = pick(i1, f0, f1, P0, P1, P2), q2 = pick(i2, f0, f1, P0, P1, P2);
-                    const V3 n = cross(sub(q1, q0), sub(q2, q0));
-                    const double den = dot(n, d);
-                    double dist = dot(n, sub(q0, p)) / den;
-                    if (den == 0.0 || !(fabs(dist) <= 1.79769313486231570815e308)) { dist = prev; ++n_degenerate; }
+                    double den;
+                    double dist = plane_distance(p, d, q0, q1, q2, den);
+                    if (den == 0.0 || !dgnn_exact::coord_finite(dist)) { dist = prev; ++n_degenerate; }
                     prev = dist;
                 }
                 if (recorded) {
@@ -245,10 +219,9 @@ k_walk(WalkIn in, WalkRec rec, int32_t* __restrict__ ray_cells, int32_t* __restr
                 if (++steps > in.nt) { status = RW_CAPPED; break; }
                 row = load_row(in.tets, nxt);
                 nrow = load_row(in.nbr, nxt);
-                const bool in0 = row.x == f0 || row.x == f1 || row.x == f2, in1 = row.y == f0 || row.y == f1 || row.y == f2;
-                const bool in2 = row.z == f0 || row.z == f1 || row.z == f2, in3 = row.w == f0 || row.w == f1 || row.w == f2;
-                if ((int)in0 + in1 + in2 + in3 != 3) { atomicOr(&st->err, MT_NOT_FACE); status = RW_STUCK; break; }   // not the cell across the facet
-                const int32_t w = !in0 ? row.x : (!in1 ? row.y : (!in2 ? row.z : row.w));
+                const int apex = facet_opposite_slot(row, f0, f1, f2);
+                if (apex < 0) { atomicOr(&st->err, MT_NOT_FACE); status = RW_STUCK; break; }   // not the cell across the facet
+                const int32_t w = row_at(row, apex);
                 const V3 W = load_v3(in.v, w);
                 const int a0 = sigma(p, s, W, P0, exact, perturbed), a1 = sigma(p, s, W, P1, exact, perturbed), a2 = sigma(p, s, W, P2, exact, perturbed);
                 // the facet opposite f_m is (w, f_m+1, f_m+2) with the signs (a_m+1, sg_m+1, -a_m+2)
@@ -301,27 +274,6 @@ __global__ void k_walk_keys(const int32_t* __restrict__ lane, const int32_t* __r
     }
 }
 
-__global__ void k_walk_runs(const uint64_t* __restrict__ keys, int64_t n, int64_t n_keys, int32_t* __restrict__ run_begin, int32_t* __restrict__ run_end) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t c = keys[i];
-        if (c >= (uint64_t)n_keys) continue;
-        if (i == 0 || keys[i - 1] != c) run_begin[c] = (int32_t)i;
-        if (i == n - 1 || keys[i + 1] != c) run_end[c] = (int32_t)(i + 1);
-    }
-}
-
-// min, max and sum of one column, continuing from memory: stat[0], stat[stride], stat[2 stride]; n = the count before the value
-struct WalkFold {
-    double lo, hi, sum;
-    __device__ __forceinline__ void load(const double* stat, int64_t stride) { lo = stat[0]; hi = stat[stride]; sum = stat[2 * stride]; }
-    __device__ __forceinline__ void store(double* stat, int64_t stride) const { stat[0] = lo; stat[stride] = hi; stat[2 * stride] = sum; }
-    __device__ __forceinline__ void add(int32_t n, double d) {
-        lo = n == 0 ? d : (d < lo ? d : lo);
-        hi = n == 0 ? d : (d > hi ? d : hi);
-        sum = sum + d;
-    }
-};
-
 // one thread per (side, cell): its run of records, ascending (ray, step), folded serially onto what the earlier chunks left.
 // cell_count [2, T], cell_stat [2, 6, T] = first min / max / sum, second min / max / sum; slot_count [2, T, 4], slot_stat [2, 3, T, 4].
 __global__ void k_walk_fold(const int32_t* __restrict__ order, const int32_t* __restrict__ run_begin, const int32_t* __restrict__ run_end, int64_t nt,
@@ -335,7 +287,7 @@ __global__ void k_walk_fold(const int32_t* __restrict__ order, const int32_t* __
         double* const cs = cell_stat + side * 6 * nt + t;
         double* const ss = slot_stat + side * 12 * nt + 4 * t;
         int32_t n = cell_count[i], n0 = slot_count[4 * i], n1 = slot_count[4 * i + 1], n2 = slot_count[4 * i + 2], n3 = slot_count[4 * i + 3];
-        WalkFold fa, fb, s0, s1, s2, s3;
+        Fold fa, fb, s0, s1, s2, s3;
         fa.load(cs, nt);
         fb.load(cs + 3 * nt, nt);
         s0.load(ss, 4 * nt);
@@ -392,14 +344,12 @@ struct WalkLayout {
     int32_t *first, *start_tet, *start_info, *pert, *offs, *scan_sums, *run_begin, *run_end;
     int32_t *rec_lane, *rec_cell, *rec_slot;
     double *rec_first, *rec_second;
-    uint64_t* keys[2];
-    int32_t *vals[2], *hist, *scanned, *sums;
+    SortBufs S;
     int64_t bytes;
 };
 WalkLayout walk_layout(void* base, int64_t nr, int64_t nt, int64_t nv, int64_t m) {
     Take t{(char*)base, 256};
     WalkLayout L{};
-    const int64_t h = dgnn_radix_sort_hist_elems(m);
     L.head = (RwHead*)base;
     L.first = t.take<int32_t>(nv);
     L.start_tet = t.take<int32_t>(2 * nr);
@@ -414,13 +364,7 @@ WalkLayout walk_layout(void* base, int64_t nr, int64_t nt, int64_t nv, int64_t m
     L.rec_slot = t.take<int32_t>(m);
     L.rec_first = t.take<double>(m);
     L.rec_second = t.take<double>(m);
-    L.keys[0] = t.take<uint64_t>(m);
-    L.keys[1] = t.take<uint64_t>(m);
-    L.vals[0] = t.take<int32_t>(m);
-    L.vals[1] = t.take<int32_t>(m);
-    L.hist = t.take<int32_t>(h);
-    L.scanned = t.take<int32_t>(h);
-    L.sums = t.take<int32_t>(dgnn_cdiv(h, 2048) + 4);
+    take_sort(t, m, L.S);
     L.bytes = t.off;
     return L;
 }
@@ -486,7 +430,7 @@ extern "C" int dgnn_ray_walk(const double* vertices, int64_t n_vertices, const i
     int32_t* const err = &L.head->st.err;
     StageClock clock(stream);
     (void)hipMemsetAsync(L.head, 0, sizeof(RwHead), stream);
-    if (n_vertices > 0) (void)hipMemsetAsync(L.first, 0x7f, sizeof(int32_t) * n_vertices, stream);   // 0x7f7f7f7f: above every ray index
+    ray_first_preset(L.first, n_vertices, stream);
     if (n_tets > 0) {
         (void)hipMemsetAsync(cell_count_out, 0, sizeof(int32_t) * 2 * n_tets, stream);
         (void)hipMemsetAsync(cell_stat_out, 0, sizeof(double) * 12 * n_tets, stream);
@@ -498,7 +442,7 @@ extern "C" int dgnn_ray_walk(const double* vertices, int64_t n_vertices, const i
     if (n_vertices > 0) hipLaunchKernelGGL(k_walk_check_coords, mesh_launch_grid(3 * n_vertices), block, 0, stream, vertices, 3 * n_vertices, err);
     if (n_rays > 0) {
         hipLaunchKernelGGL(k_walk_check_coords, mesh_launch_grid(3 * n_rays), block, 0, stream, sensors, 3 * n_rays, err);
-        hipLaunchKernelGGL(k_walk_ray_first, mesh_launch_grid(n_rays), block, 0, stream, ray_vertex, n_rays, n_vertices, unique, L.first, err);
+        hipLaunchKernelGGL(k_ray_first, mesh_launch_grid(n_rays), block, 0, stream, ray_vertex, n_rays, n_vertices, unique, L.first, err);
     }
     MtState hs{};
     int rc = mt_read_status(&hs, &L.head->st, stream, "ray_walk");
@@ -551,13 +495,13 @@ extern "C" int dgnn_ray_walk(const double* vertices, int64_t n_vertices, const i
             if ((rc = dgnn_exclusive_scan_i32(ray_cells_out + l0, l1 - l0, L.offs, L.scan_sums, stream))) break;
             hipLaunchKernelGGL((k_walk<true>), mesh_launch_grid(l1 - l0), block, 0, stream, in, rec, ray_cells_out, ray_status_out, L.pert, L.head->counters, &L.head->st);
             clock.lap(1);
-            hipLaunchKernelGGL(k_walk_keys, mesh_launch_grid(m), block, 0, stream, L.rec_lane, L.rec_cell, m, n_tets, L.keys[0], L.vals[0]);
-            if ((rc = dgnn_radix_sort_u64_i32(L.keys, L.vals, m, key_bits(2 * n_tets + 1), L.hist, L.scanned, L.sums, stream, &cur))) break;
+            hipLaunchKernelGGL(k_walk_keys, mesh_launch_grid(m), block, 0, stream, L.rec_lane, L.rec_cell, m, n_tets, L.S.keys[0], L.S.vals[0]);
+            if ((rc = sort_pairs(L.S, m, key_bits(2 * n_tets + 1), stream, &cur))) break;
             clock.lap(2);
             (void)hipMemsetAsync(L.run_begin, 0, sizeof(int32_t) * 2 * n_tets, stream);          // a cell without records: an empty run
             (void)hipMemsetAsync(L.run_end, 0, sizeof(int32_t) * 2 * n_tets, stream);
-            hipLaunchKernelGGL(k_walk_runs, mesh_launch_grid(m), block, 0, stream, L.keys[cur], m, 2 * n_tets, L.run_begin, L.run_end);
-            hipLaunchKernelGGL(k_walk_fold, mesh_launch_grid(2 * n_tets), block, 0, stream, L.vals[cur], L.run_begin, L.run_end, n_tets, L.rec_slot, L.rec_first,
+            hipLaunchKernelGGL(k_ray_runs, mesh_launch_grid(m), block, 0, stream, L.S.keys[cur], m, 2 * n_tets, L.run_begin, L.run_end);
+            hipLaunchKernelGGL(k_walk_fold, mesh_launch_grid(2 * n_tets), block, 0, stream, L.S.vals[cur], L.run_begin, L.run_end, n_tets, L.rec_slot, L.rec_first,
                                L.rec_second, cell_count_out, cell_stat_out, slot_count_out, slot_stat_out);
             if (records_capacity > 0)
                 hipLaunchKernelGGL(k_walk_copy_records, mesh_launch_grid(m), block, 0, stream, L.rec_lane, L.rec_cell, L.rec_slot, L.rec_first, L.rec_second, L.offs,

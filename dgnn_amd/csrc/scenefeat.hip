@@ -10,23 +10,19 @@
 //               lowest qualifying tet: a minimum over a set, so the row order does not matter.  The (tet, slot, dist) record of either
 //               side is stored per ray; per side the ray ids are sorted stably by tet, so every tet owns a run of ray ids in ascending
 //               order, and one thread per tet folds its run serially: counts, min / max and the sums in ascending ray index, for the tet
-//               and for each of its four slots.  No floating-point atomics: reruns are bit-identical.
-#include "exact_orient.h"
+//               and for each of its four slots.  No floating-point atomics: reruns are bit-identical.  The steps that the facet-ray walk
+//               (raywalk.hip) takes as well -- first ray per vertex, the incident-corner prologue, ray lengths, runs, the fold -- are
+//               tet_rays.h's; the facet / slot rule and the row helpers are tet_common.h's.
 #include "fixed_sum.h"
-#include "mesh_faces.h"
+#include "tet_rays.h"
 
 namespace {
 
-using dgnn_exact::V3;
-using dgnn_exact::load_v3;
-
 constexpr int SF_SIDES = 2;          // 0 = outside (towards the sensor), 1 = inside (away from it)
-constexpr int64_t SF_MAX_RAYS = 0x7f7f7f7f;   // first[] is preset bytewise to this value, which has to lie above every ray index
+constexpr int64_t SF_MAX_RAYS = RAY_FIRST_NONE;
 enum { SF_USED = 0, SF_DUPLICATE, SF_DEGENERATE, SF_NO_OUTSIDE, SF_NO_INSIDE, SF_EXACT, SF_N_STATS };
 
-__device__ __forceinline__ bool coords_ok(const V3& a) {
-    return dgnn_exact::orient_coord_ok(a.x) && dgnn_exact::orient_coord_ok(a.y) && dgnn_exact::orient_coord_ok(a.z);
-}
+using dgnn_exact::orient_coords_ok;
 
 // ---- neighbours ----------------------------------------------------------------------------------------------------------------
 __global__ void k_neighbors(const int32_t* __restrict__ tets, int64_t nt, const int32_t* __restrict__ facets, const int32_t* __restrict__ nfacets,
@@ -38,15 +34,8 @@ __global__ void k_neighbors(const int32_t* __restrict__ tets, int64_t nt, const 
         if (c < -1 || c >= nt || other < -1 || other >= nt) { atomicOr(&st->err, MT_BAD_ID); continue; }
         if (c < 0) continue;
         const int32_t f0 = facets[3 * f], f1 = facets[3 * f + 1], f2 = facets[3 * f + 2];
-        int hits = 0, slot = 0;
-#pragma unroll
-        for (int k = 3; k >= 0; --k) {
-            const int32_t a = tets[4 * (int64_t)c + k];
-            const bool hit = a == f0 || a == f1 || a == f2;
-            hits += hit;
-            if (!hit) slot = k;
-        }
-        if (hits == 3) nbr[4 * (int64_t)c + slot] = other;
+        const int slot = facet_opposite_slot(tets + 4 * (int64_t)c, f0, f1, f2);
+        if (slot >= 0) nbr[4 * (int64_t)c + slot] = other;
         else ++bad;
     }
     wave_add_atomic(bad, n_bad);
@@ -64,7 +53,7 @@ __global__ void k_cell_geometry(const double* __restrict__ v, int64_t nv, const 
     unsigned long long flat = 0;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nt; t += (int64_t)gridDim.x * blockDim.x) {
         const int32_t i0 = tets[4 * t], i1 = tets[4 * t + 1], i2 = tets[4 * t + 2], i3 = tets[4 * t + 3];
-        if (i0 < 0 || i0 >= nv || i1 < 0 || i1 >= nv || i2 < 0 || i2 >= nv || i3 < 0 || i3 >= nv) {
+        if (!tet_ids_ok(i0, i1, i2, i3, nv)) {
             atomicOr(&st->err, MT_BAD_ID);
             radius[t] = vol[t] = longest[t] = shortest[t] = 0.0;
             continue;
@@ -106,29 +95,20 @@ __global__ void k_incidence_fill(const int32_t* __restrict__ tets, int64_t n4, i
 }
 
 // ---- rays ----------------------------------------------------------------------------------------------------------------------
-// the ids of the rays, and first[v] = the lowest ray index of vertex v
-__global__ void k_ray_first(const int32_t* __restrict__ ray_vertex, int64_t nr, int64_t nv, int unique, int32_t* first, MtState* st) {
-    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < nr; r += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t a = ray_vertex[r];
-        if (a < 0 || a >= nv) atomicOr(&st->err, MT_BAD_ID);
-        else if (unique) atomicMin(first + a, (int32_t)r);
-    }
-}
-
 // the other three vertices of tet t around slot k, in slot order
 __device__ __forceinline__ void other_vertices(const double* __restrict__ v, const int32_t* __restrict__ tets, int64_t t, int k, V3& q0, V3& q1, V3& q2) {
-    q0 = load_v3(v, tets[4 * t + (k <= 0)]);
-    q1 = load_v3(v, tets[4 * t + 1 + (k <= 1)]);
-    q2 = load_v3(v, tets[4 * t + 2 + (k <= 2)]);
+    int32_t i0, i1, i2;
+    row_others(tets + 4 * t, k, i0, i1, i2);
+    q0 = load_v3(v, i0);
+    q1 = load_v3(v, i1);
+    q2 = load_v3(v, i2);
 }
 
 // the ray length from p to the plane of (q0, q1, q2) along e / |e| (flip = 0) or its negative (flip = 1)
 __device__ __forceinline__ double ray_length(const V3& p, const V3& e, int flip, const V3& q0, const V3& q1, const V3& q2) {
-    const double len = sqrt(dot(e, e));
-    V3 d{e.x / len, e.y / len, e.z / len};
-    if (flip) d = V3{-d.x, -d.y, -d.z};
-    const V3 n = cross(sub(q1, q0), sub(q2, q0));
-    return dot(n, sub(q0, p)) / dot(n, d);
+    double len, den;
+    const V3 d = unit_ray(e, flip, len);
+    return plane_distance(p, d, q0, q1, q2, den);
 }
 
 __global__ void __launch_bounds__(MESH_THREADS)
@@ -145,20 +125,18 @@ k_rays(const double* __restrict__ v, int64_t nv, const int32_t* __restrict__ tet
         bool live = true;
         if (s.x == p.x && s.y == p.y && s.z == p.z) { ++cnt[SF_DEGENERATE]; live = false; }
         else if (unique && first[vid] != (int32_t)r) { ++cnt[SF_DUPLICATE]; live = false; }
-        else if (!coords_ok(p) || !coords_ok(s)) { atomicOr(&st->err, s.x == s.x && s.y == s.y && s.z == s.z ? MT_RANGE : MT_NONFINITE); live = false; }
+        else if (!orient_coords_ok(p) || !orient_coords_ok(s)) { atomicOr(&st->err, s.x == s.x && s.y == s.y && s.z == s.z ? MT_RANGE : MT_NONFINITE); live = false; }
         if (live) {
             ++cnt[SF_USED];
-            const int64_t b = rowptr[vid], e = rowptr[vid + 1];
-            if (b < 0 || e < b || e > 4 * nt) atomicOr(&st->err, MT_BAD_ID);
-            else
+            int64_t b, e;
+            if (corner_row(rowptr, vid, nt, b, e, st))
                 for (int64_t i = b; i < e; ++i) {
-                    const int32_t ent = entries[i];
-                    if (ent < 0 || ent >= 4 * nt || tets[ent] != vid) { atomicOr(&st->err, MT_BAD_ID); continue; }   // not a corner of this vertex
-                    const int32_t t = ent >> 2;
-                    const int k = ent & 3;
+                    int32_t t;
+                    int k;
+                    if (!corner_of(tets, nt, entries[i], vid, t, k, st)) continue;
                     V3 q0, q1, q2;
                     other_vertices(v, tets, t, k, q0, q1, q2);
-                    if (!coords_ok(q0) || !coords_ok(q1) || !coords_ok(q2)) { atomicOr(&st->err, MT_RANGE); continue; }
+                    if (!orient_coords_ok(q0) || !orient_coords_ok(q1) || !orient_coords_ok(q2)) { atomicOr(&st->err, MT_RANGE); continue; }
                     // det[q0 - p, q1 - p, q2 - p] is the orientation of each facet (p, qa, qb) through p against the remaining vertex, the
                     // facets taken cyclically; the sensor qualifies on a side when it agrees with it (or lies on the plane) on all three
                     int ex[4] = {0, 0, 0, 0};
@@ -200,53 +178,31 @@ __global__ void k_ray_keys(const int32_t* __restrict__ ray_tet, int64_t nr, int 
     }
 }
 
-__global__ void k_ray_runs(const uint64_t* __restrict__ keys, int64_t nr, int64_t nt, int32_t* __restrict__ run_begin, int32_t* __restrict__ run_end) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nr; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t c = keys[i];
-        if (c >= (uint64_t)nt) continue;
-        if (i == 0 || keys[i - 1] != c) run_begin[c] = (int32_t)i;
-        if (i == nr - 1 || keys[i + 1] != c) run_end[c] = (int32_t)(i + 1);
-    }
-}
-
-struct Fold {
-    int32_t n = 0;
-    double lo = 0.0, hi = 0.0, sum = 0.0;
-    __device__ __forceinline__ void add(double d) {
-        lo = n == 0 ? d : (d < lo ? d : lo);
-        hi = n == 0 ? d : (d > hi ? d : hi);
-        sum = sum + d;
-        ++n;
-    }
-};
-
 // one thread per tet: its run of ray ids (ascending) folded serially.  count [T], stat [3, T] = min, max, sum; the same per slot with T -> 4 T.
 __global__ void k_ray_fold(const int32_t* __restrict__ order, const int32_t* __restrict__ run_begin, const int32_t* __restrict__ run_end, int64_t nt,
                            int side, const int32_t* __restrict__ ray_slot, const double* __restrict__ ray_dist, int32_t* __restrict__ tet_count,
                            double* __restrict__ tet_stat, int32_t* __restrict__ slot_count, double* __restrict__ slot_stat) {
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < nt; t += (int64_t)gridDim.x * blockDim.x) {
         Fold all, s0, s1, s2, s3;
+        int32_t n = 0, n0 = 0, n1 = 0, n2 = 0, n3 = 0;
         for (int64_t i = run_begin[t]; i < run_end[t]; ++i) {
             const int64_t r = order[i];
             const int k = ray_slot[SF_SIDES * r + side];
             const double d = ray_dist[SF_SIDES * r + side];
-            all.add(d);
-            if (k == 0) s0.add(d);
-            else if (k == 1) s1.add(d);
-            else if (k == 2) s2.add(d);
-            else s3.add(d);
+            all.add(n++, d);
+            if (k == 0) s0.add(n0++, d);
+            else if (k == 1) s1.add(n1++, d);
+            else if (k == 2) s2.add(n2++, d);
+            else s3.add(n3++, d);
         }
-        tet_count[t] = all.n;
-        tet_stat[t] = all.lo;
-        tet_stat[nt + t] = all.hi;
-        tet_stat[2 * nt + t] = all.sum;
+        tet_count[t] = n;
+        all.store(tet_stat + t, nt);
         const Fold* const f[4] = {&s0, &s1, &s2, &s3};
+        const int32_t fn[4] = {n0, n1, n2, n3};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            slot_count[4 * t + k] = f[k]->n;
-            slot_stat[4 * t + k] = f[k]->lo;
-            slot_stat[4 * nt + 4 * t + k] = f[k]->hi;
-            slot_stat[8 * nt + 4 * t + k] = f[k]->sum;
+            slot_count[4 * t + k] = fn[k];
+            f[k]->store(slot_stat + 4 * t + k, 4 * nt);
         }
     }
 }
@@ -268,19 +224,12 @@ IncLayout inc_layout(void* base, int64_t nv) {
     return L;
 }
 
-struct RayLayout { Head* head; uint64_t* keys[2]; int32_t *vals[2], *hist, *scanned, *sums, *first, *run_begin, *run_end; int64_t bytes; };
+struct RayLayout { Head* head; SortBufs S; int32_t *first, *run_begin, *run_end; int64_t bytes; };
 RayLayout ray_layout(void* base, int64_t nr, int64_t nt, int64_t nv) {
     Take t{(char*)base, 256};
     RayLayout L{};
-    const int64_t h = dgnn_radix_sort_hist_elems(nr);
     L.head = (Head*)base;
-    L.keys[0] = t.take<uint64_t>(nr);
-    L.keys[1] = t.take<uint64_t>(nr);
-    L.vals[0] = t.take<int32_t>(nr);
-    L.vals[1] = t.take<int32_t>(nr);
-    L.hist = t.take<int32_t>(h);
-    L.scanned = t.take<int32_t>(h);
-    L.sums = t.take<int32_t>(dgnn_cdiv(h, 2048) + 4);
+    take_sort(t, nr, L.S);
     L.first = t.take<int32_t>(nv);
     L.run_begin = t.take<int32_t>(nt);
     L.run_end = t.take<int32_t>(nt);
@@ -381,9 +330,9 @@ extern "C" int dgnn_vertex_rays(const double* vertices, int64_t n_vertices, cons
     const RayLayout L = ray_layout(scratch, n_rays, n_tets, n_vertices);
     const dim3 block(MESH_THREADS);
     (void)hipMemsetAsync(L.head, 0, sizeof(Head), stream);
-    if (n_vertices > 0) (void)hipMemsetAsync(L.first, 0x7f, sizeof(int32_t) * n_vertices, stream);   // 0x7f7f7f7f: above every ray index
+    ray_first_preset(L.first, n_vertices, stream);
     if (n_tets > 0) hipLaunchKernelGGL(k_check_ids, mesh_launch_grid(4 * n_tets), block, 0, stream, tetrahedra, 4 * n_tets, n_vertices, &L.head->st.err, MT_BAD_ID);
-    if (n_rays > 0) hipLaunchKernelGGL(k_ray_first, mesh_launch_grid(n_rays), block, 0, stream, ray_vertex, n_rays, n_vertices, unique, L.first, &L.head->st);
+    if (n_rays > 0) hipLaunchKernelGGL(k_ray_first, mesh_launch_grid(n_rays), block, 0, stream, ray_vertex, n_rays, n_vertices, unique, L.first, &L.head->st.err);
     MtState hs{};
     int rc = mt_read_status(&hs, &L.head->st, stream, "vertex_rays");
     if (rc) return rc;
@@ -393,13 +342,13 @@ extern "C" int dgnn_vertex_rays(const double* vertices, int64_t n_vertices, cons
     for (int side = 0; side < SF_SIDES && n_tets > 0; ++side) {
         int cur = 0;
         if (n_rays > 0) {
-            hipLaunchKernelGGL(k_ray_keys, mesh_launch_grid(n_rays), block, 0, stream, ray_tet_out, n_rays, side, n_tets, L.keys[0], L.vals[0]);
-            if ((rc = dgnn_radix_sort_u64_i32(L.keys, L.vals, n_rays, key_bits(n_tets + 1), L.hist, L.scanned, L.sums, stream, &cur))) return rc;
+            hipLaunchKernelGGL(k_ray_keys, mesh_launch_grid(n_rays), block, 0, stream, ray_tet_out, n_rays, side, n_tets, L.S.keys[0], L.S.vals[0]);
+            if ((rc = sort_pairs(L.S, n_rays, key_bits(n_tets + 1), stream, &cur))) return rc;
         }
         (void)hipMemsetAsync(L.run_begin, 0, sizeof(int32_t) * n_tets, stream);          // a tet without rays: an empty run
         (void)hipMemsetAsync(L.run_end, 0, sizeof(int32_t) * n_tets, stream);
-        if (n_rays > 0) hipLaunchKernelGGL(k_ray_runs, mesh_launch_grid(n_rays), block, 0, stream, L.keys[cur], n_rays, n_tets, L.run_begin, L.run_end);
-        hipLaunchKernelGGL(k_ray_fold, mesh_launch_grid(n_tets), block, 0, stream, L.vals[cur], L.run_begin, L.run_end, n_tets, side, ray_slot_out, ray_dist_out,
+        if (n_rays > 0) hipLaunchKernelGGL(k_ray_runs, mesh_launch_grid(n_rays), block, 0, stream, L.S.keys[cur], n_rays, n_tets, L.run_begin, L.run_end);
+        hipLaunchKernelGGL(k_ray_fold, mesh_launch_grid(n_tets), block, 0, stream, L.S.vals[cur], L.run_begin, L.run_end, n_tets, side, ray_slot_out, ray_dist_out,
                            tet_count_out + side * n_tets, tet_stat_out + side * 3 * n_tets, slot_count_out + side * 4 * n_tets,
                            slot_stat_out + side * 12 * n_tets);
     }

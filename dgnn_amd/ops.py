@@ -1658,6 +1658,29 @@ def potts_weight(binary_weight) -> int:
     return w
 
 
+def _cut_arrays(logits, edges):
+    """the inputs of a graph cut on their device, then n, F and its output arrays: labels [n], (energy, flow) int64, (steps, relabels) int32"""
+    dev = logits.device if isinstance(logits, torch.Tensor) and logits.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    logits = torch.as_tensor(logits).to(dev, torch.float32)
+    edges = torch.as_tensor(edges).to(dev, torch.int32).contiguous()
+    if logits.dim() != 2 or logits.size(1) != 2:
+        raise ValueError("logits must be [n, 2], got %s" % (tuple(logits.shape),))
+    if edges.numel() == 0:
+        edges = edges.reshape(0, 2)
+    if edges.dim() != 2 or edges.size(1) != 2:
+        raise ValueError("edges must be [F, 2], got %s" % (tuple(edges.shape),))
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    n = logits.size(0)
+    return (dev, logits, edges, n, edges.size(0), _empty(dev, torch.int32, n), torch.zeros(2, dtype=torch.int64, device=dev),
+            torch.zeros(2, dtype=torch.int32, device=dev))
+
+
+def _cut_result(labels, out64, stats, return_stats):
+    energy, flow = (int(v) for v in out64.cpu())
+    return (labels, energy, flow, _stats_dict(("steps", "relabels"), stats)) if return_stats else (labels, energy, flow)
+
+
 @on_device_of
 def binary_graph_cut(logits, edges, unary_weight, binary_weight, return_stats=False):
     """Exact minimum of the reference's two-label graph-cut energy (dgnn_graph_cut_binary):
@@ -1668,29 +1691,11 @@ def binary_graph_cut(logits, edges, unary_weight, binary_weight, return_stats=Fa
     non-finite logits, |cost| >= 2^30 or capacities that overflow int32."""
 
     w = potts_weight(binary_weight)
-    dev = logits.device if isinstance(logits, torch.Tensor) and logits.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    logits = torch.as_tensor(logits).to(dev, torch.float32)
-    edges = torch.as_tensor(edges).to(dev, torch.int32).contiguous()
-    if logits.dim() != 2 or logits.size(1) != 2:
-        raise ValueError("logits must be [n, 2], got %s" % (tuple(logits.shape),))
-    if edges.numel() == 0:
-        edges = edges.reshape(0, 2)
-    if edges.dim() != 2 or edges.size(1) != 2:
-        raise ValueError("edges must be [F, 2], got %s" % (tuple(edges.shape),))
-    if logits.stride(1) != 1:
-        logits = logits.contiguous()
-    n, f = logits.size(0), edges.size(0)
-    labels = _empty(dev, torch.int32, n)
-    out64 = torch.zeros(2, dtype=torch.int64, device=dev)
-    stats = torch.zeros(2, dtype=torch.int32, device=dev)
-    scratch = torch.empty(int(lib().dgnn_graph_cut_scratch_bytes(n, f)), dtype=torch.uint8, device=dev)
+    dev, logits, edges, n, f, labels, out64, stats = _cut_arrays(logits, edges)
+    scratch = _scratch(dev, lib().dgnn_graph_cut_scratch_bytes(n, f))
     check(lib().dgnn_graph_cut_binary(ptr(logits), max(_ld(logits), 2) if n else 2, n, ptr(edges), f, float(unary_weight), w, ptr(labels),
                                       ptr(out64), C.c_void_p(out64.data_ptr() + 8), ptr(stats), ptr(scratch), stream_ptr()), "dgnn_graph_cut_binary")
-    energy, flow = (int(v) for v in out64.cpu())
-    if return_stats:
-        s = stats.cpu()
-        return labels, energy, flow, {"steps": int(s[0]), "relabels": int(s[1])}
-    return labels, energy, flow
+    return _cut_result(labels, out64, stats, return_stats)
 
 
 @on_device_of
@@ -1701,15 +1706,7 @@ def weighted_graph_cut(logits, edges, unary_weight, row_weights, return_stats=Fa
     binary_graph_cut returns; with every weight equal to w, exactly what binary_graph_cut(..., w) returns (steps and relabels too).
     Raises ValueError for a wrong length or shape, DgnnError for a negative weight, capacities that overflow int32 and what
     binary_graph_cut raises."""
-    dev = logits.device if isinstance(logits, torch.Tensor) and logits.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    logits = torch.as_tensor(logits).to(dev, torch.float32)
-    edges = torch.as_tensor(edges).to(dev, torch.int32).contiguous()
-    if logits.dim() != 2 or logits.size(1) != 2:
-        raise ValueError("logits must be [n, 2], got %s" % (tuple(logits.shape),))
-    if edges.numel() == 0:
-        edges = edges.reshape(0, 2)
-    if edges.dim() != 2 or edges.size(1) != 2:
-        raise ValueError("edges must be [F, 2], got %s" % (tuple(edges.shape),))
+    dev, logits, edges, n, f, labels, out64, stats = _cut_arrays(logits, edges)
     rw = torch.as_tensor(row_weights)
     if rw.is_floating_point() or rw.dtype == torch.bool:
         raise ValueError("row_weights must be integers, got %s" % (rw.dtype,))
@@ -1718,21 +1715,11 @@ def weighted_graph_cut(logits, edges, unary_weight, row_weights, return_stats=Fa
     if rw.dtype == torch.int64 and rw.numel() and (int(rw.max()) > 0x7FFFFFFF or int(rw.min()) < -0x80000000):   # narrower types fit
         raise ValueError("row_weights do not fit int32")
     rw = rw.to(dev, torch.int32).contiguous()
-    if logits.stride(1) != 1:
-        logits = logits.contiguous()
-    n, f = logits.size(0), edges.size(0)
-    labels = _empty(dev, torch.int32, n)
-    out64 = torch.zeros(2, dtype=torch.int64, device=dev)
-    stats = torch.zeros(2, dtype=torch.int32, device=dev)
-    scratch = torch.empty(int(lib().dgnn_graph_cut_weighted_scratch_bytes(n, f)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_graph_cut_weighted_scratch_bytes(n, f))
     check(lib().dgnn_graph_cut_weighted(ptr(logits), max(_ld(logits), 2) if n else 2, n, ptr(edges), f, float(unary_weight), ptr(rw), ptr(labels),
                                         ptr(out64), C.c_void_p(out64.data_ptr() + 8), ptr(stats), ptr(scratch), stream_ptr()),
           "dgnn_graph_cut_weighted")
-    energy, flow = (int(v) for v in out64.cpu())
-    if return_stats:
-        s = stats.cpu()
-        return labels, energy, flow, {"steps": int(s[0]), "relabels": int(s[1])}
-    return labels, energy, flow
+    return _cut_result(labels, out64, stats, return_stats)
 
 
 CUT_TERM_KINDS = {"area": 1, "beta": 2}
@@ -1755,21 +1742,15 @@ def facet_cut_terms(vertices, tetrahedra, facets, nfacets, kind, binary_weight, 
     if not np.isfinite(bw) or bw < 0:
         raise ValueError("facet_cut_terms: binary_weight %r must be finite and >= 0" % (binary_weight,))
     dev = _dev_of(vertices, tetrahedra, facets, nfacets)
-    v = _on(vertices, dev, torch.float64, 3)
-    tets = _on(tetrahedra, dev, torch.int32, 4)
-    fac = _on(facets, dev, torch.int32, 3)
-    nfac = _on(nfacets, dev, torch.int32, 2)
-    if fac.size(0) != nfac.size(0):
-        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
+    v, tets, fac, nfac = _scene(dev, vertices, tetrahedra, facets, nfacets)
     f = fac.size(0)
     w = _empty(dev, torch.int32, f)
     q = _empty(dev, torch.float64, f) if return_q else None
     stats = torch.zeros(4, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(lib().dgnn_facet_cut_terms_scratch_bytes(f)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_facet_cut_terms_scratch_bytes(f))
     check(lib().dgnn_facet_cut_terms(ptr(v), v.size(0), ptr(tets), tets.size(0), ptr(fac), ptr(nfac), f, CUT_TERM_KINDS[kind], bw, ptr(q), ptr(w),
                                      ptr(stats), ptr(scratch), stream_ptr()), "dgnn_facet_cut_terms")
-    s = [int(x) for x in stats.cpu()]
-    sd = {"rows": s[0], "neutral_sides": s[1], "zero_weights": s[2], "max_weight": s[3]}
+    sd = _stats_dict(("rows", "neutral_sides", "zero_weights", "max_weight"), stats)
     return (w, q, sd) if return_q else (w, sd)
 
 
@@ -1798,6 +1779,60 @@ def _empty(dev, dtype, *shape):
     return torch.empty(max(n, 1), dtype=dtype, device=dev)[:n].view(*shape)
 
 
+def _zeros(dev, dtype, n):
+    """n zeros in a storage of at least one element (its pointer is never null)"""
+    return torch.zeros(max(n, 1), dtype=dtype, device=dev)[:n]
+
+
+def _scratch(dev, nbytes, overflow=None, or_one=False):
+    """`nbytes` of workspace.  overflow: the DgnnError for a size <= 0 (beyond the int32 indexing); or_one: a byte at least: the call refuses"""
+    nbytes = int(nbytes)
+    if overflow is not None and nbytes <= 0:
+        raise DgnnError(overflow)
+    return torch.empty(max(nbytes, 1) if or_one else nbytes, dtype=torch.uint8, device=dev)
+
+
+def _stats_dict(keys, stats):
+    """keys -> int, from a stats tensor or a ctypes array"""
+    return dict(zip(keys, (int(x) for x in (stats.cpu() if isinstance(stats, torch.Tensor) else stats))))
+
+
+def _scene(dev, vertices, tetrahedra, facets, nfacets):
+    """the arrays of a `<scene>_3dt.npz` on `dev`: vertices fp64 [V, 3] (None when not given), tetrahedra [T, 4], facets [F, 3], nfacets [F, 2] int32"""
+    v = None if vertices is None else _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    fac = _on(facets, dev, torch.int32, 3)
+    nfac = _on(nfacets, dev, torch.int32, 2)
+    if fac.size(0) != nfac.size(0):
+        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
+    return v, tets, fac, nfac
+
+
+def _ray_inputs(vertices, tetrahedra, ray_vertex, sensors, incidence):
+    """what the two ray operations take, on its device; (rowptr, entries) is the pair of vertex_incidence, built here when `incidence` is None"""
+    dev = _dev_of(ray_vertex, sensors, vertices, tetrahedra)
+    v = _on(vertices, dev, torch.float64, 3)
+    tets = _on(tetrahedra, dev, torch.int32, 4)
+    rv = _on(ray_vertex, dev, torch.int32).reshape(-1)
+    s = _on(sensors, dev, torch.float64, 3)
+    if s.size(0) != rv.numel():
+        raise ValueError("%d sensor positions for %d rays" % (s.size(0), rv.numel()))
+    t, nv = tets.size(0), v.size(0)
+    rowptr, entries = vertex_incidence(tets, nv) if incidence is None else (_on(incidence[0], dev, torch.int32), _on(incidence[1], dev, torch.int32))
+    if rowptr.numel() != nv + 1 or entries.numel() != 4 * t:
+        raise ValueError("incidence of %d vertices and %d corners for %d vertices and %d tets" % (rowptr.numel() - 1, entries.numel(), nv, t))
+    return dev, v, tets, rv, s, rowptr, entries
+
+
+def _side_columns(out, name, count, stat, stat_names=("",)):
+    """out["<side>_<name>_count"] = count[side] and out["<side>_<name>_<stat name>{min,max,sum}"] = stat[side, 3 i + j] for the i-th stat name"""
+    for i, side in enumerate(RAY_SIDES):
+        out["%s_%s_count" % (side, name)] = count[i]
+        for a, prefix in enumerate(stat_names):
+            for j, fold in enumerate(("min", "max", "sum")):
+                out["%s_%s_%s%s" % (side, name, prefix, fold)] = stat[i, 3 * a + j]
+
+
 @on_device_of
 def locate_points(vertices, tetrahedra, facets, nfacets, points, return_steps=False):
     """The finite cell of `<scene>_3dt.npz` that contains each point (dgnn_locate_points): vertices fp64 [V, 3], tetrahedra int [N, 4],
@@ -1805,17 +1840,12 @@ def locate_points(vertices, tetrahedra, facets, nfacets, points, return_steps=Fa
     convex hull (+ the longest walk with return_steps).  Points on a shared face / vertex get the first cell of the walk that has them on
     its boundary (include/dgnn_hip.h).  DgnnError for malformed input or a walk that hits the step cap."""
     dev = _dev_of(points, vertices)
-    v = _on(vertices, dev, torch.float64, 3)
-    tets = _on(tetrahedra, dev, torch.int32, 4)
-    fac = _on(facets, dev, torch.int32, 3)
-    nfac = _on(nfacets, dev, torch.int32, 2)
+    v, tets, fac, nfac = _scene(dev, vertices, tetrahedra, facets, nfacets)
     pts = _on(points, dev, torch.float32, 3)
-    if fac.size(0) != nfac.size(0):
-        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
     n_p, n_c = pts.size(0), tets.size(0)
     cells = _empty(dev, torch.int32, n_p)
     steps = torch.zeros(1, dtype=torch.int32, device=dev)
-    scratch = torch.empty(int(lib().dgnn_locate_scratch_bytes(n_c)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_locate_scratch_bytes(n_c))
     check(lib().dgnn_locate_points(ptr(v), v.size(0), ptr(tets), n_c, ptr(fac), ptr(nfac), fac.size(0), ptr(pts), n_p, ptr(cells), ptr(steps),
                                    ptr(scratch), stream_ptr()), "dgnn_locate_points")
     return (cells, int(steps.item())) if return_steps else cells
@@ -1834,7 +1864,7 @@ def iou_counts(cells, labels, occ_gt):
     n = cells.numel()
     out = _empty(dev, torch.int32, n)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    scratch = torch.empty(256, dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, 256)
     check(lib().dgnn_mesh_iou_counts(ptr(cells), n, ptr(labels), labels.numel(), ptr(occ), ptr(out), ptr(counts), ptr(scratch), stream_ptr()),
           "dgnn_mesh_iou_counts")
     inter, union = (int(c) for c in counts.cpu())
@@ -1870,7 +1900,7 @@ def sample_interface(vertices, facets, face_ids, n_samples, seed=0, return_cum=F
     pts = _empty(dev, torch.float32, n, 3)
     face = _empty(dev, torch.int32, n)
     cum = _empty(dev, torch.float64, nfc)
-    scratch = torch.empty(int(lib().dgnn_sample_faces_scratch_bytes(nfc)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_sample_faces_scratch_bytes(nfc))
     check(lib().dgnn_sample_faces(ptr(v), v.size(0), ptr(fac), fac.size(0), ptr(ids), nfc, n, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(pts), ptr(face),
                                   ptr(cum) if nfc else None, ptr(scratch), stream_ptr()), "dgnn_sample_faces")
     return (pts, face, cum) if return_cum else (pts, face)
@@ -1889,7 +1919,7 @@ def nearest_neighbor(ref, query):
     dist = _empty(dev, torch.float32, nq)
     idx = _empty(dev, torch.int32, nq)
     total = torch.zeros(1, dtype=torch.float64, device=dev)
-    scratch = torch.empty(int(lib().dgnn_nearest_scratch_bytes(nr, nq)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_nearest_scratch_bytes(nr, nq))
     check(lib().dgnn_nearest_neighbor(ptr(r), nr, ptr(q), nq, ptr(dist), ptr(idx), ptr(total), ptr(scratch), stream_ptr()), "dgnn_nearest_neighbor")
     return dist, idx, float(total.item())
 
@@ -1910,21 +1940,16 @@ def orient_interface(vertices, tetrahedra, facets, nfacets, labels, face_ids, or
     rule and its flat-cell cases are in include/dgnn_hip.h).  orient=False keeps the stored winding (the facets are still checked).
     -> (faces, n_undetermined) (+ whether the exact stage ran for some facet with return_exact_used).  DgnnError for malformed input."""
     dev = _dev_of(labels, face_ids, vertices)
-    v = _on(vertices, dev, torch.float64, 3)
-    tets = _on(tetrahedra, dev, torch.int32, 4)
-    fac = _on(facets, dev, torch.int32, 3)
-    nfac = _on(nfacets, dev, torch.int32, 2)
+    v, tets, fac, nfac = _scene(dev, vertices, tetrahedra, facets, nfacets)
     lab = _on(labels, dev, torch.int32).reshape(-1)
     ids = _on(face_ids, dev, torch.int32).reshape(-1)
-    if fac.size(0) != nfac.size(0):
-        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
     if lab.numel() != tets.size(0):
         raise ValueError("%d labels for %d cells" % (lab.numel(), tets.size(0)))
     k = ids.numel()
     faces = _empty(dev, torch.int32, k, 3)
     und = torch.zeros(1, dtype=torch.int64, device=dev)
     used = torch.zeros(1, dtype=torch.int32, device=dev)
-    scratch = torch.empty(int(lib().dgnn_orient_interface_scratch_bytes()), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_orient_interface_scratch_bytes())
     check(lib().dgnn_orient_interface(ptr(v), v.size(0), ptr(tets), tets.size(0), ptr(fac), ptr(nfac), fac.size(0), ptr(lab), ptr(ids), k,
                                       int(bool(orient)), ptr(faces), ptr(und), ptr(used), ptr(scratch), stream_ptr()), "dgnn_orient_interface")
     return (faces, int(und.item()), bool(used.item())) if return_exact_used else (faces, int(und.item()))
@@ -1940,7 +1965,7 @@ def compact_vertices(faces, n_vertices):
     out = _empty(dev, torch.int32, k, 3)
     kept = torch.empty(max(nv, 1), dtype=torch.int32, device=dev)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-    scratch = torch.empty(int(lib().dgnn_compact_vertices_scratch_bytes(nv)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_compact_vertices_scratch_bytes(nv))
     check(lib().dgnn_compact_vertices(ptr(f), k, nv, ptr(out), ptr(kept), ptr(cnt), ptr(scratch), stream_ptr()), "dgnn_compact_vertices")
     return out, kept[:int(cnt.item())]
 
@@ -1957,9 +1982,9 @@ def mesh_topology(faces, n_vertices):
     f = _on(faces, dev, torch.int32, 3)
     nv, k = int(n_vertices), f.size(0)
     counts = torch.zeros(5, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(lib().dgnn_mesh_topology_scratch_bytes(k, nv)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_mesh_topology_scratch_bytes(k, nv))
     check(lib().dgnn_mesh_topology(ptr(f), k, nv, ptr(counts), ptr(scratch), stream_ptr()), "dgnn_mesh_topology")
-    out = dict(zip(MESH_TOPOLOGY_KEYS, (int(c) for c in counts.cpu())))
+    out = _stats_dict(MESH_TOPOLOGY_KEYS, counts)
     out["watertight"] = int(k > 0 and out["boundary_edges"] == 0 and out["nonmanifold_edges"] == 0 and out["nonmanifold_vertices"] == 0)
     return out
 
@@ -1975,7 +2000,7 @@ def mesh_components(faces, n_vertices):
     nv, k = int(n_vertices), f.size(0)
     comp = _empty(dev, torch.int32, k)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-    scratch = torch.empty(max(int(lib().dgnn_mesh_components_scratch_bytes(k)), 1), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_mesh_components_scratch_bytes(k), or_one=True)
     check(lib().dgnn_mesh_components(ptr(f), k, nv, ptr(comp), ptr(cnt), ptr(scratch), stream_ptr()), "dgnn_mesh_components")
     return comp, int(cnt.item())
 
@@ -1993,10 +2018,8 @@ def mesh_component_measures(vertices, faces, comp, K):
     nf, k = f.size(0), int(K)
     if c.numel() != nf:
         raise ValueError("%d component ids for %d faces" % (c.numel(), nf))
-    n = torch.zeros(max(k, 1), dtype=torch.int64, device=dev)[:k]
-    area = torch.zeros(max(k, 1), dtype=torch.float64, device=dev)[:k]
-    vol = torch.zeros(max(k, 1), dtype=torch.float64, device=dev)[:k]
-    scratch = torch.empty(max(int(lib().dgnn_mesh_component_measures_scratch_bytes(nf, k)), 1), dtype=torch.uint8, device=dev)
+    n, area, vol = _zeros(dev, torch.int64, k), _zeros(dev, torch.float64, k), _zeros(dev, torch.float64, k)
+    scratch = _scratch(dev, lib().dgnn_mesh_component_measures_scratch_bytes(nf, k), or_one=True)
     check(lib().dgnn_mesh_component_measures(ptr(v), v.size(0), ptr(f), nf, ptr(c), k, ptr(n), ptr(area), ptr(vol), ptr(scratch), stream_ptr()),
           "dgnn_mesh_component_measures")
     return {"n_faces": n, "area": area, "signed_volume": vol}
@@ -2018,9 +2041,9 @@ def filter_components(faces, comp, counts, largest=False, min_faces=None):
     nf = f.size(0)
     if c.numel() != nf:
         raise ValueError("%d component ids for %d faces" % (c.numel(), nf))
-    keep = torch.zeros(max(nf, 1), dtype=torch.int32, device=dev)[:nf]
+    keep = _zeros(dev, torch.int32, nf)
     n_kept = torch.zeros(1, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(lib().dgnn_mesh_component_keep_scratch_bytes()), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_mesh_component_keep_scratch_bytes())
     check(lib().dgnn_mesh_component_keep(ptr(c), nf, ptr(cnt), cnt.numel(), 0 if largest else 1, 1 if largest else int(min_faces), ptr(keep),
                                          ptr(n_kept), ptr(scratch), stream_ptr()), "dgnn_mesh_component_keep")
     ids = torch.empty(max(nf, 1), dtype=torch.int32, device=dev)
@@ -2040,15 +2063,11 @@ def tet_neighbors(facets, nfacets, tetrahedra):
     infinite cell; facets int [F, 3], nfacets int [F, 2], tetrahedra int [T, 4] of a `_3dt.npz`.  DgnnError for ids out of range and
     for a facet that is not a face of a cell nfacets names for it."""
     dev = _dev_of(tetrahedra, facets, nfacets)
-    tets = _on(tetrahedra, dev, torch.int32, 4)
-    fac = _on(facets, dev, torch.int32, 3)
-    nfac = _on(nfacets, dev, torch.int32, 2)
-    if fac.size(0) != nfac.size(0):
-        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
+    _, tets, fac, nfac = _scene(dev, None, tetrahedra, facets, nfacets)
     t = tets.size(0)
     nbr = _empty(dev, torch.int32, t, 4)
     bad = torch.zeros(1, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(lib().dgnn_tet_neighbors_scratch_bytes()), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_tet_neighbors_scratch_bytes())
     check(lib().dgnn_tet_neighbors(ptr(tets), t, ptr(fac), ptr(nfac), fac.size(0), ptr(nbr), ptr(bad), ptr(scratch), stream_ptr()), "dgnn_tet_neighbors")
     if int(bad.item()):
         raise DgnnError("tet_neighbors: %d (facet, cell) pairs whose facet is not a face of the cell nfacets names" % int(bad.item()))
@@ -2068,7 +2087,7 @@ def cell_geometry(vertices, tetrahedra):
     cols = [_empty(dev, torch.float64, t) for _ in range(4)]
     sums = torch.zeros(2, dtype=torch.float64, device=dev)
     flat = torch.zeros(1, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(lib().dgnn_cell_geometry_scratch_bytes(t)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_cell_geometry_scratch_bytes(t))
     check(lib().dgnn_cell_geometry(ptr(v), v.size(0), ptr(tets), t, ptr(cols[0]), ptr(cols[1]), ptr(cols[2]), ptr(cols[3]), ptr(sums), ptr(flat),
                                    ptr(scratch), stream_ptr()), "dgnn_cell_geometry")
     s = sums.cpu()
@@ -2090,7 +2109,7 @@ def cell_circumspheres(vertices, tetrahedra):
     t = tets.size(0)
     rec = _empty(dev, torch.float64, t, 4)
     stats = torch.zeros(4, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(lib().dgnn_cell_circumspheres_scratch_bytes()), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_cell_circumspheres_scratch_bytes())
     check(lib().dgnn_cell_circumspheres(ptr(v), v.size(0), ptr(tets), t, ptr(rec), ptr(stats), ptr(scratch), stream_ptr()), "dgnn_cell_circumspheres")
     return {"centre": rec[:, :3], "radius": rec[:, 3], "n_flat": int(stats[3].item()), "records": rec}
 
@@ -2106,12 +2125,7 @@ def facet_geometry(vertices, tetrahedra, facets, nfacets, spheres=None):
     "hull_rows" (those whose neighbour is the infinite cell), "neutral_sides", "n_flat"}.  DgnnError for an id out of range and for a facet
     that is not a face of a cell its nfacets row names."""
     dev = _dev_of(vertices, tetrahedra, facets, nfacets)
-    v = _on(vertices, dev, torch.float64, 3)
-    tets = _on(tetrahedra, dev, torch.int32, 4)
-    fac = _on(facets, dev, torch.int32, 3)
-    nfac = _on(nfacets, dev, torch.int32, 2)
-    if fac.size(0) != nfac.size(0):
-        raise ValueError("%d facets but %d nfacets rows" % (fac.size(0), nfac.size(0)))
+    v, tets, fac, nfac = _scene(dev, vertices, tetrahedra, facets, nfacets)
     t = tets.size(0)
     rec = None
     if spheres is not None:
@@ -2124,7 +2138,7 @@ def facet_geometry(vertices, tetrahedra, facets, nfacets, spheres=None):
             rec = rec.clone()
     out = _empty(dev, torch.float64, 4, 4 * t)
     stats = torch.zeros(4, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(lib().dgnn_facet_geometry_scratch_bytes(t)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_facet_geometry_scratch_bytes(t))
     check(lib().dgnn_facet_geometry(ptr(v), v.size(0), ptr(tets), t, ptr(fac), ptr(nfac), fac.size(0), ptr(rec), ptr(out), ptr(stats), ptr(scratch),
                                     stream_ptr()), "dgnn_facet_geometry")
     s = [int(x) for x in stats.cpu()]
@@ -2142,7 +2156,7 @@ def vertex_incidence(tetrahedra, n_vertices):
     t, nv = tets.size(0), int(n_vertices)
     rowptr = torch.zeros(nv + 1, dtype=torch.int32, device=dev)
     entries = _empty(dev, torch.int32, 4 * t)
-    scratch = torch.empty(int(lib().dgnn_vertex_incidence_scratch_bytes(nv)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_vertex_incidence_scratch_bytes(nv))
     check(lib().dgnn_vertex_incidence(ptr(tets), t, nv, ptr(rowptr), ptr(entries), ptr(scratch), stream_ptr()), "dgnn_vertex_incidence")
     return rowptr, entries
 
@@ -2160,30 +2174,19 @@ def vertex_ray_features(vertices, tetrahedra, ray_vertex, sensors, unique=True, 
       "<side>_tet_count" int32 [T], "<side>_tet_{min,max,sum}" fp64 [T], "<side>_slot_count" int32 [T, 4], "<side>_slot_{min,max,sum}"
       fp64 [T, 4] for <side> in RAY_SIDES; "stats": dict of RAY_STATS -> int.
     DgnnError for ids out of range and coordinates outside the exact predicate's range."""
-    dev = _dev_of(ray_vertex, sensors, vertices, tetrahedra)
-    v = _on(vertices, dev, torch.float64, 3)
-    tets = _on(tetrahedra, dev, torch.int32, 4)
-    rv = _on(ray_vertex, dev, torch.int32).reshape(-1)
-    s = _on(sensors, dev, torch.float64, 3)
-    if s.size(0) != rv.numel():
-        raise ValueError("%d sensor positions for %d rays" % (s.size(0), rv.numel()))
+    dev, v, tets, rv, s, rowptr, entries = _ray_inputs(vertices, tetrahedra, ray_vertex, sensors, incidence)
     t, r, nv = tets.size(0), rv.numel(), v.size(0)
-    rowptr, entries = vertex_incidence(tets, nv) if incidence is None else (_on(incidence[0], dev, torch.int32), _on(incidence[1], dev, torch.int32))
-    if rowptr.numel() != nv + 1 or entries.numel() != 4 * t:
-        raise ValueError("incidence of %d vertices and %d corners for %d vertices and %d tets" % (rowptr.numel() - 1, entries.numel(), nv, t))
     ray_tet, ray_slot, ray_dist = _empty(dev, torch.int32, r, 2), _empty(dev, torch.int32, r, 2), _empty(dev, torch.float64, r, 2)
     tet_count, tet_stat = _empty(dev, torch.int32, 2, t), _empty(dev, torch.float64, 2, 3, t)
     slot_count, slot_stat = _empty(dev, torch.int32, 2, t, 4), _empty(dev, torch.float64, 2, 3, t, 4)
     stats = torch.zeros(len(RAY_STATS), dtype=torch.int64, device=dev)
-    scratch = torch.empty(max(int(lib().dgnn_vertex_rays_scratch_bytes(r, t, nv)), 1), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_vertex_rays_scratch_bytes(r, t, nv), or_one=True)
     check(lib().dgnn_vertex_rays(ptr(v), nv, ptr(tets), t, ptr(rowptr), ptr(entries), ptr(rv), ptr(s), r, int(bool(unique)), ptr(ray_tet), ptr(ray_slot),
                                  ptr(ray_dist), ptr(tet_count), ptr(tet_stat), ptr(slot_count), ptr(slot_stat), ptr(stats), ptr(scratch), stream_ptr()),
           "dgnn_vertex_rays")
-    out = {"ray_tet": ray_tet, "ray_slot": ray_slot, "ray_dist": ray_dist, "stats": dict(zip(RAY_STATS, (int(x) for x in stats.cpu())))}
-    for i, side in enumerate(RAY_SIDES):
-        out[side + "_tet_count"], out[side + "_slot_count"] = tet_count[i], slot_count[i]
-        for j, stat in enumerate(("min", "max", "sum")):
-            out["%s_tet_%s" % (side, stat)], out["%s_slot_%s" % (side, stat)] = tet_stat[i, j], slot_stat[i, j]
+    out = {"ray_tet": ray_tet, "ray_slot": ray_slot, "ray_dist": ray_dist, "stats": _stats_dict(RAY_STATS, stats)}
+    _side_columns(out, "tet", tet_count, tet_stat)
+    _side_columns(out, "slot", slot_count, slot_stat)
     return out
 
 
@@ -2209,25 +2212,13 @@ def ray_walk(vertices, tetrahedra, neighbors, ray_vertex, sensors, unique=True, 
       "ray_status" int32 [R, 2] (index into WALK_STATUS), "ray_cells" int32 [R, 2]; "stats": dict of WALK_STATS -> int;
       with return_records "records": dict of WALK_RECORD_KEYS -> tensor, ascending (ray, side, step) (the walk then runs twice).
     DgnnError for ids out of range, coordinates outside the exact predicate's range and a max_records below the longest walk."""
-    dev = _dev_of(ray_vertex, sensors, vertices, tetrahedra)
-    v = _on(vertices, dev, torch.float64, 3)
-    tets = _on(tetrahedra, dev, torch.int32, 4)
+    dev, v, tets, rv, s, rowptr, entries = _ray_inputs(vertices, tetrahedra, ray_vertex, sensors, incidence)
     nbr = _on(neighbors, dev, torch.int32, 4)
-    rv = _on(ray_vertex, dev, torch.int32).reshape(-1)
-    s = _on(sensors, dev, torch.float64, 3)
-    if s.size(0) != rv.numel():
-        raise ValueError("%d sensor positions for %d rays" % (s.size(0), rv.numel()))
     t, r, nv = tets.size(0), rv.numel(), v.size(0)
     if nbr.size(0) != t:
         raise ValueError("%d neighbour rows for %d tets" % (nbr.size(0), t))
-    rowptr, entries = vertex_incidence(tets, nv) if incidence is None else (_on(incidence[0], dev, torch.int32), _on(incidence[1], dev, torch.int32))
-    if rowptr.numel() != nv + 1 or entries.numel() != 4 * t:
-        raise ValueError("incidence of %d vertices and %d corners for %d vertices and %d tets" % (rowptr.numel() - 1, entries.numel(), nv, t))
     m = max(WALK_DEFAULT_RECORDS, t + 1) if max_records is None else int(max_records)
-    nbytes = int(lib().dgnn_ray_walk_scratch_bytes(r, t, nv, m))
-    if nbytes <= 0:
-        raise DgnnError("ray_walk: %d rays, %d tets, max_records %d exceed the int32 indexing" % (r, t, m))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_ray_walk_scratch_bytes(r, t, nv, m), "ray_walk: %d rays, %d tets, max_records %d exceed the int32 indexing" % (r, t, m))
 
     def run(capacity):
         status, cells = _empty(dev, torch.int32, r, 2), _empty(dev, torch.int32, r, 2)
@@ -2238,12 +2229,9 @@ def ray_walk(vertices, tetrahedra, neighbors, ray_vertex, sensors, unique=True, 
         check(lib().dgnn_ray_walk(ptr(v), nv, ptr(tets), t, ptr(nbr), ptr(rowptr), ptr(entries), ptr(rv), ptr(s), r, int(bool(unique)), int(outside_depth),
                                   int(inside_depth), m, ptr(status), ptr(cells), ptr(cell_count), ptr(cell_stat), ptr(slot_count), ptr(slot_stat),
                                   ptr(stats), capacity, ptr(ids), ptr(dist), ptr(scratch), stream_ptr()), "dgnn_ray_walk")
-        out = {"ray_status": status, "ray_cells": cells, "stats": dict(zip(WALK_STATS, (int(x) for x in stats.cpu())))}
-        for i, side in enumerate(RAY_SIDES):
-            out[side + "_cell_count"], out[side + "_slot_count"] = cell_count[i], slot_count[i]
-            for j, stat in enumerate(("min", "max", "sum")):
-                out["%s_cell_first_%s" % (side, stat)], out["%s_cell_second_%s" % (side, stat)] = cell_stat[i, j], cell_stat[i, 3 + j]
-                out["%s_slot_%s" % (side, stat)] = slot_stat[i, j]
+        out = {"ray_status": status, "ray_cells": cells, "stats": _stats_dict(WALK_STATS, stats)}
+        _side_columns(out, "cell", cell_count, cell_stat, ("first_", "second_"))
+        _side_columns(out, "slot", slot_count, slot_stat)
         if capacity:
             out["records"] = dict(zip(WALK_RECORD_KEYS, list(ids) + list(dist)))
         return out
@@ -2302,7 +2290,7 @@ def mesh_contains(vertices, faces, points, hash_resolution=512, max_entries=2 **
     out = _empty(dev, torch.bool, n)
     if n == 0:
         return out, 0
-    scratch = torch.empty(int(lib().dgnn_mesh_contains_scratch_bytes(nv, nf, R)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_mesh_contains_scratch_bytes(nv, nf, R))
     entries, cap = _mesh_contains_entries(dev, v, f, R, max_entries, scratch)
     dis = torch.zeros(1, dtype=torch.int64, device=dev)
     _check_value(lib().dgnn_mesh_contains(ptr(v), nv, ptr(f), nf, R, int(max_entries), ptr(pts), n, ptr(out), ptr(dis), ptr(entries), cap,
@@ -2335,7 +2323,7 @@ def face_normals(vertices, faces):
     f = _on(faces, dev, torch.int32, 3)
     nf = f.size(0)
     out = _empty(dev, torch.float64, nf, 3)
-    scratch = torch.empty(256, dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, 256)
     _check_value(lib().dgnn_face_normals(ptr(v), v.size(0), ptr(f), nf, ptr(out), ptr(scratch), stream_ptr()), "dgnn_face_normals")
     return out
 
@@ -2381,7 +2369,7 @@ def tet_sample_points(vertices, tetrahedra, n_samples, seed=0, tet_offset=0):
     if k < 1:
         raise ValueError("tet_sample_points: n_samples %d < 1" % k)
     out = _empty(dev, torch.float64, t * k, 3)
-    scratch = torch.empty(int(lib().dgnn_tet_sample_points_scratch_bytes()), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_tet_sample_points_scratch_bytes())
     check(lib().dgnn_tet_sample_points(ptr(v), v.size(0), ptr(tets), t, k, _seed64(seed), _seed64(tet_offset), ptr(out), ptr(scratch), stream_ptr()),
           "dgnn_tet_sample_points")
     return out
@@ -2406,7 +2394,7 @@ def cell_labels(mesh_vertices, mesh_faces, vertices, tetrahedra, n_samples=100, 
         raise ValueError("cell_labels: n_samples %d < 1" % k)
     if nf == 0:
         raise ValueError("cell_labels: a mesh without faces")
-    scratch = torch.empty(int(lib().dgnn_cell_labels_scratch_bytes(nv, nf, R)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_cell_labels_scratch_bytes(nv, nf, R))
     entries, cap = _mesh_contains_entries(dev, mv, mf, R, max_entries, scratch)
     count =_empty(dev, torch.int32, t)
     dis = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -2447,7 +2435,7 @@ def ray_first_hit(vertices, faces, origins, aims, t_min=0.0, grid_resolution=Non
     if nf == 0:
         raise ValueError("ray_first_hit: a mesh without faces")
     R = default_grid_resolution(nf) if grid_resolution is None else int(grid_resolution)
-    scratch = torch.empty(int(lib().dgnn_ray_first_hit_scratch_bytes(nf, R)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_ray_first_hit_scratch_bytes(nf, R))
     entries, cap = _planned_entries(dev, "dgnn_ray_first_hit_plan", lambda n_entries: lib().dgnn_ray_first_hit_plan(
         ptr(v), nv, ptr(f), nf, R, n_entries, None, ptr(scratch), stream_ptr()))
     face, t, point = _empty(dev, torch.int32, n), _empty(dev, torch.float64, n), _empty(dev, torch.float64, n, 3)
@@ -2455,7 +2443,7 @@ def ray_first_hit(vertices, faces, origins, aims, t_min=0.0, grid_resolution=Non
     _check_value(lib().dgnn_ray_first_hit(ptr(v), nv, ptr(f), nf, R, ptr(o), ptr(g), n, float(t_min), ptr(face), ptr(t), ptr(point), ptr(stats), ptr(entries),
                                           cap, ptr(scratch), stream_ptr()), "dgnn_ray_first_hit")
     if return_stats:
-        return face, t, point, dict(zip(RAY_HIT_STATS, (int(x) for x in stats.cpu())))
+        return face, t, point, _stats_dict(RAY_HIT_STATS, stats)
     return face, t, point
 
 
@@ -2472,7 +2460,7 @@ def _point_mesh_d2(vertices, faces, points, grid_resolution, what):
     if nf == 0:
         raise ValueError("%s: a mesh without faces" % what)
     R = default_grid_resolution(nf) if grid_resolution is None else int(grid_resolution)
-    scratch = torch.empty(int(lib().dgnn_point_mesh_distance_scratch_bytes(nf, R)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_point_mesh_distance_scratch_bytes(nf, R))
     entries, cap = None, 0
     if R != 0:          # (a resolution the library refuses is refused by the planning call)
         entries, cap = _planned_entries(dev, "dgnn_point_mesh_distance_plan", lambda n_entries: lib().dgnn_point_mesh_distance_plan(
@@ -2497,7 +2485,7 @@ def point_mesh_distance(vertices, faces, points, grid_resolution=None, return_st
     non-finite referenced vertex or point; DgnnError for a grid_resolution outside [0, 1024]."""
     d2, dist, face, closest, region, stats = _point_mesh_d2(vertices, faces, points, grid_resolution, "point_mesh_distance")
     out = (d2 if return_d2 else dist, face, closest, region)
-    return out + (dict(zip(MESH_DISTANCE_STATS, (int(x) for x in stats.cpu()))),) if return_stats else out
+    return out + (_stats_dict(MESH_DISTANCE_STATS, stats),) if return_stats else out
 
 
 @on_device_of
@@ -2514,7 +2502,7 @@ def distance_fold(dist, cosine=None, thresholds=()):
     thr = torch.tensor([float(t) for t in thresholds], dtype=torch.float64).to(dev) if nt else None
     sums = torch.zeros(3, dtype=torch.float64, device=dev)
     counts = torch.zeros(max(nt, 1), dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(lib().dgnn_distance_fold_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_distance_fold_scratch_bytes(n))
     check(lib().dgnn_distance_fold(ptr(d), ptr(c), n, ptr(thr), nt, ptr(sums), ptr(counts), ptr(scratch), stream_ptr()), "dgnn_distance_fold")
     s = sums.cpu()
     return float(s[0]), float(s[1]), float(s[2]), [int(x) for x in counts.cpu()[:nt]]
@@ -2530,7 +2518,7 @@ def row_dot3(a, ia, b, ib):
     if i.numel() != j.numel():
         raise ValueError("row_dot3: %d and %d indices" % (i.numel(), j.numel()))
     out = _empty(dev, torch.float64, i.numel())
-    scratch = torch.empty(256, dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, 256)
     _check_value(lib().dgnn_row_dot3(ptr(x), x.size(0), ptr(i), ptr(y), y.size(0), ptr(j), i.numel(), ptr(out), ptr(scratch), stream_ptr()), "dgnn_row_dot3")
     return out
 
@@ -2635,7 +2623,7 @@ def scale_features(x64, c_first: int, kind: str, feature_range=(0, 1), sum_cols=
     dev = x64.device
     out = torch.empty((n, c), dtype=torch.float32, device=dev)
     stats = torch.empty((2, c), dtype=torch.float64, device=dev) if return_stats else None
-    scratch = torch.empty(int(lib().dgnn_scale_features_scratch_bytes(c)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(dev, lib().dgnn_scale_features_scratch_bytes(c))
     check(lib().dgnn_scale_features_f64(ptr(x64), _ld(x64), n, c, int(c_first), SCALE_KINDS[kind], float(feature_range[0]), float(feature_range[1]),
                                         s0, s1, int(div_col or 0), d0, d1, float(div_scalar if div_scalar is not None else 1.0), k0, k1,
                                         ptr(out), c, ptr(stats), ptr(scratch), stream_ptr()), "dgnn_scale_features_f64")
@@ -2724,9 +2712,7 @@ def delaunay(points, priority=None, seed=0, cell_capacity=None):
     while True:
         cells, nbrs = _empty(dev, torch.int32, cap, 4), _empty(dev, torch.int32, cap, 4)
         nbytes = int(lib().dgnn_delaunay_scratch_bytes(n, cap))
-        if nbytes <= 0:
-            raise DgnnError("delaunay: %d points with %d cells exceed the int32 indexing" % (n, cap))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = _scratch(dev, nbytes, "delaunay: %d points with %d cells exceed the int32 indexing" % (n, cap))
         st = (C.c_int64 * 16)()
         code = lib().dgnn_delaunay(ptr(pts), n, cap, ptr(cells), ptr(nbrs), st, ptr(scratch), stream_ptr())
         if code == _E_CAPACITY:
@@ -2737,7 +2723,7 @@ def delaunay(points, priority=None, seed=0, cell_capacity=None):
             raise DgnnError("delaunay: points %d and %d are equal" % (min(a, b), max(a, b)))
         _check_value(code, "dgnn_delaunay")
         break
-    raw = dict(zip(DELAUNAY_STATS, (int(x) for x in st)))
+    raw = _stats_dict(DELAUNAY_STATS, st)
     nc = raw["cells_allocated"]
     tv, tn = cells[:nc].long(), nbrs[:nc].long()
     alive = tv[:, 0] >= 0
@@ -2811,7 +2797,7 @@ def delaunay_violations(vertices, tetrahedra):
     nbr = nbr.to(torch.int32).contiguous()
     counts = torch.zeros(len(VIOLATIONS) + 1, dtype=torch.int64, device=dev)
     check(lib().dgnn_delaunay_violations(ptr(v), v.size(0), ptr(tets), ptr(nbr), T, ptr(counts), stream_ptr()), "dgnn_delaunay_violations")
-    out = dict(zip(VIOLATIONS, (int(x) for x in counts.cpu()[:len(VIOLATIONS)])))
+    out = _stats_dict(VIOLATIONS, counts[:len(VIOLATIONS)])
     out["overfull_facets"] = overfull
     return out
 
@@ -2839,11 +2825,8 @@ def vertex_components(tetrahedra, neighbors, labels, n_vertices):
     infinite cell (tet_neighbors; of `delaunay`: the first T rows with ids >= T set to -1).  DgnnError for malformed input."""
     dev, tets, nbr, lab = _labelled_cells(tetrahedra, neighbors, labels, "vertex_components")
     t, nv = tets.size(0), int(n_vertices)
-    n_in, n_out = torch.zeros(max(nv, 1), dtype=torch.int32, device=dev)[:nv], torch.zeros(max(nv, 1), dtype=torch.int32, device=dev)[:nv]
-    nbytes = int(lib().dgnn_vertex_components_scratch_bytes(t, nv))
-    if nbytes <= 0:
-        raise DgnnError("vertex_components: %d cells with %d vertices exceed the int32 indexing" % (t, nv))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    n_in, n_out = _zeros(dev, torch.int32, nv), _zeros(dev, torch.int32, nv)
+    scratch = _scratch(dev, lib().dgnn_vertex_components_scratch_bytes(t, nv), "vertex_components: %d cells with %d vertices exceed the int32 indexing" % (t, nv))
     n_singular = C.c_int64(0)
     check(lib().dgnn_vertex_components(ptr(tets), ptr(nbr), ptr(lab), t, nv, ptr(n_in), ptr(n_out), C.byref(n_singular), ptr(scratch), stream_ptr()),
           "dgnn_vertex_components")
@@ -2866,13 +2849,10 @@ def manifold_repair(tetrahedra, neighbors, labels, n_vertices, cost=None, max_ro
         cst = _on(cost, dev, torch.int32).reshape(-1)
         if cst.numel() != t:
             raise ValueError("manifold_repair: %d costs for %d cells" % (cst.numel(), t))
-    flipped = torch.zeros(max(t, 1), dtype=torch.int32, device=dev)[:t] if return_flipped else None
-    nbytes = int(lib().dgnn_manifold_repair_scratch_bytes(t, nv))
-    if nbytes <= 0:
-        raise DgnnError("manifold_repair: %d cells with %d vertices exceed the int32 indexing" % (t, nv))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    flipped = _zeros(dev, torch.int32, t) if return_flipped else None
+    scratch = _scratch(dev, lib().dgnn_manifold_repair_scratch_bytes(t, nv), "manifold_repair: %d cells with %d vertices exceed the int32 indexing" % (t, nv))
     st = (C.c_int64 * len(MANIFOLD_STATS))()
     check(lib().dgnn_manifold_repair(ptr(tets), ptr(nbr), ptr(out), ptr(cst), t, nv, -1 if max_rounds is None else max(int(max_rounds), 0),
                                      ptr(flipped), st, ptr(scratch), stream_ptr()), "dgnn_manifold_repair")
-    stats = dict(zip(MANIFOLD_STATS, (int(x) for x in st)))
+    stats = _stats_dict(MANIFOLD_STATS, st)
     return (out, stats, flipped) if return_flipped else (out, stats)

@@ -109,6 +109,9 @@ def test_location_errors_raise():
             ops.locate_points(s["vertices"], s["tetrahedra"], s["facets"], s["nfacets"], q)
     with pytest.raises(DgnnError):
         ops.locate_points(scene["vertices"], scene["tetrahedra"], scene["facets"], scene["nfacets"], torch.full((3, 3), float("nan"), device=DEV))
+    with pytest.raises(DgnnError):          # the cell repeats a vertex and lacks the facet's vertex 2: the facet is no face of it
+        ops.locate_points(np.eye(4, 3), np.array([[0, 0, 1, 3]], dtype=np.int32), np.array([[0, 1, 2]], dtype=np.int32),
+                          np.array([[0, -1]], dtype=np.int32), q)
     assert len(_locate(scene, np.random.default_rng(0).random((5, 3)).astype(np.float32))) == 5
 
 

@@ -118,6 +118,15 @@ def test_topology_of_hand_made_meshes(case):
         assert got["nonmanifold_edges"] == 1 and got["nonmanifold_vertices"] == 0
 
 
+def test_topology_with_edge_keys_just_above_a_tile_of_the_sort():
+    """683 faces: 3 F = 2049 edge keys and 6 F = 4098 link keys, each one element into a new 2048-element tile of the radix sort
+    (RX_TILE of csrc/reorder.hip), where the histogram count of the sort's workspace steps"""
+    rng = np.random.default_rng(683)
+    faces = np.stack([rng.permutation(200)[:3] for _ in range(683)]).astype(np.int32)          # a soup: every face has three distinct vertices
+    assert 3 * len(faces) == 2048 + 1
+    assert _topology(faces, 200) == mt.topology(faces)
+
+
 def test_generic_scene_encloses_the_inside_volume():
     scene = mm.random_scene(5000, seed=11)
     labels = mm.sphere_labels(scene)
@@ -161,6 +170,10 @@ def test_invalid_input_raises():
     bad["facets"][f, 0] = next(x for x in range(len(scene["vertices"])) if x not in scene["facets"][f])
     with pytest.raises(DgnnError, match="not a face"):
         _orient(bad, labels, ids)
+    repeated = dict(vertices=np.eye(4, 3), tetrahedra=np.array([[0, 0, 1, 3]], dtype=np.int32), facets=np.array([[0, 1, 2]], dtype=np.int32),
+                    nfacets=np.array([[0, -1]], dtype=np.int32))          # three slots of the cell on the facet, and the facet's vertex 2 missing
+    with pytest.raises(DgnnError, match="not a face"):
+        _orient(repeated, np.zeros(1, dtype=np.int32), [0])
     bad = dict(scene, vertices=scene["vertices"].copy())
     bad["vertices"][scene["facets"][f, 1], 2] = np.nan
     with pytest.raises(DgnnError, match="non-finite"):

@@ -173,3 +173,37 @@ def test_tensors_stay_on_the_device_of_the_inputs(current_device_calls):
     assert current_device_calls == []
     assert all(a.device == dev for k, a in got.items() if k not in ("stats", "records")) and all(a.device == dev for a in got["records"].values())
     _assert_equal(got, rw.case("kuhn3")[6])
+
+
+@pytest.mark.parametrize("op", ["vertex_ray_features", "ray_walk"])
+def test_both_ray_operations_refuse_the_same_bad_rays_and_differ_on_an_unused_vertex(op):
+    """The checks the two operations share (csrc/tet_rays.h), on the six tets of one Kuhn cube (8 vertices), one ray per vertex.  Where they
+    check differs on purpose: vertex_ray_features looks only at the coordinates a live ray reads, ray_walk at every vertex up front."""
+    import scene_features_model as sf
+    from dgnn_amd import ops
+    from dgnn_amd._lib import DgnnError
+    v, tets, _ = rw.kuhn_grid(2)
+    assert v.shape == (8, 3) and tets.shape == (6, 4)
+    fac, nfac = sf.facets_from_tets(tets)
+    nbr = ops.tet_neighbors(_t(fac), _t(nfac), _t(tets))
+    rv, s = np.arange(8), 0.25 + 0.5 * v + np.array([0.03, 0.05, 0.07])          # sensors inside the cube, none at its vertex
+
+    def run(vertices=v, ray_vertex=rv, sensors=s, **kw):
+        args = (_t(vertices), _t(tets)) + ((nbr,) if op == "ray_walk" else ()) + (_t(ray_vertex), _t(sensors))
+        return getattr(ops, op)(*args, **kw)
+
+    assert run()["stats"]["used"] == 8
+    nan_sensor, far_sensor = s.copy(), s.copy()
+    nan_sensor[3, 1], far_sensor[5, 2] = np.nan, 2.0 ** 301
+    rowptr, entries = sf.vertex_incidence(tets, 8)
+    bad = [dict(ray_vertex=np.where(rv == 2, -1, rv)), dict(ray_vertex=np.where(rv == 6, 8, rv)), dict(sensors=nan_sensor), dict(sensors=far_sensor),
+           dict(incidence=(_t(rowptr), _t(entries[::-1].copy())))]          # the last: rows that hold other vertices' corners
+    for kw in bad:
+        with pytest.raises(DgnnError):
+            run(**kw)
+    unused = np.concatenate([v, [[2.0 ** 301, 0.0, 0.0]]])          # a ninth vertex outside the predicate's range that no tet and no ray names
+    if op == "ray_walk":
+        with pytest.raises(DgnnError):
+            run(vertices=unused)
+    else:
+        assert run(vertices=unused)["stats"]["used"] == 8

@@ -191,6 +191,14 @@ def test_bad_input_is_refused():
         ops.vertex_ray_features(v, tets, _t(rv), _t(s), incidence=(_t(rowptr), _t(entries[::-1].copy())))               # rows of other vertices
 
 
+def test_a_facet_with_a_foreign_vertex_is_no_face_of_a_cell_that_repeats_a_vertex():
+    """the cell (0, 0, 1, 3) has three slots on the facet (0, 1, 2) and still lacks its vertex 2 (csrc/tet_common.h: the facet / slot rule)"""
+    from dgnn_amd import ops
+    from dgnn_amd._lib import DgnnError
+    with pytest.raises(DgnnError):
+        ops.tet_neighbors(_t(np.array([[0, 1, 2]], dtype=np.int32)), _t(np.array([[0, -1]], dtype=np.int32)), _t(np.array([[0, 0, 1, 3]], dtype=np.int32)))
+
+
 @pytest.fixture
 def current_device_calls(monkeypatch):
     """Records every call of torch.cuda.current_device() made from the package: the ops must run where their tensors are, so with one GPU
