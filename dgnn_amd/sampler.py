@@ -439,13 +439,11 @@ class NeighborSampler:
             n_t = n_id.numel()
             off = torch.empty(n_t + 1, dtype=torch.int32, device=self.device)
             scratch = torch.empty(int(L.dgnn_khop_scratch_elems(n_t, 0)), dtype=torch.int32, device=self.device)
+            # a full neighbourhood takes the plain entry points; a size > 0 their _sampled forms, which take the draw's key as well
             size = self.sizes[hop]
-            if size < 0:
-                check(L.dgnn_khop_count(ptr(p.rowptr), ptr(n_id), n_t, int(hop == 0), ptr(self._pos), ptr(off), ptr(scratch), st),
-                      "dgnn_khop_count")
-            else:
-                check(L.dgnn_khop_count_sampled(ptr(p.rowptr), ptr(n_id), n_t, int(hop == 0), size, self.sample_seed, draw, hop, ptr(self._pos), ptr(off),
-                                                ptr(scratch), st), "dgnn_khop_count_sampled")
+            sfx, key = ("", ()) if size < 0 else ("_sampled", (size, self.sample_seed, draw, hop))
+            check(getattr(L, "dgnn_khop_count" + sfx)(ptr(p.rowptr), ptr(n_id), n_t, int(hop == 0), *key, ptr(self._pos), ptr(off), ptr(scratch), st),
+                  "dgnn_khop_count" + sfx)
             n_e = self._keep[hop] * n_t if self._regular else int(off[n_t].item())  # sizes the block tensors
             ei = torch.empty((2, n_e), dtype=torch.int64, device=self.device)
             e_src, e_dst = ei[0], ei[1]
@@ -453,14 +451,9 @@ class NeighborSampler:
             n_id_out = torch.empty(n_t + n_e, dtype=torch.int64, device=self.device)
             n_new = torch.zeros(1, dtype=torch.int32, device=self.device)
             scratch = torch.empty(int(L.dgnn_khop_scratch_elems(n_t, n_e)), dtype=torch.int32, device=self.device)
-            if size < 0:
-                check(L.dgnn_khop_expand(ptr(p.rowptr), ptr(p.src), ptr(p.eid), ptr(n_id), n_t, ptr(off), n_e, ptr(self._pos),
-                                         ptr(self._first), ptr(e_src), ptr(e_dst), ptr(e_id), ptr(n_id_out), ptr(n_new), ptr(scratch),
-                                         st), "dgnn_khop_expand")
-            else:
-                check(L.dgnn_khop_expand_sampled(ptr(p.rowptr), ptr(p.src), ptr(p.eid), ptr(n_id), n_t, ptr(off), n_e, size, self.sample_seed, draw, hop,
-                                                 ptr(self._pos), ptr(self._first), ptr(e_src), ptr(e_dst), ptr(e_id), ptr(n_id_out), ptr(n_new),
-                                                 ptr(scratch), st), "dgnn_khop_expand_sampled")
+            check(getattr(L, "dgnn_khop_expand" + sfx)(ptr(p.rowptr), ptr(p.src), ptr(p.eid), ptr(n_id), n_t, ptr(off), n_e, *key, ptr(self._pos),
+                                                       ptr(self._first), ptr(e_src), ptr(e_dst), ptr(e_id), ptr(n_id_out), ptr(n_new), ptr(scratch), st),
+                  "dgnn_khop_expand" + sfx)
             n_all = n_t + int(n_new.item())
             check(L.dgnn_khop_commit(ptr(n_id_out), n_t, n_all, ptr(self._pos), ptr(self._first), st), "dgnn_khop_commit")
             n_id = n_id_out[:n_all]

@@ -20,9 +20,11 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BATCHES = (1, 37, 128)
-REG_SIZES = ([2] * 4, [3, 1, 2], [-1, 2, -1, 3])
+FULL = [-1] * 3     # the full-neighbourhood instantiation of the builder's kernels, on both graphs
+REG_SIZES = ([2] * 4, [3, 1, 2], [-1, 2, -1, 3], FULL)
 IRR_SIZES = REG_SIZES + ([5] * 2,)
 CASES = [(name, sizes, nb) for name, sl in (("regular", REG_SIZES), ("irregular", IRR_SIZES)) for sizes, nb in itertools.product(sl, BATCHES)]
+CASES.sort(key=lambda c: c[1] is FULL)      # (stable) the FULL cases last: a case's id carries its position, and the earlier cases keep theirs
 
 
 @pytest.fixture(scope="module")
@@ -69,11 +71,7 @@ def _same_blocks(a, b):
         assert s1 == s2 and np.array_equal(e1, e2) and np.array_equal(i1, i2) and np.array_equal(o1, o2)
 
 
-# ---- 1. the builder equals the model ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,sizes,nb", CASES)
-def test_builder_equals_the_model(graphs, name, sizes, nb):
-    """n_id, both rows of every edge_index, every e_id, every size and the row offsets, integer-exact, for two seeds x two draws (the regular graph
-    takes the one-call builder, the irregular one -- in-degrees 0..12: nothing to draw, the register path, the loop path -- the hop-by-hop one)"""
+def _batch(graphs, name, nb):
     ei, n, _ = graphs[name]
     batch = np.random.default_rng(100 + nb).permutation(n)[:nb].astype(np.int64)
     if name == "irregular" and nb > 1:
@@ -81,6 +79,17 @@ def test_builder_equals_the_model(graphs, name, sizes, nb):
         head = np.asarray([int(np.nonzero(deg == d)[0][0]) for d in (0, 12, 9)], dtype=np.int64)      # the degree classes are in the batch itself, not only behind it
         batch = np.concatenate([head, batch[~np.isin(batch, head)]])[:nb]      # (nb - 3 others: the permutation prefix holds at least nb - 3 of them)
         assert batch.size == nb and len(set(batch.tolist())) == nb
+    return batch
+
+
+# ---- 1. the builder equals the model ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,sizes,nb", CASES)
+def test_builder_equals_the_model(graphs, name, sizes, nb):
+    """n_id, both rows of every edge_index, every e_id, every size and the row offsets, integer-exact, for two seeds x two draws (the regular graph
+    takes the one-call builder, the irregular one -- in-degrees 0..12: nothing to draw, the register path, the loop path -- the hop-by-hop one);
+    sizes [-1] * 3 hold the full-neighbourhood instantiation of the kernels to the model on both paths"""
+    ei, n, _ = graphs[name]
+    batch = _batch(graphs, name, nb)
     for seed, draw in itertools.product((0, 0xD1B54A32D192ED03), (0, 5)):
         loader = _sampler(graphs, name, sizes, batch_size=nb, prefetch=False, sample_seed=seed)
         got = _snapshot(loader.sample(torch.from_numpy(batch).to(DEV), draw=draw))
@@ -422,3 +431,49 @@ def test_constructor_checks_sizes_and_full_sizes_keep_the_existing_entry_points(
     _sampler(graphs, "regular", [2] * 4, batch_size=40, prefetch=False).sample(batch)
     _sampler(graphs, "irregular", [2] * 4, batch_size=40, prefetch=False).sample(batch)
     assert [c for c in called if "sampled" in c]
+
+
+# ---- 9. size = -1 through the _sampled per-hop entry points ------------------------------------------------------------------------------
+def test_sampled_entry_points_with_size_minus_one_build_the_full_blocks(graphs, monkeypatch):
+    """include/dgnn_hip.h: dgnn_khop_count_sampled / dgnn_khop_expand_sampled with size = -1 give the result of the plain entry points, whatever
+    the seed and the draw.  Two hops on the irregular graph, 37 targets with in-degrees 0, 12 and 9 among them: the loader's calls of the plain
+    entry points are redirected to the _sampled ones with (size -1, a seed, a draw, hop 0), the blocks equal the un-redirected loader's"""
+    import dgnn_amd.sampler as SM
+    batch = torch.from_numpy(_batch(graphs, "irregular", 37)).to(DEV)
+    want = _snapshot(_sampler(graphs, "irregular", [-1] * 2, batch_size=37, prefetch=False).sample(batch))
+    called = []
+    real = SM.lib()
+    split = {"dgnn_khop_count": 4, "dgnn_khop_expand": 7}       # the _sampled forms take (size, seed, draw, hop) after this many arguments
+
+    class Spy:
+        def __getattr__(self, name):
+            if name not in split:
+                return getattr(real, name)
+            called.append(name)
+            k = split[name]
+            return lambda *a: getattr(real, name + "_sampled")(*a[:k], -1, 0x9E3779B97F4A7C15, 3, 0, *a[k:])
+    monkeypatch.setattr(SM, "lib", lambda: Spy())
+    got = _snapshot(_sampler(graphs, "irregular", [-1] * 2, batch_size=37, prefetch=False).sample(batch))
+    assert called == ["dgnn_khop_count", "dgnn_khop_expand"] * 2
+    _same_blocks(got, want)
+
+
+# ---- 10. a capacity that is too small ----------------------------------------------------------------------------------------------------
+def test_a_capacity_too_small_at_hop_1_leaves_the_builder_clean(graphs):
+    """the one-call builder with cap_t[1] = 1, sizes [2, 3, 2], 37 targets: DGNN_E_INVALID that names the hop and the capacity, after hop 0 has been
+    committed -- and `pos` / `first` are as between batches, so the next block is the model's"""
+    from dgnn_amd._lib import DgnnError
+    ei, n, _ = graphs["regular"]
+    sizes = [2, 3, 2]
+    batch = _batch(graphs, "regular", 37)
+    loader = _sampler(graphs, "regular", sizes, batch_size=37, prefetch=False, sample_seed=77)
+    with torch.cuda.device(loader.device):
+        b = loader._alloc_regular(37, True)
+        cap_t = b["args_tail"][6]
+        assert list(cap_t) == [37, 37 * 3, 37 * 3 * 4]
+        cap_t[1] = 1
+        with pytest.raises(DgnnError, match=r"hop 1 needs \d+ targets / \d+ edges, capacity 1 / "):
+            loader._start_regular(torch.from_numpy(batch).to(DEV), background=False, b=b)
+    assert bool((loader._pos == -1).all().item()) and bool((loader._first == 2 ** 31 - 1).all().item())
+    rn, radjs = M.sampled_blocks(ei, n, batch, sizes, 77, 0, with_off=True)
+    _same_blocks(_snapshot(loader.sample(torch.from_numpy(batch).to(DEV), draw=0)), (37, rn, [(e, i, tuple(s), o) for e, i, s, o in radjs]))
