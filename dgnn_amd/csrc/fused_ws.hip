@@ -8,7 +8,9 @@
 // stores off) runs 1M cells in 0.31-0.34 ms at 4 resp. 2 wavefronts per SIMD: it is bound by its reads, not by latency, once nothing else shares its
 // wavefronts.  So here a 1024-thread workgroup (16 wavefronts, 4 per SIMD, <= 128 VGPRs each) is
 //   8 PRODUCERS  one group of 4 cells each per 32-cell tile: index chain two tiles ahead, 4 neighbour rows + own row as 16-byte loads, filter product on
-//                v_mfma_f32_16x16x32_f16 (per-edge power-of-two scales, 3 products), in-lane 4-term mean, the [a | x_i] row scaled by one power of two,
+//                v_mfma_f32_16x16x32_f16 (per-edge power-of-two scales; the 62 real terms of the two-part form packed into TWO products, filter_pack.h --
+//                as three products of 21 real K-slots in 32 a third of the producers' matrix instructions multiplied zeros: 128 -> 128 0.405 -> 0.390 ms,
+//                profiles/filter_two_products.md), in-lane 4-term mean, the [a | x_i] row scaled by one power of two,
 //                split (hi, lo) and parked in an LDS ring slot (1 KB per cell, XOR-swizzled 16-byte pieces, conflict-free for both sides);
 //   8 CONSUMERS  16 output channels each, their [Wj | Wi] rows resident as fp16 (hi, lo) fragments (64 VGPRs): D[channel][cell] on v_mfma_f32_16x16x32_f16
 //                with the weights as the A operand, 48 products per tile; epilogue per lane = one cell x 4 consecutive channels: inverse scales,
@@ -32,6 +34,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "filter_pack.h"
 #include "fused_common.h"
 
 namespace {
@@ -44,7 +47,7 @@ constexpr int WS_C = 128;                    // channels out (and in: CIN = 128,
 constexpr int WS_TILE = 32;                  // cells per tile
 constexpr int WS_NP = 8;                     // producer wavefronts (the other 8 of the 16 are consumers)
 // per input width CIN: ring bytes per cell = [hi of a | hi of x | lo of a | lo of x], CIN fp16 each (1 KB / 512 B); a ring slot = 32 cells (32 / 16 KB);
-// the filter operand [cb < CIN / 16][hi | lo][48] x 16 B
+// the filter operand [cb < CIN / 16][M2 | M1][64 lanes] x 16 B (filter_pack.h)
 template <int CIN> struct WsC {
     static constexpr int NCH = CIN / 16;        // channels of a cell's rows per producer lane (8 / 4)
     static constexpr int NV = NCH / 4;          // ... as 16-byte loads
@@ -52,7 +55,7 @@ template <int CIN> struct WsC {
     static constexpr int PP = CIN / 8;          // 16-byte pieces per quarter of a ring row
     static constexpr int ROWB = 8 * CIN;
     static constexpr int SLOT = WS_TILE * ROWB;
-    static constexpr int BP = NCH * 2 * 48 * 16;
+    static constexpr int BP = NCH * 2 * 64 * 16;
 };
 // RING slots of the hand-off (counters, below): 2 for the 128-wide rows, 4 for the 64-wide 16-bit rows.
 template <int CIN, int RING> struct WsL {
@@ -237,24 +240,28 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
     // 128 -> 128 0.408 -> 0.406 ms, last layer + decoder 0.500 -> 0.490 ms.
     constexpr bool LINE_OWN = !IO16 && NV == 2;
     auto chan = [](int j, int cb) { return LINE_OWN ? ((cb >> 2) * 64 + 4 * j + (cb & 3)) : NCH * j + cb; };
-    // entry (cb, part, g, j): channel c = chan(j, cb), k = 8 g .. 8 g + 7 (g < 3: attributes 0..19, the bias at k = 20, zeros)
-    for (int e = threadIdx.x; e < NCH * 48; e += blockDim.x) {
-        const int cb = e / 48, gj = e - cb * 48, g = gj >> 4, j = gj & 15;
+    // The B fragments of the two filter products (filter_pack.h): entry (cb, j) lays out channel c = chan(j, cb) for both products and all four lane
+    // groups -- the 11 words (k = 2 i, 2 i + 1; the bias at k = 20, then 0) of [We | be] . sWe split once, each slot's word picked by the map
+    for (int e = threadIdx.x; e < NCH * 16; e += blockDim.x) {
+        const int cb = e >> 4, j = e & 15;
         const int c = chan(j, cb);
-        uint32_t ph[4], pl[4];
+        uint32_t wh[11], wl[11];
 #pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            float v[2];
+        for (int i = 0; i < 10; ++i) split2h(We[(int64_t)c * FE + 2 * i] * sWe, We[(int64_t)c * FE + 2 * i + 1] * sWe, wh[i], wl[i]);
+        split2h(be[c] * sWe, 0.f, wh[10], wl[10]);
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int k = 8 * g + 2 * d + u;
-                v[u] = k < FE ? We[(int64_t)c * FE + k] : (k == FE ? be[c] : 0.f);
+        for (int m = 0; m < 2; ++m) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                uint32_t wd[4];
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    const filter_pack::Slot t = filter_pack::MAP[m][g][2 * d];
+                    wd[d] = t.k < 0 ? 0u : (t.b == filter_pack::HI ? wh[t.k >> 1] : wl[t.k >> 1]);
+                }
+                *reinterpret_cast<uint4*>(bpbuf + (((cb * 2 + m) * 64 + g * 16 + j) << 4)) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
             }
-            split2h(v[0] * sWe, v[1] * sWe, ph[d], pl[d]);
         }
-        uint4* dst = reinterpret_cast<uint4*>(bpbuf + ((cb * 2) * 48 + gj) * 16);
-        dst[0] = make_uint4(ph[0], ph[1], ph[2], ph[3]);
-        dst[48] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
     }
 
     // DEC, stage B of tile t, job (hb, b) (either role runs it, see above): hidden units 16 hb .. + 15 of cells 16 b .. + 15 -- lane (cell n = jcol, tq) ends up with
@@ -589,9 +596,11 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
                 if constexpr (IDX_LANE) return veid;
                 else return __shfl(veid, jcol);
             };
+            // the edge's attributes this lane's slots of the two filter products are made of (filter_pack.h): from 0 / 8 / 16 / 4 on in k-groups 0 / 1 / 2 / 3,
+            // eight of them (k-group 2: four).  k-group 3 reads lines the same instruction requests for k-groups 0 and 1: no more bytes from the fabric
             const float* er = ea + (int64_t)eid_of() * lde;
-            q0 = *reinterpret_cast<const f32x4_t*>(er + 8 * (tq < 2 ? tq : 2));
-            q1 = *reinterpret_cast<const f32x4_t*>(er + 8 * (tq < 1 ? tq : 1) + 4);
+            q0 = *reinterpret_cast<const f32x4_t*>(er + (tq < 3 ? 8 * tq : 4));
+            q1 = *reinterpret_cast<const f32x4_t*>(er + (tq < 2 ? 8 * tq + 4 : (tq == 2 ? 4 : 8)));
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if constexpr (IO16) {
@@ -647,13 +656,28 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
                 }
                 if (regular) {
                     if constexpr (!DEC) neighbour_rows();
+                    // The A side of the two filter products (filter_pack.h).  The lane's eight values: attributes 0 .. 7 / 8 .. 15 / 4 .. 11 in k-groups 0 / 1 / 3,
+                    // [a16 a17 a18 a19 | 1 0 | a16 a17] in k-group 2.  The hi words of their split are M1's operand in every group; M2's four words are picked
+                    // from the lane's own hi and lo words (five selects, nothing crosses lanes).
+                    using filter_pack::HI;
+                    using filter_pack::LO;
+                    static_assert(filter_pack::a_word(filter_pack::M2, 0, 0, LO, 0) && filter_pack::a_word(filter_pack::M2, 0, 1, LO, 2) &&
+                                      filter_pack::a_word(filter_pack::M2, 0, 2, HI, 2) && filter_pack::a_word(filter_pack::M2, 0, 3, HI, 0) &&
+                                      filter_pack::a_word(filter_pack::M2, 1, 0, HI, 12) && filter_pack::a_word(filter_pack::M2, 1, 1, HI, 14) &&
+                                      filter_pack::a_word(filter_pack::M2, 1, 2, LO, 12) && filter_pack::a_word(filter_pack::M2, 1, 3, LO, 14) &&
+                                      filter_pack::a_word(filter_pack::M2, 2, 0, LO, 16) && filter_pack::a_word(filter_pack::M2, 2, 1, LO, 18) &&
+                                      filter_pack::a_word(filter_pack::M2, 2, 2, HI, 18) && filter_pack::a_word(filter_pack::M2, 2, 3, HI, 20) &&
+                                      filter_pack::a_word(filter_pack::M2, 3, 0, LO, 4) && filter_pack::a_word(filter_pack::M2, 3, 3, LO, 10) &&
+                                      filter_pack::LANE_K[2][4] == FE && filter_pack::LANE_K[2][6] == 16 && filter_pack::LANE_K[3][0] == 4,
+                                  "the loads and selects here follow the map");
                     float av[8];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        av[i] = tq < 3 ? q0[i] : 0.f;
-                        av[4 + i] = tq < 2 ? q1[i] : 0.f;
-                    }
-                    if (tq == 2) av[4] = 1.0f;
+                    for (int i = 0; i < 4; ++i) av[i] = q0[i];
+                    av[4] = tq == 2 ? 1.0f : q1[0];
+                    av[5] = tq == 2 ? 0.f : q1[1];
+                    av[6] = tq == 2 ? q0[0] : q1[2];
+                    av[7] = tq == 2 ? q0[1] : q1[3];
+                    // (k-group 3 holds values the edge's other lanes hold too: the maximum over the edge's 21 values as before)
                     float mf = 0.f;
 #pragma unroll
                     for (int i = 0; i < 8; i += 2) mf = fmaxf(fmaxf(mf, fabsf(av[i])), fabsf(av[i + 1]));
@@ -665,24 +689,23 @@ __global__ void __launch_bounds__(1024) k_sage_fused_ws(const int32_t* __restric
                     float inv_e[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) inv_e[r] = __shfl(inv_sA, 4 * tq + r);
-                    const f16x8 ah = pack8h(ph), al = pack8h(pl);
+                    const uint32_t p2[4] = {tq == 1 ? ph[2] : pl[0], tq == 1 ? ph[3] : pl[1], (tq & 1) ? pl[2] : ph[1], (tq & 1) ? pl[3] : (tq == 0 ? ph[0] : ph[2])};
+                    const f16x8 a1 = pack8h(ph), a2 = pack8h(p2);
 #pragma unroll
                     for (int c4 = 0; c4 < NCH; c4 += 2) {
-                        f16x8 bh[2], bl[2];
+                        f16x8 b2[2], b1[2];
                         f32x4_t d[2];
 #pragma unroll
                         for (int u = 0; u < 2; ++u) {
-                            const char* bp = bpbuf + (((c4 + u) * 2) * 48 + (tq < 3 ? tq : 0) * 16 + jcol) * 16;   // k-group 3 re-reads group 0: its A operand is zero
-                            bh[u] = H8(*reinterpret_cast<const uint4*>(bp));
-                            bl[u] = H8(*reinterpret_cast<const uint4*>(bp + 768));
+                            const char* bp = bpbuf + ((((c4 + u) * 2) * 64 + lane) << 4);
+                            b2[u] = H8(*reinterpret_cast<const uint4*>(bp));
+                            b1[u] = H8(*reinterpret_cast<const uint4*>(bp + 1024));
                             d[u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
                         }
 #pragma unroll
-                        for (int u = 0; u < 2; ++u) d[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[u], d[u], 0, 0, 0);
+                        for (int u = 0; u < 2; ++u) d[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, b2[u], d[u], 0, 0, 0);     // small terms first
 #pragma unroll
-                        for (int u = 0; u < 2; ++u) d[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[u], d[u], 0, 0, 0);
-#pragma unroll
-                        for (int u = 0; u < 2; ++u) d[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[u], d[u], 0, 0, 0);
+                        for (int u = 0; u < 2; ++u) d[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b1[u], d[u], 0, 0, 0);
 #pragma unroll
                         for (int u = 0; u < 2; ++u) {
                             const int c8 = c4 + u;
