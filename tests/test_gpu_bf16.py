@@ -155,23 +155,44 @@ def test_first_layer_reads_fp32_rows_in_place(c_out, mode):
 
 
 def test_fused_layer_bf16_irregular_degrees_and_tail():
-    """in-degree 0..many (generic per-lane path) and a destination count that is not a multiple of the tile"""
+    """in-degree 0 .. 40 (the per-lane path between groups the matrix cores take, fused_layer_model.ragged_graph), more sources than destinations and destination
+    counts that are no multiple of the tile (TILE 32 at 64 -> 128: ten tiles with a ragged last one, and 1003), in both arithmetics: every element within the
+    bound of test_fused_layer_bf16_vs_fp64_on_rounded_inputs"""
     from dgnn_amd import ops
+    from fused_layer_model import ragged_graph
     from oracle.pyg_semantics import propagate_mean
-    g = torch.Generator().manual_seed(5)
-    n_src, n_dst, E, c_in, c_out = 1500, 1003, 5200, 64, 128
-    ei = torch.stack([torch.randint(0, n_src, (E,), generator=g), torch.randint(0, n_dst + 30, (E,), generator=g).clamp_max(n_dst - 1)])
-    x = torch.randn(n_src, c_in, generator=g)
-    ea = torch.randn(E, 20, generator=g)
-    We, be = torch.randn(c_in, 20, generator=g) * 0.3, torch.randn(c_in, generator=g)
-    Wj, Wi, bj = torch.randn(c_out, c_in, generator=g) * 0.1, torch.randn(c_out, c_in, generator=g) * 0.1, torch.randn(c_out, generator=g)
-    r = lambda t: t.to(BF).double()
-    a = propagate_mean(r(x), n_dst, ei, r(ea) @ r(We).t() + r(be))
-    ref = a.float().to(BF).double() @ r(Wj).t() + r(x)[:n_dst] @ r(Wi).t() + bj.double()
-    rowptr, src, eid = ops.plan_build(ei.to(DEV), n_dst, 1, n_other=n_src)
-    out = ops.sage_layer_fused_fwd_bf16(rowptr, src, n_dst, ops.cast_to_bf16(x.to(DEV)), c_in, ea.to(DEV), We.to(DEV), be.to(DEV), Wj.to(DEV),
-                                        bj.to(DEV), Wi.to(DEV), None, None, False, eid=eid)
-    assert rel_err(out.float(), ref) < 1.5e-2
+    c_in, c_out = 64, 128
+    for n_dst in (9 * 32 + 9, 1003):
+        n_src = n_dst + 37
+        ei = torch.from_numpy(ragged_graph(n_dst, n_src, 5 + n_dst))
+        E = ei.size(1)
+        g = torch.Generator().manual_seed(5)
+        x = torch.randn(n_src, c_in, generator=g)
+        ea = torch.randn(E, 20, generator=g)
+        We, be = torch.randn(c_in, 20, generator=g) * 0.3, torch.randn(c_in, generator=g)
+        Wj, Wi, bj = torch.randn(c_out, c_in, generator=g) * 0.1, torch.randn(c_out, c_in, generator=g) * 0.1, torch.randn(c_out, generator=g)
+        r = lambda t: t.to(BF).double()
+        rowptr, src, eid = ops.plan_build(ei.to(DEV), n_dst, 1, n_other=n_src)
+        xb = ops.cast_to_bf16(x.to(DEV))
+        for comp in (True, False):
+            p = (lambda t: t.double()) if comp else r                   # parameters / attributes as the matrix cores see them
+            a = propagate_mean(r(x), n_dst, ei, p(ea) @ p(We).t() + p(be))
+            ab = a if comp else a.float().to(BF).double()
+            ref = ab @ p(Wj).t() + r(x)[:n_dst] @ p(Wi).t() + bj.double()
+            mag = ab.abs() @ p(Wj).abs().t() + r(x)[:n_dst].abs() @ p(Wi).abs().t()
+            old, ops.BF16_MODE = ops.BF16_MODE, ops.BF16_COMPENSATED if comp else ops.BF16_SINGLE
+            try:
+                out = ops.sage_layer_fused_fwd_bf16(rowptr, src, n_dst, xb, c_in, ea.to(DEV), We.to(DEV), be.to(DEV), Wj.to(DEV), bj.to(DEV), Wi.to(DEV),
+                                                    None, None, False, eid=eid)
+            finally:
+                ops.BF16_MODE = old
+            assert out.dtype == BF and out.shape == (n_dst, c_out)
+            err = (out.cpu().double() - ref).abs()
+            bound = EPS * ref.abs() + (2.0 ** -14 * mag if comp else 2 * EPS * (ab.abs() @ p(Wj).abs().t())) + 1e-3
+            ratio = err / bound
+            print("bf16 64 -> 128, n = %d, %s: err / bound <= %.3f" % (n_dst, "compensated" if comp else "single", float(ratio.max())))
+            cell = int(ratio.max(1).values.argmax())
+            assert bool((err <= bound).all()), (n_dst, comp, float(ratio.max()), int((err > bound).sum()), cell, int((ei[1] == cell).sum()))
 
 
 @pytest.mark.parametrize("points,c_in", [(5, 128), (40, 128), (700, 128), (700, 96), (5000, 128)])

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from fused_layer_model import reference as _reference      # fp64: (result, magnitude of the terms that were added up)
 from test_gpu_parity import DEV
 
 pytestmark = pytest.mark.gpu
@@ -40,17 +41,6 @@ def _layer_inputs(c_in, n, E, seed):
     Wj[::7] *= 30.0                                # weight rows far apart: the per-consumer scales
     scale, shift = torch.rand(128, generator=g) + 0.5, torch.randn(128, generator=g)
     return x, ea, We, be, Wj, bj, Wi, scale, shift
-
-
-def _reference(x, ea, ei, n, We, be, Wj, bj, Wi, scale, shift):
-    """fp64: (result, magnitude of the terms that were added up)"""
-    from oracle.pyg_semantics import propagate_mean
-    d = lambda t: t.double()
-    a = propagate_mean(d(x), n, ei, d(ea) @ d(We).t() + d(be))
-    amag = propagate_mean(d(x).abs(), n, ei, d(ea).abs() @ d(We).abs().t() + d(be).abs())
-    ref = torch.relu((a @ d(Wj).t() + d(x)[:n] @ d(Wi).t() + d(bj)) * d(scale) + d(shift))
-    mag = (amag @ d(Wj).abs().t() + d(x)[:n].abs() @ d(Wi).abs().t() + d(bj).abs()) * d(scale).abs() + d(shift).abs()
-    return ref, mag
 
 
 @pytest.mark.parametrize("c_in", [64, 128])
