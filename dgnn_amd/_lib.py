@@ -148,6 +148,12 @@ SIGNATURES = {
     "dgnn_distance_fold_scratch_bytes": (i64, [i64]),
     "dgnn_distance_fold": (i32, [vp, vp, i64, vp, i32, vp, vp, vp, vp]),
     "dgnn_row_dot3": (i32, [vp, i64, vp, vp, i64, vp, i64, vp, vp, vp]),
+    "dgnn_knn_scratch_bytes": (i64, [i64, i32]),
+    "dgnn_knn": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
+    "dgnn_knn_mean_distance": (i32, [vp, vp, i64, i32, vp, vp]),
+    "dgnn_outlier_mask_scratch_bytes": (i64, [i64]),
+    "dgnn_outlier_mask": (i32, [vp, i64, f64, vp, vp, vp, vp, vp]),
+    "dgnn_knn_normals": (i32, [vp, i64, vp, i32, vp, vp, vp, vp, vp]),
     "dgnn_insphere_sign": (i32, [vp, i64, vp, vp, vp]),
     "dgnn_delaunay_default_capacity": (i64, [i64]),
     "dgnn_delaunay_scratch_bytes": (i64, [i64, i64]),

@@ -2586,6 +2586,101 @@ def surface_metrics(a_vertices, a_faces, b_vertices, b_faces, n_samples, thresho
     return out
 
 
+# ---- exact k nearest neighbours and the scan operations on them (csrc/knn.hip) ---------------------------------------------
+KNN_STATS = ("shells", "candidates", "placed")
+KNN_MAX_K = 64
+KNN_CELLS_PER_SQRT_POINT = 0.175
+
+
+def default_knn_resolution(n_points):
+    """The grid resolution ops.knn takes when none is given: 0.175 sqrt(n_points) cells along the longest axis, within [1, 512] -- on a scanned
+    surface, whose points fill about 3 R^2 of the R^3 cells, some ten points per occupied cell: the fastest or within 5 % of it at k = 8, 16, 32
+    and 64 on scans of 150 000 and 1 000 000 points (the sweep is in profiles/knn.md).  The answer does not depend on it."""
+    return max(1, min(512, int(round(KNN_CELLS_PER_SQRT_POINT * float(n_points) ** 0.5))))
+
+
+@on_device_of
+def knn(points, k, queries=None, grid_resolution=None, return_stats=False):
+    """The k nearest of `points` (fp16 / fp32 / fp64 [n, 3], promoted to fp64) for every query, exactly (dgnn_knn; the rule and the tie rule
+    are in include/dgnn_hip.h): -> (idx int32 [Q, k], d2 fp64 [Q, k]) on the GPU, each row ascending in (d2, index).  queries None: the points
+    are their own queries and query i leaves out point i by index (a duplicate of it is its neighbour at d2 = 0); with queries [Q, 3] nothing is
+    left out.  Where fewer than k points qualify the row ends in idx = -1, d2 = +inf.  grid_resolution sizes the candidate grid (None:
+    default_knn_resolution of the point count; 0: no grid, every point is tested for every query); the answer does not depend on it.  With
+    return_stats also a dict of KNN_STATS -> int, summed over the call.  ValueError for k outside [1, 64] and for a non-finite coordinate;
+    DgnnError for a grid_resolution outside [0, 1024]."""
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError("knn: k = %d outside [1, %d]" % (k, KNN_MAX_K))
+    dev = _dev_of(points, queries)
+    p = _points64(points, dev)
+    q = None if queries is None else _points64(queries, dev)
+    n, nq = p.size(0), (p.size(0) if q is None else q.size(0))
+    R = default_knn_resolution(n) if grid_resolution is None else int(grid_resolution)
+    scratch = _scratch(dev, lib().dgnn_knn_scratch_bytes(n, R))
+    idx, d2 = _empty(dev, torch.int32, nq, k), _empty(dev, torch.float64, nq, k)
+    stats = torch.zeros(len(KNN_STATS), dtype=torch.int64, device=dev)
+    _check_value(lib().dgnn_knn(ptr(p), n, ptr(q), nq, k, R, ptr(idx), ptr(d2), ptr(stats), ptr(scratch), stream_ptr()), "dgnn_knn")
+    return (idx, d2, _stats_dict(KNN_STATS, stats)) if return_stats else (idx, d2)
+
+
+@on_device_of
+def knn_mean_distance(d2, idx):
+    """m fp64 [n]: per row of ops.knn's (d2, idx) [n, k] the sum of sqrt(d2) over the valid entries (idx >= 0), in rank order, divided by
+    their number (dgnn_knn_mean_distance); a row without a valid entry gives 0 / 0."""
+    dev = _dev_of(d2, idx)
+    d = _on(d2, dev, torch.float64)
+    i = _on(idx, dev, torch.int32)
+    if d.dim() != 2 or d.shape != i.shape or d.size(1) < 1:
+        raise ValueError("knn_mean_distance: d2 %s and idx %s must be one [n, k] shape" % (tuple(d.shape), tuple(i.shape)))
+    n, k = d.shape
+    m = _empty(dev, torch.float64, n)
+    check(lib().dgnn_knn_mean_distance(ptr(d), ptr(i), n, k, ptr(m), stream_ptr()), "dgnn_knn_mean_distance")
+    return m
+
+
+@on_device_of
+def outlier_mask(points, k=16, std_ratio=2.0, grid_resolution=None):
+    """Statistical outlier removal (PCL / Open3D, with the population deviation): m_i = the mean distance from point i to its min(k, n - 1)
+    nearest neighbours (knn, knn_mean_distance), mu = sum(m) / n, sigma = sqrt(sum((m_i - mu)^2) / n), both sums in a fixed order,
+    threshold = mu + std_ratio sigma, keep_i = m_i <= threshold (dgnn_outlier_mask).  -> (keep bool [n] on the GPU, dict of mean_distance
+    (fp64 [n], on the GPU), mu, sigma, threshold, n_removed).  ValueError for fewer than 2 points."""
+    dev = _dev_of(points)
+    p = _points64(points, dev)
+    n = p.size(0)
+    if n < 2:
+        raise ValueError("outlier_mask: %d points, at least 2 are needed" % n)
+    idx, d2 = knn(p, min(int(k), n - 1), grid_resolution=grid_resolution)
+    m = knn_mean_distance(d2, idx)
+    keep = _empty(dev, torch.uint8, n)
+    values = torch.zeros(3, dtype=torch.float64, device=dev)
+    removed = torch.zeros(1, dtype=torch.int64, device=dev)
+    scratch = _scratch(dev, lib().dgnn_outlier_mask_scratch_bytes(n))
+    _check_value(lib().dgnn_outlier_mask(ptr(m), n, float(std_ratio), ptr(keep), ptr(values), ptr(removed), ptr(scratch), stream_ptr()), "dgnn_outlier_mask")
+    v = values.cpu()
+    return keep.bool(), {"mean_distance": m, "mu": float(v[0]), "sigma": float(v[1]), "threshold": float(v[2]), "n_removed": int(removed.item())}
+
+
+@on_device_of
+def estimate_normals(points, k=16, sensors=None, grid_resolution=None):
+    """PCA normals: for every point the eigenvector of the smallest eigenvalue of the scatter matrix of (the point, then its min(k, n - 1)
+    nearest neighbours in rank order), by six cyclic Jacobi sweeps (dgnn_knn_normals; every operation is in include/dgnn_hip.h).  Its sign
+    makes the component of largest magnitude positive; with sensors [n, 3] it is negated where n . (sensor - point) < 0, the rule of
+    scan_mesh's own normals.  -> (normals fp64 [n, 3], eigenvalues fp64 [n, 3] ascending) on the GPU.  ValueError for fewer than 3 points."""
+    dev = _dev_of(points, sensors)
+    p = _points64(points, dev)
+    n = p.size(0)
+    if n < 3:
+        raise ValueError("estimate_normals: %d points, at least 3 are needed" % n)
+    s = None if sensors is None else _points64(sensors, dev)
+    if s is not None and s.size(0) != n:
+        raise ValueError("estimate_normals: %d sensors for %d points" % (s.size(0), n))
+    idx, d2 = knn(p, min(int(k), n - 1), grid_resolution=grid_resolution)
+    normals, eig = _empty(dev, torch.float64, n, 3), _empty(dev, torch.float64, n, 3)
+    scratch = _scratch(dev, 256)
+    _check_value(lib().dgnn_knn_normals(ptr(p), n, ptr(idx), idx.size(1), ptr(s), ptr(normals), ptr(eig), ptr(scratch), stream_ptr()), "dgnn_knn_normals")
+    return normals, eig
+
+
 # ---- ingest: feature scaling (csrc/ingest.hip) ------------------------------------------------------------------------------------
 SCALE_KINDS = {"none": 0, "standard": 1, "minmax": 2, "robust": 3}
 

@@ -1419,6 +1419,67 @@ int dgnn_row_dot3(const double* a, int64_t n_a, const int32_t* ia, const double*
                   void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The k nearest neighbours of every query among a set of points, exactly, and the scan operations on the lists: the mean neighbour
+ * distance, the statistical outlier mask, PCA normals (ops.knn, ops.knn_mean_distance, ops.outlier_mask, ops.estimate_normals).  DESIGN.md
+ * section 34.  Every *, +, -, / and sqrt below is one fp64 rounding, in the order written (no contraction).
+ *
+ * dgnn_knn: points fp64 [n_points, 3], queries fp64 [n_queries, 3] or NULL, 1 <= k <= 64.  For a query q and a point j:
+ *   dx = q.x - p_j.x, dy = q.y - p_j.y, dz = q.z - p_j.z, d2 = (dx dx + dy dy) + dz dz.
+ *   answer    row i of idx_out int32 [Q, k] and d2_out fp64 [Q, k] = the k smallest of ALL (d2_j, j) in lexicographic order, ascending.
+ *             queries == NULL: the queries are the points themselves (Q = n_points, n_queries is not read) and query i leaves out point i BY
+ *             INDEX, not by distance: a duplicate of a point is its neighbour at d2 = 0.  With queries nothing is left out.  Where fewer
+ *             than k points qualify the row ends in idx = -1, d2 = +inf.  Row offsets are int64: Q k has no int32 limit.
+ *   grid      grid_resolution R = 0: no grid; tiles of 256 points pass through LDS and every query meets every point.  R in [1, 1024]: a
+ *             uniform grid over the box of the points, R cells along the longest axis, ceil(extent / (longest / R)) on the others (1
+ *             without extent), the cell of a coordinate x on axis a being trunc((x - lo_a) inv_a) clamped to the grid; the points are
+ *             binned as (x, y, z, index) records.  One wavefront per query keeps the sorted list one entry per lane, reads the cells in
+ *             Chebyshev shells about the query's (clamped) cell and stops when the list is full and its k-th d2 is strictly below the
+ *             squared distance, shrunk by 2^-46 of the largest coordinate magnitude of the box and the query, to every cell not yet read
+ *             (csrc/knn.hip has the derivation); a list that is not full reads on to the last shell.  The result does not depend on R.
+ *   stats_out DEVICE int64 [3], summed over the call: shells read (R = 0: 0); candidates evaluated = the records of the cells read, the
+ *             query's own included (R = 0: Q n_points); survivors placed in a list.
+ *   scratch   dgnn_knn_scratch_bytes(n_points, grid_resolution) bytes.
+ * DGNN_E_INVALID: k outside [1, 64], a non-finite coordinate of a point or of a query (validated before any kernel uses them: the call
+ * SYNCHRONISES `stream` once); DGNN_E_UNSUPPORTED: R outside [0, 1024], n_points or Q >= 2^31 - 1.  No floating-point atomics and a total
+ * order: bit-identical from run to run, whatever order the bins were filled in.
+ *
+ * dgnn_knn_mean_distance: d2 fp64 [n, k], idx int32 [n, k] (dgnn_knn's) -> mean_out fp64 [n]: s = 0, then s = s + sqrt(d2[i, r]) over the
+ *   entries with idx[i, r] >= 0 in rank order r, divided by their number (as a double; none: 0 / 0).
+ *
+ * dgnn_outlier_mask: mean_distance fp64 [n], n >= 2 (DEVICE) -> mu = S(m) / n, sigma = sqrt(S((m_i - mu) (m_i - mu)) / n), threshold = mu +
+ *   std_ratio sigma (one product, one sum), keep_out uint8 [n] = m_i <= threshold; values_out DEVICE fp64 [3] = mu, sigma, threshold;
+ *   n_removed_out DEVICE int64 [1].  S is fixed_sum.h's sum: serial sums over chunks of 256 elements, then the chunk totals serially.
+ *   PCL / Open3D's statistical outlier removal with the population deviation.  scratch: dgnn_outlier_mask_scratch_bytes(n) bytes.
+ *
+ * dgnn_knn_normals: points fp64 [n, 3], idx int32 [n, k] with entries in [-1, n) (validated first: SYNCHRONISES once), sensors fp64 [n, 3] or
+ *   NULL -> normals_out fp64 [n, 3], eigenvalues_out fp64 [n, 3].  One lane per point.  The neighbourhood of point i is the point itself, then
+ *   the points idx[i, r] >= 0 in rank order; m is their number, as a double.  Every sum below runs over the neighbourhood in that order, serially.
+ *   centroid  c = (sum p) / m per coordinate.
+ *   sums      with d = p - c: a00 = sum dx dx, a11 = sum dy dy, a22 = sum dz dz, a01 = sum dx dy, a02 = sum dx dz, a12 = sum dy dz (not
+ *             divided by m), the symmetric matrix A; V = the identity.
+ *   Jacobi    SIX cyclic sweeps over (p, q) = (0, 1), (0, 2), (1, 2), r the third index.  A rotation with a_pq == 0.0 is skipped.  Else
+ *             theta = (a_qq - a_pp) / (2 a_pq); t = sign / (|theta| + sqrt(theta theta + 1)) with sign = 1 for theta >= 0, else -1 (theta
+ *             theta overflowing to inf gives t = 0); c = 1 / sqrt(t t + 1); s = t c; then, all from the old values,
+ *               a_pp = a_pp - t a_pq;  a_qq = a_qq + t a_pq;  a_rp = c a_rp - s a_rq;  a_rq = s a_rp + c a_rq;  a_pq = 0;
+ *               v_ip = c v_ip - s v_iq;  v_iq = s v_ip + c v_iq   for the rows i = 0, 1, 2 of V.
+ *             Six is a count, not a tolerance: fixed-sweep Jacobi reaches its floor at four (DESIGN section 34 has the measurement).
+ *   normal    the column of V at the smallest diagonal entry of A (ties: the lower column), each component divided by the column's length
+ *             sqrt((x x + y y) + z z); negated when its component of largest magnitude (ties: the lowest axis) is negative; then, with
+ *             sensors, negated when (n.x t.x + n.y t.y) + n.z t.z < 0 for t = sensor_i - p_i: the rule of scan_mesh's own normals.
+ *   eigenvalues  the three diagonal entries ascending, ties by column.
+ *   Only + - * / sqrt are used, each correctly rounded on the device and in numpy: tests/knn_model.py agrees bit for bit.  scratch: 256 bytes.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_knn_scratch_bytes(int64_t n_points, int32_t grid_resolution);
+int dgnn_knn(const double* points, int64_t n_points, const double* queries, int64_t n_queries, int32_t k, int32_t grid_resolution,
+             int32_t* idx_out, double* d2_out, int64_t* stats_out, void* scratch, void* stream);
+int dgnn_knn_mean_distance(const double* d2, const int32_t* idx, int64_t n, int32_t k, double* mean_out, void* stream);
+int64_t dgnn_outlier_mask_scratch_bytes(int64_t n);
+int dgnn_outlier_mask(const double* mean_distance, int64_t n, double std_ratio, uint8_t* keep_out, double* values_out, int64_t* n_removed_out,
+                      void* scratch, void* stream);
+int dgnn_knn_normals(const double* points, int64_t n, const int32_t* idx, int32_t k, const double* sensors, double* normals_out,
+                     double* eigenvalues_out, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-scene standardisation (reference processing/data.py:444-506 sklearn StandardScaler + :512-519
  * float32 cast): out[i,c] = float((x[i,c] - mean_c) / std_c) for c >= c_first, plain cast for c < c_first;
  * fp64 statistics (population variance, zero scale -> 1).  scratch: dgnn_standardize_scratch_doubles(c) doubles.
