@@ -154,6 +154,10 @@ SIGNATURES = {
     "dgnn_outlier_mask_scratch_bytes": (i64, [i64]),
     "dgnn_outlier_mask": (i32, [vp, i64, f64, vp, vp, vp, vp, vp]),
     "dgnn_knn_normals": (i32, [vp, i64, vp, i32, vp, vp, vp, vp, vp]),
+    "dgnn_voxel_subsample_scratch_bytes": (i64, [i64]),
+    "dgnn_voxel_subsample": (i32, [vp, i64, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dgnn_min_distance_thin_scratch_bytes": (i64, [i64, i32]),
+    "dgnn_min_distance_thin": (i32, [vp, i64, f64, vp, u64, i32, vp, vp, vp, vp]),
     "dgnn_insphere_sign": (i32, [vp, i64, vp, vp, vp]),
     "dgnn_delaunay_default_capacity": (i64, [i64]),
     "dgnn_delaunay_scratch_bytes": (i64, [i64, i64]),

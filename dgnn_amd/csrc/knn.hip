@@ -9,7 +9,7 @@
 //              each; a ballot against the k-th entry drops nearly all of them once the list is warm; a survivor's place is the number of
 //              entries below it (the popcount of a ballot), the lanes above that place take their lower neighbour's entry, the lane at it
 //              takes the candidate.  All 64 lanes keep a sorted list; the answer is its first k.
-//   grid       mesh_grid.h's frame over the box of the points and its monotone cell map.  The points are binned by count / scan / fill as
+//   grid       mesh_grid.h's frame over the box of the points and its monotone cell map.  The points are binned (point_grid.h) by count / scan / fill as
 //              (x, y, z, index) records, cell after cell, z fastest: the cells of one (x, y) column that a shell touches are one run of
 //              records, read 64 at a time.  The order inside a cell is whatever the atomics give; the total order does not see it.
 //   search     Chebyshev shells of cells about the query's (clamped) cell.  After shell s the block B = [c - s, c + s]^3 (cut to the grid) has
@@ -32,55 +32,27 @@
 #include <math.h>
 
 #include "fixed_sum.h"
-#include "mesh_grid.h"
+#include "point_grid.h"
 
 namespace {
 
-constexpr int KNN_MAX_K = 64, KNN_MAX_R = 1024;
+constexpr int KNN_MAX_K = 64;
 constexpr double KNN_MARGIN = 0x1p-46;          // of max(M, |q|_inf): 128 u, u = 2^-53, against a need of 12 u (the derivation is above)
 constexpr double KNN_SHRINK = 1.0 - 0x1p-50;
-constexpr int32_t KNN_NONFINITE = 1, KNN_BAD_ID = 2;
 constexpr int32_t KNN_NONE = INT32_MAX;          // the index of an empty entry: above every point's
 constexpr int KNN_TILE = 256, KNN_WAVES = MESH_THREADS / DGNN_WAVE;
 enum { KNN_SHELLS = 0, KNN_CANDIDATES, KNN_PLACED, KNN_N_STATS };
 
 struct KnnState {
-    int32_t err, pad;
-    unsigned long long lo[3], hi[3];          // bbox of the points (f64_key)
+    PointBox box;          // err, the bbox of the points
     unsigned long long stats[KNN_N_STATS];
 };
 static_assert(sizeof(KnnState) <= 256, "KnnState must fit the first scratch slot");
 
-struct KnnPoint { double x, y, z; int32_t id, pad; };          // a binned record
-
-// ---- validation, the box, the bins -----------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(MESH_THREADS) k_knn_bbox(const double* __restrict__ p, int64_t n, KnnState* st) {
-    unsigned long long lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0, 0, 0};
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        for (int a = 0; a < 3; ++a) {
-            const double x = p[3 * i + a];
-            if (!isfinite(x)) { atomicOr(&st->err, KNN_NONFINITE); continue; }
-            const unsigned long long k = f64_key(x);
-            lo[a] = k < lo[a] ? k : lo[a];
-            hi[a] = k > hi[a] ? k : hi[a];
-        }
-    for (int a = 0; a < 3; ++a) wave_minmax_atomic(lo[a], hi[a], st->lo + a, st->hi + a);
-}
-
+// ---- validation (the box and the bins are point_grid.h's) ---------------------------------------------------------------------------------
 __global__ void k_knn_check_finite(const double* __restrict__ p, int64_t n3, KnnState* st) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n3; i += (int64_t)gridDim.x * blockDim.x)
-        if (!isfinite(p[i])) atomicOr(&st->err, KNN_NONFINITE);
-}
-
-// fill == 0: ccnt[cell] += 1; fill != 0: rec[cursor[cell]++] = (x, y, z, i).  Both passes map a point to the same cell, so a cursor never
-// leaves its cell's run and every slot is below n.
-__global__ void k_knn_bin(const double* __restrict__ p, int64_t n, CellGrid g, int fill, int32_t* __restrict__ ccnt, KnnPoint* __restrict__ rec) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const double x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
-        const int64_t cell = ((int64_t)grid_cell(g, 0, x) * g.n[1] + grid_cell(g, 1, y)) * g.n[2] + grid_cell(g, 2, z);
-        const int32_t slot = atomicAdd(ccnt + cell, 1);
-        if (fill) rec[slot] = KnnPoint{x, y, z, (int32_t)i, 0};
-    }
+        if (!isfinite(p[i])) atomicOr(&st->box.err, KNN_NONFINITE);
 }
 
 // ---- the list: lane r holds the r-th smallest (d2, id) met so far ------------------------------------------------------------------------
@@ -118,11 +90,6 @@ __device__ __forceinline__ void knn_offer(KnnList& L, int k, bool valid, double 
         L.kid = __shfl(L.id, k - 1);
         ++L.placed;
     }
-}
-
-__device__ __forceinline__ double knn_d2(const double (&q)[3], double x, double y, double z) {
-    const double dx = q[0] - x, dy = q[1] - y, dz = q[2] - z;
-    return (dx * dx + dy * dy) + dz * dz;
 }
 
 __device__ __forceinline__ void knn_store(const KnnList& L, int k, int64_t row, int32_t* __restrict__ idx_out, double* __restrict__ d2_out) {
@@ -420,23 +387,15 @@ __global__ void __launch_bounds__(MESH_THREADS) k_knn_normals(const double* __re
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-struct KnnLayout { KnnState* st; int32_t *ccnt, *rowptr, *sums; KnnPoint* rec; int64_t bytes; };
+struct KnnLayout { KnnState* st; PointBins bins; int64_t bytes; };
 KnnLayout knn_layout(void* base, int64_t n, int64_t R) {
     Take t{(char*)base, 256};
     KnnLayout L{};
     L.st = (KnnState*)base;
-    if (R > 0) {
-        const int64_t cells = R * R * R;
-        L.ccnt = t.take<int32_t>(cells + 1);
-        L.rowptr = t.take<int32_t>(cells + 1);
-        L.sums = t.take<int32_t>(dgnn_cdiv(cells + 1, 2048) + 2);
-        L.rec = t.take<KnnPoint>(n);
-    }
+    if (R > 0) L.bins = take_point_bins(t, n, R);
     L.bytes = t.off;
     return L;
 }
-
-bool knn_resolution_ok(int32_t R) { return R >= 0 && R <= KNN_MAX_R; }
 
 }  // namespace
 
@@ -458,28 +417,21 @@ extern "C" int dgnn_knn(const double* points, int64_t n_points, const double* qu
     const KnnLayout L = knn_layout(scratch, n, R);
     const dim3 block(MESH_THREADS);
     KnnState hs{};
-    hs.lo[0] = hs.lo[1] = hs.lo[2] = ~0ull;
+    hs.box.lo[0] = hs.box.lo[1] = hs.box.lo[2] = ~0ull;
     (void)hipMemcpyAsync(L.st, &hs, sizeof(KnnState), hipMemcpyHostToDevice, stream);
-    if (n > 0) hipLaunchKernelGGL(k_knn_bbox, mesh_launch_grid(n), block, 0, stream, points, n, L.st);
+    if (n > 0) hipLaunchKernelGGL(k_knn_bbox, mesh_launch_grid(n), block, 0, stream, points, n, &L.st->box);
     if (queries && nq > 0) hipLaunchKernelGGL(k_knn_check_finite, mesh_launch_grid(3 * nq), block, 0, stream, queries, 3 * nq, L.st);
     int rc = dgnn_check_launch("knn");
     if (rc || (rc = mm_read(&hs, L.st, sizeof(KnnState), stream, "knn"))) return rc;
-    DGNN_REQUIRE(!hs.err, DGNN_E_INVALID, "knn: a non-finite coordinate of a point or of a query");
+    DGNN_REQUIRE(!hs.box.err, DGNN_E_INVALID, "knn: a non-finite coordinate of a point or of a query");
     if (nq > 0) {
         const dim3 grid(dgnn_grid_cap(dgnn_cdiv(nq, KNN_WAVES)));
         if (R == 0 || n == 0) {
             hipLaunchKernelGGL(k_knn_all_pairs, grid, block, 0, stream, points, n, queries, nq, k, idx_out, d2_out, L.st);
         } else {
-            double lo[3], hi[3];
-            bbox_unkey(hs.lo, hs.hi, lo, hi);
-            const CellGrid g = cell_grid_frame(lo, hi, R);
-            const int64_t cells = (int64_t)g.n[0] * g.n[1] * g.n[2];
-            (void)hipMemsetAsync(L.ccnt, 0, sizeof(int32_t) * (cells + 1), stream);
-            hipLaunchKernelGGL(k_knn_bin, mesh_launch_grid(n), block, 0, stream, points, n, g, 0, L.ccnt, (KnnPoint*)nullptr);
-            if ((rc = dgnn_exclusive_scan_i32(L.ccnt, cells, L.rowptr, L.sums, stream))) return rc;
-            (void)hipMemcpyAsync(L.ccnt, L.rowptr, sizeof(int32_t) * (cells + 1), hipMemcpyDeviceToDevice, stream);   // the fill's cursors
-            hipLaunchKernelGGL(k_knn_bin, mesh_launch_grid(n), block, 0, stream, points, n, g, 1, L.ccnt, L.rec);
-            hipLaunchKernelGGL(k_knn_search, grid, block, 0, stream, L.rec, L.rowptr, g, queries, nq, k, idx_out, d2_out, L.st);
+            CellGrid g;
+            if ((rc = bin_points(points, n, hs.box, R, L.bins, nullptr, &g, stream))) return rc;
+            hipLaunchKernelGGL(k_knn_search, grid, block, 0, stream, L.bins.rec, L.bins.rowptr, g, queries, nq, k, idx_out, d2_out, L.st);
         }
     }
     (void)hipMemcpyAsync(stats_out, L.st->stats, sizeof(int64_t) * KNN_N_STATS, hipMemcpyDeviceToDevice, stream);

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "mix64.h"
 
 namespace {
 
@@ -91,10 +92,7 @@ __device__ __forceinline__ void block_add_atomic(unsigned long long* dst, long l
 }
 
 __device__ __forceinline__ uint64_t mm_hash(uint64_t seed, uint64_t ctr) {
-    uint64_t z = seed + ctr * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
+    return mix64(seed + ctr * 0x9E3779B97F4A7C15ull);
 }
 __device__ __forceinline__ double mm_u01(uint64_t h) { return (double)(h >> 11) * 0x1p-53; }           // [0, 1)
 __device__ __forceinline__ double mm_u01_open0(uint64_t h) { return (double)((h >> 11) + 1) * 0x1p-53; }   // (0, 1]

@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "mix64.h"
 
 namespace {
 
@@ -31,12 +32,6 @@ struct KhopDraw {
     uint64_t base;   // mix64(seed + 0x9E3779B97F4A7C15 * (draw + 1))
     uint64_t hop;    // builder hop << 32
 };
-
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {   // the splitmix64 finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 inline KhopDraw khop_draw(int size, uint64_t seed, int64_t draw, int hop) {
     return KhopDraw{size, mix64(seed + 0x9E3779B97F4A7C15ull * ((uint64_t)draw + 1ull)), (uint64_t)(uint32_t)hop << 32};

@@ -2681,6 +2681,75 @@ def estimate_normals(points, k=16, sensors=None, grid_resolution=None):
     return normals, eig
 
 
+# ---- subsampling a scan: voxel grid and exact minimum-distance thinning (csrc/scansub.hip) -----------------------------------
+THIN_STATS = ("n_kept", "rounds", "candidates")
+THIN_MAX_RESOLUTION = 512
+THIN_CELLS_PER_RADIUS = 0.25
+
+
+@on_device_of
+def voxel_subsample(points, voxel_size, origin=(0.0, 0.0, 0.0)):
+    """One row per occupied voxel of edge `voxel_size` (dgnn_voxel_subsample; the rule is in include/dgnn_hip.h): a point's voxel is
+    floor((x - origin) / voxel_size) per axis, the voxels are numbered by their lowest member.  -> dict on the GPU: "voxel" int32 [n] (the
+    point's voxel row), "count" int32 [m], "first" int32 [m] (the lowest member), "centroid" fp64 [m, 3] (the members summed in ascending
+    index, fixed_sum.h's order), "nearest" int32 [m] (the member with the smallest (d2 to the centroid, index)), and "m".  The same input
+    gives the same bytes.  ValueError for a voxel_size that is not finite and positive, a non-finite coordinate, and a voxel coordinate
+    outside (-2^20, 2^20)."""
+    dev = _dev_of(points)
+    p = _points64(points, dev)
+    n = p.size(0)
+    org = (C.c_double * 3)(*[float(x) for x in origin])
+    voxel, count, first, nearest = (_empty(dev, torch.int32, n) for _ in range(4))
+    centroid = _empty(dev, torch.float64, n, 3)
+    m = torch.zeros(1, dtype=torch.int64, device=dev)
+    scratch = _scratch(dev, lib().dgnn_voxel_subsample_scratch_bytes(n))
+    _check_value(lib().dgnn_voxel_subsample(ptr(p), n, float(voxel_size), org, ptr(voxel), ptr(count), ptr(first), ptr(centroid), ptr(nearest), ptr(m),
+                                            ptr(scratch), stream_ptr()), "dgnn_voxel_subsample")
+    m = int(m.item())
+    return dict(voxel=voxel, count=count[:m], first=first[:m], centroid=centroid[:m], nearest=nearest[:m], m=m)
+
+
+def default_thin_resolution(extent, radius):
+    """The grid resolution ops.min_distance_thin takes when none is given: floor(0.25 extent / radius) cells along the longest axis (extent:
+    its length), within [1, 512]: a cell's edge is four radii, and a point reads 8 to 27 cells.  A choice, not a need: the answer is the same
+    at every resolution.  One cell per radius, the natural first guess, reads a quarter of the candidates but was 6 - 25 % slower on scans of
+    150 000 and 999 997 points at 1, 2 and 4 mean spacings: its cells hold a point or two, so a wavefront reads 27 nearly empty runs (the
+    sweep is in profiles/scan_subsample.md)."""
+    extent, radius = float(extent), float(radius)
+    if not (extent > 0.0 and radius > 0.0):          # no extent, radius 0 (nothing conflicts), or a NaN (the library refuses it): one cell
+        return 1
+    cells = THIN_CELLS_PER_RADIUS * extent / radius
+    return THIN_MAX_RESOLUTION if cells >= THIN_MAX_RESOLUTION else max(1, int(cells))
+
+
+@on_device_of
+def min_distance_thin(points, radius, priority=None, seed=0, grid_resolution=None, return_stats=False):
+    """Exact minimum-distance (Poisson-disk) thinning (dgnn_min_distance_thin; the rule is in include/dgnn_hip.h): points i and j conflict iff
+    d2(i, j) < radius^2; the points are walked in the order of (key_i, i) -- key_i = priority[i] (int64, lower first), or without one the
+    splitmix64 hash of (seed, i) -- and a point is kept iff it conflicts with no point kept before it.  -> keep bool [n] on the GPU, the
+    lexicographically first maximal independent set; with return_stats also a dict of THIN_STATS -> int.  grid_resolution sizes the candidate
+    grid (None: default_thin_resolution of the longest extent; 0: all pairs); the answer does not depend on it.  ValueError for a radius that
+    is not finite and >= 0 and for a non-finite coordinate; DgnnError for a grid_resolution outside [0, 1024]."""
+    dev = _dev_of(points, priority)
+    p = _points64(points, dev)
+    n = p.size(0)
+    pr = None
+    if priority is not None:
+        pr = _on(priority, dev, torch.int64).reshape(-1)
+        if pr.numel() != n:
+            raise ValueError("min_distance_thin: %d priorities for %d points" % (pr.numel(), n))
+    if grid_resolution is None:
+        R = default_thin_resolution(float((p.max(dim=0).values - p.min(dim=0).values).max()), radius) if n else 1
+    else:
+        R = int(grid_resolution)
+    scratch = _scratch(dev, lib().dgnn_min_distance_thin_scratch_bytes(n, R))
+    keep = _empty(dev, torch.uint8, n)
+    stats = torch.zeros(len(THIN_STATS), dtype=torch.int64, device=dev)
+    _check_value(lib().dgnn_min_distance_thin(ptr(p), n, float(radius), ptr(pr), int(seed) & 0xFFFFFFFFFFFFFFFF, R, ptr(keep), ptr(stats), ptr(scratch),
+                                              stream_ptr()), "dgnn_min_distance_thin")
+    return (keep.bool(), _stats_dict(THIN_STATS, stats)) if return_stats else keep.bool()
+
+
 # ---- ingest: feature scaling (csrc/ingest.hip) ------------------------------------------------------------------------------------
 SCALE_KINDS = {"none": 0, "standard": 1, "minmax": 2, "robust": 3}
 

@@ -1480,6 +1480,51 @@ int dgnn_knn_normals(const double* points, int64_t n, const int32_t* idx, int32_
                      double* eigenvalues_out, void* scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Subsampling a scan before it is triangulated: one point per occupied voxel, and exact minimum-distance (Poisson-disk) thinning
+ * (ops.voxel_subsample, ops.min_distance_thin).  DESIGN.md section 35.  Every *, +, -, / below is one fp64 rounding, in the order written (no
+ * contraction); d2 is dgnn_knn's.  Both results depend on the input alone: bit-identical from run to run.
+ *
+ * dgnn_voxel_subsample: points fp64 [n, 3], the voxel's edge h, origin HOST fp64 [3].
+ *   voxel     c_a = floor((x_a - o_a) / h) per axis a; a point's voxel is (c_x, c_y, c_z).  A point ON a voxel face belongs to the voxel above.
+ *   numbering voxel v is the one whose lowest member index is the v-th smallest ("numbered by first member").
+ *   outputs   for m occupied voxels (every array has room for n rows; rows >= m are not written): voxel_out int32 [n] the point's voxel row;
+ *             count_out int32 [m]; first_out int32 [m] the lowest member; centroid_out fp64 [m, 3]; nearest_out int32 [m]; m_out DEVICE int64 [1].
+ *   centroid  per axis S(x) / count (count as a double) over the members in ascending index; S is fixed_sum.h's sum: s = 0, s = s + x over a
+ *             chunk of 256 members, total = 0, total = total + s over the chunks in order (at most 256 members: a plain left-to-right sum).
+ *   nearest   the member with the smallest (d2, index), d2 = (dx dx + dy dy) + dz dz, dx = centroid.x - p.x and so on (where every d2 is a
+ *             NaN, the sums having overflowed both ways: the first member).
+ *   scratch   dgnn_voxel_subsample_scratch_bytes(n) bytes.  n = 0: m = 0.
+ * DGNN_E_INVALID, nothing written: h not finite or <= 0, a non-finite origin, a non-finite coordinate, any |c_a| >= 2^20 (the triple is a
+ * 63-bit key: three fields of 21 bits); the points are validated before anything is written: the call SYNCHRONISES `stream` once.
+ * DGNN_E_UNSUPPORTED: n >= 2^31 - 1.  The voxels are found by a stable radix sort of (key, index); no result depends on an atomic's order.
+ *
+ * dgnn_min_distance_thin: points fp64 [n, 3], radius r finite and >= 0, priority int64 [n] or NULL, seed.
+ *   conflict  r2 = r r; i and j conflict iff d2(i, j) < r2 (d2 == r2 is no conflict; r = 0 keeps everything, duplicates included).
+ *   order     by (key_i, i), lexicographic.  With a priority key_i = priority[i], signed, lower first; without one
+ *             key_i = mix(mix(seed + 0x9E3779B97F4A7C15) + i) modulo 2^64, compared unsigned, mix the splitmix64 finaliser
+ *             z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.
+ *   answer    walk the points in that order and keep a point iff it conflicts with no point kept before it: the lexicographically first
+ *             maximal independent set of the conflict graph.  keep_out uint8 [n].
+ *   rounds    computed in parallel rounds over the undecided points (one wavefront each): an earlier conflicting point kept -> removed; none
+ *             undecided -> kept; else the point waits.  The earliest undecided point is decided in every round.  With the hashed key the
+ *             number of rounds is O(log n) with high probability; a priority can make a chain as long as n.
+ *   grid      grid_resolution R = 0: all pairs, tiles of 256 points through LDS.  R in [1, 1024]: dgnn_knn's grid and records; a point reads
+ *             the cells of x_a - r' .. x_a + r' on each axis, r' = r (1 + 2^-46) (csrc/scansub.hip has the count).  The answer does not depend
+ *             on R, cells smaller than r included.
+ *   stats_out DEVICE int64 [3]: the points kept; the rounds that had an undecided point; candidates evaluated = the records (R = 0: points)
+ *             read, summed over the rounds.
+ *   scratch   dgnn_min_distance_thin_scratch_bytes(n, grid_resolution) bytes.  n = 0: nothing kept, no round.
+ * DGNN_E_INVALID, nothing written: r not finite or < 0, a non-finite coordinate.  DGNN_E_UNSUPPORTED: R outside [0, 1024], n >= 2^31 - 1.
+ * The call SYNCHRONISES `stream` once for the validation and once per four rounds.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t dgnn_voxel_subsample_scratch_bytes(int64_t n);
+int dgnn_voxel_subsample(const double* points, int64_t n, double h, const double* origin, int32_t* voxel_out, int32_t* count_out, int32_t* first_out,
+                         double* centroid_out, int32_t* nearest_out, int64_t* m_out, void* scratch, void* stream);
+int64_t dgnn_min_distance_thin_scratch_bytes(int64_t n, int32_t grid_resolution);
+int dgnn_min_distance_thin(const double* points, int64_t n, double radius, const int64_t* priority, uint64_t seed, int32_t grid_resolution,
+                           uint8_t* keep_out, int64_t* stats_out, void* scratch, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Per-scene standardisation (reference processing/data.py:444-506 sklearn StandardScaler + :512-519
  * float32 cast): out[i,c] = float((x[i,c] - mean_c) / std_c) for c >= c_first, plain cast for c < c_first;
  * fp64 statistics (population variance, zero scale -> 1).  scratch: dgnn_standardize_scratch_doubles(c) doubles.
